@@ -9,10 +9,12 @@ segmentation and cross-fade as formal_test_bwe, testing/blind_bwe_tester.py:421-
 babe_amd/testing/long_file.py) that run as one batch of 2 with per-clip semantics.  Weak scaling: every rank restores its own clips; one RCCL all_gather of
 the restored audio + filters closes each step.
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 N>1: either launched by torch.distributed.run (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE in the env), or run plainly,
 in which case this process spawns the N ranks itself (as a child torch.distributed.run, before touching the GPU).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR: after the timed region rank 0 writes what the last timed step returned
+(restored clips, fitted filter parameters) as DIR/<name>.npy, so that two builds can be compared output for output; the
+inputs (synthetic clips, seeded noise) depend only on the arguments.
 """
 import argparse
 import json
@@ -212,6 +214,33 @@ def conv_traffic(precision):
             "source": f"profiles/{PMC_TRAFFIC_FILE} (separate PMC passes of this command, not live)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays {name: float tensor} -> out_dir/<name>.npy (float64 stays float64, every other float dtype becomes float32).
+    Above `limit` bytes in all, each array keeps a share of the budget proportional to its size: a fixed-seed sample of its
+    flattened elements, in index order.  Returns {name: {shape, dtype, sampled}}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, t in arrays.items():
+        assert t.is_floating_point(), name
+        arrs[name] = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    budget = limit - 4096 * len(arrs)                  # (room for the .npy headers)
+    info = {}
+    for name, a in arrs.items():
+        shape, sampled = list(a.shape), total > budget
+        if sampled:
+            keep = int(a.size * (budget / total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = {"shape": shape, "dtype": str(a.dtype), "sampled": sampled}
+    return info
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks under torch.distributed.run as a CHILD process
     (this parent never touches the GPU) and relay their output and exit code."""
@@ -272,7 +301,12 @@ def main():
     ap.add_argument("--no-pin", action="store_true", help="do not pin this rank's host threads to its own block of CPUs")
     ap.add_argument("--profile-steps", type=int, default=1,
                     help="timed steps whose launches are bracketed by HIP events (0 = no roofline/hbm blocks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (restored_audio, filter_params) as "
+                         "DIR/<name>.npy, float32, at most 64 MB in all (a fixed-seed sample beyond that)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.dry_run:
         # the plan only: which rank drives which device and restores which clips of one step (block partition, babe_amd/dist.py);
@@ -415,6 +449,9 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax)
     finite = bool(torch.isfinite(out[0]).all())
+    dumped = None
+    if a.dump_outputs and rank == 0:                 # outside the timed region; `out` = the last timed step's return value
+        dumped = dump_outputs(a.dump_outputs, {"restored_audio": out[0], "filter_params": out[1]})
 
     if rank == 0:
         value = world * a.steps * C_ * CLIP_SEC / dt
@@ -542,6 +579,8 @@ def main():
             "roofline": roof,
             "hbm": hbm,
         }
+        if dumped is not None:
+            rec["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
         if world == 1 and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline()
         print(json.dumps(rec), flush=True)

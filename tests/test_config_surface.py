@@ -1,37 +1,47 @@
 """Config surface: every tester YAML of the reference goes through babe_amd.config.load_yaml and the
 sampler class its `sampler_callable` string names (the reference resolves that string with dnnlib.call_func_by_name,
-/root/reference/utils/setup.py:75-87, /root/reference/testing/blind_bwe_tester.py:214; INTEGRATION.md maps
-`testing.X.Y` -> `babe_amd.testing.X.Y`).  Build container only: /root/reference never travels, so the test is skipped
-wherever it is absent.  Constructors only - no GPU work."""
-import glob
+utils/setup.py:75-87, testing/blind_bwe_tester.py:214; INTEGRATION.md maps `testing.X.Y` -> `babe_amd.testing.X.Y`).
+The reference's conf/ tree is stored as data in tests/golden/config_surface.yaml.gz (tests/golden/make_config_golden.py):
+every conf/tester/*.yaml, the exp / network / diff_params files composed with them, and which sampler modules exist in the
+reference tree.  Constructors only - no GPU work."""
+import gzip
 import importlib
 import os
 
 import pytest
 
-REF = "/root/reference"
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "conf", "tester")), reason="reference tree absent")
+FIXTURE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "config_surface.yaml.gz")
 
 
-def compose(tester_yaml, exp="maestro44k_8s"):
+@pytest.fixture(scope="module")
+def conf(tmp_path_factory):
+    """The stored conf/ tree, read back through babe_amd.config.load_yaml (a YAML file, like the reference's own)."""
+    from babe_amd.config import load_yaml
+    p = tmp_path_factory.mktemp("conf") / "config_surface.yaml"
+    with gzip.open(FIXTURE, "rb") as f:
+        p.write_bytes(f.read())
+    return load_yaml(str(p))
+
+
+def compose(conf, tester, exp="maestro44k_8s"):
     """What hydra composes for test.py (conf/conf.yaml defaults + the tester/exp overrides of testing_blindbwe.sh)."""
-    from babe_amd.config import load_yaml, to_attr
-    return to_attr(dict(exp=load_yaml(f"{REF}/conf/exp/{exp}.yaml"), network=load_yaml(f"{REF}/conf/network/cqtdiff+.yaml"),
-                        diff_params=load_yaml(f"{REF}/conf/diff_params/edm.yaml"), tester=load_yaml(tester_yaml)))
+    from babe_amd.config import to_attr
+    return to_attr(dict(exp=conf.exp[exp], network=conf.network["cqtdiff+"], diff_params=conf.diff_params.edm,
+                        tester=conf.tester[tester]))
 
 
 class _Model:                      # the constructors never call the model
     CQTransform = None
 
 
-def survey():
+def survey(conf):
     from babe_amd.diff_params.edm import EDM
     res = dict(ok=[], notimpl=[], error=[], no_such_class=[])
-    for p in sorted(glob.glob(f"{REF}/conf/tester/*.yaml")):
-        name = os.path.basename(p)
-        args = compose(p)
+    assert len(conf.tester) == 87
+    for name in sorted(conf.tester):
+        args = compose(conf, name)
         mod, cls = args.tester.sampler_callable.rsplit(".", 1)
-        in_reference = os.path.exists(f"{REF}/{mod.replace('.', '/')}.py")
+        in_reference = mod in conf.reference_modules
         # YAMLs written for the `testing.blind_bwe.` package layout the reference no longer ships: same class one level up
         mod_here = mod.replace("testing.blind_bwe.", "testing.")
         try:
@@ -49,8 +59,8 @@ def survey():
     return res
 
 
-def test_every_tester_yaml_constructs_its_sampler():
-    r = survey()
+def test_every_tester_yaml_constructs_its_sampler(conf):
+    r = survey(conf)
     print({k: len(v) for k, v in r.items()})
     for k in ("notimpl", "error", "no_such_class"):
         for row in r[k]:
@@ -72,12 +82,12 @@ def test_every_tester_yaml_constructs_its_sampler():
     assert len([n for n, inref in r["ok"] if not inref]) == 15
 
 
-def test_default_args_restates_the_benchmark_yaml():
+def test_default_args_restates_the_benchmark_yaml(conf):
     """babe_amd.config.default_args() == conf/tester/blind_bwe_formal_3000_opt_2.yaml + conf/network/cqtdiff+.yaml +
     conf/exp/maestro44k_8s.yaml + conf/diff_params/edm.yaml on every key it carries (= every key the sampler, the EDM
     wrapper and the network read)."""
     from babe_amd.config import default_args
-    a = compose(f"{REF}/conf/tester/blind_bwe_formal_3000_opt_2.yaml")
+    a = compose(conf, "blind_bwe_formal_3000_opt_2.yaml")
     d = default_args()
     skipped = {"tester.posterior_sampling.stft_distance.logmag",        # read with .get(..., False); not in this YAML
                "network.attention_dict"}                                # attention is off (attention_layers all 0)
@@ -102,12 +112,12 @@ def test_default_args_restates_the_benchmark_yaml():
 
 @pytest.mark.parametrize("exp,tester", [("maestro22k_8s", "edm_DC_correction_4s"), ("CocoChorales_16k_8s", "blind_bwe_denoise_brass"),
                                         ("maestro44k_8s", "blind_bwe_formal_3000_opt_2")])
-def test_edm_overrides_follow_the_yaml(exp, tester):
+def test_edm_overrides_follow_the_yaml(conf, exp, tester):
     """update_diff_params (:52-60) copies tester.diff_params over the training values: check on the three configurations
     BASELINE.json names."""
     from babe_amd.diff_params.edm import EDM
     mod = {"edm_DC_correction_4s": ("babe_amd.testing.edm_sampler", "Sampler")}.get(tester, ("babe_amd.testing.blind_bwe_sampler", "BlindSampler"))
-    args = compose(f"{REF}/conf/tester/{tester}.yaml", exp)
+    args = compose(conf, f"{tester}.yaml", exp)
     e = EDM(args)
     getattr(importlib.import_module(mod[0]), mod[1])(_Model(), e, args, False)
     src = args.tester.diff_params

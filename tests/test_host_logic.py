@@ -215,6 +215,25 @@ def test_committed_bench_line_follows_the_contract():
     assert c["kind"] == "port" and c["cores"] >= 1
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files, whole below the limit, a fixed-seed sample above it."""
+    import bench
+    x = torch.randn(3, 1000, generator=torch.Generator().manual_seed(0))
+    fp = torch.randn(3, 10, dtype=torch.float64)
+    info = bench.dump_outputs(str(tmp_path / "all"), {"restored_audio": x, "filter_params": fp})
+    assert np.array_equal(np.load(tmp_path / "all" / "restored_audio.npy"), x.numpy())
+    assert np.load(tmp_path / "all" / "filter_params.npy").dtype == np.float64
+    assert info["restored_audio"] == {"shape": [3, 1000], "dtype": "float32", "sampled": False}
+    limit = 4096 * 2 + 4000
+    for d in ("s1", "s2"):
+        info = bench.dump_outputs(str(tmp_path / d), {"restored_audio": x, "filter_params": fp}, limit=limit)
+        assert info["restored_audio"]["sampled"] and info["restored_audio"]["shape"] == [3, 1000]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= limit
+    a = np.load(tmp_path / "s1" / "restored_audio.npy")
+    assert a.dtype == np.float32 and 0 < a.size < x.numel() and np.isin(a, x.numpy()).all()
+    assert np.array_equal(a, np.load(tmp_path / "s2" / "restored_audio.npy"))        # same sample every time
+
+
 def test_bench_gpus_flag_without_launcher_spawns_ranks_or_fails_loudly(monkeypatch):
     """`python bench.py --gpus N` with WORLD_SIZE unset must start N ranks (never silently run one); with a launcher whose
     WORLD_SIZE disagrees it must exit non-zero.  No GPU is touched: the spawn is intercepted."""
