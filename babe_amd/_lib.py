@@ -68,6 +68,11 @@ _SIGS = {
     "babe_gn_bwd_partial": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P],
     "babe_gn_bwd_apply": [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _L, _I, _F, _P],
     "babe_gn_bwd_apply_merge": [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _L, _I, _F, _P, _P, _F, _F],
+    "babe_gn_bwd_partial_nogelu": [_P, _P, _P, _P, _I, _I, _I, _L, _I, _P],
+    "babe_gn_bwd_apply_nogelu": [_P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _L, _I, _F, _P],
+    "babe_attn_buckets": [_P, _I, _I, _I],
+    "babe_attn_fwd": [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P],
+    "babe_attn_vjp": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "babe_resample": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _F, _P],
     "babe_resample_res": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _F, _P],
     "babe_axpby4d": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],

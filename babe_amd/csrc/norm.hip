@@ -311,7 +311,9 @@ __global__ __launch_bounds__(256) void scale_gelu_units_kernel(const float* __re
     }
 }
 
-// grid: (S, B*G).  A group is cg channels of hw elements, contiguous: n = cg*hw.
+// grid: (S, B*G).  A group is cg channels of hw elements, contiguous: n = cg*hw.  GELU = false: the VJP of GroupNorm * FiLM
+// alone (the attention branch's norm2, babe_gn_bwd_*_nogelu): du = da.
+template <bool GELU>
 __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dadu,
                                                              const float* __restrict__ scale,
                                                              double* __restrict__ part, int C, int G, long hw, int S) {
@@ -337,10 +339,12 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
             const float sc = scale[b * C + g * cg + cl];
             double sc_sum = 0;
             auto term = [&](const float4 xv, float4 dv) {
-                dv.x *= gelu_grad_f(xv.x * sc);
-                dv.y *= gelu_grad_f(xv.y * sc);
-                dv.z *= gelu_grad_f(xv.z * sc);
-                dv.w *= gelu_grad_f(xv.w * sc);
+                if (GELU) {
+                    dv.x *= gelu_grad_f(xv.x * sc);
+                    dv.y *= gelu_grad_f(xv.y * sc);
+                    dv.z *= gelu_grad_f(xv.z * sc);
+                    dv.w *= gelu_grad_f(xv.w * sc);
+                }
                 return (double)dv.x * xv.x + (double)dv.y * xv.y + (double)dv.z * xv.z + (double)dv.w * xv.w;
             };
             const long st = (long)blockDim.x * 4;
@@ -363,6 +367,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
 }
 
 // grid: (blocks, C, B)
+template <bool GELU>
 __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ da,
                                                            const float* __restrict__ gy,
                                                            const float* __restrict__ scale,
@@ -399,10 +404,12 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
         const float4 xv = x4[i];
         float4 dv = d4[i];
-        dv.x *= gelu_grad_f(xv.x * sc);          // du, recomputed instead of round-tripping it through HBM
-        dv.y *= gelu_grad_f(xv.y * sc);
-        dv.z *= gelu_grad_f(xv.z * sc);
-        dv.w *= gelu_grad_f(xv.w * sc);
+        if (GELU) {
+            dv.x *= gelu_grad_f(xv.x * sc);      // du, recomputed instead of round-tripping it through HBM
+            dv.y *= gelu_grad_f(xv.y * sc);
+            dv.z *= gelu_grad_f(xv.z * sc);
+            dv.w *= gelu_grad_f(xv.w * sc);
+        }
         float4 o;
         o.x = sc * dv.x - (xv.x - mean) * coef;
         o.y = sc * dv.y - (xv.y - mean) * coef;
@@ -528,13 +535,25 @@ extern "C" int babe_gn_bwd_partial(const float* x, const float* da, const float*
     BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_partial: hw=%ld C=%d G=%d unsupported", hw, C, G);
     if (abl_gn() & 2) return BABE_OK;
     BabeProfScope prof(BABE_SLOT_GN_BWD_PARTIAL, 8.0 * B * C * (double)hw, 0, 0, stream);
-    hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
+    hipLaunchKernelGGL(gn_bwd_partial_kernel<true>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
                        part, C, G, hw, S);
     BABE_LAUNCH_CHECK();
     return BABE_OK;
 }
 
-static int gn_bwd_apply_launch(const float* acc, float ca, float cb, const float* x, const float* da, const float* gy, const float* scale,
+/* babe_gn_bwd_partial of GroupNorm * FiLM without the GELU (forward a = x * scale; the time-attention branch's norm2) */
+extern "C" int babe_gn_bwd_partial_nogelu(const float* x, const float* da, const float* scale, double* part, int B, int C,
+                                          int G, long hw, int S, void* stream) {
+    BABE_CHECK_ARG(x && da && scale && part, "gn_bwd_partial_nogelu: null pointer");
+    BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_partial_nogelu: hw=%ld C=%d G=%d unsupported", hw, C, G);
+    BabeProfScope prof(BABE_SLOT_GN_BWD_PARTIAL, 8.0 * B * C * (double)hw, 0, 0, stream);
+    hipLaunchKernelGGL(gn_bwd_partial_kernel<false>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
+                       part, C, G, hw, S);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
+
+static int gn_bwd_apply_launch(bool gelu, const float* acc, float ca, float cb, const float* x, const float* da, const float* gy, const float* scale,
                                  const float* stats, const double* part, float* gx, float rbeta, int B, int C, int G,
                                  long hw, int S, float eps, void* stream) {
     BABE_CHECK_ARG(x && da && scale && stats && part && gx, "gn_bwd_apply: null pointer");
@@ -543,8 +562,12 @@ static int gn_bwd_apply_launch(const float* acc, float ca, float cb, const float
     int bx = cdiv(hw / 4, 256 * 4);
     if (bx < 1) bx = 1;
     if (bx > 64) bx = 64;
-    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, da, gy, scale, stats,
-                       part, gx, rbeta, C, G, hw, S, eps, acc, ca, cb);
+    if (gelu)
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, da, gy, scale, stats,
+                           part, gx, rbeta, C, G, hw, S, eps, acc, ca, cb);
+    else
+        hipLaunchKernelGGL(gn_bwd_apply_kernel<false>, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, da, gy, scale, stats,
+                           part, gx, rbeta, C, G, hw, S, eps, acc, ca, cb);
     BABE_LAUNCH_CHECK();
     return BABE_OK;
 }
@@ -552,7 +575,14 @@ static int gn_bwd_apply_launch(const float* acc, float ca, float cb, const float
 extern "C" int babe_gn_bwd_apply(const float* x, const float* da, const float* gy, const float* scale,
                                  const float* stats, const double* part, float* gx, float rbeta, int B, int C, int G,
                                  long hw, int S, float eps, void* stream) {
-    return gn_bwd_apply_launch(nullptr, 0.f, 0.f, x, da, gy, scale, stats, part, gx, rbeta, B, C, G, hw, S, eps, stream);
+    return gn_bwd_apply_launch(true, nullptr, 0.f, 0.f, x, da, gy, scale, stats, part, gx, rbeta, B, C, G, hw, S, eps, stream);
+}
+
+/* babe_gn_bwd_apply of GroupNorm * FiLM without the GELU (part from babe_gn_bwd_partial_nogelu) */
+extern "C" int babe_gn_bwd_apply_nogelu(const float* x, const float* da, const float* gy, const float* scale,
+                                        const float* stats, const double* part, float* gx, float rbeta, int B, int C, int G,
+                                        long hw, int S, float eps, void* stream) {
+    return gn_bwd_apply_launch(false, nullptr, 0.f, 0.f, x, da, gy, scale, stats, part, gx, rbeta, B, C, G, hw, S, eps, stream);
 }
 
 /* the same pass with the block's tail merged in: out = ca*acc + cb*(the gx babe_gn_bwd_apply would store); acc: dense [B][C][hw] */
@@ -560,6 +590,6 @@ extern "C" int babe_gn_bwd_apply_merge(const float* x, const float* da, const fl
                                  const float* stats, const double* part, float* gx, float rbeta, int B, int C, int G,
                                  long hw, int S, float eps, void* stream, const float* acc, float ca, float cb) {
     BABE_CHECK_ARG(acc && ((uintptr_t)acc & 15) == 0, "gn_bwd_apply_merge: acc must be a 16-byte aligned dense tensor");
-    return gn_bwd_apply_launch(acc, ca, cb, x, da, gy, scale, stats, part, gx, rbeta, B, C, G, hw, S, eps, stream);
+    return gn_bwd_apply_launch(true, acc, ca, cb, x, da, gy, scale, stats, part, gx, rbeta, B, C, G, hw, S, eps, stream);
 }
 

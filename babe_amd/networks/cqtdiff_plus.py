@@ -8,8 +8,8 @@ reference's checkpoints load with ``load_state_dict(state['ema'])``; ``net(x[B,L
 sampler code - which calls ``torch.autograd.grad`` through the model - runs on it unchanged.
 There is no CPU path: device must be a GPU and libbabe_hip.so must be present.
 
-Not implemented (disabled in every blind-BWE config, conf/network/cqtdiff+.yaml:8,23):
-frequency encodings (``use_fencoding``) and time-attention layers.
+Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run in fp32 on the Python sequencer
+(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them).  Not implemented: frequency encodings (``use_fencoding``).
 """
 import math
 import os
@@ -22,14 +22,26 @@ from ..cqt import CQT_nsgt
 from .unet_engine import UnetEngine
 
 
-def param_specs(Ns, num_dils, emb_dim=256, num_octs=7):
-    """[(key, shape, init)] for every parameter/buffer of the reference module, init in {'w','gate','ones','rff','buf'}."""
+def attention_options(attention_dict):
+    """(num_heads, bias_qkv, use_rel_pos, num_buckets, max_distance) of a reference attention_dict (its defaults where absent)."""
+    d = attention_dict or {}
+    g = (lambda k, v: d.get(k, v)) if hasattr(d, "get") else (lambda k, v: getattr(d, k, v))
+    return (int(g("num_heads", 8)), bool(g("bias_qkv", False)), bool(g("use_rel_pos", True)), int(g("rel_pos_num_buckets", 32)),
+            int(g("rel_pos_max_distance", 64)))
+
+
+def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, attention_dict=None, bins_per_oct=64):
+    """[(key, shape, init)] for every parameter/buffer of the reference module, init in {'w','gate','ones','rff','buf','randn'}.
+    attention_layers: one flag per octave plus the bottleneck (reference ResnetBlock attention_dict); the attention keys of a
+    block come after all of its other keys, so an attention-off net has exactly the keys (and init order) it always had."""
+    att = list(attention_layers or [0] * (num_octs + 1))
+    heads, bias_qkv, rel_pos, nbk, _ = attention_options(attention_dict)
     out = [("embedding.RFF_freq", (1, 32), "rff")]
     for i, (o, k) in enumerate([(128, 64), (256, 128), (emb_dim, 256)]):
         out += [(f"embedding.MLP.{i}.weight", (o, k), "w"), (f"embedding.MLP.{i}.bias", (o,), "zero")]
     out += [("downsamplerT.kernel", (8,), "buf"), ("upsamplerT.kernel", (8,), "buf")]
 
-    def block(p, dim, dim_out, nd, k, after):
+    def block(p, dim, dim_out, nd, k, after, Fdim=0):
         N = dim if after else dim_out
         r = []
         if after and N != dim_out:
@@ -43,31 +55,44 @@ def param_specs(Ns, num_dils, emb_dim=256, num_octs=7):
                   (p + f"affine.{d}.weight", (N, emb_dim), "w"), (p + f"affine.{d}.bias", (N,), "zero"),
                   (p + f"gate.{d}.weight", (N, emb_dim), "gate"), (p + f"gate.{d}.bias", (N,), "zero"),
                   (p + f"H.{d}.weight", (N, N, k[0], k[1]), "w")]
+        if Fdim:
+            hF = heads * Fdim
+            r += [(p + "norm2.gamma", (1, N, 1, 1), "ones"),
+                  (p + "affine2.weight", (N, emb_dim), "w"), (p + "affine2.bias", (N,), "zero"),
+                  (p + "gate2.weight", (N, emb_dim), "gate"), (p + "gate2.bias", (N,), "zero"),
+                  (p + "attn_block.qk.weight", (2 * hF, hF, 1), "w")]
+            if bias_qkv:
+                r.append((p + "attn_block.qk.bias", (2 * hF,), "zero"))
+            r += [(p + "attn_block.proj_in.weight", (heads, N, 1, 1), "w"), (p + "attn_block.proj_out.weight", (N, heads, 1, 1), "w")]
+            if rel_pos:
+                r.append((p + "attn_block.rel_pos.relative_attention_bias.weight", (nbk, heads), "randn"))
         return r
 
     for i in range(num_octs):
         din, dout = (Ns[0], Ns[0]) if i == 0 else (Ns[i - 1], Ns[i])
         out += block(f"downs.{i}.0.", 2, din, 1, (1, 1), False)
         out.append((f"downs.{i}.1.weight", (dout, 2, 5, 3), "w"))
-        out += block(f"downs.{i}.2.", din, dout, num_dils[i], (5, 3), False)
+        out += block(f"downs.{i}.2.", din, dout, num_dils[i], (5, 3), False, (i + 1) * bins_per_oct if att[i] else 0)
     out += block("middle.0.0.", Ns[-1], 2, 1, (1, 1), True)
-    out += block("middle.0.1.", Ns[-1], Ns[-1], num_dils[-1], (5, 3), False)
+    out += block("middle.0.1.", Ns[-1], Ns[-1], num_dils[-1], (5, 3), False, num_octs * bins_per_oct if att[-1] else 0)
     for ii, i in enumerate(range(num_octs - 1, -1, -1)):
         din, dout = (Ns[0] * 2, Ns[0]) if i == 0 else (Ns[i] * 2, Ns[i - 1])
         out += block(f"ups.{ii}.0.", dout, 2, 1, (1, 1), True)
-        out += block(f"ups.{ii}.1.", din, dout, num_dils[i], (5, 3), False)
+        out += block(f"ups.{ii}.1.", din, dout, num_dils[i], (5, 3), False, (i + 1) * bins_per_oct if att[i] else 0)
     return out
 
 
 CUBIC = [-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875]
 
 
-def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7):
+def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7, attention_layers=None, attention_dict=None):
     """Random weights with the reference's init rule (kaiming_uniform * sqrt(1/3); gates * 1e-7, cqtdiff+.py:599-600).
-    gate_scale=1 gives O(1) gates (an untrained net with 1e-7 gates has numerically dead residual branches)."""
+    gate_scale=1 gives O(1) gates (an untrained net with 1e-7 gates has numerically dead residual branches).
+    Attention layers (param_specs) draw after everything else of their block; the relative-position tables are N(0,1)
+    (nn.Embedding)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for key, shape, kind in param_specs(Ns, num_dils, emb_dim):
+    for key, shape, kind in param_specs(Ns, num_dils, emb_dim, attention_layers=attention_layers, attention_dict=attention_dict):
         if kind in ("w", "gate"):
             fan_in = int(np.prod(shape[1:]))
             w = math.sqrt(3.0 / fan_in) * (torch.rand(shape, generator=g) * 2 - 1)
@@ -78,6 +103,8 @@ def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7):
             sd[key] = torch.ones(shape)
         elif kind == "rff":
             sd[key] = 16 * torch.randn(shape, generator=g)
+        elif kind == "randn":
+            sd[key] = torch.randn(shape, generator=g)
         else:
             sd[key] = torch.tensor(CUBIC)
     return sd
@@ -121,8 +148,13 @@ class Unet_CQT_oct_with_attention(nn.Module):
         self.precision = precision or nw.get("precision", "f32")
         if nw.get("use_fencoding", False):
             raise NotImplementedError("use_fencoding=True (disabled in the blind-BWE configs)")
-        if any(nw.get("attention_layers", [0])):
-            raise NotImplementedError("attention layers (disabled in the blind-BWE configs)")
+        self.attention_layers = [int(bool(v)) for v in (nw.get("attention_layers", None) or [0] * 8)]
+        self.attention_dict = nw.get("attention_dict", None) if any(self.attention_layers) else None
+        if any(self.attention_layers):
+            if len(self.attention_layers) != 8:
+                raise ValueError(f"attention_layers needs one flag per octave plus the bottleneck (8), got {self.attention_layers}")
+            if self.precision != "f32":
+                raise NotImplementedError(f"attention layers run in fp32 only (precision={self.precision!r})")
         if not nw.get("use_norm", True):
             raise NotImplementedError("use_norm=False")
         self.Ns, self.num_dils = list(nw.Ns), list(nw.num_dils)
@@ -137,16 +169,23 @@ class Unet_CQT_oct_with_attention(nn.Module):
         win = ("kaiser", nw.cqt.beta) if nw.cqt.window == "kaiser" else nw.cqt.window
         self.CQTransform = CQT_nsgt(self.num_octs, self.bins_per_oct, mode="oct", window=win,
                                     fs=args.exp.sample_rate, audio_len=args.exp.audio_len, device=self.device)
-        for key, t in init_state_dict(self.Ns, self.num_dils, self.emb_dim).items():
+        for key, t in init_state_dict(self.Ns, self.num_dils, self.emb_dim, attention_layers=self.attention_layers,
+                                      attention_dict=self.attention_dict).items():
             _attach(self, key, t.to(self.device), is_buffer=key.endswith(".kernel"))
         self._engine = None
         self.register_load_state_dict_post_hook(lambda m, k: setattr(m, "_engine", None))
+
+    @property
+    def has_attention(self):
+        """True if any ResnetBlock carries a time-attention layer (the library-side sequencers do not support those)."""
+        return any(self.attention_layers)
 
     # ---------------------------------------------------------------- engine
     def engine(self):
         if self._engine is None:
             sd = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in self.state_dict().items()}
-            self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision)
+            self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision,
+                                      attention_layers=self.attention_layers, attention_dict=self.attention_dict)
             self._lanes = None
         return self._engine
 

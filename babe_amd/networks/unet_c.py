@@ -82,6 +82,9 @@ class CUnet:
     def __init__(self, eng, plan=None):
         _register()
         assert eng.precision == "f32", "the library-side engine sequences the fp32 network"
+        if getattr(eng, "has_attention", False):
+            raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
+                                      "(such networks run on the Python sequencer)")
         self.eng = eng
         self.n = eng.nocts
         L = lib()

@@ -24,10 +24,42 @@ USE_C = os.environ.get("BABE_UNET_C", "0") == "1"
 MERGE_TAIL = os.environ.get("BABE_MERGE_TAIL", "1") != "0"      # 0: N -> N block VJP stores gz and merges with axpby2 (A/B switch)
 
 
+class _Attn:
+    """The time-attention branch of a ResnetBlock (reference ResnetBlock.forward with attention_dict, TimeAttentionBlock):
+        a1  = proj_in(z * scale2)                        scale2 = norm2.gamma * (affine2(emb) + 1) / (std_g(z) + eps)  (no GELU)
+        qk  = Conv1d(a1.view(B, H*F, T))                 a (1,1) conv on the [B, H*F, 1, T] view
+        o   = attention(qk, V = a1)                      csrc/attention.hip
+        z'  = (gate2(emb) * proj_out(o) + z) / sqrt2
+    z is the block's proj_in output, z' feeds the dilated conv stack."""
+
+    def __init__(self, g, Fdim, N, film_index, opts):
+        self.H, self.bias_qkv, self.rel_pos, self.nbk, self.maxd = opts
+        self.F = Fdim
+        self.scale = float(Fdim) ** -0.5
+        self.gamma = g("norm2.gamma").reshape(-1).contiguous()
+        self.film_off = (film_index.add(g("affine2.weight"), g("affine2.bias")), film_index.add(g("gate2.weight"), g("gate2.bias")))
+        self.proj_in = ops.PackedConv(g("attn_block.proj_in.weight"))
+        self.proj_out = ops.PackedConv(g("attn_block.proj_out.weight"))
+        w = g("attn_block.qk.weight")
+        self.qk = ops.PackedConv(w.reshape(w.shape[0], w.shape[1], 1, 1))
+        self.qk_bias = g("attn_block.qk.bias").contiguous() if self.bias_qkv else None
+        self.emb = g("attn_block.rel_pos.relative_attention_bias.weight").contiguous() if self.rel_pos else None
+        self._buckets = {}
+
+    def buckets(self, T, dev):
+        if not self.rel_pos:
+            return None
+        t = self._buckets.get(T)
+        if t is None:
+            t = self._buckets[T] = ops.attn_buckets(T, self.nbk, self.maxd).to(dev)
+        return t
+
+
 class _Block:
     """One ResnetBlock: packed weights + per-call saved tensors."""
 
-    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32"):
+    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32", attn=None):
+        """attn: (Fdim, attention options) if the block carries a time-attention layer."""
         self.p = prefix
         self.nd = num_dils
         self.proj_after = proj_after
@@ -44,7 +76,9 @@ class _Block:
         for d in range(num_dils):
             self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias")),
                                   film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"))))
+        self.attn = _Attn(g, attn[0], self.N, film_index, attn[1]) if attn else None
         self.saved = None
+        self.attn_saved = None
 
     def dil(self, d):
         return 2 ** d if self.k53 else 1
@@ -70,9 +104,17 @@ class _FilmIndex:
 
 
 class UnetEngine:
-    def __init__(self, sd, Ns, num_dils, num_octs=7, bins_per_oct=64, precision="f32"):
+    def __init__(self, sd, Ns, num_dils, num_octs=7, bins_per_oct=64, precision="f32", attention_layers=None, attention_dict=None):
         """sd: dict of DEVICE fp32 tensors with the reference's state_dict key names.
-        precision: conv arithmetic, 'f32' (exact fp32 MFMA, the parity path), 'bf16x3' or 'bf16'."""
+        precision: conv arithmetic, 'f32' (exact fp32 MFMA, the parity path), 'bf16x3' or 'bf16'.
+        attention_layers / attention_dict: the reference's time-attention flags (one per octave + the bottleneck); fp32 only."""
+        from .cqtdiff_plus import attention_options
+        att = [int(bool(v)) for v in (attention_layers or [0] * (num_octs + 1))]
+        self.has_attention = any(att)
+        if self.has_attention and precision != "f32":
+            raise NotImplementedError(f"attention layers run in fp32 only (precision={precision!r})")
+        opts = attention_options(attention_dict)
+        A = lambda flag, Fd: (Fd, opts) if flag else None
         self.precision = precision
         self.Ns, self.num_dils, self.nocts, self.bpo = list(Ns), list(num_dils), num_octs, bins_per_oct
         self.dev = sd["embedding.RFF_freq"].device
@@ -83,14 +125,14 @@ class UnetEngine:
         for i in range(num_octs):
             self.init_blk.append(_Block(sd, f"downs.{i}.0.", 1, fi, precision=precision))
             self.pyr_conv.append(ops.PackedConv(sd[f"downs.{i}.1.weight"], precision))
-            self.main_blk.append(_Block(sd, f"downs.{i}.2.", num_dils[i], fi, precision=precision))
-        self.mid_blk = _Block(sd, "middle.0.1.", num_dils[-1], fi, precision=precision)
+            self.main_blk.append(_Block(sd, f"downs.{i}.2.", num_dils[i], fi, precision=precision, attn=A(att[i], (i + 1) * bins_per_oct)))
+        self.mid_blk = _Block(sd, "middle.0.1.", num_dils[-1], fi, precision=precision, attn=A(att[-1], num_octs * bins_per_oct))
         self.mid_out = _Block(sd, "middle.0.0.", 1, fi, proj_after=True, precision=precision)
         self.up_out, self.up_blk = [], []
         for i in range(num_octs):
             j = num_octs - 1 - i
             self.up_out.append(_Block(sd, f"ups.{i}.0.", 1, fi, proj_after=True, precision=precision))
-            self.up_blk.append(_Block(sd, f"ups.{i}.1.", num_dils[j], fi, precision=precision))
+            self.up_blk.append(_Block(sd, f"ups.{i}.1.", num_dils[j], fi, precision=precision, attn=A(att[j], (j + 1) * bins_per_oct)))
         fi.finalize()
         self.film_idx = fi
         self._scratch = {}
@@ -149,6 +191,8 @@ class UnetEngine:
         else:
             assert x2 is None
             z = x if x.is_contiguous() else ops.axpby(x, self.buf(B, N, Fq, T))
+        if blk.attn is not None:
+            z = self.attn_fwd(blk, z, film)
         saved = []
         # precision='bf16': the GELU output goes to the conv as bf16 units (half the bytes, both conv operands by LDS-DMA)
         units = blk.nd > 0 and ops.units_ok(blk.H[0], N, N, T) and z.is_contiguous()
@@ -184,6 +228,39 @@ class UnetEngine:
         blk.saved = saved
         return out
 
+    def attn_fwd(self, blk, z, film):
+        """z' = (gate2 * proj_out(attention(...)) + z)/sqrt2 (class _Attn); keeps what attn_vjp needs in blk.attn_saved."""
+        at = blk.attn
+        B, N, Fq, T = z.shape
+        H = at.H
+        assert Fq == at.F, f"attention layer built for F={at.F}, got F={Fq}"
+        stats, scale = ops.gn_scale(z, at.gamma, self._film(film, at.film_off[0], N))
+        a1 = ops.conv2d(z, at.proj_in, self.buf(B, H, Fq, T), in_scale=scale)          # proj_in(norm2(z) * (affine2 + 1))
+        qk = ops.conv2d(a1.view(B, H * Fq, 1, T), at.qk, self.buf(B, 2 * H * Fq, 1, T))
+        o = self.buf(B, H, Fq, T)
+        lse = self.buf(B, H, T)
+        ops.attn_fwd(qk, a1, o, lse, at.scale, qk_bias=at.qk_bias, bucket=at.buckets(T, self.dev), emb=at.emb)
+        gate = self._film(film, at.film_off[1], N).contiguous()
+        zn = ops.conv2d(o, at.proj_out, self.buf(B, N, Fq, T), res=z, oscale=gate, alpha=RS2, rbeta=RS2)
+        blk.attn_saved = (z, stats, scale, gate, a1, qk, o, lse)
+        return zn
+
+    def attn_vjp(self, blk, gz, c):
+        """gz <- gradient w.r.t. the attention branch's input z, given c*gz = gradient w.r.t. its output z' (in place)."""
+        at = blk.attn
+        z, stats, scale, gate, a1, qk, o, lse = blk.attn_saved
+        B, N, Fq, T = z.shape
+        H = at.H
+        do = ops.conv2d(gz, at.proj_out, self.buf(B, H, Fq, T), transpose=True, in_scale=gate, alpha=RS2 * c)
+        dqk = self.buf(B, 2 * H * Fq, 1, T)
+        dv = self.buf(B, H, Fq, T)
+        ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=at.buckets(T, self.dev), emb=at.emb)
+        da1 = ops.conv2d(dqk, at.qk, self.buf(B, H * Fq, 1, T), transpose=True, res=dv.view(B, H * Fq, 1, T), rbeta=1.0)
+        da0 = ops.conv2d(da1.view(B, H, Fq, T), at.proj_in, self.buf(B, N, Fq, T), transpose=True)
+        ops.gn_bwd_nogelu(z, da0, gz, scale, stats, gz, RS2 * c)
+        blk.attn_saved = None
+        return gz
+
     def block_vjp(self, blk, g_out, g_in, accumulate=False, consume=False):
         """g_in (+)= VJP of the block w.r.t. its (concatenated) input. g_out: [B,Cout,F,T] (may be strided).
         consume=True: g_out is a dense buffer owned by the caller that may be overwritten (saves a full copy)."""
@@ -191,7 +268,7 @@ class UnetEngine:
         N = blk.N
         beta = 1.0 if accumulate else 0.0
         if (blk.res_conv is None and blk.proj_out is None and blk.proj_in is None and not accumulate and blk.nd > 0
-                and g_out.is_contiguous() and ops.AXPBY2):
+                and g_out.is_contiguous() and ops.AXPBY2 and blk.attn is None):
             # N -> N block (every main block of the encoder, the middle block): the residual path's RS2*g_out and the main path's
             # c*gz are merged in ONE pass at the end (12 instead of 8 + 12 bytes per element).  For that g_out has to survive the
             # chain: the first layer's gn_bwd reads it as its residual input and writes into a buffer of its own (same traffic),
@@ -234,6 +311,9 @@ class UnetEngine:
             z, stats, scale, gate = blk.saved[d]
             fs = ops.conv2d(gz, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, N // 8))
             ops.gn_bwd(z, da, gz, scale, stats, gz, RS2, fused=fs)
+        if blk.attn is not None:
+            self.attn_vjp(blk, gz, c)
+            c = 1.0
         if blk.proj_in is not None:
             ops.conv2d(gz, blk.proj_in, g_in, transpose=True, res=g_in, alpha=c, rbeta=1.0)
         else:
@@ -245,7 +325,7 @@ class UnetEngine:
     def _c_engine(self):
         """The library-side sequencer for this engine STATE (networks/unet_c.py), or None: fp32 only, BABE_UNET_C=0 switches it
         off, the measurement hook's per-launch events work with either."""
-        if not USE_C or self.precision != "f32":
+        if not USE_C or self.precision != "f32" or self.has_attention:
             return None
         cu = self.__dict__.get("_cunet")
         if cu is None:

@@ -436,3 +436,54 @@ def rff(cnoise, freq):
     out = torch.empty(B, 2 * R, device=cnoise.device, dtype=torch.float32)
     check(lib().babe_rff(ptr(cnoise.contiguous()), ptr(freq.contiguous()), ptr(out), B, R, stream()), "rff")
     return out
+
+
+def gn_bwd_nogelu(x, da, gy, scale, stats, gx, rbeta, G=8, eps=1e-7):
+    """gx = rbeta*gy + input-VJP of a = x*scale (BiasFreeGroupNorm * FiLM, no GELU: the attention branch's norm2) for da."""
+    B, Cc, F, T = x.shape
+    assert x.is_contiguous() and da.is_contiguous() and gx.is_contiguous() and (gy is None or gy.is_contiguous())
+    n = (Cc // G) * F * T
+    S = _splits(n, B, G)
+    part = torch.empty(B * G * S, device=x.device, dtype=torch.float64)
+    L = lib()
+    check(L.babe_gn_bwd_partial_nogelu(ptr(x), ptr(da), ptr(scale), ptr(part), B, Cc, G, F * T, S, stream()), "gn_bwd_partial_nogelu")
+    check(L.babe_gn_bwd_apply_nogelu(ptr(x), ptr(da), ptr(gy), ptr(scale), ptr(stats), ptr(part), ptr(gx), rbeta, B, Cc, G, F * T,
+                                     S, eps, stream()), "gn_bwd_apply_nogelu")
+    return gx
+
+
+def attn_buckets(T, num_buckets=32, max_distance=64):
+    """int32 [2T-1] host tensor: T5 bidirectional bucket of every key-minus-query offset d = -(T-1) .. T-1 (entry d + T - 1),
+    bit-exact with the reference's float32 evaluation."""
+    out = torch.empty(2 * T - 1, dtype=torch.int32)
+    check(lib().babe_attn_buckets(C.c_void_p(out.data_ptr()), T, num_buckets, max_distance), "attn_buckets")
+    return out
+
+
+def attn_fwd(qk, a, out, lse, scale, qk_bias=None, bucket=None, emb=None):
+    """Time attention forward.  qk [B,2HF,T], a/out [B,H,F,T], lse [B,H,T], all dense; bucket int32 [2T-1] and emb [nb,H]
+    (device) or both None."""
+    B, H, F, T = a.shape
+    for t in (qk, a, out, lse):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert qk.numel() == B * 2 * H * F * T and out.shape == a.shape and lse.numel() == B * H * T
+    nb = 0
+    if bucket is not None:
+        assert bucket.dtype == torch.int32 and bucket.numel() == 2 * T - 1 and emb.is_contiguous() and emb.shape[1] == H
+        nb = emb.shape[0]
+    check(lib().babe_attn_fwd(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), B, H, F, T, scale,
+                              stream()), "attn_fwd")
+    return out, lse
+
+
+def attn_vjp(qk, a, out, lse, dout, dqk, dv, scale, qk_bias=None, bucket=None, emb=None):
+    """Input-VJP of attn_fwd for the gradient dout: writes dqk [B,2HF,T] and dv [B,H,F,T] (deterministic, no atomics)."""
+    B, H, F, T = a.shape
+    for t in (qk, a, out, lse, dout, dqk, dv):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert dout.shape == a.shape and dv.shape == a.shape and dqk.numel() == qk.numel()
+    nb = 0 if bucket is None else emb.shape[0]
+    D = torch.empty(B, H, T, device=a.device, dtype=torch.float32)
+    check(lib().babe_attn_vjp(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(D),
+                              ptr(dqk), ptr(dv), B, H, F, T, scale, stream()), "attn_vjp")
+    return dqk, dv

@@ -166,6 +166,13 @@ int babe_gn_bwd_apply_merge(const float* x, const float* da, const float* gy, co
                             const float* stats, const double* part, float* gx, float rbeta,
                             int B, int C, int G, long hw, int S, float eps, void* stream,
                             const float* acc, float ca, float cb);
+/* babe_gn_bwd_partial / babe_gn_bwd_apply for GroupNorm * FiLM WITHOUT the GELU (forward a = x * scale, the time-attention
+ * branch's norm2): du = da.  Same arguments and partial-sum layout. */
+int babe_gn_bwd_partial_nogelu(const float* x, const float* da, const float* scale, double* part, int B, int C, int G, long hw,
+                               int S, void* stream);
+int babe_gn_bwd_apply_nogelu(const float* x, const float* da, const float* gy, const float* scale, const float* stats,
+                             const double* part, float* gx, float rbeta, int B, int C, int G, long hw, int S, float eps,
+                             void* stream);
 
 /* ---- UpDownResample ('cubic', reflect): cqtdiff+.py:549-580 (conv1d / conv_transpose1d with a
  * dense diagonal weight) as a depth-wise 8-tap polyphase FIR.  mode: 0 down, 1 up, 2 down^T, 3 up^T.
@@ -499,6 +506,21 @@ int babe_dn_stft(const float* x, long x_bs, int L, float* X, int B, int nfft, in
 int babe_dn_istft(const float* P, float* frames_ws, float* y, long y_bs, int Lout, int B, int nfft, int hop, int frames,
                   const float* tw4096, void* stream);
 
+
+/* ---- time attention of the CQTDiff+ ResnetBlock (csrc/attention.hip), fp32 MFMA.  Per batch item b and head h (H heads of F
+ * features, F a multiple of 64 up to 448, any T >= 1), all tensors dense fp32 with T contiguous:
+ *   qk  [B][2HF][T]  Conv1d output: Q = rows h*2F + f, K = rows h*2F + F + f;  qk_bias [2HF] added to both, or NULL
+ *   a   [B][H][F][T] values V;  out [B][H][F][T];  lse [B][H][T] (log-sum-exp of each query's scores, for the VJP)
+ *   S[n][m] = (Q[:,n].K[:,m] + emb[bucket[m - n + T - 1]][h]) * scale;  out[:,n] = sum_m softmax_m(S[n]) V[:,m]
+ * bucket [2T-1] (babe_attn_buckets) and emb [num_buckets][H] (at most 64 buckets): both NULL without the relative bias. */
+int babe_attn_buckets(int* out, int T, int num_buckets, int max_distance);   /* host function: T5 bidirectional buckets */
+int babe_attn_fwd(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
+                  float* out, float* lse, int B, int H, int F, int T, float scale, void* stream);
+/* input-VJP of babe_attn_fwd for the gradient dout of out: dqk [B][2HF][T] (dQ and dK, the gradients w.r.t. the qk rows) and
+ * dv [B][H][F][T] (w.r.t. a through V), every element written once (no atomics: deterministic); D [B][H][T] is scratch. */
+int babe_attn_vjp(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
+                  const float* out, const float* lse, const float* dout, float* D, float* dqk, float* dv, int B, int H, int F,
+                  int T, float scale, void* stream);
 
 #ifdef __cplusplus
 }
