@@ -32,6 +32,14 @@ class ConvArgs(C.Structure):
     ]
 
 
+class CPackedConv(C.Structure):
+    """babe_packed_conv: the images of one ops.PackedConv (its `desc`), for babe_conv2d_auto and the UNet plan."""
+    _fields_ = [("Cout", C.c_int), ("Cin", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("nt", C.c_int), ("splits", C.c_int),
+                ("fwd", C.c_void_p), ("bwd", C.c_void_p), ("fwd_wino", C.c_void_p), ("bwd_wino", C.c_void_p),
+                ("fwd_wino4", C.c_void_p), ("bwd_wino4", C.c_void_p), ("fwd_wino45", C.c_void_p), ("bwd_wino45", C.c_void_p),
+                ("w_raw", C.c_void_p), ("fwd_wino85", C.c_void_p), ("bwd_wino85", C.c_void_p)]
+
+
 _P, _L, _I, _F = C.c_void_p, C.c_long, C.c_int, C.c_float
 _SIGS = {
     "babe_conv2d": [C.POINTER(ConvArgs), _P],
@@ -54,6 +62,7 @@ _SIGS = {
     "babe_conv2d_wino85_supported": [C.POINTER(ConvArgs)],
     "babe_conv2d_wino85_preferred": [C.POINTER(ConvArgs)],
     "babe_conv2d_wino85_stat_slots": [C.POINTER(ConvArgs)],
+    "babe_conv2d_auto": [C.POINTER(ConvArgs), C.POINTER(CPackedConv), _I, _P],
     "babe_conv_pack_weights_wino45": [_P, _P, _I, _I, _I, _I, _I, _P],
     "babe_conv_pack_weights_bf16": [_P, _P, _I, _I, _I, _I, _I, _I, _P],
     "babe_gn_partial": [_P, _P, _I, _I, _L, _I, _P],

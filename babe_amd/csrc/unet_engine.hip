@@ -16,10 +16,11 @@
 #include <cstdlib>
 #include <cstring>
 
-/* out = alpha*conv(in[,in2]; W)*oscale + rbeta*res with the kernel chosen by the library (what babe_amd/ops.py::conv2d did in
- * Python): few-output-channel vector kernel, nested Winograd F(2,5)xF(4,3) where its tiles are full, F(4,3), F(2,3), direct /
- * pipelined (1,1).  The caller fills every field of *a except w_packed, Cin, Cout, KH, KW (taken from pc and transpose).  A requested
- * fused reduction (a->stat_mode) is formed only by the F(4,5) kernels: on return a->stat_mode is 0 if it was NOT produced. */
+/* out = alpha*conv(in[,in2]; W)*oscale + rbeta*res with the kernel chosen by the library - the one place that choice is made
+ * (babe_amd/ops.py::conv2d calls this too): bf16 images, few-output-channel vector kernel, nested Winograd F(4,5)xF(4,3) /
+ * F(2,5)xF(4,3) where their tiles are full, F(4,3), F(2,3), direct / pipelined (1,1); an image left NULL takes its kernel out.
+ * The caller fills every field of *a except w_packed, Cin, Cout, KH, KW (taken from pc and transpose).  A requested fused
+ * reduction (a->stat_mode) is formed only by the F(4,5) kernels: on return a->stat_mode is 0 if it was NOT produced. */
 extern "C" int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, int transpose, void* stream) {
     BABE_CHECK_ARG(a && pc, "conv2d_auto: null arguments");
     a->Cin = transpose ? pc->Cout : pc->Cin;

@@ -7,15 +7,9 @@ import ctypes as C
 
 import torch
 
-from .._lib import check, lib, ptr, stream
+from .._lib import CPackedConv, check, lib, ptr, stream
 
 _I, _P = C.c_int, C.c_void_p
-
-
-class CPackedConv(C.Structure):
-    _fields_ = [("Cout", _I), ("Cin", _I), ("KH", _I), ("KW", _I), ("nt", _I), ("splits", _I), ("fwd", _P), ("bwd", _P),
-                ("fwd_wino", _P), ("bwd_wino", _P), ("fwd_wino4", _P), ("bwd_wino4", _P), ("fwd_wino45", _P), ("bwd_wino45", _P),
-                ("w_raw", _P), ("fwd_wino85", _P), ("bwd_wino85", _P)]
 
 
 class CBlock(C.Structure):
@@ -50,19 +44,13 @@ def _register():
     L.babe_unet_fwd.restype = _I
     L.babe_unet_vjp.argtypes = [_P, _P, C.POINTER(_P), C.POINTER(_P), _P]
     L.babe_unet_vjp.restype = _I
-    L.babe_conv2d_auto.restype = _I
     _registered = True
 
 
 def _pc(dst, pc):
-    """PackedConv -> CPackedConv (absent layer: Cout stays 0)."""
-    if pc is None:
-        return
-    g = lambda k: ptr(getattr(pc, k, None)) if getattr(pc, k, None) is not None else None
-    dst.Cout, dst.Cin, dst.KH, dst.KW, dst.nt, dst.splits = pc.Cout, pc.Cin, pc.KH, pc.KW, pc.nt, pc.splits
-    dst.fwd, dst.bwd = g("fwd"), g("bwd")
-    for k in ("fwd_wino", "bwd_wino", "fwd_wino4", "bwd_wino4", "fwd_wino45", "bwd_wino45", "w_raw", "fwd_wino85", "bwd_wino85"):
-        setattr(dst, k, g(k))
+    """PackedConv -> CPackedConv: a copy of its descriptor (absent layer: Cout stays 0)."""
+    if pc is not None:
+        C.memmove(C.addressof(dst), C.addressof(pc.desc), C.sizeof(CPackedConv))
 
 
 def _blk(dst, b):

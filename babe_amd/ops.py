@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvArgs, check, lib, ptr, stream
+from ._lib import ConvArgs, CPackedConv, check, lib, ptr, stream
 
 RSQRT2 = 1.0 / math.sqrt(2.0)
 
@@ -23,13 +23,14 @@ BF16_HBM_F32 = os.environ.get("BABE_BF16_HBM_F32", "1") != "0"
 # debug switch for the (5,3) fp32 convs: 0 = direct kernel only, 2 = Winograd F(2,3) only, 4 (default) = F(4,3) where the
 # problem qualifies, F(2,3) otherwise
 _W = os.environ.get("BABE_CONV_WINO", "4")
+# BABE_CONV_FEWCO=0: no raw-weight image, so the few-output-channel kernel never runs
 FEWCO = os.environ.get("BABE_CONV_FEWCO", "1") != "0"
 WINOGRAD = _W != "0"
 WINOGRAD4 = _W not in ("0", "2", "1")
 # nested Winograd F(2,5) x F(4,3) (csrc/conv_wino45.hip) for the (5,3) layers it supports; BABE_CONV_WINO45=0 switches it off
 WINOGRAD45 = WINOGRAD4 and os.environ.get("BABE_CONV_WINO45", "1") != "0"
 # nested Winograd F(4,5) x F(4,3) (csrc/conv_wino85.hip) for the (5,3) layers with 128-channel output tiles whose row quads are
-# at least 80 % full (babe_conv2d_wino85_preferred); BABE_CONV_F45=0 leaves them to the F(2,5) x F(4,3) kernel
+# at least 80 % full (the rule babe_conv2d_auto applies); BABE_CONV_F45=0 leaves them to the F(2,5) x F(4,3) kernel
 WINOGRAD85 = WINOGRAD45 and os.environ.get("BABE_CONV_F45", "1") != "0"
 
 
@@ -39,12 +40,18 @@ WINOGRAD85 = WINOGRAD45 and os.environ.get("BABE_CONV_F45", "1") != "0"
 _C11_NT = int(os.environ.get("BABE_CONV11_NT", "2"))
 
 
+_DESC_FIELDS = frozenset(k for k, _ in CPackedConv._fields_)
+
+
 class PackedConv:
     """Conv2d weights packed for babe_conv2d, forward and input-VJP (flipped/transposed) versions.
-    precision: 'f32' (exact fp32 MFMA), 'bf16' or 'bf16x3' (bf16 MFMA, see csrc/conv_bf16.hip)."""
+    precision: 'f32' (exact fp32 MFMA), 'bf16' or 'bf16x3' (bf16 MFMA, see csrc/conv_bf16.hip).
+    `desc` is the C descriptor (babe_packed_conv) babe_conv2d_auto picks the kernel from: every shape and image attribute is
+    written through to it, so assigning None to an image after construction takes its kernel out of the dispatch."""
 
     def __init__(self, w, precision="f32", nt=0):
         """nt: row tiles (x32 output channels) per workgroup of the direct kernel, 0 = default (include/babe_hip.h)."""
+        self.desc = CPackedConv()
         self.precision = precision
         self.nt = nt
         if nt == 0 and _C11_NT and w.shape[2] * w.shape[3] == 1 and ((w.shape[0] + 31) // 32) % _C11_NT == 0 \
@@ -64,6 +71,11 @@ class PackedConv:
             return
         self._init_f32(w)
 
+    def __setattr__(self, k, v):
+        object.__setattr__(self, k, v)
+        if k in _DESC_FIELDS:
+            setattr(self.desc, k, ptr(v) if torch.is_tensor(v) else v)
+
     def _init_bf16(self, w):
         assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
         w = w.contiguous()
@@ -82,7 +94,7 @@ class PackedConv:
         w = w.contiguous()
         self.Cout, self.Cin, self.KH, self.KW = w.shape
         # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip)
-        self.w_raw = w if (self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
+        self.w_raw = w if (FEWCO and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
         L = lib()
         nf = L.babe_conv_packed_size(self.Cout, self.Cin, self.KH, self.KW, 0)
         nb = L.babe_conv_packed_size(self.Cout, self.Cin, self.KH, self.KW, 1)
@@ -134,7 +146,8 @@ FUSE_GN_FWD = os.environ.get("BABE_FUSE_GN_FWD", "1") != "0"
 
 def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=None, oscale=None, alpha=1.0, rbeta=0.0,
            force_nested=False, force_f45=False, vjp_stat=None, fwd_stat=None):
-    """out = alpha*conv(x[,x2]; W)*oscale + rbeta*res   (transpose=True: input-VJP weights).
+    """out = alpha*conv(x[,x2]; W)*oscale + rbeta*res   (transpose=True: input-VJP weights), on the kernel the library picks
+    from pc.desc (babe_conv2d_auto).
     force_nested: take the nested-Winograd F(2,5) x F(4,3) kernel whenever it CAN run the problem (tests), not only when it is
     preferred; force_f45: the same for the F(4,5) x F(4,3) kernel.
     vjp_stat=(z, scale, cg): if the launch takes the F(4,5) kernel, its epilogue also forms the partial sums of the GroupNorm /
@@ -172,39 +185,33 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     a.alpha, a.rbeta = alpha, rbeta
     a.B, a.Cin, a.Cout, a.F, a.T = B, Cin, Cout, F, T
     a.KH, a.KW, a.dil = pc.KH, pc.KW, dil
-    if pc.splits:
-        check(lib().babe_conv2d_bf16(C.byref(a), ptr(wq), pc.splits, stream()), "conv2d_bf16")
-    elif FEWCO and getattr(pc, "w_raw", None) is not None and Cout <= 4 and lib().babe_conv2d_fewco_supported(C.byref(a)):
-        check(lib().babe_conv2d_fewco(C.byref(a), ptr(pc.w_raw), int(transpose), stream()), "conv2d_fewco")
-    elif getattr(pc, "bwd_wino85" if transpose else "fwd_wino85", None) is not None and x2 is None and not force_nested and (
-            lib().babe_conv2d_wino85_supported(C.byref(a)) if force_f45 else lib().babe_conv2d_wino85_preferred(C.byref(a))):
-        fused = None
-        if vjp_stat is not None and FUSE_GN:
-            z, scale, cg = vjp_stat
-            assert z.is_contiguous() and out.is_contiguous() and z.shape == out.shape and scale.is_contiguous()
-            a.stat_mode, a.stat_cg, a.stat_x, a.stat_scale = 2, cg, ptr(z), ptr(scale)
-            S = lib().babe_conv2d_wino85_stat_slots(C.byref(a))
-            part = torch.empty(B * (Cout // cg) * S, device=x.device, dtype=torch.float64)
-            a.stat_part = ptr(part)
-            fused = (part, S)
-        elif fwd_stat is not None and FUSE_GN_FWD and out.is_contiguous():
-            a.stat_mode, a.stat_cg = 1, fwd_stat
-            S = lib().babe_conv2d_wino85_stat_slots(C.byref(a))
-            part = torch.empty(B * (Cout // fwd_stat) * S * 2, device=x.device, dtype=torch.float64)
-            a.stat_part = ptr(part)
-            fused = (part, S)
-        check(lib().babe_conv2d_wino85(C.byref(a), ptr(pc.bwd_wino85 if transpose else pc.fwd_wino85), stream()), "conv2d_wino85")
-        return fused if (vjp_stat is not None or fwd_stat is not None) else out
-    elif getattr(pc, "bwd_wino45" if transpose else "fwd_wino45", None) is not None and (lib().babe_conv2d_wino45_supported(C.byref(a)) if force_nested
-                                                          else lib().babe_conv2d_wino45_preferred(C.byref(a))):
-        check(lib().babe_conv2d_wino45(C.byref(a), ptr(pc.bwd_wino45 if transpose else pc.fwd_wino45), stream()), "conv2d_wino45")
-    elif getattr(pc, "fwd_wino4", None) is not None and lib().babe_conv2d_wino4_supported(C.byref(a)):
-        check(lib().babe_conv2d_wino4(C.byref(a), ptr(pc.bwd_wino4 if transpose else pc.fwd_wino4), stream()), "conv2d_wino4")
-    elif getattr(pc, "fwd_wino", None) is not None and lib().babe_conv2d_wino_supported(C.byref(a)):
-        check(lib().babe_conv2d_wino(C.byref(a), ptr(pc.bwd_wino if transpose else pc.fwd_wino), stream()), "conv2d_wino")
+    L = lib()
+    w85 = getattr(pc, "bwd_wino85" if transpose else "fwd_wino85", None)
+    f45 = w85 is not None and x2 is None and not force_nested         # the F(4,5) kernel may run: it alone fuses the sums
+    if f45 and vjp_stat is not None and FUSE_GN:
+        z, scale, cg = vjp_stat
+        assert z.is_contiguous() and out.is_contiguous() and z.shape == out.shape and scale.is_contiguous()
+        a.stat_mode, a.stat_cg, a.stat_x, a.stat_scale = 2, cg, ptr(z), ptr(scale)
+    elif f45 and fwd_stat is not None and FUSE_GN_FWD and out.is_contiguous():
+        a.stat_mode, a.stat_cg = 1, fwd_stat
+    if a.stat_mode:                                                     # (mode 1: two sums per slot, mode 2: one)
+        S = L.babe_conv2d_wino85_stat_slots(C.byref(a))
+        part = torch.empty(B * (Cout // a.stat_cg) * S * (3 - a.stat_mode), device=x.device, dtype=torch.float64)
+        a.stat_part = ptr(part)
+    w45 = getattr(pc, "bwd_wino45" if transpose else "fwd_wino45", None)
+    if force_nested and w45 is not None and L.babe_conv2d_wino45_supported(C.byref(a)):
+        check(L.babe_conv2d_wino45(C.byref(a), ptr(w45), stream()), "conv2d_wino45")
+    elif force_f45 and f45 and L.babe_conv2d_wino85_supported(C.byref(a)):
+        check(L.babe_conv2d_wino85(C.byref(a), ptr(w85), stream()), "conv2d_wino85")
     else:
-        check(lib().babe_conv2d_nt(C.byref(a), pc.nt, stream()), "conv2d")
-    return None if (vjp_stat is not None or fwd_stat is not None) else out
+        desc = pc.desc
+        if force_nested:                                                # a forced nested conv never takes the F(4,5) kernel
+            desc = CPackedConv.from_buffer_copy(desc)
+            desc.fwd_wino85 = desc.bwd_wino85 = None
+        check(L.babe_conv2d_auto(C.byref(a), C.byref(desc), int(transpose), stream()), "conv2d_auto")
+    if vjp_stat is None and fwd_stat is None:
+        return out
+    return (part, S) if a.stat_mode else None
 
 
 def _splits(n, B, G):

@@ -105,8 +105,8 @@ long babe_conv_packed_size_wino4(int Cout, int Cin, int KH, int transpose_flip);
  * w_wino45 from babe_conv_pack_weights_wino45: [3 passes][ceil8(Cin)][ceil64(Cout)][12].  Needs KH x KW = 5 x 3,
  * T % 4 == 0, T >= 64, Cin % 16 == 0, Cout > 32, 16-byte aligned in/out/res rows, ONE source (no in2), views < 1 GiB. */
 /* Two tilings behind the one entry point: 64-channel tiles x 64 units (any Cout; a PADC variant skips the MFMAs of waves whose
- * channels are padding, e.g. Cout = 96) and, for Cout % 128 == 0, 128-channel tiles x 32 units that transform 16 input
- * channels at a time (BABE_CONV_WINO45W=0 turns the second one off).  Same arithmetic in the same order in both. */
+ * channels are padding, e.g. Cout = 96) and, for Cout % 128 == 0 or Cout % 96 == 0 where they fill at least as well, 128- / 96-
+ * channel tiles x 32 units that transform 16 input channels at a time.  Same arithmetic in the same order in both. */
 int babe_conv2d_wino45(const babe_conv_args* a, const float* w_wino45, void* stream);
 int babe_conv2d_wino45_supported(const babe_conv_args* a);   /* the kernel CAN run this problem */
 int babe_conv2d_wino45_preferred(const babe_conv_args* a);   /* ... and its tiles are full enough to beat the F(4,3) kernel */
@@ -196,7 +196,7 @@ int babe_resample_sinc(const float* x, long x_bs, float* out, long out_bs, int B
  * networks/cqtdiff+.py:79-88, 433-436): 3.0 multiplies per output instead of 4.5 (csrc/conv_wino85.hip).  Output-channel tiles of
  * 128, 96 or 64 (Cout a multiple of one of them), Cin % 16 == 0, one source; weights [2 passes][Cin/4][2][Cout/16][3][4][16][4] from
  * babe_conv_pack_weights_wino85.  _preferred: the problem is supported AND its row quads x time tiles are >= 80 % full - what
- * babe_conv2d_auto and babe_amd/ops.py::conv2d dispatch on (BABE_CONV_F45=0 in the Python host leaves everything to wino45). */
+ * babe_conv2d_auto dispatches on (BABE_CONV_F45=0 in the Python host packs no F(4,5) images: everything is left to wino45). */
 long babe_conv_packed_size_wino85(int Cout, int Cin, int transpose_flip);
 int babe_conv_pack_weights_wino85(const float* w, float* dst, int Cout, int Cin, int KH, int KW, int transpose_flip, void* stream);
 int babe_conv2d_wino85_supported(const babe_conv_args* a);

@@ -125,9 +125,13 @@ def test_conv2d_two_sources_and_views(ops):
     (1, 20, 44, 64, 12, 16, 8),       # source split inside an 8-channel slab, shortest rows (T = 16), taps skipped
 ])
 def test_conv2d_winograd_vs_direct_and_oracle(ops, B, C1, C2, Cout, Fq, T, dil):
-    """Winograd F(2,3)-along-time kernel (csrc/conv_wino.hip) against the direct kernel and the float64 oracle."""
+    """Winograd F(2,3)-along-time kernel (csrc/conv_wino.hip) against the direct kernel and the float64 oracle.  The launch
+    counters check that stripping an image (assigning None) really takes its kernel out of the dispatch."""
     import ctypes as C
-    from babe_amd._lib import lib
+    from babe_amd._lib import dispatch_counts, lib
+
+    def launched():
+        return {k for k, n in dispatch_counts().items() if n}
     g = torch.Generator().manual_seed(C1 + Cout + T)
     Cin = C1 + C2
     x = torch.randn(B, Cin, Fq, T, generator=g)
@@ -145,21 +149,28 @@ def test_conv2d_winograd_vs_direct_and_oracle(ops, B, C1, C2, Cout, Fq, T, dil):
         pc.fwd_wino45 = pc.bwd_wino45 = pc.fwd_wino85 = pc.bwd_wino85 = None
     xc = x.cuda()
     x1, x2 = (xc[:, :C1].contiguous(), xc[:, C1:].contiguous()) if C2 else (xc, None)
-    outs = []
+    outs, kinds = [], []
     for pc in (pcw, pcd, pc4):
         big = torch.zeros(B, Cout, 2 * Fq, T, device="cuda")
         o = big[:, :, Fq:, :]
         o.copy_(res.cuda())
+        dispatch_counts(reset=True)
         ops.conv2d(x1, pc, o, dil=dil, x2=x2, res=o, oscale=osc.cuda(), alpha=0.7, rbeta=0.3)
+        kinds.append(launched())
         assert float(big[:, :, :Fq, :].abs().max()) == 0.0
         outs.append(o.clone())
+    assert "conv53_wino4" not in kinds[0] and kinds[1] == {"conv53_direct"}, kinds
     assert rel(outs[0], ref) < 2e-6 and rel(outs[1], ref) < 2e-6 and rel(outs[2], ref) < 3e-6
     assert rel(outs[0], outs[1]) < 2e-6
     # input-VJP weights
     gy = torch.randn(B, Cout, Fq, T, generator=g).cuda()
     gx = [torch.empty(B, Cin, Fq, T, device="cuda") for _ in range(3)]
+    dispatch_counts(reset=True)
     ops.conv2d(gy, pcw, gx[0], dil=dil, transpose=True)
+    assert "conv53_wino4" not in launched()
+    dispatch_counts(reset=True)
     ops.conv2d(gy, pcd, gx[1], dil=dil, transpose=True)
+    assert launched() == {"conv53_direct"}
     ops.conv2d(gy, pc4, gx[2], dil=dil, transpose=True)
     xr = x.double().requires_grad_(True)
     gref, = torch.autograd.grad((UN.conv_same(xr, w.double(), dil) * gy.cpu().double()).sum(), xr)
@@ -603,7 +614,7 @@ def test_gelu_one_exponential_form_is_within_fp32_roundoff_of_erf(ops):
 
 
 def test_nested_winograd_wide_and_64_channel_tiles_are_bit_identical(ops):
-    """conv_wino45w (128- / 96-channel tiles, transform over 16 input channels at a time) and conv_wino45 (64-channel tiles)
+    """conv_wino45x (128- / 96-channel tiles, transform over 16 input channels at a time) and conv_wino45 (64-channel tiles)
     do the same arithmetic in the same order: a 128- (192-) channel conv on the wide kernel equals, bit for bit, the same
     conv done as two (three) 64-channel convs on the 64-channel-tile kernel."""
     from babe_amd._lib import dispatch_counts

@@ -10,7 +10,8 @@ for i in range(7):
     pc=ops.PackedConv(w)
     gy=torch.randn(B,N,F,T,device="cuda"); out=torch.empty(B,2,F,T,device="cuda")
     for mode in ("fewco","mfma"):
-        ops.FEWCO = mode=="fewco"
+        if mode == "mfma":
+            pc.w_raw = None          # no raw-weight image: the MFMA kernels take the conv
         for _ in range(2): ops.conv2d(gy,pc,out,transpose=True)
         torch.cuda.synchronize()
         e0,e1=torch.cuda.Event(enable_timing=True),torch.cuda.Event(enable_timing=True)
