@@ -32,6 +32,15 @@ class ConvArgs(C.Structure):
     ]
 
 
+class WgradArgs(C.Structure):
+    """babe_wgrad_args (include/babe_hip.h): operands of the conv weight gradient."""
+    _fields_ = [("x", C.c_void_p), ("x_bs", C.c_long), ("x_cs", C.c_long),
+                ("x2", C.c_void_p), ("x2_bs", C.c_long), ("x2_cs", C.c_long), ("cin_split", C.c_int),
+                ("g", C.c_void_p), ("g_bs", C.c_long), ("g_cs", C.c_long),
+                ("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("F", C.c_int), ("T", C.c_int),
+                ("KH", C.c_int), ("KW", C.c_int), ("dil", C.c_int)]
+
+
 class CPackedConv(C.Structure):
     """babe_packed_conv: the images of one ops.PackedConv (its `desc`), for babe_conv2d_auto and the UNet plan."""
     _fields_ = [("Cout", C.c_int), ("Cin", C.c_int), ("KH", C.c_int), ("KW", C.c_int), ("nt", C.c_int), ("splits", C.c_int),
@@ -88,6 +97,10 @@ _SIGS = {
     "babe_axpby2_4d": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],
     "babe_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "babe_rff": [_P, _P, _P, _I, _I, _P],
+    "babe_conv_wgrad_rows": [C.POINTER(WgradArgs), _P, _P, _F, _P, _P, _L, _F, _P, _L, _P],
+    "babe_rows_sum": [_P, _L, _I, _L, _P, _F, _P],
+    "babe_gn_param_grad": [_P, _P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P],
+    "babe_linear_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P],
 }
 
 
@@ -118,6 +131,10 @@ def lib():
             fn.argtypes = sig
             fn.restype = C.c_int
         L.babe_units_size.restype = C.c_long
+        L.babe_conv_wgrad_workspace.restype = C.c_long
+        L.babe_conv_wgrad_workspace.argtypes = [C.POINTER(WgradArgs)]
+        L.babe_linear_bwd_workspace.restype = C.c_long
+        L.babe_linear_bwd_workspace.argtypes = [_I, _I, _I]
         L.babe_prof_nslots.restype = C.c_int
         L.babe_prof_slot_name.restype = C.c_char_p
         L.babe_prof_slot_name.argtypes = [_I]

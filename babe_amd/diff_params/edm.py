@@ -43,6 +43,32 @@ class EDM:
     def sample_prior(self, shape, sigma):
         return torch.randn(shape) * sigma
 
+    # ---------------------------------------------------------------- training (reference edm.py:88-96, :161-206)
+    def sample_ptrain_safe(self, N):
+        """N training noise levels drawn like the sampling schedule: torch.rand(N) on the CPU generator."""
+        a = torch.rand(N)
+        return (self.sigma_max ** (1 / self.ro_train) + a * (self.sigma_min ** (1 / self.ro_train) -
+                                                              self.sigma_max ** (1 / self.ro_train))) ** self.ro_train
+
+    def prepare_train_preconditioning(self, x, sigma):
+        """(cin*(x+n), (x - cskip*(x+n))/cout, cnoise) with n = randn(x.shape) * sigma drawn on the CPU generator (as the
+        reference's sample_prior) and moved to x's device."""
+        noise = torch.randn(x.shape).to(sigma.device) * sigma
+        cskip, cout, cin, cnoise = self.cskip(sigma), self.cout(sigma), self.cin(sigma), self.cnoise(sigma)
+        target = (1 / cout) * (x - cskip * (x + noise))
+        return cin * (x + noise), target, cnoise
+
+    def loss_fn(self, net, x):
+        """(error**2 [B,L], sigma [B,1]) of the denoising objective for clean audio x [B,L]: draws sigma (torch.rand) then the
+        noise (torch.randn), like the reference.  The reference's DC correction reads args.net.use_cqt_DC_correction - a key no
+        configuration defines (they have exp.use_cqt_DC_correction) - inside a bare except, so it never runs; it is left out
+        here for the same result.  A-weighting is refused at construction."""
+        sigma = self.sample_ptrain_safe(x.shape[0]).unsqueeze(-1).to(x.device)
+        inp, target, cnoise = self.prepare_train_preconditioning(x, sigma)
+        estimate = net(inp, cnoise)
+        error = estimate - target
+        return error ** 2, sigma
+
     def cskip(self, sigma):
         return self.sigma_data ** 2 * (sigma ** 2 + self.sigma_data ** 2) ** -1
 

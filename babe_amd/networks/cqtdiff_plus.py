@@ -110,6 +110,16 @@ def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7, attentio
     return sd
 
 
+# The reference trains every parameter except embedding.RFF_freq (requires_grad=False, networks/cqtdiff+.py:176); the resampler
+# kernels are buffers.
+NOT_TRAINABLE = ("embedding.RFF_freq",)
+
+
+def is_trainable(key):
+    """True for the parameters the reference's optimizer updates."""
+    return key not in NOT_TRAINABLE
+
+
 class _Node(nn.Module):
     """Anonymous container so that parameter paths reproduce the reference's dotted names."""
 
@@ -128,14 +138,23 @@ def _attach(root, key, tensor, is_buffer):
 
 
 class _UnetFn(torch.autograd.Function):
+    """net(x, cnoise) with the hand-wired HIP backward.  Extra inputs: the parameters that require grad (net._grad_keys order);
+    their gradients are formed only if autograd asks for one of them."""
+
     @staticmethod
-    def forward(ctx, x, cnoise, net):
+    def forward(ctx, x, cnoise, net, *params):
         ctx.net = net
-        return net.fwd_nograd(x, cnoise)
+        ctx.train = any(ctx.needs_input_grad[3:])
+        if ctx.train:
+            ctx.keys = net._grad_keys
+        return net.fwd_nograd(x, cnoise, train=ctx.train)
 
     @staticmethod
     def backward(ctx, g):
-        return ctx.net.vjp(g.contiguous()), None, None
+        if not ctx.train:
+            return ctx.net.vjp(g.contiguous()), None, None
+        gx, grads = ctx.net._vjp_train(g.contiguous())
+        return (gx if ctx.needs_input_grad[0] else None, None, None) + tuple(grads[k] for k in ctx.keys)
 
 
 class Unet_CQT_oct_with_attention(nn.Module):
@@ -173,7 +192,15 @@ class Unet_CQT_oct_with_attention(nn.Module):
                                       attention_dict=self.attention_dict).items():
             _attach(self, key, t.to(self.device), is_buffer=key.endswith(".kernel"))
         self._engine = None
-        self.register_load_state_dict_post_hook(lambda m, k: setattr(m, "_engine", None))
+        self.register_load_state_dict_post_hook(lambda m, k: m._reset_params())
+        self._reset_params()
+
+    def _reset_params(self):
+        """Drop the engine and re-read the Parameter objects (load_state_dict(assign=True) and _apply may replace them): the
+        version check and the parameters handed to autograd are always the module's current ones."""
+        self._engine = None
+        self._params = list(self.named_parameters())
+        self._versions = None
 
     @property
     def has_attention(self):
@@ -181,13 +208,54 @@ class Unet_CQT_oct_with_attention(nn.Module):
         return any(self.attention_layers)
 
     # ---------------------------------------------------------------- engine
+    def _engine_sd(self):
+        return {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in self.state_dict().items()}
+
     def engine(self):
         if self._engine is None:
-            sd = {k: v.detach().to(self.device, torch.float32).contiguous() for k, v in self.state_dict().items()}
+            sd = self._engine_sd()
             self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision,
                                       attention_layers=self.attention_layers, attention_dict=self.attention_dict)
             self._lanes = None
+            self._versions = self._param_versions()
         return self._engine
+
+    def _param_versions(self):
+        return tuple(p._version for _, p in self._params)
+
+    def _refresh_weights(self):
+        """The engine packs the weights once; a parameter changed in place since then (optimizer.step(), a no_grad copy_)
+        shows as a new _version: repack every conv IN PLACE (lane clones and the library-side plan keep their pointers) and
+        rebuild the concatenated FiLM matrix.  Costs nothing on the GPU while the parameters stay as they are."""
+        if self._engine is None:
+            return
+        v = self._param_versions()
+        if v != self._versions:
+            self._engine.refresh(self._engine_sd())
+            self._versions = v
+
+    # ---------------------------------------------------------------- training
+    def set_trainable(self, flag=True):
+        """requires_grad on exactly the reference's trainable set (is_trainable), so torch.optim.Adam(net.parameters()) updates
+        what the reference's Adam updates.  Parameter gradients run in fp32 on attention-free networks (others raise on the
+        forward)."""
+        for k, p in self.named_parameters():
+            p.requires_grad_(bool(flag) and is_trainable(k))
+        return self
+
+    def _grad_params(self):
+        """[(key, parameter)] that require grad, in named_parameters order; raises where parameter gradients are not built."""
+        ps = [(k, p) for k, p in self._params if p.requires_grad]
+        if not ps:
+            return ps
+        if self.has_attention:
+            raise NotImplementedError("parameter gradients of networks with attention layers are not implemented")
+        if self.precision != "f32":
+            raise NotImplementedError(f"parameter gradients run in fp32 only (precision={self.precision!r})")
+        bad = [k for k, _ in ps if not is_trainable(k)]
+        if bad:
+            raise NotImplementedError(f"{bad} is not trainable (fixed in the reference); use set_trainable()")
+        return ps
 
     # Batch items are independent, so they run on separate HIP streams (one engine state each, shared packed weights):
     # the HBM-bound passes of one item (GroupNorm / GELU / resampling, (1,1) convs) then overlap the MFMA-bound (5,3)
@@ -231,7 +299,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._engine = None
-        return super()._apply(fn, *a, **k)
+        out = super()._apply(fn, *a, **k)
+        self._reset_params()
+        return out
 
     # ---------------------------------------------------------------- raw (no autograd) interface
     supports_lanes = True
@@ -261,7 +331,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
     def lane_engine(self, lane):
         """Engine state number `lane` (saved activations + scratch of its own over the shared packed weights): a caller that
         pipelines independent clips on its own streams (BlindSampler) passes lane=k to fwd_nograd / vjp, which then run
-        entirely on the CALLER's current stream with that state instead of forking streams themselves."""
+        entirely on the CALLER's current stream with that state instead of forking streams themselves.  Also the entry of the
+        library-side evaluation (testing/eval_c.py), so the weight refresh runs here too."""
+        self._refresh_weights()
         eng = self.engine()
         if getattr(self, "_lane_engines", None) is None or self._lane_engines[0] is not eng:
             self._lane_engines = [eng]
@@ -269,11 +341,51 @@ class Unet_CQT_oct_with_attention(nn.Module):
             self._lane_engines.append(eng.clone_state())
         return self._lane_engines[lane]
 
-    def fwd_nograd(self, x, cnoise, lane=None):
-        """x [B,L], cnoise [B,1] -> [B,L]; keeps what vjp() needs until the next call (of the same lane)."""
+    def fwd_nograd(self, x, cnoise, lane=None, train=False):
+        """x [B,L], cnoise [B,1] -> [B,L]; keeps what vjp() needs until the next call (of the same lane).
+        train=True: also what the parameter gradients need (_vjp_train); fp32, attention-free, the module's own lanes."""
         assert x.device == self.device, f"input on {x.device}, network on {self.device}"
         with torch.cuda.device(self.device):       # every launch below goes to THIS device's current stream
+            if lane is None:
+                self._refresh_weights()            # (the lane path refreshes in lane_engine)
+            if train:
+                assert lane is None
+                return self._fwd_train(x, cnoise)
             return self._fwd_nograd(x, cnoise, lane)
+
+    def _fwd_train(self, x, cnoise):
+        eng = self.engine()
+        x = x.detach().contiguous().float()
+        assert x.shape[-1] == self.CQTransform.Ls, "input length must equal exp.audio_len (the CQT is built for it)"
+        keep = []
+        film = eng.embed(cnoise.detach().reshape(-1, 1).contiguous().float(), keep=keep)
+        co = self.CQTransform.fwd_planar(x)
+        B = x.shape[0]
+        self._train_keep = keep
+        if self._get_lanes(B) is None:
+            outs = eng.forward(co, film, train=True)
+        else:
+            parts = self._run_lanes(B, lambda e, b0, b1: e.forward([c[b0:b1] for c in co], film[b0:b1], train=True))
+            outs = [torch.cat([p[j] for p in parts], 0) for j in range(len(co))]
+        return self.CQTransform.bwd_planar(outs)
+
+    def _vjp_train(self, g):
+        """(gradient w.r.t. x, {key: gradient of every parameter}) of <net(x), g> for the last fwd_nograd(train=True)."""
+        from .unet_engine import ParamGrads
+        with torch.cuda.device(self.device):
+            eng = self.engine()
+            B = g.shape[0]
+            pg = ParamGrads.new(eng, B)
+            gouts = self.CQTransform.bwd_adjoint(g.contiguous())
+            if self._get_lanes(B) is None:
+                gC = eng.vjp(gouts, pg=pg)
+            else:
+                parts = self._run_lanes(B, lambda e, b0, b1: e.vjp([c[b0:b1] for c in gouts], pg=pg.lane(b0, b1)))
+                gC = [torch.cat([p[j] for p in parts], 0) for j in range(len(gouts))]
+            gx = self.CQTransform.fwd_adjoint(gC)
+            grads = eng.param_grads(pg, self._train_keep)
+            self._train_keep = None
+            return gx, grads
 
     def _fwd_nograd(self, x, cnoise, lane=None):
         if lane is not None:
@@ -317,6 +429,11 @@ class Unet_CQT_oct_with_attention(nn.Module):
 
     # ---------------------------------------------------------------- nn.Module call
     def forward(self, inputs, sigma):
-        if torch.is_grad_enabled() and inputs.requires_grad:
-            return _UnetFn.apply(inputs, sigma, self)
+        if torch.is_grad_enabled():
+            ps = self._grad_params()
+            if ps:
+                self._grad_keys = [k for k, _ in ps]
+                return _UnetFn.apply(inputs, sigma, self, *[p for _, p in ps])
+            if inputs.requires_grad:
+                return _UnetFn.apply(inputs, sigma, self)
         return self.fwd_nograd(inputs, sigma)

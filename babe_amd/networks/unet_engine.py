@@ -69,16 +69,18 @@ class _Block:
         self.res_conv = PC(g("res_conv.weight")) if g("res_conv.weight") is not None else None
         self.proj_out = PC(g("proj_out.weight")) if (proj_after and g("proj_out.weight") is not None) else None
         self.H = [PC(g(f"H.{d}.weight")) for d in range(num_dils)]
+        self.Hw = [g(f"H.{d}.weight").contiguous() for d in range(num_dils)]       # raw weights (the FiLM gate gradient)
         self.gamma = [g(f"norm.{d}.gamma").reshape(-1).contiguous() for d in range(num_dils)]
         self.N = self.H[0].Cout
         self.k53 = self.H[0].KH > 1
         self.film_off = []            # (affine offset, gate offset) into the batched FiLM output
         for d in range(num_dils):
-            self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias")),
-                                  film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"))))
+            self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias"), prefix + f"affine.{d}"),
+                                  film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"), prefix + f"gate.{d}")))
         self.attn = _Attn(g, attn[0], self.N, film_index, attn[1]) if attn else None
         self.saved = None
         self.attn_saved = None
+        self.inp = self.zpo = None    # training: the block's input(s) and proj_out's input, for the weight gradients
 
     def dil(self, d):
         return 2 ** d if self.k53 else 1
@@ -89,18 +91,52 @@ class _FilmIndex:
 
     def __init__(self):
         self.W, self.b, self.J = [], [], 0
+        self.keys = []                 # (state_dict prefix of the Linear, row offset, rows)
 
-    def add(self, W, b):
+    def add(self, W, b, key=None):
         off = self.J
         self.W.append(W)
         self.b.append(b)
         self.J += W.shape[0]
+        self.keys.append((key, off, W.shape[0]))
         return off
 
     def finalize(self):
         self.Wcat = torch.cat(self.W, 0).contiguous()
         self.bcat = torch.cat(self.b, 0).contiguous()
+        self._parts = (self.W, self.b)
         self.W = self.b = None
+
+    def refresh(self):
+        """Rebuild Wcat / bcat in place from the (parameter-aliasing) pieces after an optimizer step."""
+        torch.cat(self._parts[0], 0, out=self.Wcat)
+        torch.cat(self._parts[1], 0, out=self.bcat)
+
+
+class ParamGrads:
+    """Per-call parameter-gradient buffers of a training step, shared by the clip lanes: every lane writes only its own batch
+    rows, and one fixed-order reduction over the rows after the join (UnetEngine.param_grads) makes the result independent of
+    the lane count.  rows [B, n]: per-row weight gradients of every conv and GroupNorm gamma, flat (layout: key -> (offset,
+    shape)); dfilm [B, J]: gradient w.r.t. the concatenated FiLM Linear output."""
+
+    def __init__(self, layout, rows, dfilm):
+        self.layout, self.rows, self.dfilm = layout, rows, dfilm
+
+    @classmethod
+    def new(cls, eng, B):
+        rows = torch.zeros(B, eng.grad_numel, device=eng.dev, dtype=torch.float32)
+        dfilm = torch.zeros(B, eng.film_idx.J, device=eng.dev, dtype=torch.float32)
+        return cls(eng.grad_layout, rows, dfilm)
+
+    def lane(self, b0, b1):
+        return ParamGrads(self.layout, self.rows[b0:b1], self.dfilm[b0:b1])
+
+    def row(self, key):
+        off, shape = self.layout[key]
+        n = 1
+        for v in shape:
+            n *= v
+        return self.rows[:, off:off + n]
 
 
 class UnetEngine:
@@ -136,6 +172,42 @@ class UnetEngine:
         fi.finalize()
         self.film_idx = fi
         self._scratch = {}
+        self._train = False
+        # training: flat per-row layout of the conv weights and GroupNorm gammas (ParamGrads), the convs the refresh repacks
+        self.grad_layout, self.grad_numel, self.packs = {}, 0, []
+        for blk in self.blocks():
+            for name in ("proj_in", "res_conv", "proj_out"):
+                if getattr(blk, name) is not None:
+                    self._add_grad(blk.p + name + ".weight", getattr(blk, name))
+            for d in range(blk.nd):
+                self._add_grad(blk.p + f"H.{d}.weight", blk.H[d])
+                self._add_grad(blk.p + f"norm.{d}.gamma", None, (1, blk.N, 1, 1))
+            if blk.attn is not None:
+                at = blk.attn
+                self.packs += [(blk.p + "attn_block.proj_in.weight", at.proj_in), (blk.p + "attn_block.proj_out.weight", at.proj_out),
+                               (blk.p + "attn_block.qk.weight", at.qk)]
+        for i, pc in enumerate(self.pyr_conv):
+            self._add_grad(f"downs.{i}.1.weight", pc)
+
+    def _add_grad(self, key, pc, shape=None):
+        if pc is not None:
+            shape = (pc.Cout, pc.Cin, pc.KH, pc.KW)
+            self.packs.append((key, pc))
+        n = 1
+        for v in shape:
+            n *= v
+        self.grad_layout[key] = (self.grad_numel, tuple(shape))
+        self.grad_numel += n
+
+    def blocks(self):
+        return self.init_blk + self.main_blk + [self.mid_blk, self.mid_out] + self.up_out + self.up_blk
+
+    def refresh(self, sd):
+        """After an optimizer step: repack every conv IN PLACE from sd (the current parameters) and rebuild Wcat / bcat.  The
+        GroupNorm gammas and the embedding MLP are views of the parameters already."""
+        for key, pc in self.packs:
+            pc.repack(sd[key].reshape(pc.Cout, pc.Cin, pc.KH, pc.KW))
+        self.film_idx.refresh()
 
     def clone_state(self):
         """A second engine over the SAME packed weights with its own per-call state (saved activations, scratch), so that
@@ -171,11 +243,16 @@ class UnetEngine:
             self._scratch[name] = t
         return t[:numel]
 
-    def embed(self, cnoise):
-        """cnoise [B,1] -> FiLM vectors for every layer [B, J] (RFF_MLP_Block + all affine/gate Linears)."""
+    def embed(self, cnoise, keep=None):
+        """cnoise [B,1] -> FiLM vectors for every layer [B, J] (RFF_MLP_Block + all affine/gate Linears).
+        keep: a list that receives the MLP's input and layer outputs (training)."""
         h = ops.rff(cnoise, self.rff_freq)
+        if keep is not None:
+            keep.append(h)
         for W, b in self.emb_W:
             h = ops.linear(h, W, b, relu=True)
+            if keep is not None:
+                keep.append(h)
         return ops.linear(h, self.film_idx.Wcat, self.film_idx.bcat, relu=False)
 
     def _film(self, film, off, N):
@@ -186,6 +263,8 @@ class UnetEngine:
         """out <- ResnetBlock(cat(x,x2)); out may be a strided frequency sub-view."""
         B, _, Fq, T = x.shape
         N = blk.N
+        if self._train:
+            blk.inp = (x, x2)
         if blk.proj_in is not None:
             z = ops.conv2d(x, blk.proj_in, self.buf(B, N, Fq, T), x2=x2)
         else:
@@ -220,6 +299,8 @@ class UnetEngine:
             saved.append((z, stats, scale, gate))
             z = znew
         if blk.proj_out is not None:
+            if self._train:
+                blk.zpo = z
             z = ops.conv2d(z, blk.proj_out, self.buf(B, blk.proj_out.Cout, Fq, T))
         if blk.res_conv is not None:
             ops.conv2d(x, blk.res_conv, out, x2=x2, res=z, alpha=RS2, rbeta=RS2)
@@ -261,12 +342,77 @@ class UnetEngine:
         blk.attn_saved = None
         return gz
 
-    def block_vjp(self, blk, g_out, g_in, accumulate=False, consume=False):
+    # ------------------------------------------------------------------ training: parameter gradients
+    def _wg(self, pg, key, x, g, pc, alpha, x2=None, dil=1, **kw):
+        """pg.row(key) <- per-row weight gradient of conv `pc` (input cat(x, x2), output gradient alpha * oscale * g)."""
+        n = ops.conv_wgrad_workspace(x, g, pc.KH, pc.KW, dil, x2)
+        ops.conv_wgrad_rows(x, g, pc.KH, pc.KW, pg.row(key), dil=dil, x2=x2, alpha=alpha, ws=self.scratch("wg", n), **kw)
+
+    def _layer_wgrad(self, pg, blk, d, G, c):
+        """Dilation layer d, znew = rs2*(gate*H(a) + z), a = gelu(z*scale) recomputed into the "a" scratch (the transposed conv
+        overwrites it with da next): H's weight gradient and the gate gradient, for the output gradient c*G."""
+        z, stats, scale, gate = blk.saved[d]
+        B, N, Fq, T = z.shape
+        a = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
+        ops.scale_gelu(z, scale, a)
+        goff = blk.film_off[d][1]
+        self._wg(pg, blk.p + f"H.{d}.weight", a, G, blk.H[d], c * RS2, dil=blk.dil(d), oscale=gate, w=blk.Hw[d],
+                 dgate=pg.dfilm[:, goff:goff + N], galpha=c * RS2)
+
+    def _layer_gn_grad(self, pg, blk, d, da, c):
+        """gamma / affine gradients of layer d from da = (dL/da)/c, the transposed conv's output."""
+        z, stats, scale, gate = blk.saved[d]
+        N = blk.N
+        aoff = blk.film_off[d][0]
+        ops.gn_param_grad(z, da, scale, stats, blk.gamma[d], self._film(self._film_saved, aoff, N), pg.row(blk.p + f"norm.{d}.gamma"),
+                          pg.dfilm[:, aoff:aoff + N], cs=c)
+
+    def _block_out_wgrad(self, pg, blk, g_out):
+        """res_conv / proj_out weight gradients (both see rs2*g_out): before the VJP consumes g_out."""
+        x, x2 = blk.inp
+        if blk.res_conv is not None:
+            self._wg(pg, blk.p + "res_conv.weight", x, g_out, blk.res_conv, RS2, x2=x2)
+        if blk.proj_out is not None:
+            self._wg(pg, blk.p + "proj_out.weight", blk.zpo, g_out, blk.proj_out, RS2)
+
+    def param_grads(self, pg, emb_keep):
+        """After the (joined) reverse sweep: {state_dict key: gradient} of every trainable parameter.  One fixed-order sum over
+        the batch rows of pg.rows, then the FiLM Linear and embedding-MLP backward from pg.dfilm (emb_keep: embed(keep=))."""
+        flat = ops.rows_sum(pg.rows, self.buf(self.grad_numel))
+        grads = {}
+        for key, (off, shape) in self.grad_layout.items():
+            n = 1
+            for v in shape:
+                n *= v
+            grads[key] = flat[off:off + n].view(shape)
+        h0, h1, h2, h3 = emb_keep
+        B = h3.shape[0]
+        fi = self.film_idx
+        dWcat, dbcat = self.buf(fi.J, h3.shape[1]), self.buf(fi.J)
+        dh = self.buf(B, h3.shape[1])
+        ops.linear_bwd(pg.dfilm, h3, fi.Wcat, dWcat, dbcat, dx=dh)
+        for key, off, n in fi.keys:
+            grads[key + ".weight"] = dWcat[off:off + n]
+            grads[key + ".bias"] = dbcat[off:off + n]
+        hs = [h0, h1, h2, h3]
+        for i in (2, 1, 0):
+            W, _ = self.emb_W[i]
+            dW, db = self.buf(*W.shape), self.buf(W.shape[0])
+            dx = self.buf(B, W.shape[1]) if i > 0 else None
+            ops.linear_bwd(dh, hs[i], W, dW, db, dx=dx, y=hs[i + 1])
+            grads[f"embedding.MLP.{i}.weight"], grads[f"embedding.MLP.{i}.bias"] = dW, db
+            dh = dx
+        return grads
+
+    def block_vjp(self, blk, g_out, g_in, accumulate=False, consume=False, pg=None):
         """g_in (+)= VJP of the block w.r.t. its (concatenated) input. g_out: [B,Cout,F,T] (may be strided).
-        consume=True: g_out is a dense buffer owned by the caller that may be overwritten (saves a full copy)."""
+        consume=True: g_out is a dense buffer owned by the caller that may be overwritten (saves a full copy).
+        pg: ParamGrads of a training step (the block's parameter gradients go to its rows), None otherwise."""
         B, _, Fq, T = g_out.shape
         N = blk.N
         beta = 1.0 if accumulate else 0.0
+        if pg is not None:
+            self._block_out_wgrad(pg, blk, g_out)
         if (blk.res_conv is None and blk.proj_out is None and blk.proj_in is None and not accumulate and blk.nd > 0
                 and g_out.is_contiguous() and ops.AXPBY2 and blk.attn is None):
             # N -> N block (every main block of the encoder, the middle block): the residual path's RS2*g_out and the main path's
@@ -279,7 +425,11 @@ class UnetEngine:
             merged = g_in.is_contiguous() and MERGE_TAIL
             for d in reversed(range(blk.nd)):
                 z, stats, scale, gate = blk.saved[d]
+                if pg is not None:                       # src is the output gradient / rs2 throughout this chain
+                    self._layer_wgrad(pg, blk, d, src, RS2)
                 fs = ops.conv2d(src, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, N // 8))
+                if pg is not None:
+                    self._layer_gn_grad(pg, blk, d, da, RS2)
                 if d == 0 and merged:
                     # the last layer's VJP pass writes g_in = RS2*g_out + RS2*gz itself (gz is never stored)
                     ops.gn_bwd(z, da, src, scale, stats, g_in, RS2, merge=(g_out, RS2, RS2), fused=fs)
@@ -291,6 +441,7 @@ class UnetEngine:
             if not merged:
                 ops.axpby2(g_out, gz, g_in, RS2, RS2)
             blk.saved = None
+            blk.inp = blk.zpo = None
             return g_in
         # residual path
         if blk.res_conv is not None:
@@ -309,16 +460,24 @@ class UnetEngine:
         da = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
         for d in reversed(range(blk.nd)):
             z, stats, scale, gate = blk.saved[d]
+            if pg is not None:
+                self._layer_wgrad(pg, blk, d, gz, c)
             fs = ops.conv2d(gz, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, N // 8))
+            if pg is not None:
+                self._layer_gn_grad(pg, blk, d, da, c)
             ops.gn_bwd(z, da, gz, scale, stats, gz, RS2, fused=fs)
         if blk.attn is not None:
             self.attn_vjp(blk, gz, c)
             c = 1.0
+        if pg is not None and blk.proj_in is not None:
+            x, x2 = blk.inp
+            self._wg(pg, blk.p + "proj_in.weight", x, gz, blk.proj_in, c, x2=x2)
         if blk.proj_in is not None:
             ops.conv2d(gz, blk.proj_in, g_in, transpose=True, res=g_in, alpha=c, rbeta=1.0)
         else:
             ops.axpby(gz, g_in, alpha=c, beta=1.0)
         blk.saved = None
+        blk.inp = blk.zpo = None
         return g_in
 
     # ------------------------------------------------------------------ forward
@@ -335,9 +494,12 @@ class UnetEngine:
             self._cunet = cu
         return cu
 
-    def forward(self, C_list, film):
-        """C_list[j]: planar [B,2,bpo,T_j], index 0 = lowest octave. Returns same structure."""
-        cu = self._c_engine()
+    def forward(self, C_list, film, train=False):
+        """C_list[j]: planar [B,2,bpo,T_j], index 0 = lowest octave. Returns same structure.
+        train=True: also keep what the parameter gradients need (vjp(pg=...)); always on this Python sequencer."""
+        self._train = bool(train)
+        self._film_saved = film if train else None
+        cu = None if train else self._c_engine()
         if cu is not None:
             self._c_fwd = True
             return cu.fwd([c.contiguous() for c in C_list], film)
@@ -366,6 +528,8 @@ class UnetEngine:
                 ops.axpby(pyrs[-1], pyr_new[:, :, bpo:, :])
                 pyr = pyr_new
             pyrs.append(pyr)
+            if train:
+                self.pyrs = pyrs
             H = self.block_fwd(self.main_blk[i], XC, film, self.buf(B, Ns[i], Fi, Ts[i]))
             hs.append(H)
             if i < n - 1:
@@ -394,8 +558,11 @@ class UnetEngine:
         return outs
 
     # ------------------------------------------------------------------ input-VJP
-    def vjp(self, gouts):
-        """gouts[i]: gradient w.r.t. outs[i] (index 0 = lowest octave). Returns gradients w.r.t. C_list."""
+    def vjp(self, gouts, pg=None):
+        """gouts[i]: gradient w.r.t. outs[i] (index 0 = lowest octave). Returns gradients w.r.t. C_list.
+        pg: ParamGrads (rows of this call's batch items) after a forward(train=True): also every conv / GroupNorm parameter
+        gradient and the FiLM output gradient."""
+        assert pg is None or self._train, "parameter gradients need forward(..., train=True)"
         if getattr(self, "_c_fwd", False):
             return self._c_engine().vjp([g.contiguous() for g in gouts])
         n, bpo, Ns, Ts, B = self.nocts, self.bpo, self.Ns, self.Ts, self.B
@@ -417,23 +584,25 @@ class UnetEngine:
                 accumulate = False
             # O_j = up_out(R_j) entered Xout as rs2*O_j
             gO = ops.axpby(gXOp, self.buf(B, 2, Fj, Ts[j]), alpha=RS2)
-            self.block_vjp(self.up_out[i], gO, gR, accumulate=accumulate, consume=True)
+            self.block_vjp(self.up_out[i], gO, gR, accumulate=accumulate, consume=True, pg=pg)
             gXO_prev = ops.axpby(gXOp, self.buf(B, 2, Fj, Ts[j]), alpha=RS2)
             gcat = self.buf(B, 2 * Ns[j], Fj, Ts[j])
-            self.block_vjp(self.up_blk[i], gR, gcat, consume=True)
+            self.block_vjp(self.up_blk[i], gR, gcat, consume=True, pg=pg)
             gX_prev = gcat[:, :Ns[j]]
             gH[j] = gcat[:, Ns[j]:]
         # middle: Xout_6 = mid_out(M); X_6 = M
         gM = self.buf(B, Ns[-1], bpo * n, Ts[-1])
         ops.axpby(gX_prev, gM)
-        self.block_vjp(self.mid_out, gXO_prev, gM, accumulate=True, consume=True)
-        gXm = self.block_vjp(self.mid_blk, gM, self.buf(*gM.shape), consume=True)
+        self.block_vjp(self.mid_out, gXO_prev, gM, accumulate=True, consume=True, pg=pg)
+        gXm = self.block_vjp(self.mid_blk, gM, self.buf(*gM.shape), consume=True, pg=pg)
         # encoder
         gC = [None] * n
         gpyr_next = None                   # gradient flowing into pyr_i from level i+1
         gP = None
         for i in reversed(range(n)):
             Fi = bpo * (i + 1)
+            if pg is not None:                 # pyramid conv: its output entered as rs2 * pconv(pyr)
+                self._wg(pg, f"downs.{i}.1.weight", self.pyrs[i], gXm if i == n - 1 else gP, self.pyr_conv[i], RS2)
             if i == n - 1:
                 gHi = ops.axpby2(gH[i], gXm, self.buf(B, Ns[i], Fi, Ts[i]), 1.0, RS2)
                 gpyr = ops.conv2d(gXm, self.pyr_conv[i], self.buf(B, 2, Fi, Ts[i]), transpose=True, alpha=RS2)
@@ -444,9 +613,9 @@ class UnetEngine:
                 ops.conv2d(gP, self.pyr_conv[i], gpyr, transpose=True, alpha=RS2,
                            res=gpyr_next if gpyr_next is not None else None, rbeta=1.0 if gpyr_next is not None else 0.0)
             Nin = Ns[max(i - 1, 0)]
-            gXC = self.block_vjp(self.main_blk[i], gHi, self.buf(B, Nin, Fi, Ts[i]), consume=True)
+            gXC = self.block_vjp(self.main_blk[i], gHi, self.buf(B, Nin, Fi, Ts[i]), consume=True, pg=pg)
             gCi = self.buf(B, 2, bpo, Ts[i])
-            self.block_vjp(self.init_blk[i], gXC[:, :, :bpo, :], gCi)
+            self.block_vjp(self.init_blk[i], gXC[:, :, :bpo, :], gCi, pg=pg)
             gP = gXC[:, :, bpo:, :] if i > 0 else None
             # pyramid
             if i == n - 1:
@@ -459,4 +628,7 @@ class UnetEngine:
                 ops.resample(gpyr, gCi, 2, beta=1.0)
             gC[n - 1 - i] = gCi
         self.hs = None
+        if pg is not None:
+            self.pyrs = self._film_saved = None
+            self._train = False
         return gC

@@ -6,7 +6,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvArgs, CPackedConv, check, lib, ptr, stream
+from ._lib import ConvArgs, CPackedConv, WgradArgs, check, lib, ptr, stream
 
 RSQRT2 = 1.0 / math.sqrt(2.0)
 
@@ -75,6 +75,29 @@ class PackedConv:
         object.__setattr__(self, k, v)
         if k in _DESC_FIELDS:
             setattr(self.desc, k, ptr(v) if torch.is_tensor(v) else v)
+
+    def repack(self, w):
+        """Pack new weights of the same shape IN PLACE into the existing images, so that every pointer to them (this `desc`, the
+        descriptors of the library-side plan, engine states sharing this object) stays valid: the refresh after an optimizer
+        step.  The same pack calls as construction, so the images are exactly those a freshly built PackedConv would hold."""
+        assert w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (self.Cout, self.Cin, self.KH, self.KW)
+        w = w.contiguous()
+        L = lib()
+        shp = (self.Cout, self.Cin, self.KH, self.KW)
+        if self.splits:
+            for tf, dst in ((0, self.fwd), (1, self.bwd)):
+                check(L.babe_conv_pack_weights_bf16(ptr(w), ptr(dst), *shp, tf, self.splits, stream()), "pack_bf16")
+            return
+        if self.w_raw is not None and self.w_raw.data_ptr() != w.data_ptr():
+            self.w_raw.copy_(w)
+        for tf, dst in ((0, self.fwd), (1, self.bwd)):
+            check(L.babe_conv_pack_weights_nt(ptr(w), ptr(dst), *shp, tf, self.nt, stream()), "pack")
+        for name, fn in (("wino", L.babe_conv_pack_weights_wino), ("wino4", L.babe_conv_pack_weights_wino4),
+                         ("wino45", L.babe_conv_pack_weights_wino45), ("wino85", L.babe_conv_pack_weights_wino85)):
+            for tf, d in ((0, "fwd_"), (1, "bwd_")):
+                dst = getattr(self, d + name)
+                if dst is not None:
+                    check(fn(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
 
     def _init_bf16(self, w):
         assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
@@ -494,3 +517,88 @@ def attn_vjp(qk, a, out, lse, dout, dqk, dv, scale, qk_bias=None, bucket=None, e
     check(lib().babe_attn_vjp(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(D),
                               ptr(dqk), ptr(dv), B, H, F, T, scale, stream()), "attn_vjp")
     return dqk, dv
+
+
+# ---------------------------------------------------------------------------------------------------- training (csrc/wgrad.hip)
+def _wgrad_args(x, g, KH, KW, dil=1, x2=None):
+    B, Cout, F, T = g.shape
+    xp, xbs, xcs = _view(x)
+    gp, gbs, gcs = _view(g)
+    a = WgradArgs()
+    a.x, a.x_bs, a.x_cs = xp, xbs, xcs
+    Cin = x.shape[1]
+    if x2 is not None:
+        a.x2, a.x2_bs, a.x2_cs = _view(x2)
+        a.cin_split = x.shape[1]
+        Cin += x2.shape[1]
+        assert x2.shape[0] == B and x2.shape[2:] == (F, T)
+    assert x.shape[0] == B and x.shape[2:] == (F, T), (x.shape, g.shape)
+    a.g, a.g_bs, a.g_cs = gp, gbs, gcs
+    a.B, a.Cin, a.Cout, a.F, a.T, a.KH, a.KW, a.dil = B, Cin, Cout, F, T, KH, KW, dil
+    return a
+
+
+def conv_wgrad_workspace(x, g, KH, KW, dil=1, x2=None):
+    """Floats of workspace conv_wgrad_rows needs for these operands."""
+    n = lib().babe_conv_wgrad_workspace(C.byref(_wgrad_args(x, g, KH, KW, dil, x2)))
+    if n < 0:
+        raise _lib.BabeHipError(f"conv_wgrad: unsupported shape x{tuple(x.shape)} g{tuple(g.shape)} k=({KH},{KW})")
+    return n
+
+
+def conv_wgrad_rows(x, g, KH, KW, rows, *, dil=1, x2=None, oscale=None, alpha=1.0, w=None, dgate=None, galpha=1.0, ws=None):
+    """Per-batch-row conv weight gradient (babe_conv_wgrad_rows): rows[b] (a [B, Cout*Cin*KH*KW] view, any row stride) <-
+    alpha * oscale[b, co] * sum_{f,t} g[b, co] * shifted cat(x, x2)[b, ci]; dgate[b, co] <- galpha * <w[co], that sum without
+    oscale>.  x, x2, g: [B, C, F, T] views with contiguous rows (frequency sub-views allowed); ws: workspace (allocated if None)."""
+    a = _wgrad_args(x, g, KH, KW, dil, x2)
+    n = conv_wgrad_workspace(x, g, KH, KW, dil, x2)
+    if ws is None:
+        ws = torch.empty(n, device=g.device, dtype=torch.float32)
+    assert ws.numel() >= n and ws.is_contiguous()
+    assert rows.dim() == 2 and rows.shape[0] == a.B and rows.shape[1] == a.Cout * a.Cin * KH * KW and rows.stride(1) == 1
+    if oscale is not None:
+        assert oscale.is_contiguous() and oscale.shape == (a.B, a.Cout)
+    if dgate is not None:
+        assert w is not None and w.is_contiguous() and w.numel() == a.Cout * a.Cin * KH * KW
+        assert dgate.shape == (a.B, a.Cout) and dgate.stride(1) == 1
+    check(lib().babe_conv_wgrad_rows(C.byref(a), ptr(ws), ptr(oscale), alpha, ptr(w), ptr(dgate),
+                                     dgate.stride(0) if dgate is not None else 0, galpha, ptr(rows), rows.stride(0), stream()),
+          "conv_wgrad_rows")
+    return rows
+
+
+def rows_sum(rows, out, beta=0.0):
+    """out[i] = beta*out[i] + sum_b rows[b, i] (b in increasing order: the fixed-order batch reduction of the parameter grads)."""
+    B, n = rows.shape
+    assert rows.stride(1) == 1 and out.is_contiguous() and out.numel() == n
+    check(lib().babe_rows_sum(ptr(rows), rows.stride(0), B, n, ptr(out), beta, stream()), "rows_sum")
+    return out
+
+
+def gn_param_grad(z, da, scale, stats, gamma, film_aff, dgamma_rows, dfilm, cs=1.0, G=8):
+    """GroupNorm * FiLM parameter gradients of a = gelu(z * scale) given da (babe_gn_param_grad): dgamma_rows[b, c] (summed over b
+    later by rows_sum) and dfilm[b, c] (the gradient of the FiLM affine output); cs scales da."""
+    B, Cc, F, T = z.shape
+    assert z.is_contiguous() and da.is_contiguous() and da.shape == z.shape
+    assert film_aff.stride(1) == 1 and dgamma_rows.stride(1) == 1 and dfilm.stride(1) == 1
+    assert dgamma_rows.shape == (B, Cc) and dfilm.shape == (B, Cc)
+    check(lib().babe_gn_param_grad(ptr(z), ptr(da), ptr(scale), ptr(stats), ptr(gamma), ptr(film_aff), film_aff.stride(0), cs,
+                                   ptr(dgamma_rows), dgamma_rows.stride(0), ptr(dfilm), dfilm.stride(0), B, Cc, G, F * T, stream()),
+          "gn_param_grad")
+
+
+def linear_bwd(dy, x, W, dW, db, dx=None, y=None, beta=0.0, ws=None):
+    """Backward of linear(x, W, bias, relu=y is not None) with output y: dW (+)= dp^T x, db (+)= sum_b dp, dx = dp W,
+    dp = dy * (y > 0) (babe_linear_bwd; fixed-order sums)."""
+    B, K = x.shape
+    J = W.shape[0]
+    assert dy.shape == (B, J) and all(t.is_contiguous() for t in (dy, x, W, dW)) and dW.shape == (J, K)
+    assert db is None or (db.is_contiguous() and db.numel() == J)
+    assert y is None or (y.is_contiguous() and y.shape == (B, J))
+    if dx is not None:
+        assert dx.is_contiguous() and dx.shape == (B, K)
+        if ws is None:
+            ws = torch.empty(lib().babe_linear_bwd_workspace(B, K, J), device=x.device, dtype=torch.float32)
+    check(lib().babe_linear_bwd(ptr(dy), ptr(y), ptr(x), ptr(W), ptr(dW), ptr(db), ptr(dx), ptr(ws), B, K, J, beta, stream()),
+          "linear_bwd")
+    return dW

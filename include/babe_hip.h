@@ -522,6 +522,44 @@ int babe_attn_vjp(const float* qk, const float* qk_bias, const float* a, const i
                   const float* out, const float* lse, const float* dout, float* D, float* dqk, float* dv, int B, int H, int F,
                   int T, float scale, void* stream);
 
+
+/* ---- training: parameter gradients of the CQTDiff+ UNet (csrc/wgrad.hip), fp32, no float atomics (every result is a
+ * fixed-order sum: bit-identical run to run and independent of how batch rows are split between calls).
+ *
+ * Conv weight gradient (autograd's convolution_backward w.r.t. the weight of Conv2d "same", no bias):
+ *   P_b[co][ci][kh][kw] = sum_{f,t} g[b][co][f][t] * X[b][ci][f + dil*(kh - KH/2)][t + kw - KW/2]   (zero outside [0,F) x [0,T))
+ * X channels [0,cin_split) come from x, [cin_split,Cin) from x2 (the conv's two-source input); x, x2 and g are [B][C][F][T]
+ * views with T contiguous and row stride T (batch / channel strides given: frequency sub-views need no copy).
+ * KH x KW is 5x3 or 1x1; Cin, Cout <= 512; dil >= 1; any F, T. */
+typedef struct {
+    const float* x;  long x_bs,  x_cs;
+    const float* x2; long x2_bs, x2_cs; int cin_split;      /* x2 NULL: single source (cin_split ignored) */
+    const float* g;  long g_bs,  g_cs;
+    int B, Cin, Cout, F, T, KH, KW, dil;
+} babe_wgrad_args;
+/* Workspace of babe_conv_wgrad_rows in floats (B * chunks * Cout * Cin * KH * KW, chunks a function of the shape only). */
+long babe_conv_wgrad_workspace(const babe_wgrad_args* a);
+/* rows[b*rows_bs + (co*Cin + ci)*KH*KW + kh*KW + kw] = alpha * oscale[b*Cout + co] * P_b[co][ci][kh][kw]   (oscale NULL: 1)
+ * dgate (optional) [b*dgate_bs + co] = galpha * sum_k w[co][k] * P_b[co][k], w the conv's weights [Cout][Cin][KH][KW]: the FiLM
+ * gate gradient of znew = rs2*(gate*conv(a) + z) without recomputing the conv (galpha = rs2 * upstream scale). */
+int babe_conv_wgrad_rows(const babe_wgrad_args* a, float* ws, const float* oscale, float alpha, const float* w, float* dgate,
+                         long dgate_bs, float galpha, float* rows, long rows_bs, void* stream);
+/* out[i] = beta*out[i] + sum_{b=0..B-1} rows[b*rows_bs + i], b in increasing order, i < n. */
+int babe_rows_sum(const float* rows, long rows_bs, int B, long n, float* out, float beta, void* stream);
+/* Per-channel GroupNorm * FiLM parameter gradient of a = gelu(z * scale), scale[b][c] = gamma[c]*(film_aff[b][c]+1)*r[b][g],
+ * r = stats[(b*G+g)*3+2] (babe_gn_finalize), given da = dL/da (dense [B][C][hw]):
+ *   dscale[b][c] = cs * sum_i da*gelu'(z*scale)*z    (double partial sums, fixed order)
+ *   dgamma_rows[b*dg_bs + c] = dscale * (film_aff[b*film_bs + c] + 1) * r;   dfilm[b*dfilm_bs + c] = dscale * gamma[c] * r */
+int babe_gn_param_grad(const float* z, const float* da, const float* scale, const float* stats, const float* gamma,
+                       const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
+                       long dfilm_bs, int B, int C, int G, long hw, void* stream);
+/* Backward of babe_linear (y = x W^T + bias, optionally ReLU): dp = dy * (y > 0) (y NULL: no mask),
+ *   dW[j][k] = beta*dW + sum_b dp[b][j] x[b][k];  db[j] = beta*db + sum_b dp[b][j];  dx[b][k] = sum_j dp[b][j] W[j][k] (dx may be NULL)
+ * ws: babe_linear_bwd_workspace(B, K, J) floats. */
+long babe_linear_bwd_workspace(int B, int K, int J);
+int babe_linear_bwd(const float* dy, const float* y, const float* x, const float* W, float* dW, float* db, float* dx, float* ws,
+                    int B, int K, int J, float beta, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,135 @@
+"""One training step of the full-width CQTDiff+ prior at the reference geometry (B=4, L=368368, 44.1 kHz), split into forward,
+input-VJP, parameter-gradient work (and the conv weight-gradient calls in it), reductions and repack, plus the conv weight-gradient kernel's rate per level against the 157.3
+TFLOP/s fp32 MFMA peak.  Prints one JSON document (profiles/train_bench.json).
+
+    python tools/train_bench.py [--B 4] [--L 368368] [--reps 3]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PEAK = 157.3e12
+
+
+def timed(fn, reps):
+    """median ms of fn() over reps runs (HIP events on the current stream, synchronised)."""
+    ts = []
+    for _ in range(reps):
+        torch.cuda.synchronize()
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return sorted(ts)[len(ts) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=4)
+    ap.add_argument("--L", type=int, default=368368)
+    ap.add_argument("--reps", type=int, default=3)
+    a = ap.parse_args()
+    from babe_amd import ops
+    from babe_amd.config import default_args
+    from babe_amd.networks.cqtdiff_plus import Unet_CQT_oct_with_attention, init_state_dict
+    from tests.golden_weights import FULL_DILS, FULL_NS
+
+    args = default_args(sample_rate=44100, audio_len=a.L)
+    net = Unet_CQT_oct_with_attention(args, "cuda")
+    net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0))
+    net.set_trainable(True)
+    gen = torch.Generator().manual_seed(0)
+    x = (0.1 * torch.randn(a.B, a.L, generator=gen)).cuda()
+    cn = torch.linspace(-1, 0.5, a.B).reshape(a.B, 1).cuda()
+    w = torch.randn(a.B, a.L, generator=gen).cuda()
+    res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES)}
+
+    # input-VJP alone (the sampler's path) and the forward without training state
+    def fwd_vjp():
+        net.fwd_nograd(x, cn)
+        net.vjp(w)
+    t_fwd_vjp = timed(fwd_vjp, a.reps)
+    res["forward_ms"] = timed(lambda: net.fwd_nograd(x, cn, train=True), a.reps)
+    res["input_vjp_ms"] = t_fwd_vjp - timed(lambda: net.fwd_nograd(x, cn), a.reps)
+
+    # the parameter-gradient backward: input-VJP + parameter-gradient work + reductions (param_grads timed on its own); the conv
+    # weight-gradient calls themselves (babe_conv_wgrad_rows, partial + chunk-sum kernels) timed per call on their lane's stream
+    from babe_amd.networks import unet_engine as ue
+    wg_ev = []
+    orig_wg = ue.UnetEngine._wg
+
+    def wg(self, *args, **kw):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        orig_wg(self, *args, **kw)
+        e.record()
+        wg_ev.append((s, e))
+    ue.UnetEngine._wg = wg
+    eng = net.engine()
+    red = []
+    orig = eng.param_grads
+
+    def param_grads(pg, keep):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        out = orig(pg, keep)
+        e.record()
+        red.append((s, e))
+        return out
+    eng.param_grads = param_grads
+    bwd = []
+    for _ in range(a.reps):
+        net.fwd_nograd(x, cn, train=True)
+        bwd.append(timed(lambda: net._vjp_train(w), 1))
+    torch.cuda.synchronize()
+    eng.param_grads = orig
+    ue.UnetEngine._wg = orig_wg
+    res["train_backward_ms"] = sorted(bwd)[len(bwd) // 2]
+    res["reductions_ms"] = sorted(s.elapsed_time(e) for s, e in red)[len(red) // 2]
+    # everything the parameter gradients add to the backward: conv weight gradients, the recomputed GELU, the GroupNorm / FiLM
+    # reductions, the zero-fill of the gradient buffers (the FiLM / MLP backward is in reductions_ms)
+    res["param_grad_work_ms"] = res["train_backward_ms"] - res["input_vjp_ms"] - res["reductions_ms"]
+    # sum over the conv weight-gradient calls of one backward (calls of the two lanes overlap in time, so this sum can exceed
+    # their share of the wall time)
+    res["wgrad_calls_per_backward"] = len(wg_ev) // a.reps
+    res["wgrad_calls_ms_sum"] = sum(s.elapsed_time(e) for s, e in wg_ev) / a.reps
+    sd = net._engine_sd()
+    res["repack_ms"] = timed(lambda: eng.refresh(sd), a.reps)
+
+    # full step through autograd + Adam (loss = <net(x), w>)
+    opt = torch.optim.Adam(net.parameters(), lr=1e-6)
+
+    def step():
+        opt.zero_grad()
+        y = net(x, cn)
+        (y * w).sum().backward()
+        opt.step()
+    step()
+    res["step_ms"] = timed(step, a.reps)
+
+    # weight-gradient kernel per level: the (5,3) H convs of the main blocks at this geometry, B rows per call
+    Ts = [c.shape[-1] for c in net.CQTransform.fwd_planar(x[:1])][::-1]
+    lv = []
+    for i, N in enumerate(FULL_NS):
+        F, T = 64 * (i + 1), Ts[i]
+        xa = torch.randn(a.B, N, F, T, device="cuda")
+        g = torch.randn(a.B, N, F, T, device="cuda")
+        rows = torch.empty(a.B, N * N * 15, device="cuda")
+        ws = torch.empty(ops.conv_wgrad_workspace(xa, g, 5, 3, 1), device="cuda")
+        ms = timed(lambda: ops.conv_wgrad_rows(xa, g, 5, 3, rows, dil=2, ws=ws), a.reps + 2)
+        fl = 2.0 * a.B * N * N * 15 * F * T
+        lv.append({"level": i, "C": N, "F": F, "T": T, "ms": round(ms, 4), "tflops": round(fl / ms / 1e9, 2),
+                   "frac_peak": round(fl / ms / 1e9 / (PEAK / 1e12), 3)})
+        del xa, g, rows, ws
+    res["wgrad_levels"] = lv
+    print(json.dumps(res, indent=1))
+
+
+if __name__ == "__main__":
+    main()
