@@ -9,12 +9,15 @@ segmentation and cross-fade as formal_test_bwe, testing/blind_bwe_tester.py:421-
 babe_amd/testing/long_file.py) that run as one batch of 2 with per-clip semantics.  Weak scaling: every rank restores its own clips; one RCCL all_gather of
 the restored audio + filters closes each step.
 
-Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+Usage:  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 N>1: either launched by torch.distributed.run (one rank per GPU, RANK/LOCAL_RANK/WORLD_SIZE in the env), or run plainly,
 in which case this process spawns the N ranks itself (as a child torch.distributed.run, before touching the GPU).
 Prints ONE JSON line on rank 0.  --dump-outputs DIR: after the timed region rank 0 writes what the last timed step returned
 (restored clips, fitted filter parameters) as DIR/<name>.npy, so that two builds can be compared output for output; the
 inputs (synthetic clips, seeded noise) depend only on the arguments.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the dump and the line (its roofline / hbm
+blocks come from HIP events of that same run).  --full adds what takes time of its own: the CPU-oracle baseline
+(`cpu_baseline`, minutes of host time on one rank).
 """
 import argparse
 import json
@@ -47,13 +50,16 @@ def synth_clip(clip_id, n=CLIP, fs=FS):
         f0 = 440.0 * 2 ** ((midi - 69) / 12)
         dur = 0.25 + 1.5 * float(torch.rand(1, generator=g))
         npart = int(torch.randint(8, 17, (1,), generator=g))
-        tt = (t - onset).clamp(min=0)
-        gate = (t >= onset).double()
+        # a note sounds from its onset on: only the samples t >= onset are touched (before it the gated partials add exact
+        # zeros), bit for bit the clip of the whole-length form (tests/test_host_logic.py)
+        i0 = int(torch.searchsorted(t, onset))
+        tt = t[i0:] - onset
+        xs = x[i0:]
         for k in range(1, npart + 1):
             fk = f0 * k * math.sqrt(1 + 4e-4 * k * k)
             if fk > fs / 2 * 0.98:
                 break
-            x += gate * (1.0 / k) * torch.exp(-tt * (1.5 + 0.6 * k)) * torch.sin(2 * math.pi * fk * tt)
+            xs += (1.0 / k) * torch.exp(-tt * (1.5 + 0.6 * k)) * torch.sin(2 * math.pi * fk * tt)
         onset += dur * 0.5
     x = x + 1e-3 * torch.randn(n, generator=g, dtype=torch.float64)
     return x.float()
@@ -110,8 +116,8 @@ def cpu_baseline():
         params = torch.tensor([list(smp.fc_init), list(smp.A_init)], dtype=torch.float32)
         t0 = time.perf_counter()
         smp.evaluate(x, sched[0], y, params, blind=True)                    # warm-up evaluation (untimed)
-        # (a leg whose warm-up evaluation already took seconds - hundreds of threads on small ops - times ONE evaluation: the
-        # default bench run has to finish within minutes)
+        # (a leg whose warm-up evaluation already took seconds - hundreds of threads on small ops - times ONE evaluation: a
+        # --full run has to finish within minutes)
         evals = (sched[0], sched[1], sched[1]) if time.perf_counter() - t0 < 3.0 else (sched[0],)
         timers = {}
         t0 = time.perf_counter()
@@ -160,7 +166,7 @@ def cpu_baseline():
         full_legs = []
         for n in cand:
             if n != best and warm_s > 60.0:
-                continue                                                    # (a slow host: keep the default run within minutes)
+                continue                                                    # (a slow host: keep a --full run within minutes)
             torch.set_num_threads(n)
             timers = {}
             t0 = time.perf_counter()
@@ -285,7 +291,10 @@ def main():
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--T", type=int, default=35, help="EDM steps (35 = the benchmark; anything else is a debug run)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the CPU-oracle baseline (cpu_baseline; one rank only, "
+                         "minutes of host time after the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU-oracle baseline out")
     ap.add_argument("--clips-per-gpu", type=int, default=1,
                     help="10 s clips restored per GPU per step (1 = the benchmark's single-clip workload; larger values "
                          "batch more independent segments per kernel launch, cf. configs[2])")
@@ -581,7 +590,7 @@ def main():
         }
         if dumped is not None:
             rec["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baseline()
         print(json.dumps(rec), flush=True)
     if world > 1 or launched:

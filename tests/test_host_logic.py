@@ -234,6 +234,39 @@ def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
     assert np.array_equal(a, np.load(tmp_path / "s2" / "restored_audio.npy"))        # same sample every time
 
 
+def _synth_clip_whole_length(clip_id, n, fs):
+    """bench.synth_clip as first written: every note's partials gated over the whole clip."""
+    import math
+    g = torch.Generator().manual_seed(1000 + clip_id)
+    t = torch.arange(n, dtype=torch.float64) / fs
+    x = torch.zeros(n, dtype=torch.float64)
+    onset = 0.0
+    while onset < n / fs:
+        midi = int(torch.randint(40, 88, (1,), generator=g))
+        f0 = 440.0 * 2 ** ((midi - 69) / 12)
+        dur = 0.25 + 1.5 * float(torch.rand(1, generator=g))
+        npart = int(torch.randint(8, 17, (1,), generator=g))
+        tt = (t - onset).clamp(min=0)
+        gate = (t >= onset).double()
+        for k in range(1, npart + 1):
+            fk = f0 * k * math.sqrt(1 + 4e-4 * k * k)
+            if fk > fs / 2 * 0.98:
+                break
+            x += gate * (1.0 / k) * torch.exp(-tt * (1.5 + 0.6 * k)) * torch.sin(2 * math.pi * fk * tt)
+        onset += dur * 0.5
+    x = x + 1e-3 * torch.randn(n, generator=g, dtype=torch.float64)
+    return x.float()
+
+
+@pytest.mark.parametrize("clip_id", [0, 1, 7, 24])
+def test_bench_synth_clip_is_bit_identical_to_the_whole_length_form(clip_id):
+    """bench.py's inputs: synth_clip touches each note's samples from its onset on only; the clip must stay bit for bit the
+    whole-length gated form, at the benchmark's length and at an odd one."""
+    import bench
+    for n in (bench.CLIP, 100003):
+        assert torch.equal(bench.synth_clip(clip_id, n=n), _synth_clip_whole_length(clip_id, n, bench.FS)), (clip_id, n)
+
+
 def test_bench_gpus_flag_without_launcher_spawns_ranks_or_fails_loudly(monkeypatch):
     """`python bench.py --gpus N` with WORLD_SIZE unset must start N ranks (never silently run one); with a launcher whose
     WORLD_SIZE disagrees it must exit non-zero.  No GPU is touched: the spawn is intercepted."""
