@@ -93,6 +93,9 @@ _SIGS = {
     "babe_attn_vjp": [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P],
     "babe_resample": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _F, _P],
     "babe_resample_res": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _I, _F, _F, _P],
+    "babe_resample_sinc_adjoint": [_P, _L, _P, _L, _I, _L, _L, _P, _P, _I, _I, _I, _P],
+    "babe_iir_filter": [_P, _L, _P, _L, _I, _L, _P, _P, _I, _I, _I, _P, _L, _P, _L, _P],
+    "babe_decimate": [_P, _L, _P, _L, _I, _L, _L, _I, _I, _P],
     "babe_axpby4d": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],
     "babe_axpby2_4d": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],
     "babe_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -134,6 +137,8 @@ def lib():
         L.babe_conv_wgrad_workspace.restype = C.c_long
         L.babe_conv_wgrad_workspace.argtypes = [C.POINTER(WgradArgs)]
         L.babe_linear_bwd_workspace.restype = C.c_long
+        L.babe_iir_workspace.restype = C.c_long
+        L.babe_iir_workspace.argtypes = [_I, _L, _I]
         L.babe_linear_bwd_workspace.argtypes = [_I, _I, _I]
         L.babe_prof_nslots.restype = C.c_int
         L.babe_prof_slot_name.restype = C.c_char_p

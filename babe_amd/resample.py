@@ -102,3 +102,24 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
         check(lib().babe_resample_sinc(ptr(x), x.stride(0), ptr(out), out.stride(0), B, L, Lo, ptr(kern), ptr(krange), orig, new,
                                        width, stream(x)), "resample_sinc")
     return out.reshape(*shape[:-1], Lo)
+
+
+def resample_adjoint(g, orig_freq, new_freq, length, lowpass_filter_width=6, rolloff=0.99):
+    """Transpose of `resample` for an input of `length` samples: g [..., ceil(new length / orig)] device tensor ->
+    [..., length] (csrc/degrade.hip, babe_resample_sinc_adjoint: a gather per input sample, deterministic)."""
+    if int(orig_freq) == int(new_freq):
+        return g
+    if not g.is_cuda:
+        raise RuntimeError("babe_amd.resample_adjoint runs on the GPU only (no CPU fallback)")
+    Lo = resampled_length(length, orig_freq, new_freq)
+    if g.shape[-1] != Lo:
+        raise ValueError(f"resample_adjoint: g has {g.shape[-1]} samples, the resampler yields {Lo} from {length}")
+    shape = g.shape
+    gg = g.reshape(-1, Lo).contiguous().float()
+    B = gg.shape[0]
+    kern, krange, width, orig, new = _table(orig_freq, new_freq, lowpass_filter_width, rolloff, gg.device)
+    out = torch.empty(B, int(length), device=gg.device, dtype=torch.float32)
+    with torch.cuda.device(gg.device):
+        check(lib().babe_resample_sinc_adjoint(ptr(gg), gg.stride(0), ptr(out), out.stride(0), B, int(length), Lo, ptr(kern),
+                                               ptr(krange), orig, new, width, stream(gg)), "resample_sinc_adjoint")
+    return out.reshape(*shape[:-1], int(length))

@@ -178,7 +178,7 @@ class STFTOps:
                                                r.shape[1], mode, float(beta), stream()), "residual_seed_alt")
             return out
         check(lib().babe_residual_seed(ptr(r), r.stride(0), ptr(part), self.NBLK, ptr(self.env_inv) if post else None, ptr(out),
-                                       out.stride(0), B, self.L, stream()), "residual_seed")
+                                       out.stride(0), B, r.shape[1], stream()), "residual_seed")
         return out
 
     def mag_stats(self, specX, specY, shared=False):

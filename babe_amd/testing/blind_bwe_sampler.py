@@ -21,8 +21,10 @@ high-pass, UNet input-VJP).  All tensor work is C-ABI calls; the host only seque
 """
 import os
 
+import numpy as np
 import torch
 
+from ..degrade import DecimateDegradation, IIRDegradation, ResampleDegradation
 from ..stft import STFTOps, add_obs_noise, fir_same, lincomb, make_fit_cfg, mask_blend
 from .._lib import check, lib, ptr, stream
 
@@ -98,6 +100,7 @@ class BlindSampler:
         self._stft = None
         self._ceval = {}               # BABE_EVAL_C=1: one library-side evaluation descriptor per lane (testing/eval_c.py)
         self.fir_taps = None
+        self.degr = None               # predict_bwe's other known degradations (babe_amd/degrade.py): .fwd = A, .adj = A^T
         self.ar_mask = None            # predict_bwe_AR: degradation(x) = mask*x + (1-mask)*A(x)
         self.dc = None                 # (smooth_mask, y_smooth_masked) of the replacement data-consistency step
 
@@ -136,6 +139,16 @@ class BlindSampler:
             g = sd["ops"].distance_grad(rec, y, sd["w"], sd["mode"], shared=self.batch_semantics == "reference")
             return st.residual_seed(g, None, post=post, norm="ready") if post else g
         return st.residual_seed(r, part, post=post, norm=self.norm, y=y, beta=self.smoothl1_beta)
+
+    def _known(self):
+        """True while a known degradation with forward and adjoint runs: the FIR taps or one of self.degr."""
+        return self.fir_taps is not None or self.degr is not None
+
+    def _A(self, x):
+        return fir_same(x, self.fir_taps) if self.fir_taps is not None else self.degr.fwd(x)
+
+    def _At(self, g):
+        return fir_same(g, self.fir_taps, adjoint=True) if self.fir_taps is not None else self.degr.adj(g)
 
     def _lane_kw(self, lane):
         return {"lane": lane} if (lane is not None and getattr(self.model, "supports_lanes", False)) else {}
@@ -222,12 +235,13 @@ class BlindSampler:
             m = self.inpaint_mask
             r = lincomb(torch.empty_like(y), 1.0, y, -1.0, mask_blend(m, x_den, None))
             g_den = mask_blend(m, self._seed(st, r, y, self._sumsq(r), post=False), None)
-        elif self.fir_taps is not None:
-            # known FIR degradation (edm_sampler.py:245-252): residual, then the transpose FIR
-            rec = fir_same(x_den, self.fir_taps)
+        elif self._known():
+            # known degradation (edm_sampler.py:245-252; blind_bwe_sampler.py:211-230): residual, then the transpose.  For
+            # 'resample' / 'decimate' y (and r, seed) are shorter than x; A^T maps back to x's length
+            rec = self._A(x_den)
             r = lincomb(torch.empty_like(y), 1.0, y, -1.0, rec)
             seed = self._seed(st, r, y, self._sumsq(r), post=False)
-            g_den = fir_same(seed, self.fir_taps, adjoint=True)
+            g_den = self._At(seed)
         else:
             specX = st.stft(x_den)
             if blind and specX_fit is None:
@@ -262,8 +276,8 @@ class BlindSampler:
             x0 = lincomb(torch.empty_like(x), 1.0, x, -float(t), d)
             if getattr(self, "inpaint_mask", None) is not None:
                 a0 = mask_blend(self.inpaint_mask, x0, None)
-            elif self.fir_taps is not None:
-                a0 = fir_same(x0, self.fir_taps)
+            elif self._known():
+                a0 = self._A(x0)
             else:
                 H = st.design_filter(filter_params)
                 a0 = st.ola(st.filter_frames(st.stft(x0), H if H.shape[0] == B else H[0]), normalise=True)
@@ -302,11 +316,11 @@ class BlindSampler:
             y = y.contiguous().float()
             if self.obs_snr is not None:
                 y = y.clone()                  # the observation noise is added in place: never to the caller's tensor
-            shape = y.shape
+            shape = y.shape if shape is None else tuple(shape)      # (resample / decimate: the state is longer than y)
         B, L = shape
         with torch.cuda.device(device):
             st = self.stft_ops(L, device)
-            specY = st.stft(y) if (y is not None and self.fir_taps is None) else None
+            specY = st.stft(y) if (y is not None and not self._known()) else None
             T = self.nb_steps
             if rid:
                 data_denoised = torch.zeros((T, B, L))
@@ -394,16 +408,17 @@ class BlindSampler:
         """(:75-135) s * grad_x ||y - A(x_hat)|| / t_i with s = xi / (||grad|| / sqrt(audio_len) + 1e-6), for x_hat = the estimate
         the LAST get_denoised_estimate(x, t) call returned: where the reference differentiates through the network with autograd,
         this runs the network's hand-wired VJP on the state that call left (so it must directly follow it, as in the reference's
-        get_score).  L2 norm and STFT-domain low-pass A = filter_params [2,K] (or the FIR taps set by predict_bwe(..., 'firwin'));
+        get_score).  L2 norm and STFT-domain low-pass A = filter_params [2,K] (or the known degradation predict_bwe(..., 'firwin' /
+        'cheby1' / 'biquad' / 'resample' / 'decimate') sets);
         `degradation` is accepted for the signature and not called.  The sampling loop does the same inside evaluate()."""
         if self.norm != 2 or self.stft_dist is not None or self.obs_snr is not None:
             raise NotImplementedError("get_rec_grads helper: default guidance distance only (the sampling loop handles the others)")
         st = self.stft_ops(y.shape[-1], y.device)
         cskip, cout, cin = self._c
         x_hat, y = x_hat.contiguous(), y.contiguous()
-        if self.fir_taps is not None:
-            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, fir_same(x_hat, self.fir_taps))
-            g_den = fir_same(self._seed(st, r, y, self._sumsq(r), post=False), self.fir_taps, adjoint=True)
+        if self._known():
+            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, self._A(x_hat))
+            g_den = self._At(self._seed(st, r, y, self._sumsq(r), post=False))
         else:
             H = st.design_filter(torch.as_tensor(filter_params, dtype=torch.float32, device=y.device))
             Hq = H[0] if (H.dim() == 2 and H.shape[0] != x_hat.shape[0]) else H
@@ -443,7 +458,7 @@ class BlindSampler:
         return (self.LANES > 1 and B >= 2 and y is not None and not rid and self.batch_semantics == "per_clip" and
                 getattr(self.model, "supports_lanes", False) and
                 self.ar_mask is None and self.dc is None and self.obs_snr is None and not self.sigma_den and
-                self.fir_taps is None and filter_params.shape[0] == B)
+                not self._known() and filter_params.shape[0] == B)
 
     def _lane_step(self, ln, i, t, gamma, noise, blind, snoise, half):
         """One half of stochastic Heun step i on lane `ln` (enqueued on the current stream): half 0 = noise injection +
@@ -529,10 +544,27 @@ class BlindSampler:
 
     def predict_bwe(self, ylpf, filt, filt_type, rid=False, test_filter_fit=False, compute_sweep=False):
         """Known-degradation variant (:306-364 -> predict_conditional :387-404 -> predict :406-498).
-        filt_type 'fc_A' (filt = [2,K] breakpoints) or 'firwin' / 'firwin_hpf' (filt = FIR taps applied with
-        conv1d(padding="same"), :211-218).  rid=True returns (x, data_denoised, data_score, t) like predict."""
+        filt_type 'fc_A' (filt = [2,K] breakpoints), 'firwin' / 'firwin_hpf' (filt = FIR taps applied with
+        conv1d(padding="same"), :211-218), 'cheby1' (filt = (b, a): lfilter, clamp=False, :219-221), 'biquad' (filt = the six
+        coefficients of design_biquad_lpf: lfilter with clamp=True, :222-224), 'resample' (filt = factor: torchaudio resample
+        int(100 factor) -> 100, :228-230) or 'decimate' (filt = factor: x[..., 0:-1:factor], :225-226).  rid=True returns
+        (x, data_denoised, data_score, t) like predict - except for 'resample' / 'decimate', which run predict_resample
+        (:376-385): state of shape (B, audio_len), y shorter, x returned alone whatever rid is."""
         dev = ylpf.device
-        if filt_type == "fc_A":
+        if filt_type in ("resample", "decimate"):
+            return self._predict_resample(ylpf, filt, filt_type)
+        self.degr = None
+        if filt_type in ("cheby1", "biquad"):
+            if filt_type == "cheby1":
+                b, a = filt
+                b, a = torch.as_tensor(np.asarray(b, dtype=np.float64)).float(), torch.as_tensor(np.asarray(a, dtype=np.float64)).float()
+            else:
+                c6 = [float(torch.as_tensor(v).reshape(-1)[0]) for v in filt]       # torch.Tensor(b0) ... as float32 (:228-236)
+                b, a = torch.tensor(c6[:3], dtype=torch.float32), torch.tensor(c6[3:], dtype=torch.float32)
+            self.degr = IIRDegradation(b, a, clamp=(filt_type == "biquad"), device=dev)
+            self.fir_taps = None
+            params = torch.zeros(1, 2, 1, device=dev)
+        elif filt_type == "fc_A":
             p = torch.as_tensor(filt, dtype=torch.float32)
             if p.dim() == 1:
                 p = p.unsqueeze(1)
@@ -548,8 +580,33 @@ class BlindSampler:
             res = self._sample(ylpf, params, blind=False, rid=rid, snoise=self.diff_params.Snoise,
                                diag=(bool(test_filter_fit), bool(compute_sweep)))
         finally:
-            self.fir_taps = None
+            self.fir_taps, self.degr = None, None
         return res if rid else res[0]
+
+    def _predict_resample(self, ylpf, filt, filt_type):
+        """predict_bwe(..., 'resample' / 'decimate') -> predict_resample (:376-385) -> predict(shape, device): rid, test_filter_fit
+        and compute_sweep are not passed on there.  The reference adds y to the initial noise with start_sigma and to A(x0) with
+        data_consistency - shapes that differ here, so it fails: refused up front instead."""
+        if self.start_sigma is not None:
+            raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.start_sigma must be None (y has fewer samples "
+                             f"than the state of shape (B, audio_len); the reference fails on that shape mismatch)")
+        if self.data_consistency:
+            raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.data_consistency is not available (y has fewer "
+                             f"samples than the state; the reference fails on that shape mismatch)")
+        B, L = ylpf.shape[0], int(self.args.exp.audio_len)
+        self.degr = ResampleDegradation(filt, L) if filt_type == "resample" else DecimateDegradation(filt, L)
+        if ylpf.shape[-1] != self.degr.out_length():
+            n = self.degr.out_length()
+            self.degr = None
+            raise ValueError(f"predict_bwe(..., {filt_type!r}): y has {ylpf.shape[-1]} samples, the degradation of audio_len = {L} "
+                             f"yields {n}")
+        self.fir_taps = None
+        try:
+            res = self._sample(ylpf, torch.zeros(1, 2, 1, device=ylpf.device), blind=False, rid=False,
+                               snoise=self.diff_params.Snoise, shape=(B, L))
+        finally:
+            self.degr = None
+        return res[0]
 
     def predict_unconditional(self, shape, device, rid=False):
         """Unguided sampling from the prior (:366-374): score = (D(x) - x)/t^2, no observations."""

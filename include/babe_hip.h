@@ -191,6 +191,25 @@ int babe_resample_res(const float* in, long in_bs, long in_cs, const float* res,
  * with xpad = x padded by (width, width + orig) zeros; L_out = ceil(new_ L_in / orig). */
 int babe_resample_sinc(const float* x, long x_bs, float* out, long out_bs, int B, long L_in, long L_out, const float* kernel,
                        const int* krange, int orig, int new_, int width, void* stream);
+/* Transpose of babe_resample_sinc (same kernel / krange / rates): g [B][L_out] -> out [B][L_in], a gather per input sample
+ * (deterministic, no atomics).  The guidance VJP of predict_bwe(..., 'resample'). */
+int babe_resample_sinc_adjoint(const float* g, long g_bs, float* out, long out_bs, int B, long L_in, long L_out,
+                               const float* kernel, const int* krange, int orig, int new_, int width, void* stream);
+
+/* ---- known degradations of predict_bwe beyond the FIR (testing/blind_bwe_sampler.py:219-230; csrc/degrade.hip) ----------
+ * IIR filter with torchaudio.functional.lfilter semantics: y[n] = sum_{k=0..order} b[k] x[n-k] - sum_{k=1..order} a[k] y[n-k],
+ * zero initial state; b, a [order+1] fp32 already normalised by a[0] (a[0] is not read), order 1..16; recursion state in fp64,
+ * parallel over time (chunked state-space scan, exact).  clamp: output clipped to [-1, 1] (lfilter's default, biquad); the
+ * forward then writes mask [B][L] = (|y| <= 1) if mask is not NULL.  adjoint=1: out = reverse(lfilter(reverse(g))), the
+ * transpose; with clamp the seed is first zeroed where mask is 0 (mask required).  x and y must not alias.  Workspace:
+ * babe_iir_workspace(B, L, order) bytes (-1 for bad arguments). */
+long babe_iir_workspace(int B, long L, int order);
+int babe_iir_filter(const float* x, long x_bs, float* y, long y_bs, int B, long L, const float* b, const float* a, int order,
+                    int clamp, int adjoint, unsigned char* mask, long mask_bs, void* workspace, long workspace_bytes, void* stream);
+/* Decimation x[..., 0:-1:factor]: adjoint=0 out[b][m] = in[b][m factor], m < L_dec (in has L_full samples); adjoint=1 the
+ * zero-stuffing transpose, in [B][L_dec] -> out [B][L_full].  Requires (L_dec - 1) factor < L_full. */
+int babe_decimate(const float* in, long in_bs, float* out, long out_bs, int B, long L_full, long L_dec, int factor, int adjoint,
+                  void* stream);
 
 /* ---- nested Winograd F(4,5) along frequency x F(4,3) along time for the same (5,3) convs as babe_conv2d_wino45 (Conv2d at
  * networks/cqtdiff+.py:79-88, 433-436): 3.0 multiplies per output instead of 4.5 (csrc/conv_wino85.hip).  Output-channel tiles of
