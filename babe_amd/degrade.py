@@ -1,7 +1,7 @@
-"""Known degradations of BlindSampler.predict_bwe beyond the FIR - the reference's 'cheby1' (torchaudio.functional.lfilter,
-clamp=False), 'biquad' (torchaudio.functional.biquad: lfilter with its default clamp=True), 'resample'
-(torchaudio.functional.resample(x, int(100 factor), 100)) and 'decimate' (x[..., 0:-1:factor]),
-testing/blind_bwe_sampler.py:219-230 - each as a forward A and its adjoint A^T on the HIP kernels of csrc/degrade.hip.
+"""The observation models y = A(x) the samplers guide against, each an object of one protocol (class Degradation below), and
+the kernels of the reference's 'cheby1' (torchaudio.functional.lfilter, clamp=False), 'biquad' (torchaudio.functional.biquad:
+lfilter with its default clamp=True), 'resample' (torchaudio.functional.resample(x, int(100 factor), 100)) and 'decimate'
+(x[..., 0:-1:factor]), testing/blind_bwe_sampler.py:219-230 - forward A and adjoint A^T on the HIP kernels of csrc/degrade.hip.
 
 Coefficients are prepared on the host the way lfilter sees them: rounded to float32 (`torch.Tensor(b)`), divided by a[0] in
 float32.  The recursion itself runs in float64 on the GPU.  Device tensors only, no CPU fallback."""
@@ -10,6 +10,7 @@ import torch
 
 from ._lib import check, lib, ptr, stream
 from .resample import resample, resample_adjoint, resampled_length
+from .stft import STFTOps, _register, fir_same, lincomb, mask_blend
 
 MAX_ORDER = 16
 
@@ -104,8 +105,116 @@ def decimate(x, factor, adjoint=False, length=None):
     return out.reshape(*shape[:-1], n_out)
 
 
-# ---- the degradation objects BlindSampler runs: fwd = A, adj = A^T ---------------------------------------------------------
-class IIRDegradation:
+def sumsq_partial(g, nblk=STFTOps.NBLK):
+    """Per-block partial sums of squares of g [B, n] -> [B, nblk] float64 (fixed-order: what the norm kernels reduce)."""
+    _register()
+    B, n = g.shape
+    part = torch.empty(B, nblk, device=g.device, dtype=torch.float64)
+    check(lib().babe_sumsq_partial(ptr(g), g.stride(0), ptr(part), nblk, B, n, stream()), "sumsq_partial")
+    return part
+
+
+# ---- the degradation objects the samplers run ----------------------------------------------------------------------------
+class Degradation:
+    """One observation model: fwd = A, adj = A^T, and the two compositions a score evaluation makes of them."""
+
+    post = False        # True: the guidance seed carries the overlap-add envelope (the STFT filter alone)
+
+    def residual(self, x, y):
+        """(r = y - A(x), the per-block sums of r^2 the guidance seed normalises with)."""
+        r = lincomb(torch.empty_like(y), 1.0, y, -1.0, self.fwd(x))
+        return r, sumsq_partial(r)
+
+    def guidance(self, x, y, seed):
+        """A^T applied to d(distance)/d(rec) at rec = A(x); seed(r, y, part, post) is the sampler's distance gradient.  y (and r,
+        the seed) may be shorter than x ('resample' / 'decimate'): A^T maps back to x's length."""
+        r, part = self.residual(x, y)
+        return self.adj(seed(r, y, part, self.post))
+
+    def fwd_dc(self, x):
+        """A(x) of the replacement data-consistency step x0 <- y + x0 - A(x0)."""
+        return self.fwd(x)
+
+    def bind(self, st, filter_params, B):
+        """This degradation for one evaluation (only a mix over the STFT filter depends on the evaluation's filter_params)."""
+        return self
+
+
+class FIRDegradation(Degradation):
+    """'firwin' / 'firwin_hpf': F.conv1d(padding="same") with the taps (:211-218; edm_sampler.py:245-252)."""
+
+    def __init__(self, taps, device):
+        self.taps = torch.as_tensor(taps, dtype=torch.float32).reshape(-1).contiguous().to(device)
+
+    def fwd(self, x):
+        return fir_same(x, self.taps)
+
+    def adj(self, g):
+        return fir_same(g, self.taps, adjoint=True)
+
+
+class MaskDegradation(Degradation):
+    """A(x) = mask * x of edm_sampler.Sampler.predict_inpainting (edm_sampler.py:231-243); mask [L] or [B,L], self-adjoint."""
+
+    def __init__(self, mask, device):
+        self.mask = torch.as_tensor(mask, dtype=torch.float32).contiguous().to(device)
+
+    def fwd(self, x):
+        return mask_blend(self.mask, x, None)
+
+    adj = fwd
+
+
+class STFTFilterDegradation(Degradation):
+    """The piecewise STFT-domain filter of filter_params [2,K] or [P,2,K] (blind and 'fc_A'; one filter per clip of the batch of B,
+    or one shared), built per evaluation.  spec: the STFT of the signal residual() will see, where the caller has taken it
+    already (the blind fit needs it first).  adj is the transpose up to the overlap-add envelope, which the seed carries."""
+
+    post = True
+
+    def __init__(self, st, filter_params, B, spec=None):
+        H = st.design_filter(torch.as_tensor(filter_params, dtype=torch.float32, device=st.dev))
+        self.st, self.spec, self.H = st, spec, H if (H.dim() == 1 or H.shape[0] == B) else H[0]
+
+    def _apply(self, spec, normalise, y=None):
+        return self.st.ola(self.st.filter_frames(spec, self.H), normalise=normalise, y=y)
+
+    def fwd(self, x):
+        return self._apply(self.st.stft(x), True)
+
+    def adj(self, g):
+        return self._apply(self.st.stft(g), False)
+
+    def residual(self, x, y):
+        return self._apply(self.spec if self.spec is not None else self.st.stft(x), True, y)      # (fused into the overlap-add)
+
+
+class MaskMixDegradation(Degradation):
+    """predict_bwe_AR (:280-288): mask*x + (1-mask)*A(x) with A = `inner` - a FIRDegradation, or None for the STFT filter of
+    the evaluation's filter_params ('fc_A'), which bind() builds."""
+
+    def __init__(self, mask, inner):
+        self.mask, self.inner = mask, inner
+
+    def bind(self, st, filter_params, B):
+        return self if self.inner is not None else MaskMixDegradation(self.mask, STFTFilterDegradation(st, filter_params, B))
+
+    def fwd(self, x):
+        return mask_blend(self.mask, x, self.inner.fwd(x))
+
+    def guidance(self, x, y, seed):
+        r, part = self.residual(x, y)
+        s = seed(r, y, part, False)                                      # -r/||r||: the observed part takes it as it is
+        gA = self.inner.adj(mask_blend(self.mask, None, seed(r, y, part, True) if self.inner.post else s))
+        return lincomb(torch.empty_like(gA), 1.0, mask_blend(self.mask, s, None), 1.0, gA)
+
+    def fwd_dc(self, x):
+        # The classic replacement step of an AR run (posterior_sampling.data_consistency on, inpaint_DC off) applies the inner
+        # filter WITHOUT the mask mix the guidance uses (the reference has no working step in that configuration).  Kept as is.
+        return self.inner.fwd(x)
+
+
+class IIRDegradation(Degradation):
     """'cheby1' (clamp=False) or 'biquad' (clamp=True).  The clamp mask of the LAST forward is what adj() differentiates
     through - the sampler always runs A^T right after the A it belongs to."""
 
@@ -115,9 +224,9 @@ class IIRDegradation:
         self.clamp = bool(clamp)
         self.mask = None
 
-    def fwd(self, x, keep_mask=True):
+    def fwd(self, x):
         mask = None
-        if self.clamp and keep_mask:
+        if self.clamp:
             mask = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
             self.mask = mask
         return iir_filter(x, self.b, self.a, clamp=self.clamp, mask=mask, prepared=True)
@@ -126,7 +235,7 @@ class IIRDegradation:
         return iir_filter(g, self.b, self.a, clamp=self.clamp, adjoint=True, mask=self.mask, prepared=True)
 
 
-class ResampleDegradation:
+class ResampleDegradation(Degradation):
     """'resample': torchaudio.functional.resample(x, orig_freq=int(100 factor), new_freq=100); y is shorter than x."""
 
     def __init__(self, factor, length):
@@ -135,14 +244,14 @@ class ResampleDegradation:
     def out_length(self):
         return resampled_length(self.length, self.orig, self.new)
 
-    def fwd(self, x, keep_mask=True):
+    def fwd(self, x):
         return resample(x, self.orig, self.new)
 
     def adj(self, g):
         return resample_adjoint(g, self.orig, self.new, self.length)
 
 
-class DecimateDegradation:
+class DecimateDegradation(Degradation):
     """'decimate': x[..., 0:-1:factor]; y is shorter than x."""
 
     def __init__(self, factor, length):
@@ -151,8 +260,29 @@ class DecimateDegradation:
     def out_length(self):
         return decimated_length(self.length, self.factor)
 
-    def fwd(self, x, keep_mask=True):
+    def fwd(self, x):
         return decimate(x, self.factor)
 
     def adj(self, g):
         return decimate(g, self.factor, adjoint=True, length=self.length)
+
+
+def make_degradation(filt, filt_type, device, length=None):
+    """(filt, filt_type) of predict_bwe / predict_bwe_AR -> (degradation, filter_params [1,2,K] on `device`); the degradation is
+    None for 'fc_A', the STFT filter of the returned filter_params.  length: the state's, for 'resample' / 'decimate'."""
+    if filt_type == "fc_A":
+        p = torch.as_tensor(filt, dtype=torch.float32)
+        return None, (p.unsqueeze(1) if p.dim() == 1 else p).unsqueeze(0).contiguous().to(device)
+    if filt_type in ("firwin", "firwin_hpf"):
+        deg = FIRDegradation(filt, device)
+    elif filt_type == "cheby1":
+        deg = IIRDegradation(*filt, clamp=False, device=device)
+    elif filt_type == "biquad":
+        c6 = [float(torch.as_tensor(v).reshape(-1)[0]) for v in filt]       # torch.Tensor(b0) ... as float32 (:228-236)
+        deg = IIRDegradation(c6[:3], c6[3:], clamp=True, device=device)
+    elif filt_type in ("resample", "decimate"):
+        deg = (ResampleDegradation if filt_type == "resample" else DecimateDegradation)(filt, length)
+    else:
+        raise NotImplementedError(f"filt_type={filt_type!r}: 'fc_A', 'firwin', 'firwin_hpf', 'cheby1', 'biquad', 'resample' and "
+                                  f"'decimate' run on the HIP path")
+    return deg, torch.zeros(1, 2, 1, device=device)

@@ -19,13 +19,13 @@ high-pass, UNet input-VJP).  All tensor work is C-ABI calls; the host only seque
   'per_clip'  - every clip has its own filter and guidance norm (== the reference run at B=1 per
                 clip); this is what independent-clip batching/sharding uses.  Identical at B=1.
 """
+import contextlib
 import os
 
-import numpy as np
 import torch
 
-from ..degrade import DecimateDegradation, IIRDegradation, ResampleDegradation
-from ..stft import STFTOps, add_obs_noise, fir_same, lincomb, make_fit_cfg, mask_blend
+from ..degrade import MaskMixDegradation, STFTFilterDegradation, make_degradation, sumsq_partial
+from ..stft import STFTOps, add_obs_noise, freq_weights, lincomb, make_fit_cfg, mask_blend
 from .._lib import check, lib, ptr, stream
 
 # Every score evaluation of the default configuration is ONE library call (csrc/score_eval.hip through testing/eval_c.py: the path
@@ -40,6 +40,7 @@ class BlindSampler:
     SCORE_MODE = 0          # guidance scaling of blind_bwe_sampler.py:125-135
 
     obs_snr, sigma_den = None, 0.0        # (class defaults: testing/edm_sampler.Sampler has no observation-noise options)
+    _lane_streams, fc_s, A_s = None, None, None        # (made on first use: _sample_lanes, compute_sweep)
 
     def __init__(self, model, diff_params, args, rid=False, batch_semantics="per_clip", noise_device="cpu",
                  max_segments_in_flight=32):
@@ -48,18 +49,8 @@ class BlindSampler:
         segment between forward and VJP, so 32 in flight = 115 GB of the 288 GB).  Ignored for 'reference' semantics,
         where the clips of a batch are coupled through the shared filter."""
         self.max_in_flight = int(max_segments_in_flight)
-        self.model = model
-        self.diff_params = diff_params
-        self.args = args
-        if not args.tester.diff_params.same_as_training:
-            self.update_diff_params()
+        self._init_common(model, diff_params, args, batch_semantics, noise_device)
         ps = args.tester.posterior_sampling
-        self.order = args.tester.order
-        self.xi = ps.xi
-        self.data_consistency = ps.data_consistency
-        self._dc_cfg = bool(ps.data_consistency)       # the blind loop reads the CONFIG value (:704, :748), never the
-        # attribute that predict_bwe_AR flips for good (:300); the known-filter loop reads the attribute (:178)
-        self.nb_steps = args.tester.T
         bb = args.tester.blind_bwe
         self.mu = [bb.optimization.mu[0], bb.optimization.mu[1]]
         self.fcmin = bb.fcmin
@@ -89,20 +80,39 @@ class BlindSampler:
         self.obs_snr = None if snr_db == "None" else 10.0 ** (float(snr_db) / 10.0)
         self.sigma_den = float(bb.get("sigma_den_estimate", 0) or 0)
 
-        assert batch_semantics in ("per_clip", "reference")
-        self.batch_semantics = batch_semantics
-        self.noise_device = noise_device
         self.fit_cfg = make_fit_cfg(mu=self.mu, tol=self.tol, max_iter=bb.optimization.max_iter, fcmin=self.fcmin,
                                     fcmax=self.fcmax, Amin=self.Amin, Amax=self.Amax,
                                     clamp_fc=bb.optimization.clamp_fc, clamp_A=bb.optimization.clamp_A,
                                     only_negative_A=bb.optimization.only_negative_A,
                                     weighting=ps.freq_weighting_filter)
+
+    def _init_common(self, model, diff_params, args, batch_semantics, noise_device):
+        """The state BlindSampler and testing/edm_sampler.Sampler share (both constructors call this)."""
+        assert batch_semantics in ("per_clip", "reference")
+        self.model, self.diff_params, self.args = model, diff_params, args
+        if not args.tester.diff_params.same_as_training:
+            self.update_diff_params()
+        self.order = args.tester.order
+        self.nb_steps = args.tester.T
+        self.xi = args.tester.posterior_sampling.xi
+        self.data_consistency = args.tester.posterior_sampling.data_consistency
+        self._dc_cfg = bool(self.data_consistency)     # the blind loop reads the CONFIG value (:704, :748), never the
+        # attribute that predict_bwe_AR flips for good (:300); the known-filter loop reads the attribute (:178)
+        self.batch_semantics, self.noise_device = batch_semantics, noise_device
         self._stft = None
         self._ceval = {}               # BABE_EVAL_C=1: one library-side evaluation descriptor per lane (testing/eval_c.py)
-        self.fir_taps = None
-        self.degr = None               # predict_bwe's other known degradations (babe_amd/degrade.py): .fwd = A, .adj = A^T
-        self.ar_mask = None            # predict_bwe_AR: degradation(x) = mask*x + (1-mask)*A(x)
-        self.dc = None                 # (smooth_mask, y_smooth_masked) of the replacement data-consistency step
+        self.degradation = None        # the observation model of the running call (babe_amd/degrade.py); None = the STFT
+        # filter of the current filter_params (blind and 'fc_A')
+        self.dc = None                 # (smooth_mask, y_smooth_masked) of predict_bwe_AR's replacement data-consistency step
+
+    @contextlib.contextmanager
+    def _guiding(self, degradation, dc=None):
+        """Every entry point that samples against a known degradation sets it here and leaves the sampler clean."""
+        self.degradation, self.dc = degradation, dc
+        try:
+            yield
+        finally:
+            self.degradation, self.dc = None, None
 
     def update_diff_params(self):
         dp, src = self.diff_params, self.args.tester.diff_params
@@ -120,19 +130,12 @@ class BlindSampler:
             return torch.randn(shape).to(device)          # reference: CPU draw then copy (:513, edm.py:105)
         return torch.randn(shape, device=device)
 
-    def _sumsq(self, g):
-        B, n = g.shape
-        part = torch.empty(B, self.NBLK, device=g.device, dtype=torch.float64)
-        check(lib().babe_sumsq_partial(ptr(g), g.stride(0), ptr(part), self.NBLK, B, n, stream()), "sumsq_partial")
-        return part
-
-    def _seed(self, st, r, y, part, post):
-        """d(distance)/d(rec) for the configured guidance distance (get_rec_grads :99-117)."""
+    def _seed(self, r, y, part, post):
+        """d(distance)/d(rec) for the configured guidance distance (get_rec_grads :99-117), from r = y - rec."""
+        st = self._stft
         if self.stft_dist is not None:
             sd = self.stft_dist
             if sd.get("ops") is None or sd["ops"].L != r.shape[1] or sd["ops"].dev != r.device:
-                from ..stft import STFTOps
-                from ..stft import freq_weights
                 sd["ops"] = STFTOps(sd["nfft"], r.shape[1], self.args.exp.sample_rate, r.device)
                 sd["w"] = freq_weights(sd["ops"].nbins, sd["weight"]).to(r.device)
             rec = lincomb(torch.empty_like(r), 1.0, y, -1.0, r)             # r = y - rec
@@ -140,15 +143,12 @@ class BlindSampler:
             return st.residual_seed(g, None, post=post, norm="ready") if post else g
         return st.residual_seed(r, part, post=post, norm=self.norm, y=y, beta=self.smoothl1_beta)
 
-    def _known(self):
-        """True while a known degradation with forward and adjoint runs: the FIR taps or one of self.degr."""
-        return self.fir_taps is not None or self.degr is not None
-
-    def _A(self, x):
-        return fir_same(x, self.fir_taps) if self.fir_taps is not None else self.degr.fwd(x)
-
-    def _At(self, g):
-        return fir_same(g, self.fir_taps, adjoint=True) if self.fir_taps is not None else self.degr.adj(g)
+    def _degradation(self, st, filter_params, B, spec=None):
+        """The observation model of one evaluation: the one the entry point set, or the STFT filter of filter_params
+        (spec: the STFT of the estimate, which the caller has taken already)."""
+        if self.degradation is None:
+            return STFTFilterDegradation(st, filter_params, B, spec)
+        return self.degradation.bind(st, filter_params, B)
 
     def _lane_kw(self, lane):
         return {"lane": lane} if (lane is not None and getattr(self.model, "supports_lanes", False)) else {}
@@ -193,71 +193,36 @@ class BlindSampler:
                 return ce(self, x, t, y, specY, filter_params, blind)
         x_den = self.get_denoised_estimate(x, t, lane)
         cskip, cout, cin = self._c
-        specX_fit = None
+        fitted = False
         if y is not None and (self.obs_snr is not None or (blind and self.sigma_den)):
             # reference order of the draws inside one evaluation: fit_params (y, then the denoised estimate), get_rec_grads (y)
             if blind:
                 if self.obs_snr is not None:
                     add_obs_noise(y, self._randn(y.shape, y.device).contiguous(), self.obs_snr)
                     specY = st.stft(y)
+                den_fit = x_den
                 if self.sigma_den:
                     den_fit = lincomb(torch.empty_like(x_den), 1.0, x_den, self.sigma_den, self._randn(x_den.shape, x_den.device).contiguous())
-                    specX_fit = st.stft(den_fit)
-                else:
-                    specX_fit = st.stft(x_den)
-                filter_params, self.last_n_iter = self.fit_params(specX_fit, specY, filter_params)
+                filter_params, self.last_n_iter = self.fit_params(st.stft(den_fit), specY, filter_params)
+                fitted = True
             if self.obs_snr is not None:
                 add_obs_noise(y, self._randn(y.shape, y.device).contiguous(), self.obs_snr)
         if y is None:
             # unconditional (get_score :160-170): d = -t*(x_den - x)/t^2
             return lincomb(torch.empty_like(x), 1.0 / float(t), x, -1.0 / float(t), x_den), x_den, filter_params
-        if self.ar_mask is not None:
-            # mask-mixed degradation of predict_bwe_AR (:280-288): mask*x + (1-mask)*A(x), A = fc_A filter or FIR
-            m = self.ar_mask
-            if self.fir_taps is not None:
-                rec0 = fir_same(x_den, self.fir_taps)
-            else:
-                H = st.design_filter(filter_params)
-                Hq = H if H.shape[0] == B else H[0]
-                rec0 = st.ola(st.filter_frames(st.stft(x_den), Hq), normalise=True)
-            rec = mask_blend(m, x_den, rec0)
-            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, rec)
-            part = self._sumsq(r)
-            seed_raw = self._seed(st, r, y, part, post=False)                # -r/||r||
-            if self.fir_taps is not None:
-                gA = fir_same(mask_blend(m, None, seed_raw), self.fir_taps, adjoint=True)
-            else:
-                u = mask_blend(m, None, self._seed(st, r, y, part, post=True))
-                gA = st.ola(st.filter_frames(st.stft(u), Hq), normalise=False)
-            g_den = lincomb(torch.empty_like(gA), 1.0, mask_blend(m, seed_raw, None), 1.0, gA)
-        elif getattr(self, "inpaint_mask", None) is not None:
-            # masking degradation of edm_sampler.Sampler.predict_inpainting (edm_sampler.py:231-243): A(x) = mask * x, self-adjoint
-            m = self.inpaint_mask
-            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, mask_blend(m, x_den, None))
-            g_den = mask_blend(m, self._seed(st, r, y, self._sumsq(r), post=False), None)
-        elif self._known():
-            # known degradation (edm_sampler.py:245-252; blind_bwe_sampler.py:211-230): residual, then the transpose.  For
-            # 'resample' / 'decimate' y (and r, seed) are shorter than x; A^T maps back to x's length
-            rec = self._A(x_den)
-            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, rec)
-            seed = self._seed(st, r, y, self._sumsq(r), post=False)
-            g_den = self._At(seed)
-        else:
-            specX = st.stft(x_den)
-            if blind and specX_fit is None:
-                filter_params, self.last_n_iter = self.fit_params(specX, specY, filter_params)
-            H = st.design_filter(filter_params)                     # [P,nbins]
-            Hq = H if H.shape[0] == B else H[0]
-            # reconstruction guidance: forward residual and hand-wired VJP
-            r, part = st.ola(st.filter_frames(specX, Hq), normalise=True, y=y)
-            seed = self._seed(st, r, y, part, post=True)
-            g_den = st.ola(st.filter_frames(st.stft(seed), Hq), normalise=False)
+        spec = None
+        if self.degradation is None:
+            spec = st.stft(x_den)               # (taken again after a fit on the noisy estimate above, like the reference)
+            if blind and not fitted:
+                filter_params, self.last_n_iter = self.fit_params(spec, specY, filter_params)
+        # reconstruction guidance: forward residual and hand-wired VJP of the degradation
+        g_den = self._degradation(st, filter_params, B, spec).guidance(x_den, y, self._seed)
         if self.args.tester.filter_out_cqt_DC_Nyq:
             g_den = cq.apply_hpf_DC(g_den)                      # zero-phase real filter: self-adjoint
         g_net = lincomb(torch.empty_like(g_den), cout, g_den)
         g_xin = self.model.vjp(g_net, **self._lane_kw(lane))
         g_x = lincomb(torch.empty_like(g_den), cskip, g_den, cin, g_xin)
-        gpart = self._sumsq(g_x)
+        gpart = sumsq_partial(g_x, self.NBLK)
         d = torch.empty_like(x)
         check(lib().babe_score_direction(ptr(x_den), ptr(x), ptr(g_x), ptr(gpart), self.NBLK, ptr(d), float(t),
                                          float(self.xi), float(self.args.exp.audio_len),
@@ -274,13 +239,7 @@ class BlindSampler:
             # posterior_sampling.data_consistency (conf/tester/blind_bwe_DC.yaml, bwe_formal_1000_DC.yaml): the classic
             # replacement x0 <- y + x0 - A(x0) with the CURRENT degradation (:63-73; :178-188, :704-709, :748-753)
             x0 = lincomb(torch.empty_like(x), 1.0, x, -float(t), d)
-            if getattr(self, "inpaint_mask", None) is not None:
-                a0 = mask_blend(self.inpaint_mask, x0, None)
-            elif self._known():
-                a0 = self._A(x0)
-            else:
-                H = st.design_filter(filter_params)
-                a0 = st.ola(st.filter_frames(st.stft(x0), H if H.shape[0] == B else H[0]), normalise=True)
+            a0 = self._degradation(st, filter_params, B).fwd_dc(x0)
             x0 = lincomb(torch.empty_like(x), 1.0, x0, 1.0, y, -1.0, a0)
             d = lincomb(torch.empty_like(x), 1.0 / float(t), x, -1.0 / float(t), x0)
         return d, x_den, filter_params
@@ -291,18 +250,36 @@ class BlindSampler:
         (move_timestep :509-516), score evaluation, 2nd-order correction unless t_next == 0 or order == 1.
         Returns (x_next, filter_params, rec) with rec = dict(x_hat, t_hat, x_den, d) of the first evaluation.
         Exposed so that a step can be teacher-forced from recorded reference state (tests/test_gpu_sampler.py)."""
-        t_hat = t_i + gamma_i * t_i
-        x_hat = lincomb(torch.empty_like(x), 1.0, x, float((t_hat ** 2 - t_i ** 2) ** (1 / 2)) * float(snoise), eps)
-        d, x_den, filter_params = self.evaluate(x_hat, float(t_hat), y, specY, filter_params, blind, lane)
-        rec = dict(x_hat=x_hat, t_hat=float(t_hat), x_den=x_den, d=d, filter_params=filter_params)
-        h = float(t_next - t_hat)
-        if float(t_next) != 0 and self.order == 2:
-            x_prime = lincomb(torch.empty_like(x), 1.0, x_hat, h, d)
-            d2, _, filter_params = self.evaluate(x_prime, float(t_next), y, specY, filter_params, blind, lane)
-            x = lincomb(torch.empty_like(x), 1.0, x_hat, 0.5 * h, d, 0.5 * h, d2)
-        else:
-            x = lincomb(torch.empty_like(x), 1.0, x_hat, h, d)
-        return x, filter_params, rec
+        s = dict(x=x, fp=filter_params)
+        ev = lambda x_, t_, fp: self.evaluate(x_, t_, y, specY, fp, blind, lane)
+        self._heun_first(s, t_i, gamma_i, t_next, eps, snoise, ev)
+        rec = dict(x_hat=s["x_hat"], t_hat=float(s["t_hat"]), x_den=s["x_den"], d=s["d"], filter_params=s["fp"])
+        self._heun_second(s, t_next, ev)
+        return s["x"], s["fp"], rec
+
+    # The stochastic Heun step in two halves on a state dict s (keys x, fp; the halves keep x_hat, t_hat, d, x_den in it), because
+    # the lanes interleave the halves of different clips.  ev(x, t, filter_params) is the caller's score evaluation.
+    def _inject(self, x, t, gamma, eps, snoise):
+        """(move_timestep :509-516) -> (x_hat = x + sqrt(t_hat^2 - t^2) * snoise * eps, t_hat = t + gamma t)."""
+        t_hat = t + gamma * t
+        return lincomb(torch.empty_like(x), 1.0, x.contiguous(), float((t_hat ** 2 - t ** 2) ** (1 / 2)) * float(snoise), eps), t_hat
+
+    def _heun_first(self, s, t_i, gamma_i, t_next, eps, snoise, ev):
+        """Noise injection (eps None: none, the state is evaluated as it is at t_i), first score evaluation, and the Euler update
+        when the step has no correction (t_next == 0 or order 1)."""
+        s["x_hat"], s["t_hat"] = (s["x"], t_i) if eps is None else self._inject(s["x"], t_i, gamma_i, eps, snoise)
+        s["d"], s["x_den"], s["fp"] = ev(s["x_hat"], float(s["t_hat"]), s["fp"])
+        s["heun"] = float(t_next) != 0 and self.order == 2
+        if not s["heun"]:
+            s["x"] = lincomb(torch.empty_like(s["x_hat"]), 1.0, s["x_hat"], float(t_next - s["t_hat"]), s["d"])
+
+    def _heun_second(self, s, t_next, ev):
+        """The Heun correction (nothing where the first half made the Euler update)."""
+        if s["heun"]:
+            h = float(t_next - s["t_hat"])
+            x_prime = lincomb(torch.empty_like(s["x_hat"]), 1.0, s["x_hat"], h, s["d"])
+            d2, _, s["fp"] = ev(x_prime, float(t_next), s["fp"])
+            s["x"] = lincomb(torch.empty_like(x_prime), 1.0, s["x_hat"], 0.5 * h, s["d"], 0.5 * h, d2)
 
     def _sample(self, y, filter_params, blind, rid, snoise=1.0, shape=None, device=None, diag=(False, False)):
         """y None: unconditional sampling of `shape` on `device` (predict_unconditional :366-374).
@@ -320,7 +297,7 @@ class BlindSampler:
         B, L = shape
         with torch.cuda.device(device):
             st = self.stft_ops(L, device)
-            specY = st.stft(y) if (y is not None and not self._known()) else None
+            specY = st.stft(y) if (y is not None and self.degradation is None) else None     # (the filter fit and the library evaluation read it)
             T = self.nb_steps
             if rid:
                 data_denoised = torch.zeros((T, B, L))
@@ -384,10 +361,7 @@ class BlindSampler:
     # ---- the reference's helper methods under their own names and signatures (third-party code that pokes at the sampler)
     def move_timestep(self, x, t, gamma, Snoise=1):
         """(:509-516) x_hat = x + sqrt(t_hat^2 - t^2) * Snoise * eps, t_hat = t + gamma t; the noise is drawn here, like there."""
-        t_hat = t + gamma * t
-        eps = self._randn(tuple(x.shape), x.device).contiguous()
-        x_hat = lincomb(torch.empty_like(x), 1.0, x.contiguous(), float((t_hat ** 2 - t ** 2) ** (1 / 2)) * float(Snoise), eps)
-        return x_hat, t_hat
+        return self._inject(x, t, gamma, self._randn(tuple(x.shape), x.device).contiguous(), Snoise)
 
     def apply_filter_fcA(self, x, filter_params):
         """(:518-520) x [B,L] through the piecewise filter filter_params [2,K]."""
@@ -409,21 +383,14 @@ class BlindSampler:
         the LAST get_denoised_estimate(x, t) call returned: where the reference differentiates through the network with autograd,
         this runs the network's hand-wired VJP on the state that call left (so it must directly follow it, as in the reference's
         get_score).  L2 norm and STFT-domain low-pass A = filter_params [2,K] (or the known degradation predict_bwe(..., 'firwin' /
-        'cheby1' / 'biquad' / 'resample' / 'decimate') sets);
+        'cheby1' / 'biquad' / 'resample' / 'decimate') sets while it runs);
         `degradation` is accepted for the signature and not called.  The sampling loop does the same inside evaluate()."""
         if self.norm != 2 or self.stft_dist is not None or self.obs_snr is not None:
             raise NotImplementedError("get_rec_grads helper: default guidance distance only (the sampling loop handles the others)")
         st = self.stft_ops(y.shape[-1], y.device)
         cskip, cout, cin = self._c
         x_hat, y = x_hat.contiguous(), y.contiguous()
-        if self._known():
-            r = lincomb(torch.empty_like(y), 1.0, y, -1.0, self._A(x_hat))
-            g_den = self._At(self._seed(st, r, y, self._sumsq(r), post=False))
-        else:
-            H = st.design_filter(torch.as_tensor(filter_params, dtype=torch.float32, device=y.device))
-            Hq = H[0] if (H.dim() == 2 and H.shape[0] != x_hat.shape[0]) else H
-            r, part = st.ola(st.filter_frames(st.stft(x_hat), Hq), normalise=True, y=y)
-            g_den = st.ola(st.filter_frames(st.stft(self._seed(st, r, y, part, post=True)), Hq), normalise=False)
+        g_den = self._degradation(st, filter_params, x_hat.shape[0]).guidance(x_hat, y, self._seed)
         if self.args.tester.filter_out_cqt_DC_Nyq:
             g_den = self.model.CQTransform.apply_hpf_DC(g_den)
         g_xin = self.model.vjp(lincomb(torch.empty_like(g_den), cout, g_den))
@@ -436,7 +403,7 @@ class BlindSampler:
         (15 x 12, one break point): returns (norms [15,12], grads [15,12,2]) on the host.  One launch evaluates all 180 points
         from the per-bin sufficient statistics (babe_filter_loss_grad); the reference runs 180 autograd passes."""
         st = self.stft_ops(y.shape[-1], y.device)
-        if getattr(self, "fc_s", None) is None:
+        if self.fc_s is None:
             self.fc_s, self.A_s = torch.logspace(2.5, 4, 15), torch.linspace(-80, -5, 12)
         stats = st.mag_stats(st.stft(denoised_estimate.contiguous()), st.stft(y.contiguous()), shared=True)
         nf, na = self.fc_s.numel(), self.A_s.numel()
@@ -457,27 +424,8 @@ class BlindSampler:
     def _use_lanes(self, B, y, rid, filter_params):
         return (self.LANES > 1 and B >= 2 and y is not None and not rid and self.batch_semantics == "per_clip" and
                 getattr(self.model, "supports_lanes", False) and
-                self.ar_mask is None and self.dc is None and self.obs_snr is None and not self.sigma_den and
-                not self._known() and filter_params.shape[0] == B)
-
-    def _lane_step(self, ln, i, t, gamma, noise, blind, snoise, half):
-        """One half of stochastic Heun step i on lane `ln` (enqueued on the current stream): half 0 = noise injection +
-        first score evaluation (+ the Euler update when the step has no correction), half 1 = the Heun correction."""
-        t_hat = t[i] + gamma[i] * t[i]
-        h = float(t[i + 1] - t_hat)
-        heun = float(t[i + 1]) != 0 and self.order == 2
-        if half == 0:
-            eps = noise[ln["sl"]]
-            x_hat = lincomb(torch.empty_like(ln["x"]), 1.0, ln["x"].contiguous(),
-                            float((t_hat ** 2 - t[i] ** 2) ** (1 / 2)) * float(snoise), eps)
-            d, _, ln["fp"] = self.evaluate(x_hat, float(t_hat), ln["y"], ln["specY"], ln["fp"], blind, ln["k"])
-            ln["x_hat"], ln["d"] = x_hat, d
-            if not heun:
-                ln["x"] = lincomb(torch.empty_like(x_hat), 1.0, x_hat, h, d)
-        elif heun:
-            x_prime = lincomb(torch.empty_like(ln["x_hat"]), 1.0, ln["x_hat"], h, ln["d"])
-            d2, _, ln["fp"] = self.evaluate(x_prime, float(t[i + 1]), ln["y"], ln["specY"], ln["fp"], blind, ln["k"])
-            ln["x"] = lincomb(torch.empty_like(x_prime), 1.0, ln["x_hat"], 0.5 * h, ln["d"], 0.5 * h, d2)
+                self.degradation is None and self.dc is None and self.obs_snr is None and not self.sigma_den and
+                filter_params.shape[0] == B)
 
     # (Rounds 2-4 carried an opt-in HIP-graph replay of the lanes' Heun steps, BABE_SAMPLER_GRAPHS=1.  Measured again on the
     # driver's command in round 5, same box: 2.129 (graphs) vs 2.140 / 2.140 (eager) audio-sec/s - the eager loop has no host
@@ -495,7 +443,7 @@ class BlindSampler:
         nl = min(self.LANES, B) if lanes_ok else 1
         per = -(-B // nl)
         main = torch.cuda.current_stream(dev)
-        if getattr(self, "_lane_streams", None) is None or len(self._lane_streams) < nl:
+        if self._lane_streams is None or len(self._lane_streams) < nl:
             self._lane_streams = [torch.cuda.Stream(device=dev) for _ in range(nl)]
         noises = [self._randn((B, L), dev).contiguous() for _ in range(T)]          # reference order: one draw per step
         lanes = []
@@ -510,9 +458,13 @@ class BlindSampler:
             ln["st"].wait_event(ready)
         for i in range(T):
             for half in (0, 1):                                # first evaluation of step i lane after lane, then the second
-                for ln in lanes:
+                for ln in lanes:               # (half 0 ends with the Euler update when step i has no correction)
+                    ev = lambda x_, t_, fp, ln=ln: self.evaluate(x_, t_, ln["y"], ln["specY"], fp, blind, ln["k"])
                     with torch.cuda.stream(ln["st"]):
-                        self._lane_step(ln, i, t, gamma, noises[i], blind, snoise, half)
+                        if half == 0:
+                            self._heun_first(ln, t[i], gamma[i], t[i + 1], noises[i][ln["sl"]], snoise, ev)
+                        else:
+                            self._heun_second(ln, t[i + 1], ev)
         for ln in lanes:
             done = torch.cuda.Event()
             done.record(ln["st"])
@@ -550,63 +502,26 @@ class BlindSampler:
         int(100 factor) -> 100, :228-230) or 'decimate' (filt = factor: x[..., 0:-1:factor], :225-226).  rid=True returns
         (x, data_denoised, data_score, t) like predict - except for 'resample' / 'decimate', which run predict_resample
         (:376-385): state of shape (B, audio_len), y shorter, x returned alone whatever rid is."""
-        dev = ylpf.device
+        L = int(self.args.exp.audio_len)
+        deg, params = make_degradation(filt, filt_type, ylpf.device, L)
+        kw = dict(diag=(bool(test_filter_fit), bool(compute_sweep)))
         if filt_type in ("resample", "decimate"):
-            return self._predict_resample(ylpf, filt, filt_type)
-        self.degr = None
-        if filt_type in ("cheby1", "biquad"):
-            if filt_type == "cheby1":
-                b, a = filt
-                b, a = torch.as_tensor(np.asarray(b, dtype=np.float64)).float(), torch.as_tensor(np.asarray(a, dtype=np.float64)).float()
-            else:
-                c6 = [float(torch.as_tensor(v).reshape(-1)[0]) for v in filt]       # torch.Tensor(b0) ... as float32 (:228-236)
-                b, a = torch.tensor(c6[:3], dtype=torch.float32), torch.tensor(c6[3:], dtype=torch.float32)
-            self.degr = IIRDegradation(b, a, clamp=(filt_type == "biquad"), device=dev)
-            self.fir_taps = None
-            params = torch.zeros(1, 2, 1, device=dev)
-        elif filt_type == "fc_A":
-            p = torch.as_tensor(filt, dtype=torch.float32)
-            if p.dim() == 1:
-                p = p.unsqueeze(1)
-            params = p.unsqueeze(0).contiguous().to(dev)
-            self.fir_taps = None
-        elif filt_type in ("firwin", "firwin_hpf"):
-            self.fir_taps = torch.as_tensor(filt, dtype=torch.float32).reshape(-1).contiguous().to(dev)
-            params = torch.zeros(1, 2, 1, device=dev)
-        else:
-            raise NotImplementedError(f"filt_type={filt_type!r}: 'fc_A' and 'firwin' run on the HIP path (the IIR / "
-                                      f"resample degradations are torchaudio paths no target config uses)")
-        try:
-            res = self._sample(ylpf, params, blind=False, rid=rid, snoise=self.diff_params.Snoise,
-                               diag=(bool(test_filter_fit), bool(compute_sweep)))
-        finally:
-            self.fir_taps, self.degr = None, None
+            # predict_resample (:376-385) -> predict(shape, device): rid, test_filter_fit and compute_sweep are not passed on there.
+            # The reference adds y to the initial noise with start_sigma and to A(x0) with data_consistency - shapes that differ
+            # here, so it fails: refused up front instead.
+            if self.start_sigma is not None:
+                raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.start_sigma must be None (y has fewer samples "
+                                 f"than the state of shape (B, audio_len); the reference fails on that shape mismatch)")
+            if self.data_consistency:
+                raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.data_consistency is not available (y has fewer "
+                                 f"samples than the state; the reference fails on that shape mismatch)")
+            if ylpf.shape[-1] != deg.out_length():
+                raise ValueError(f"predict_bwe(..., {filt_type!r}): y has {ylpf.shape[-1]} samples, the degradation of audio_len = {L} "
+                                 f"yields {deg.out_length()}")
+            rid, kw = False, dict(shape=(ylpf.shape[0], L))
+        with self._guiding(deg):
+            res = self._sample(ylpf, params, blind=False, rid=rid, snoise=self.diff_params.Snoise, **kw)
         return res if rid else res[0]
-
-    def _predict_resample(self, ylpf, filt, filt_type):
-        """predict_bwe(..., 'resample' / 'decimate') -> predict_resample (:376-385) -> predict(shape, device): rid, test_filter_fit
-        and compute_sweep are not passed on there.  The reference adds y to the initial noise with start_sigma and to A(x0) with
-        data_consistency - shapes that differ here, so it fails: refused up front instead."""
-        if self.start_sigma is not None:
-            raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.start_sigma must be None (y has fewer samples "
-                             f"than the state of shape (B, audio_len); the reference fails on that shape mismatch)")
-        if self.data_consistency:
-            raise ValueError(f"predict_bwe(..., {filt_type!r}): posterior_sampling.data_consistency is not available (y has fewer "
-                             f"samples than the state; the reference fails on that shape mismatch)")
-        B, L = ylpf.shape[0], int(self.args.exp.audio_len)
-        self.degr = ResampleDegradation(filt, L) if filt_type == "resample" else DecimateDegradation(filt, L)
-        if ylpf.shape[-1] != self.degr.out_length():
-            n = self.degr.out_length()
-            self.degr = None
-            raise ValueError(f"predict_bwe(..., {filt_type!r}): y has {ylpf.shape[-1]} samples, the degradation of audio_len = {L} "
-                             f"yields {n}")
-        self.fir_taps = None
-        try:
-            res = self._sample(ylpf, torch.zeros(1, 2, 1, device=ylpf.device), blind=False, rid=False,
-                               snoise=self.diff_params.Snoise, shape=(B, L))
-        finally:
-            self.degr = None
-        return res[0]
 
     def predict_unconditional(self, shape, device, rid=False):
         """Unguided sampling from the prior (:366-374): score = (D(x) - x)/t^2, no observations."""
@@ -642,27 +557,15 @@ class BlindSampler:
         ylpf = ylpf.contiguous().float()
         mask = mask.to(dev).float().contiguous()
         y_masked = y_masked.to(dev).float().contiguous()
-        B, L = ylpf.shape
-        if filt_type == "fc_A":
-            p = torch.as_tensor(filt, dtype=torch.float32)
-            if p.dim() == 1:
-                p = p.unsqueeze(1)
-            params = p.unsqueeze(0).contiguous().to(dev)
-            self.fir_taps = None
-        elif filt_type == "firwin":
-            self.fir_taps = torch.as_tensor(filt, dtype=torch.float32).reshape(-1).contiguous().to(dev)
-            params = torch.zeros(1, 2, 1, device=dev)
-        else:
+        if filt_type not in ("fc_A", "firwin"):
             raise NotImplementedError(filt_type)
+        inner, params = make_degradation(filt, filt_type, dev)
         y = mask_blend(mask, y_masked, ylpf)
-        self.ar_mask = mask
-        self.dc = None
+        dc = None
         if self.args.tester.complete_recording.inpaint_DC:
             sm = self.prepare_smooth_mask(mask, 50)
-            self.dc = (sm, mask_blend(sm, y_masked, None))
+            dc = (sm, mask_blend(sm, y_masked, None))
             self.data_consistency = True                      # the reference flips this permanently (:300)
-        try:
+        with self._guiding(MaskMixDegradation(mask, inner), dc):
             res = self._sample(y, params, blind=False, rid=rid, snoise=self.diff_params.Snoise)
-        finally:
-            self.ar_mask, self.dc, self.fir_taps = None, None, None
         return res if rid else res[0]

@@ -53,7 +53,7 @@ def supported(smp, y, blind):
     time-attention layers: those run on the Python sequencer)."""
     m = smp.model
     return (y is not None and smp.norm == 2 and smp.stft_dist is None and smp.obs_snr is None and not smp.sigma_den
-            and smp.ar_mask is None and smp.fir_taps is None and getattr(smp, "degr", None) is None and smp.dc is None and getattr(smp, "inpaint_mask", None) is None
+            and smp.degradation is None and smp.dc is None
             and not (smp._dc_cfg if blind else smp.data_consistency)
             and getattr(m, "precision", None) == "f32" and not getattr(m, "has_attention", False) and hasattr(m, "lane_engine") and cqt_plan_of(m.CQTransform) is not None)
 

@@ -188,7 +188,7 @@ def test_predict_bwe_iir_vs_reference_golden(name):
             assert rel(dscore[i][:, ::16], s[f"{name}_score_sub16"][i]) < 2e-3, i
     xs = x[:, ::4]
     assert rms_err(xs, s[f"{name}_x_sub4"]) < 1e-3 and rel(xs, s[f"{name}_x_sub4"]) < 2e-3
-    assert smp.degr is None
+    assert smp.degradation is None
 
 
 @pytest.mark.parametrize("ftype,filt", [("resample", 22050 / 4000), ("decimate", 2)])
@@ -203,12 +203,15 @@ def test_predict_bwe_resample_decimate_vs_reference_golden(ftype, filt):
 
 
 def test_library_evaluation_falls_back_for_the_new_degradations():
-    from babe_amd.degrade import DecimateDegradation, IIRDegradation
+    from babe_amd.degrade import (DecimateDegradation, FIRDegradation, IIRDegradation, MaskDegradation, MaskMixDegradation,
+                                  ResampleDegradation)
     from babe_amd.testing import eval_c
     smp = _sampler(0.05)
     y = torch.zeros(1, 92092, device="cuda")
-    smp.degr = IIRDegradation([0.5, 0.5], [1.0, -0.5], clamp=False, device="cuda")
-    assert not eval_c.supported(smp, y, False)
-    assert not smp._use_lanes(2, y, False, torch.zeros(2, 2, 1))
-    smp.degr = DecimateDegradation(2, 92092)
-    assert not eval_c.supported(smp, y, False)
+    fir, mask = FIRDegradation(torch.ones(5) / 5, "cuda"), torch.ones(1, 92092, device="cuda")
+    for deg in (IIRDegradation([0.5, 0.5], [1.0, -0.5], clamp=False, device="cuda"), DecimateDegradation(2, 92092),
+                ResampleDegradation(2.0, 92092), fir, MaskDegradation(mask, "cuda"), MaskMixDegradation(mask, fir),
+                MaskMixDegradation(mask, None)):
+        smp.degradation = deg
+        assert not eval_c.supported(smp, y, False), type(deg).__name__
+        assert not smp._use_lanes(2, y, False, torch.zeros(2, 2, 1)), type(deg).__name__

@@ -243,6 +243,7 @@ def test_predict_bwe_AR_T3_vs_reference_golden():
     smp._randn = lambda shape, device: next(it).to(device)
     x = smp.predict_bwe_AR(s["ylpf"].cuda(), y_masked.cuda(), torch.tensor([[2000.0], [-40.0]]), "fc_A", mask=mask.cuda())
     assert rms_err(x, s["x"]) < 1e-3 and rel(x, s["x"]) < 2e-3
+    assert smp.degradation is None and smp.dc is None
     # the observed (masked) region is reproduced by the data-consistency step
     assert float((x[:, : ov - 60].cpu() - clean[:, : ov - 60]).abs().max()) < 5e-2
 
@@ -459,6 +460,7 @@ def test_predict_unconditional_and_predict_bwe_firwin_vs_reference_golden():
         if i < 2:
             assert rel(dscore[i][:, ::16], s["fir_score_sub16"][i]) < 2e-3, i
     assert rms_err(xf, s["fir_x"]) < 1e-3 and rel(xf, s["fir_x"]) < 2e-3
+    assert smp.degradation is None
 
 
 def test_sub_batching_equals_one_batch_and_bf16_sampler_tolerance():
@@ -750,4 +752,4 @@ def test_edm_sampler_inpainting_T3_vs_reference_golden():
     x = smp.predict_inpainting(s["y"].cuda(), s["mask"])
     print(f"inpainting: RMS err {rms_err(x, s['x']):.2e}, rel {rel(x, s['x']):.2e}")
     assert rms_err(x, s["x"]) < 1e-3 and rel(x, s["x"]) < 2e-3
-    assert smp.inpaint_mask is None
+    assert smp.degradation is None

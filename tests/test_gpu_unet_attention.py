@@ -155,5 +155,5 @@ def test_attention_refused_by_bf16_and_library_sequencers():
 
     class Smp:                                   # every other condition of the default evaluation holds
         model = net
-        norm, stft_dist, obs_snr, sigma_den, ar_mask, fir_taps, dc, inpaint_mask, _dc_cfg, data_consistency = 2, None, None, 0, None, None, None, None, False, False
+        norm, stft_dist, obs_snr, sigma_den, degradation, dc, _dc_cfg, data_consistency = 2, None, None, 0, None, None, False, False
     assert not eval_c.supported(Smp(), torch.zeros(1), True)
