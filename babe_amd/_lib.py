@@ -96,6 +96,12 @@ _SIGS = {
     "babe_resample_sinc_adjoint": [_P, _L, _P, _L, _I, _L, _L, _P, _P, _I, _I, _I, _P],
     "babe_iir_filter": [_P, _L, _P, _L, _I, _L, _P, _P, _I, _I, _I, _P, _L, _P, _L, _P],
     "babe_decimate": [_P, _L, _P, _L, _I, _L, _L, _I, _I, _P],
+    "babe_clip_residual": [_P, _L, _P, _L, _F, _P, _L, _P, _L, _P, _I, _I, _L, _P],
+    "babe_clip_fwd": [_P, _L, _F, _P, _L, _I, _L, _P],
+    "babe_clip_adj": [_P, _L, _P, _L, _P, _L, _I, _L, _P],
+    "babe_stft_mag_fwd": [_P, _L, _L, _P, _I, _I, _P, _P, _I, _I, _P, _P],
+    "babe_stft_mag_vjp": [_P, _P, _P, _I, _I, _P, _L, _L, _I, _I, _P, _P, _L, _P],
+    "babe_specnorm_seed": [_P, _L, _I, _I, _I, _P, _L, _I, _P, _L, _P],
     "babe_axpby4d": [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],
     "babe_axpby2_4d": [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P],
     "babe_linear": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
@@ -140,6 +146,10 @@ def lib():
         L.babe_iir_workspace.restype = C.c_long
         L.babe_iir_workspace.argtypes = [_I, _L, _I]
         L.babe_linear_bwd_workspace.argtypes = [_I, _I, _I]
+        L.babe_specnorm_workspace.restype = C.c_long
+        L.babe_specnorm_workspace.argtypes = [_I, _I, _I]
+        L.babe_stft_mag_workspace.restype = C.c_long
+        L.babe_stft_mag_workspace.argtypes = [_I, _I, _I]
         L.babe_prof_nslots.restype = C.c_int
         L.babe_prof_slot_name.restype = C.c_char_p
         L.babe_prof_slot_name.argtypes = [_I]

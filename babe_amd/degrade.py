@@ -267,6 +267,164 @@ class DecimateDegradation(Degradation):
         return decimate(g, self.factor, adjoint=True, length=self.length)
 
 
+def clip_residual(x, y, clip_value, nblk=STFTOps.NBLK):
+    """One pass over x, y [B, L] (device): (r = y - clip(x, -c, c), mask uint8 = |x| <= c, the block sums sumsq_partial(r) gives)."""
+    if not (x.is_cuda and y.is_cuda):
+        raise RuntimeError("babe_amd.clip_residual runs on the GPU only (no CPU fallback)")
+    B, L = x.shape
+    assert y.shape == x.shape and x.stride(1) == 1 and y.stride(1) == 1
+    r = torch.empty(B, L, device=x.device, dtype=torch.float32)
+    mask = torch.empty(B, L, device=x.device, dtype=torch.uint8)
+    part = torch.empty(B, nblk, device=x.device, dtype=torch.float64)
+    with torch.cuda.device(x.device):
+        check(lib().babe_clip_residual(ptr(x), x.stride(0), ptr(y), y.stride(0), float(clip_value), ptr(r), r.stride(0), ptr(mask),
+                                       mask.stride(0), ptr(part), nblk, B, L, stream(x)), "clip_residual")
+    return r, mask, part
+
+
+SPECNORM_ITERS = 32
+
+
+def specnorm_seed(r, rows, cols, iters=SPECNORM_ITERS):
+    """d s1(R) / d(rec) = -u1 v1^T for the residual r [B, rows * cols] = y - rec (device), s1 the largest singular value of
+    R = r[b] as [rows, cols]: the gradient of torch.linalg.norm(y - rec, dim=(1, 2), ord=2).  `iters` power iterations on R^T R
+    from u = ones; the error shrinks by (s2 / s1)^2 per iteration (32 reach float32 for s2 / s1 <= 0.75; where the two
+    largest singular values coincide the gradient does not exist, in torch either)."""
+    if not r.is_cuda:
+        raise RuntimeError("babe_amd.specnorm_seed runs on the GPU only (no CPU fallback)")
+    B = r.shape[0]
+    r = r.reshape(B, -1).contiguous()
+    if r.shape[1] != rows * cols:
+        raise ValueError(f"specnorm_seed: r has {r.shape[1]} entries per row, expected {rows} x {cols}")
+    out = torch.empty_like(r)
+    nbytes = int(lib().babe_specnorm_workspace(B, rows, cols))
+    ws = torch.empty(nbytes, device=r.device, dtype=torch.uint8)
+    with torch.cuda.device(r.device):
+        check(lib().babe_specnorm_seed(ptr(r), r.stride(0), rows, cols, int(iters), ptr(out), out.stride(0), B, ptr(ws), nbytes,
+                                       stream(r)), "specnorm_seed")
+    return out
+
+
+def stft_mag_frames(length, hop):
+    """Frames of torch.stft(cat(x, zeros(win)), win, hop, center=False) on `length` samples: 1 + length // hop."""
+    return 1 + int(length) // int(hop)
+
+
+class ClipDegradation(Degradation):
+    """Declipping: A(x) = clip(x, -c, c).  adj multiplies by the mask |x| <= c of the LAST forward or residual (torch.clip's
+    gradient: 1 on the closed interval, 0 outside) - the sampler always runs A^T right after the A it belongs to."""
+
+    def __init__(self, clip_value):
+        self.c = float(clip_value)
+        if not self.c >= 0.0:
+            raise ValueError(f"ClipDegradation: clip_value {clip_value!r} must be >= 0")
+        self.mask = None
+
+    def fwd(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("babe_amd.ClipDegradation runs on the GPU only (no CPU fallback)")
+        x = x.contiguous()
+        out = torch.empty_like(x)
+        self.mask = None                      # (the plain forward leaves no mask: residual() is what precedes adj)
+        with torch.cuda.device(x.device):
+            check(lib().babe_clip_fwd(ptr(x), x.stride(0), self.c, ptr(out), out.stride(0), x.shape[0], x.shape[1], stream(x)),
+                  "clip_fwd")
+        return out
+
+    def residual(self, x, y):
+        r, self.mask, part = clip_residual(x.contiguous(), y.contiguous(), self.c)       # (fused: one pass)
+        return r, part
+
+    def adj(self, g):
+        if self.mask is None or tuple(self.mask.shape) != tuple(g.shape):
+            raise ValueError("ClipDegradation.adj: needs the mask of a residual() on a signal of this shape")
+        g = g.contiguous()
+        out = torch.empty_like(g)
+        with torch.cuda.device(g.device):
+            check(lib().babe_clip_adj(ptr(g), g.stride(0), ptr(self.mask), self.mask.stride(0), ptr(out), out.stride(0), g.shape[0],
+                                      g.shape[1], stream(g)), "clip_adj")
+        return out
+
+
+class STFTMagnitudeDegradation(Degradation):
+    """Phase retrieval: A(x) = |torch.stft(cat(x, zeros(win)), win, hop, hamming_window(win), center=False)| on x [B, length],
+    flattened to [B, bins * frames] (bins = win/2 + 1 major, frames = 1 + length // hop: torch.stft's layout) so that the norm and
+    seed kernels take it as a signal.  adj(g) is the vector-Jacobian product at the x of the LAST fwd, whose spectrum it keeps.
+    Where a bin is exactly zero the VJP is DEFINED as 0: torch's sqrt(re^2 + im^2) has a NaN gradient there, which the reference
+    returns whenever a frame lies wholly in the zero padding (length % hop == 0)."""
+
+    def __init__(self, win, hop, length, device, matrix_norm=False):
+        """matrix_norm: guidance() differentiates the MATRIX 2-norm of the bins x frames residual (its largest singular value),
+        which is what the reference's torch.linalg.norm(y - A(x), dim=(1, 2), ord=2) computes for its 3-D observation, and
+        ignores the sampler's seed; False: the sampler's distance on the flattened residual, like every other degradation."""
+        self.matrix_norm = bool(matrix_norm)
+        win, hop, length = int(win), int(hop), int(length)
+        if win < 256 or win > 4096 or win & (win - 1):
+            raise ValueError(f"STFTMagnitudeDegradation: win = {win} is not a power of two in 256...4096")
+        if not 1 <= hop <= win:
+            raise ValueError(f"STFTMagnitudeDegradation: hop = {hop} outside 1...win = {win}")
+        if length < 1:
+            raise ValueError(f"STFTMagnitudeDegradation: length = {length} < 1")
+        self.win, self.hop, self.length, self.dev = win, hop, length, torch.device(device)
+        self.bins, self.frames = win // 2 + 1, stft_mag_frames(length, hop)
+        self.spec = None
+        self._tables = None
+
+    def out_shape(self):
+        return (self.bins, self.frames)
+
+    def _tab(self):
+        if self.dev.type != "cuda":
+            raise RuntimeError("babe_amd.STFTMagnitudeDegradation runs on the GPU only (no CPU fallback)")
+        if self._tables is None:
+            q = np.arange(2048, dtype=np.float64)
+            tw = torch.tensor(np.stack([np.cos(2 * np.pi * q / 4096), -np.sin(2 * np.pi * q / 4096)], -1), dtype=torch.float32)
+            window = torch.hamming_window(self.win, dtype=torch.float32)           # periodic, float32, like the reference
+            self._tables = (window.to(self.dev), tw.contiguous().to(self.dev))
+        return self._tables
+
+    def fwd(self, x):
+        if not x.is_cuda:
+            raise RuntimeError("babe_amd.STFTMagnitudeDegradation runs on the GPU only (no CPU fallback)")
+        if x.dim() != 2 or x.shape[1] != self.length:
+            raise ValueError(f"STFTMagnitudeDegradation.fwd: x of shape {tuple(x.shape)}, expected [B, {self.length}]")
+        window, tw = self._tab()
+        x = x.contiguous()
+        B = x.shape[0]
+        self.spec = torch.empty(B, self.frames, self.bins, 2, device=x.device, dtype=torch.float32)
+        mag = torch.empty(B, self.bins * self.frames, device=x.device, dtype=torch.float32)
+        with torch.cuda.device(x.device):
+            check(lib().babe_stft_mag_fwd(ptr(x), x.stride(0), self.length, ptr(window), self.win, self.hop, ptr(self.spec), ptr(mag),
+                                          B, self.frames, ptr(tw), stream(x)), "stft_mag_fwd")
+        return mag
+
+    def adj(self, g):
+        if not g.is_cuda:
+            raise RuntimeError("babe_amd.STFTMagnitudeDegradation runs on the GPU only (no CPU fallback)")
+        B = g.shape[0]
+        if self.spec is None or self.spec.shape[0] != B or g.numel() != B * self.bins * self.frames:
+            raise ValueError("STFTMagnitudeDegradation.adj: needs the spectrum of a fwd() on a batch of this size")
+        window, tw = self._tab()
+        g = g.reshape(B, -1).contiguous()
+        gx = torch.empty(B, self.length, device=g.device, dtype=torch.float32)
+        nbytes = int(lib().babe_stft_mag_workspace(B, self.frames, self.win))
+        ws = torch.empty(nbytes, device=g.device, dtype=torch.uint8)
+        with torch.cuda.device(g.device):
+            check(lib().babe_stft_mag_vjp(ptr(g), ptr(self.spec), ptr(window), self.win, self.hop, ptr(gx), gx.stride(0), self.length,
+                                          B, self.frames, ptr(tw), ptr(ws), nbytes, stream(g)), "stft_mag_vjp")
+        return gx
+
+    def guidance(self, x, y, seed):
+        if not self.matrix_norm:
+            return super().guidance(x, y, seed)
+        r = lincomb(torch.empty_like(y), 1.0, y, -1.0, self.fwd(x))
+        return self.adj(specnorm_seed(r, self.bins, self.frames))
+
+    def fwd_dc(self, x):
+        raise NotImplementedError("STFTMagnitudeDegradation: no data-consistency step (the reference calls "
+                                  "data_consistency_step_phase_retrieval, which it never defines)")
+
+
 def make_degradation(filt, filt_type, device, length=None):
     """(filt, filt_type) of predict_bwe / predict_bwe_AR -> (degradation, filter_params [1,2,K] on `device`); the degradation is
     None for 'fc_A', the STFT filter of the returned filter_params.  length: the state's, for 'resample' / 'decimate'."""

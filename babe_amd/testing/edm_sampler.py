@@ -8,10 +8,15 @@ prior sample (:177-179); no noise is drawn on steps with gamma == 0 (:187-198); 
 the guidance scale is xi/(||g||/sqrt(L)*t + 1e-6) without the extra 1/t (:78-92).
 Only the FIR degradation ('firwin' / 'firwin_hpf') runs on the HIP path; IIR/biquad/resample/decimate
 are torchaudio paths that no target config uses.
+
+Declipping, compressed sensing and phase retrieval (:308-384) are the same loop with another observation operator:
+predict_declipping, predict_compsens, predict_pr.  The reference's own SamplerDeclipping / SamplerCompSens /
+SamplerPhaseRetrieval cannot be constructed (they hand seven arguments to this class's four-argument constructor and read an
+``args.inference`` no YAML defines), so the entry points live here, on the base class the reference's fixtures come from.
 """
 import torch
 
-from ..degrade import FIRDegradation, MaskDegradation
+from ..degrade import ClipDegradation, FIRDegradation, MaskDegradation, STFTMagnitudeDegradation
 from ..stft import STFTOps, lincomb
 from .blind_bwe_sampler import BlindSampler
 
@@ -52,6 +57,54 @@ class Sampler(BlindSampler):
         with self._guiding(MaskDegradation(mask, y_masked.device)):
             return self.predict_conditional(y_masked)
 
+    def _require_guidance(self, what, allow_dc=False):
+        """The rules the reference's task subclasses assert (:314-315, :340-341, :366): guidance on, no replacement step."""
+        if not self.xi > 0:
+            raise ValueError(f"{what}: posterior_sampling.xi must be > 0 (reconstruction guidance is the only way this "
+                             f"observation enters), got {self.xi}")
+        if self.data_consistency and not allow_dc:
+            raise ValueError(f"{what}: posterior_sampling.data_consistency must be False (the replacement step "
+                             f"x0 <- y + x0 - A(x0) holds for linear A only)")
+
+    def predict_declipping(self, y_clipped, clip_value):
+        """Declipping (SamplerDeclipping :308-332): A(x) = clip(x, -clip_value, clip_value), y_clipped [B,L] on the GPU.
+        Needs xi > 0 and data_consistency off."""
+        self._require_guidance("predict_declipping")
+        with self._guiding(ClipDegradation(clip_value)):
+            return self.predict_conditional(y_clipped)
+
+    def predict_compsens(self, y_masked, mask):
+        """Compressed sensing (SamplerCompSens :334-357): A(x) = mask * x with a random 0/1 mask [L] or [B,L] - the operator of
+        predict_inpainting, under the rules of the reference's subclass: xi > 0, data_consistency off."""
+        self._require_guidance("predict_compsens")
+        with self._guiding(MaskDegradation(mask, y_masked.device)):
+            return self.predict_conditional(y_masked)
+
+    def predict_pr(self, y, win_size=None, hop_size=None):
+        """Phase retrieval (SamplerPhaseRetrieval :359-384): y = |STFT(cat(x, zeros(win)))| with a periodic Hamming window,
+        center=False, as [B, win/2+1, frames] or flattened [B, (win/2+1) frames]; the state has shape (B, args.exp.audio_len).
+        win_size / hop_size default to tester.phase_retrieval.win_size / hop_size (1024 / 256 where the YAML has no such key).
+        Needs xi > 0; with data_consistency the reference calls a step it never defines: NotImplementedError.  The gradient of
+        the magnitude at a bin that is exactly zero is taken as 0 (degrade.STFTMagnitudeDegradation).
+        The guidance distance is the reference's: torch.linalg.norm(y - A(x), dim=(1, 2), ord=2) on its 3-D observation is
+        the MATRIX 2-norm, the largest singular value of the bins x frames residual (degrade.specnorm_seed), not the vector
+        norm of the other tasks - whichever layout y arrives in."""
+        self._require_guidance("predict_pr", allow_dc=True)
+        if self.data_consistency:
+            raise NotImplementedError("predict_pr: posterior_sampling.data_consistency has no step to run (the reference calls "
+                                      "data_consistency_step_phase_retrieval, which is defined nowhere)")
+        pr = self.args.tester.get("phase_retrieval", None) or {}
+        win = int(win_size if win_size is not None else pr.get("win_size", 1024))
+        hop = int(hop_size if hop_size is not None else pr.get("hop_size", 256))
+        L = int(self.args.exp.audio_len)
+        deg = STFTMagnitudeDegradation(win, hop, L, y.device, matrix_norm=True)
+        B = y.shape[0]
+        if tuple(y.shape[1:]) not in (deg.out_shape(), (deg.bins * deg.frames,)):
+            raise ValueError(f"predict_pr: y has shape {tuple(y.shape)}, the degradation of audio_len = {L} yields "
+                             f"(B, {deg.bins}, {deg.frames})")
+        with self._guiding(deg):
+            return self.predict_conditional(y.reshape(B, -1), shape=(B, L))
+
     def predict_unconditional(self, shape, device):
         """Unguided sampling (edm_sampler.py:231-243 -> predict :166-229 with y = None)."""
         return self.predict_conditional(None, shape=tuple(shape), device=torch.device(device))
@@ -60,7 +113,7 @@ class Sampler(BlindSampler):
         dp = self.diff_params
         if y is not None:
             y = y.contiguous().float()
-            shape, device = y.shape, y.device
+            shape, device = (y.shape if shape is None else tuple(shape)), y.device      # (predict_pr: y is not a signal)
         B, L = shape
         self.stft_ops(L, device)
         T = self.nb_steps

@@ -211,6 +211,38 @@ int babe_iir_filter(const float* x, long x_bs, float* y, long y_bs, int B, long 
 int babe_decimate(const float* in, long in_bs, float* out, long out_bs, int B, long L_full, long L_dec, int factor, int adjoint,
                   void* stream);
 
+/* ---- observation operators of the EDM sampler's declipping and phase-retrieval tasks (testing/edm_sampler.py:308-384;
+ * csrc/edm_tasks.hip).  No atomics: repeats are bit-identical, a row never depends on B.
+ * Clip A(x) = clip(x, -c, c), c >= 0.  babe_clip_residual, one pass over [B][L]: r = y - clip(x), mask [B][L] (uint8) = |x| <= c
+ * (torch.clip's gradient: 1 on the closed interval), part [B][nblk] = the sums of r^2 babe_sumsq_partial(r, nblk) writes, bit for
+ * bit.  babe_clip_adj: out = g where mask != 0, else 0.  16-byte loads and stores where the rows are 16-byte aligned (mask rows:
+ * 4-byte), element-wise otherwise; any L. */
+int babe_clip_residual(const float* x, long x_bs, const float* y, long y_bs, float c, float* r, long r_bs, unsigned char* mask,
+                       long mask_bs, double* part, int nblk, int B, long L, void* stream);
+int babe_clip_fwd(const float* x, long x_bs, float c, float* out, long out_bs, int B, long L, void* stream);
+int babe_clip_adj(const float* g, long g_bs, const unsigned char* mask, long mask_bs, float* out, long out_bs, int B, long L,
+                  void* stream);
+/* STFT magnitude A(x) = |torch.stft(cat(x, zeros(win)), win, hop, window, center=False)|: frames = 1 + L / hop, samples at or
+ * beyond L read as zero (no padded copy).  win a power of two in 256..4096, 1 <= hop <= win; window [win] (the host passes the
+ * periodic Hamming window); tw4096 [2048][2] = exp(-2 pi i q / 4096).  Forward: mag [B][win/2+1][frames] (torch.stft's layout)
+ * and spec [B][frames][win/2+1] complex, which the VJP reads.  VJP of G [B][win/2+1][frames]: per bin Z = G X / |X|, and 0
+ * where |X| == 0 (torch's sqrt has a NaN gradient there); the adjoint of the one-sided real transform
+ * f[n] = sum_k Re(Z_k) cos(2 pi k n / win) - Im(Z_k) sin(2 pi k n / win), interior bins NOT doubled (not irfft); the window; the
+ * overlap-add into gx [B][L] as a gather, every sample summing its frames in ascending order, the padding dropped.  Workspace:
+ * babe_stft_mag_workspace(B, frames, win) bytes (-1 for bad arguments). */
+/* Gradient of the matrix 2-norm (largest singular value s1) of a residual r [B][rows][cols] = y - rec with respect to rec:
+ * out = -u1 v1^T, by `iters` power iterations on r^T r started from u = ones (the error shrinks by (s2 / s1)^2 per iteration);
+ * 0 where r is zero.  What torch.linalg.norm(y - rec, dim=(1, 2), ord=2) differentiates to: the guidance distance the
+ * reference's EDM sampler applies to a 3-D observation (phase retrieval).  Workspace: babe_specnorm_workspace bytes. */
+long babe_specnorm_workspace(int B, int rows, int cols);
+int babe_specnorm_seed(const float* r, long r_bs, int rows, int cols, int iters, float* out, long out_bs, int B, void* workspace,
+                       long workspace_bytes, void* stream);
+long babe_stft_mag_workspace(int B, int frames, int win);
+int babe_stft_mag_fwd(const float* x, long x_bs, long L, const float* window, int win, int hop, float* spec, float* mag, int B,
+                      int frames, const float* tw4096, void* stream);
+int babe_stft_mag_vjp(const float* G, const float* spec, const float* window, int win, int hop, float* gx, long gx_bs, long L,
+                      int B, int frames, const float* tw4096, void* workspace, long workspace_bytes, void* stream);
+
 /* ---- nested Winograd F(4,5) along frequency x F(4,3) along time for the same (5,3) convs as babe_conv2d_wino45 (Conv2d at
  * networks/cqtdiff+.py:79-88, 433-436): 3.0 multiplies per output instead of 4.5 (csrc/conv_wino85.hip).  Output-channel tiles of
  * 128, 96 or 64 (Cout a multiple of one of them), Cin % 16 == 0, one source; weights [2 passes][Cin/4][2][Cout/16][3][4][16][4] from
