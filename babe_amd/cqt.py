@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._cabi import CqtBands
 from ._lib import check, lib, ptr, stream
 
 
@@ -127,18 +128,6 @@ def small_radices(N):
 DFT_SLOT = 5        # BABE_SLOT_DFT_STAGE (csrc/prof.h)
 
 
-class _BandsStruct(C.Structure):
-    _fields_ = [("nbands", C.c_int), ("L", C.c_int), ("KX", C.c_int),
-                ("c", C.c_void_p), ("M", C.c_void_p), ("woff", C.c_void_p), ("log2T", C.c_void_p),
-                ("oct", C.c_void_p), ("binoct", C.c_void_p), ("tw4096", C.c_void_p),
-                ("nocts", C.c_int), ("binsoct", C.c_int), ("coef", C.c_void_p * 8),
-                ("wg_first", C.c_void_p), ("wg_count", C.c_void_p), ("nwg", C.c_int),
-                ("wg_rec", C.c_void_p), ("band_rec", C.c_void_p), ("abl", C.c_int),
-                ("max_wg_count", C.c_int), ("min_log2T", C.c_int), ("max_log2T", C.c_int),
-                ("sum_T", C.c_long), ("sum_M", C.c_long), ("sum_TlogT", C.c_double),
-                ("kdeg", C.c_int), ("kpoly", C.c_float * 12)]
-
-
 def kaiser_poly(beta, tol=1e-9, max_deg=11):
     """Coefficients of the truncated power series I0(beta sqrt(a)) / I0(beta) = sum_j (beta^2/4)^j / (j!)^2 / I0(beta) a^j for
     a in [0, 1] (include/babe_hip.h, babe_cqt_bands::kpoly): smallest degree whose first dropped term is below `tol`
@@ -159,34 +148,10 @@ def kaiser_poly(beta, tol=1e-9, max_deg=11):
     return deg, co
 
 
-def _register_sigs():
-    L = lib()
-    P, I, F, Lg = C.c_void_p, C.c_int, C.c_float, C.c_long
-    L.babe_cqt_plan_create.restype = P
-    L.babe_cqt_plan_create.argtypes = [C.c_double, I, I, I, C.c_double]
-    L.babe_cqt_plan_destroy.argtypes = [P]
-    L.babe_cqt_workspace_bytes.restype = Lg
-    L.babe_cqt_workspace_bytes.argtypes = [P, I]
-    for n in ("babe_cqt_fwd", "babe_cqt_bwd", "babe_cqt_fwd_adjoint", "babe_cqt_bwd_adjoint", "babe_cqt_hpf"):
-        getattr(L, n).restype = I
-        getattr(L, n).argtypes = [P, P, P, P, I, P]
-    L.babe_fft_twiddle_transpose.argtypes = [P, P, P, I, I, I, I, P]
-    L.babe_rfft_mixed.argtypes = [P, P, P, P, P, I, I, I, I, P, I, P, I, P, P, P, I, P]
-    L.babe_rfft_mixed.restype = C.c_int
-    L.babe_cqt_band_analysis.argtypes = [C.POINTER(_BandsStruct), P, P, I, P]
-    L.babe_cqt_band_synthesis.argtypes = [C.POINTER(_BandsStruct), P, P, Lg, I, P]
-    L.babe_cqt_gather.argtypes = [P, Lg, P, P, P, P, I, I, F, P, I, P]
-    L.babe_spec_scale.argtypes = [P, P, P, P, I, I, F, F, I, P]
-    for n in ("babe_fft_twiddle_transpose", "babe_cqt_band_analysis", "babe_cqt_band_synthesis", "babe_cqt_gather",
-              "babe_spec_scale"):
-        getattr(L, n).restype = C.c_int
-
-
 class RealFFT:
     """Length-L real DFT / its transpose on the GPU (four-step, dense DFT stages on the MFMA conv kernel)."""
 
     def __init__(self, L, device):
-        _register_sigs()                     # (a RealFFT used on its own: ctypes must know the pointer arguments are 64-bit)
         self.L = L
         N1, N2 = factor_len(L)
         self.N1, self.N2 = N1, N2
@@ -298,7 +263,6 @@ class CQT_nsgt:
             raise NotImplementedError("only ('kaiser', beta) windows are implemented")
         if dtype != torch.float32:
             raise NotImplementedError("fp32 only")
-        _register_sigs()
         self.Ls, self.fs, self.numocts, self.binsoct = int(audio_len), fs, numocts, binsoct
         self.device = torch.device(device)
         d = design_bands(fs, self.Ls, numocts, binsoct, float(window[1]))
@@ -391,7 +355,7 @@ class CQT_nsgt:
 
     # ------------------------------------------------------------------ internals
     def _bands(self, coefs):
-        s = _BandsStruct()
+        s = CqtBands()
         d = self.design
         s.nbands, s.L, s.KX = d["nb"], self.Ls, self.fft.KX
         for k in ("c", "M", "woff", "log2T", "oct", "binoct", "wg_first", "wg_count", "wg_rec", "band_rec"):

@@ -10,7 +10,7 @@ import torch
 
 from ._lib import check, lib, ptr, stream
 from .resample import resample, resample_adjoint, resampled_length
-from .stft import STFTOps, _register, fir_same, lincomb, mask_blend
+from .stft import STFTOps, fir_same, lincomb, mask_blend
 
 MAX_ORDER = 16
 
@@ -107,7 +107,6 @@ def decimate(x, factor, adjoint=False, length=None):
 
 def sumsq_partial(g, nblk=STFTOps.NBLK):
     """Per-block partial sums of squares of g [B, n] -> [B, nblk] float64 (fixed-order: what the norm kernels reduce)."""
-    _register()
     B, n = g.shape
     part = torch.empty(B, nblk, device=g.device, dtype=torch.float64)
     check(lib().babe_sumsq_partial(ptr(g), g.stride(0), ptr(part), nblk, B, n, stream()), "sumsq_partial")

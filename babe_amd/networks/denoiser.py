@@ -13,47 +13,10 @@ import math
 import torch
 import torch.nn as nn
 
+from .._cabi import DnConvArgs
 from .._lib import check, lib, ptr, stream
 
 NS = [64, 64, 64, 128, 128, 256, 512]        # denoiser.py:243
-
-
-class DnConvArgs(C.Structure):
-    _fields_ = [("in_", C.c_void_p), ("in_bs", C.c_long), ("in_cs", C.c_long), ("IH", C.c_int), ("IW", C.c_int),
-                ("bias", C.c_void_p),
-                ("out", C.c_void_p), ("out_bs", C.c_long), ("out_cs", C.c_long), ("out_H", C.c_int), ("out_W", C.c_int),
-                ("out_hstep", C.c_int), ("out_h0", C.c_int), ("out_wstep", C.c_int), ("out_w0", C.c_int),
-                ("res", C.c_void_p), ("res_bs", C.c_long), ("res_cs", C.c_long),
-                ("B", C.c_int), ("Cin", C.c_int), ("Cout", C.c_int), ("OH", C.c_int), ("OW", C.c_int),
-                ("KH", C.c_int), ("KW", C.c_int), ("stride", C.c_int), ("pad_t", C.c_int), ("pad_l", C.c_int),
-                ("pad_mode", C.c_int), ("act", C.c_int), ("ksplit", C.c_int), ("ws", C.c_void_p)]
-
-
-_registered = False
-
-
-def _register():
-    global _registered
-    if _registered:
-        return
-    L = lib()
-    P, I, Lg = C.c_void_p, C.c_int, C.c_long
-    sig = {
-        "babe_dn_conv2d": [C.POINTER(DnConvArgs), P, P],
-        "babe_dn_pack_weights": [P, P, I, I, I, I, I, I, I, P],
-        "babe_dn_upsample_add": [P, Lg, Lg, P, Lg, Lg, I, I, I, I, I, I, I, I, P],
-        "babe_dn_sam_gate": [P, P, P, Lg, Lg, P, Lg, Lg, I, I, Lg, P],
-        "babe_dn_fill_input": [P, P, P, I, I, I, I, P],
-        "babe_dn_stft": [P, Lg, I, P, I, I, I, I, P, P],
-        "babe_dn_istft": [P, P, P, Lg, I, I, I, I, I, P, P],
-    }
-    for n, s in sig.items():
-        fn = getattr(L, n)
-        fn.argtypes = s
-        fn.restype = C.c_int
-    L.babe_dn_packed_size.argtypes = [I, I, I, I]
-    L.babe_dn_packed_size.restype = Lg
-    _registered = True
 
 
 def param_shapes(cfg):
@@ -151,7 +114,6 @@ class _Packed:
     """One convolution's weights in the kernel's layout (+ bias)."""
 
     def __init__(self, w, b, tconv=False):
-        _register()
         L = lib()
         w = w.contiguous()
         self.bias = b.contiguous()
@@ -217,7 +179,6 @@ class DenoiserEngine:
     """Launch sequence of MultiStage_denoise.forward over packed weights; buffers are cached per input shape."""
 
     def __init__(self, sd, cfg):
-        _register()
         self.cfg = cfg
         self.depth, self.n = cfg["depth"], cfg["num_tfc"]
         self.dev = next(iter(sd.values())).device

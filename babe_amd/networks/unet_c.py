@@ -7,44 +7,8 @@ import ctypes as C
 
 import torch
 
-from .._lib import CPackedConv, check, lib, ptr, stream
-
-_I, _P = C.c_int, C.c_void_p
-
-
-class CBlock(C.Structure):
-    _fields_ = [("N", _I), ("nd", _I), ("k53", _I), ("proj_in", CPackedConv), ("res_conv", CPackedConv), ("proj_out", CPackedConv),
-                ("H", CPackedConv * 8), ("gamma", _P * 8), ("film_aff", _I * 8), ("film_gate", _I * 8)]
-
-
-class CPlanDesc(C.Structure):
-    _fields_ = [("nocts", _I), ("bpo", _I), ("Ns", _I * 8), ("init_blk", CBlock * 8), ("main_blk", CBlock * 8), ("up_out", CBlock * 8),
-                ("up_blk", CBlock * 8), ("mid_blk", CBlock), ("mid_out", CBlock), ("pyr_conv", CPackedConv * 8)]
-
-
-_registered = False
-
-
-def _register():
-    global _registered
-    if _registered:
-        return
-    L = lib()
-    L.babe_unet_plan_create.argtypes = [C.POINTER(CPlanDesc)]
-    L.babe_unet_plan_create.restype = _P
-    L.babe_unet_plan_destroy.argtypes = [_P]
-    L.babe_unet_plan_destroy.restype = None
-    L.babe_unet_state_create.argtypes = []
-    L.babe_unet_state_create.restype = _P
-    L.babe_unet_state_destroy.argtypes = [_P]
-    L.babe_unet_state_destroy.restype = None
-    L.babe_unet_workspace_bytes.argtypes = [_P, _I, C.POINTER(_I)]
-    L.babe_unet_workspace_bytes.restype = C.c_long
-    L.babe_unet_fwd.argtypes = [_P, _P, C.POINTER(_P), _P, C.c_long, _I, C.POINTER(_I), _P, C.c_long, C.POINTER(_P), _P]
-    L.babe_unet_fwd.restype = _I
-    L.babe_unet_vjp.argtypes = [_P, _P, C.POINTER(_P), C.POINTER(_P), _P]
-    L.babe_unet_vjp.restype = _I
-    _registered = True
+from .._cabi import CPackedConv, CPlanDesc
+from .._lib import check, lib, ptr, stream
 
 
 def _pc(dst, pc):
@@ -68,7 +32,6 @@ class CUnet:
     """Plan (shared, immutable) + one state and workspace per engine state (= per clip lane)."""
 
     def __init__(self, eng, plan=None):
-        _register()
         assert eng.precision == "f32", "the library-side engine sequences the fp32 network"
         if getattr(eng, "has_attention", False):
             raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
@@ -119,7 +82,7 @@ class CUnet:
         B = C_list[0].shape[0]
         Ts = [int(c.shape[-1]) for c in C_list]
         assert all(c.is_contiguous() and c.dtype == torch.float32 for c in C_list) and film.stride(1) == 1
-        T_oct = (_I * n)(*Ts)
+        T_oct = (C.c_int * n)(*Ts)
         key = (B, tuple(Ts))
         if key != self.key:
             nbytes = L.babe_unet_workspace_bytes(self.plan, B, T_oct)
@@ -128,8 +91,8 @@ class CUnet:
             self.ws = torch.empty(nbytes, device=C_list[0].device, dtype=torch.uint8)
             self.key = key
         outs = [torch.empty_like(c) for c in C_list]
-        cin = (_P * n)(*[ptr(c) for c in C_list])
-        cout = (_P * n)(*[ptr(o) for o in outs])
+        cin = (C.c_void_p * n)(*[ptr(c) for c in C_list])
+        cout = (C.c_void_p * n)(*[ptr(o) for o in outs])
         self._keep = (C_list, film)              # inputs are read again by nothing after the call, but keep them until the VJP
         check(L.babe_unet_fwd(self.plan, self.state, cin, ptr(film), film.stride(0), B, T_oct, ptr(self.ws), self.ws.numel(), cout,
                               stream()), "unet_fwd")
@@ -140,8 +103,8 @@ class CUnet:
         n = self.n
         assert all(g.is_contiguous() and g.dtype == torch.float32 for g in gouts)
         gC = [torch.empty_like(g) for g in gouts]
-        gin = (_P * n)(*[ptr(g) for g in gouts])
-        gout = (_P * n)(*[ptr(g) for g in gC])
+        gin = (C.c_void_p * n)(*[ptr(g) for g in gouts])
+        gout = (C.c_void_p * n)(*[ptr(g) for g in gC])
         check(L.babe_unet_vjp(self.plan, self.state, gin, gout, stream()), "unet_vjp")
         self._keep = None
         return gC

@@ -6,7 +6,8 @@ import os
 import torch
 
 from . import _lib
-from ._lib import ConvArgs, CPackedConv, WgradArgs, check, lib, ptr, stream
+from ._cabi import ConvArgs, CPackedConv, WgradArgs
+from ._lib import check, lib, ptr, stream
 
 RSQRT2 = 1.0 / math.sqrt(2.0)
 
@@ -38,6 +39,30 @@ WINOGRAD85 = WINOGRAD45 and os.environ.get("BABE_CONV_F45", "1") != "0"
 # the library default of up to 128: more workgroups on the small planes of the deep levels, where a launch has a few hundred
 # (whole-job A/B, same box: 2.431 / 2.432 vs 2.423 / 2.424 audio-sec/s; one tile: 2.399 / 2.395).  0 = library default.
 _C11_NT = int(os.environ.get("BABE_CONV11_NT", "2"))
+
+
+def _io(pc, tf):
+    """(input, output) channels of the op a direction's image EXECUTES: tf 0 the conv, 1 its input-VJP (the transposed conv)."""
+    return (pc.Cout, pc.Cin) if tf else (pc.Cin, pc.Cout)
+
+
+# The Winograd image families of an fp32 PackedConv, which construction and repack() both walk: (suffix of the fwd_ / bwd_
+# attribute, size function, pack function, may direction tf be packed?).  Images exist only for the direction(s) their kernel can
+# take (the *_supported rules of include/babe_hip.h, on the executed op's channels):
+#   wino / wino4   F(2,3) / F(4,3) along time: every 3-tap kernel
+#   wino45         nested F(2,5) x F(4,3), 36 floats per weight pair: input channels % 16 == 0, more than 32 output channels
+#   wino85         nested F(4,5) x F(4,3): input channels % 16 == 0, output channels a multiple of a tile width (128, 96 or 64)
+_FAMILIES = (
+    ("wino", lambda L, pc, tf: L.babe_conv_packed_size_wino(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino,
+     lambda pc, tf: pc.KW == 3 and WINOGRAD),
+    ("wino4", lambda L, pc, tf: L.babe_conv_packed_size_wino4(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino4,
+     lambda pc, tf: pc.KW == 3 and WINOGRAD4),
+    ("wino45", lambda L, pc, tf: L.babe_conv_packed_size_wino45(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino45,
+     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and WINOGRAD45 and _io(pc, tf)[0] % 16 == 0 and _io(pc, tf)[1] > 32),
+    ("wino85", lambda L, pc, tf: L.babe_conv_packed_size_wino85(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino85,
+     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and WINOGRAD85 and _io(pc, tf)[0] % 16 == 0
+     and any(_io(pc, tf)[1] % tile == 0 for tile in (128, 96, 64))),
+)
 
 
 _DESC_FIELDS = frozenset(k for k, _ in CPackedConv._fields_)
@@ -92,12 +117,11 @@ class PackedConv:
             self.w_raw.copy_(w)
         for tf, dst in ((0, self.fwd), (1, self.bwd)):
             check(L.babe_conv_pack_weights_nt(ptr(w), ptr(dst), *shp, tf, self.nt, stream()), "pack")
-        for name, fn in (("wino", L.babe_conv_pack_weights_wino), ("wino4", L.babe_conv_pack_weights_wino4),
-                         ("wino45", L.babe_conv_pack_weights_wino45), ("wino85", L.babe_conv_pack_weights_wino85)):
+        for name, _, pack, _ in _FAMILIES:
             for tf, d in ((0, "fwd_"), (1, "bwd_")):
                 dst = getattr(self, d + name)
                 if dst is not None:
-                    check(fn(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
+                    check(pack(L)(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
 
     def _init_bf16(self, w):
         assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
@@ -125,37 +149,13 @@ class PackedConv:
         self.bwd = torch.empty(nb, device=w.device, dtype=torch.float32)
         check(L.babe_conv_pack_weights_nt(ptr(w), ptr(self.fwd), self.Cout, self.Cin, self.KH, self.KW, 0, self.nt, stream()), "pack")
         check(L.babe_conv_pack_weights_nt(ptr(w), ptr(self.bwd), self.Cout, self.Cin, self.KH, self.KW, 1, self.nt, stream()), "pack")
-        # Winograd F(2,3)-along-time images for the 3-tap kernels (used whenever the problem qualifies)
-        self.fwd_wino = self.bwd_wino = None
-        if self.KW == 3 and WINOGRAD:
-            self.fwd_wino = torch.empty(L.babe_conv_packed_size_wino(self.Cout, self.Cin, self.KH, 0), device=w.device)
-            self.bwd_wino = torch.empty(L.babe_conv_packed_size_wino(self.Cout, self.Cin, self.KH, 1), device=w.device)
-            check(L.babe_conv_pack_weights_wino(ptr(w), ptr(self.fwd_wino), self.Cout, self.Cin, self.KH, self.KW, 0, stream()), "pack_wino")
-            check(L.babe_conv_pack_weights_wino(ptr(w), ptr(self.bwd_wino), self.Cout, self.Cin, self.KH, self.KW, 1, stream()), "pack_wino")
-        self.fwd_wino4 = self.bwd_wino4 = None
-        if self.KW == 3 and WINOGRAD4:
-            self.fwd_wino4 = torch.empty(L.babe_conv_packed_size_wino4(self.Cout, self.Cin, self.KH, 0), device=w.device)
-            self.bwd_wino4 = torch.empty(L.babe_conv_packed_size_wino4(self.Cout, self.Cin, self.KH, 1), device=w.device)
-            check(L.babe_conv_pack_weights_wino4(ptr(w), ptr(self.fwd_wino4), self.Cout, self.Cin, self.KH, self.KW, 0, stream()), "pack_wino4")
-            check(L.babe_conv_pack_weights_wino4(ptr(w), ptr(self.bwd_wino4), self.Cout, self.Cin, self.KH, self.KW, 1, stream()), "pack_wino4")
-        # nested-Winograd images (36 floats per weight pair and direction): only for the direction(s) the kernel can take -
-        # babe_conv2d_wino45_supported needs the EXECUTED op's input channels % 16 == 0 and more than 32 output channels
-        self.fwd_wino45 = self.bwd_wino45 = None
-        if self.KH == 5 and self.KW == 3 and WINOGRAD45:
-            if self.Cin % 16 == 0 and self.Cout > 32:
-                self.fwd_wino45 = torch.empty(L.babe_conv_packed_size_wino45(self.Cout, self.Cin, 0), device=w.device)
-                check(L.babe_conv_pack_weights_wino45(ptr(w), ptr(self.fwd_wino45), self.Cout, self.Cin, self.KH, self.KW, 0, stream()), "pack_wino45")
-            if self.Cout % 16 == 0 and self.Cin > 32:
-                self.bwd_wino45 = torch.empty(L.babe_conv_packed_size_wino45(self.Cout, self.Cin, 1), device=w.device)
-                check(L.babe_conv_pack_weights_wino45(ptr(w), ptr(self.bwd_wino45), self.Cout, self.Cin, self.KH, self.KW, 1, stream()), "pack_wino45")
-        self.fwd_wino85 = self.bwd_wino85 = None
-        if self.KH == 5 and self.KW == 3 and WINOGRAD85:
-            if self.Cin % 16 == 0 and self.Cout % 32 == 0 and (self.Cout % 128 == 0 or self.Cout % 96 == 0 or self.Cout % 64 == 0):   # its tile widths
-                self.fwd_wino85 = torch.empty(L.babe_conv_packed_size_wino85(self.Cout, self.Cin, 0), device=w.device)
-                check(L.babe_conv_pack_weights_wino85(ptr(w), ptr(self.fwd_wino85), self.Cout, self.Cin, self.KH, self.KW, 0, stream()), "pack_wino85")
-            if self.Cout % 16 == 0 and (self.Cin % 128 == 0 or self.Cin % 96 == 0 or self.Cin % 64 == 0):
-                self.bwd_wino85 = torch.empty(L.babe_conv_packed_size_wino85(self.Cout, self.Cin, 1), device=w.device)
-                check(L.babe_conv_pack_weights_wino85(ptr(w), ptr(self.bwd_wino85), self.Cout, self.Cin, self.KH, self.KW, 1, stream()), "pack_wino85")
+        for name, size, pack, eligible in _FAMILIES:
+            for tf, d in ((0, "fwd_"), (1, "bwd_")):
+                img = None
+                if eligible(self, tf):
+                    img = torch.empty(size(L, self, tf), device=w.device)
+                    check(pack(L)(ptr(w), ptr(img), self.Cout, self.Cin, self.KH, self.KW, tf, stream()), "pack_" + name)
+                setattr(self, d + name, img)
 
 
 # GroupNorm-VJP partial sums formed in the F(4,5) transposed conv's epilogue instead of babe_gn_bwd_partial's own pass: OFF by

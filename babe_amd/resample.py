@@ -10,7 +10,6 @@ tests/golden/make_resample_golden.py pins it the day `import torchaudio` works).
 The kernel TABLE ([new][2 width + orig] float32) is built on the host with the published sequence of float32 operations; the
 convolution - all the arithmetic on audio - is the HIP kernel.  Device tensors only, no CPU fallback.
 """
-import ctypes as C
 import math
 
 import numpy as np
@@ -19,17 +18,6 @@ import torch
 from ._lib import check, lib, ptr, stream
 
 _tables = {}
-_registered = False
-
-
-def _register():
-    global _registered
-    if not _registered:
-        L = lib()
-        L.babe_resample_sinc.restype = C.c_int
-        L.babe_resample_sinc.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_long, C.c_long, C.c_void_p,
-                                         C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        _registered = True
 
 
 def sinc_resample_kernel(orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
@@ -91,7 +79,6 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
         return waveform
     if not waveform.is_cuda:
         raise RuntimeError("babe_amd.resample runs on the GPU only (no CPU fallback)")
-    _register()
     shape = waveform.shape
     x = waveform.reshape(-1, shape[-1]).contiguous().float()
     B, L = x.shape

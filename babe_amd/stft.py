@@ -11,56 +11,13 @@ import math
 import numpy as np
 import torch
 
+from ._cabi import FitCfg
 from ._lib import check, lib, ptr, stream
 
 _WEIGHTS = {"None": 0, "sqrt": 1, "linear": 2, "log": 3}
 
 
-class FitCfg(C.Structure):
-    _fields_ = [("mu_fc", C.c_float), ("mu_A", C.c_float), ("tol_fc", C.c_float), ("tol_A", C.c_float),
-                ("fcmin", C.c_float), ("fcmax", C.c_float), ("Amin", C.c_float), ("Amax", C.c_float),
-                ("max_iter", C.c_int), ("clamp_fc", C.c_int), ("clamp_A", C.c_int), ("only_negative_A", C.c_int),
-                ("weighting", C.c_int), ("kernel", C.c_int)]
-
-
-_registered = False
-
-
-def _register():
-    global _registered
-    if _registered:
-        return
-    L = lib()
-    P, I, F, Lg = C.c_void_p, C.c_int, C.c_float, C.c_long
-    sig = {
-        "babe_stft_fwd": [P, Lg, I, P, P, I, I, I, P, P],
-        "babe_spec_filter_istft": [P, P, Lg, P, I, I, I, P, P],
-        "babe_ola": [P, P, P, Lg, P, Lg, P, I, I, I, I, I, P],
-        "babe_residual_seed": [P, Lg, P, I, P, P, Lg, I, I, P],
-        "babe_stft_mag_stats": [P, P, P, I, I, I, I, P],
-        "babe_design_filter": [P, P, I, I, I, F, I, P],
-        "babe_filter_fit": [P, P, P, I, I, I, F, I, C.POINTER(FitCfg), P],
-        "babe_filter_loss_grad": [P, Lg, P, P, I, I, I, F, I, C.POINTER(FitCfg), P],
-        "babe_lincomb3": [P, F, P, F, P, F, P, Lg, P],
-        "babe_add_obs_noise": [P, Lg, P, Lg, F, I, Lg, P],
-        "babe_sumsq_partial": [P, Lg, P, I, I, Lg, P],
-        "babe_cos_partial": [P, Lg, P, Lg, P, I, I, Lg, P],
-        "babe_stft_dist_partial": [P, P, P, P, I, I, I, I, I, P],
-        "babe_stft_dist_grad": [P, P, P, P, I, P, I, I, I, I, I, P],
-        "babe_residual_seed_alt": [P, Lg, P, Lg, P, I, P, P, Lg, I, I, I, F, P],
-        "babe_score_direction": [P, P, P, P, I, P, F, F, F, I, I, I, Lg, P],
-        "babe_fir_same": [P, Lg, P, I, P, Lg, I, I, I, P],
-        "babe_mask_blend": [P, P, Lg, P, P, I, Lg, P],
-    }
-    for n, s in sig.items():
-        fn = getattr(L, n)
-        fn.argtypes = s
-        fn.restype = C.c_int
-    _registered = True
-
-
 def lincomb(out, a, x, b=0.0, y=None, c=0.0, z=None):
-    _register()
     n = x.numel()
     assert x.is_contiguous() and out.is_contiguous() and (y is None or y.is_contiguous()) and (z is None or z.is_contiguous())
     check(lib().babe_lincomb3(ptr(out), a, ptr(x), b, ptr(y), c, ptr(z), n, stream()), "lincomb3")
@@ -69,7 +26,6 @@ def lincomb(out, a, x, b=0.0, y=None, c=0.0, z=None):
 
 def add_obs_noise(y, noise, snr):
     """y[b] += sqrt(var(y[b]) / snr) * noise[b] IN PLACE (get_rec_grads :80-86, fit_params :542-548); snr linear."""
-    _register()
     B, L = y.shape
     assert y.stride(1) == 1 and noise.stride(1) == 1 and noise.shape == y.shape
     check(lib().babe_add_obs_noise(ptr(y), y.stride(0), ptr(noise), noise.stride(0), float(snr), B, L, stream()), "add_obs_noise")
@@ -78,7 +34,6 @@ def add_obs_noise(y, noise, snr):
 
 def fir_same(x, taps, adjoint=False):
     """F.conv1d(x[:,None], taps[None,None], padding="same") or its transpose; x [B,L] device, taps [ntaps] device."""
-    _register()
     B, L = x.shape
     out = torch.empty_like(x)
     taps = taps.reshape(-1).contiguous()
@@ -89,7 +44,6 @@ def fir_same(x, taps, adjoint=False):
 
 def mask_blend(mask, a=None, b=None):
     """mask*a + (1-mask)*b with a/b optional (None = 0); mask [L] (shared) or [B,L]."""
-    _register()
     ref = a if a is not None else b
     B, n = ref.shape
     out = torch.empty_like(ref)
@@ -116,7 +70,6 @@ class STFTOps:
     NBLK = 64
 
     def __init__(self, nfft, L, fs, device):
-        _register()
         self.nfft, self.L, self.fs, self.dev = int(nfft), int(L), float(fs), torch.device(device)
         self.hop = self.nfft // 2
         self.frames = 1 + self.L // self.hop

@@ -10,14 +10,12 @@ import numpy as np
 import torch
 
 from .._lib import check, lib, ptr, stream
-from ..networks.denoiser import _register
 
 
 class DenoiserPrepass:
     def __init__(self, denoiser, dargs, device="cuda"):
         """denoiser: babe_amd.networks.denoiser.MultiStage_denoise (on the GPU); dargs: the `tester.denoiser` config node
         (sample_rate_denoiser, segment_size [s], stft_win_size, stft_hop_size, num_stages)."""
-        _register()
         self.denoiser = denoiser
         self.dargs = dargs
         self.device = torch.device(device)

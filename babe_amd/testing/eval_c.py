@@ -6,41 +6,13 @@ import ctypes as C
 
 import torch
 
+from .._cabi import EvalDesc
 from .._lib import check, lib, ptr, stream
-from ..stft import FitCfg
-
-_P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_long
-
-
-class EvalDesc(C.Structure):
-    _fields_ = [("unet_plan", _P), ("unet_state", _P), ("cqt_plan", _P), ("L", _I),
-                ("rff_freq", _P), ("rff_n", _I), ("emb_W", _P * 3), ("emb_b", _P * 3), ("emb_dim", _I * 4),
-                ("film_W", _P), ("film_b", _P), ("film_J", _I),
-                ("nfft", _I), ("fs", _F), ("env_inv", _P), ("tw4096", _P), ("K", _I), ("fit", FitCfg),
-                ("blind", _I), ("shared", _I), ("hpf", _I), ("xi", _F), ("score_mode", _I), ("audio_len_norm", _F)]
-
-
-_registered = False
-
-
-def _register():
-    global _registered
-    if _registered:
-        return
-    L = lib()
-    L.babe_eval_workspace_bytes.restype = _L
-    L.babe_eval_workspace_bytes.argtypes = [C.POINTER(EvalDesc), _I]
-    L.babe_score_eval.restype = _I
-    L.babe_score_eval.argtypes = [C.POINTER(EvalDesc), _P, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]
-    L.babe_cqt_plan_create.restype = _P
-    L.babe_cqt_plan_create.argtypes = [C.c_double, _I, _I, _I, C.c_double]
-    _registered = True
 
 
 def cqt_plan_of(cq):
     """The library-side plan of a CQT_nsgt object: its own (the default), or one made here for an object that sequences the kernels
     itself (BABE_CQT_C=0); None where the library cannot plan the length."""
-    _register()
     if getattr(cq, "_plan", None):
         return cq._plan
     if getattr(cq, "_plan_eval", None) is None:
@@ -62,7 +34,6 @@ class CEval:
     """One lane's descriptor + workspace (the UNet state and the workspace belong to one stream at a time)."""
 
     def __init__(self, smp, lane):
-        _register()
         from ..networks.unet_c import CUnet
         net, st = smp.model, smp._stft
         eng = net.lane_engine(lane or 0)

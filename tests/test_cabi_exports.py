@@ -20,49 +20,125 @@ def test_exports_match_header():
     assert b"gfx950" in L.babe_version()
 
 
-def test_unet_plan_structs_have_the_headers_layout(tmp_path):
-    """babe_amd/networks/unet_c.py mirrors babe_packed_conv / babe_unet_block / babe_unet_plan_desc with ctypes: sizes and a few
-    field offsets must be what a C compiler gives the header (a silent mismatch would hand the library garbage pointers)."""
+def _prototypes():
+    """{name: (return type, [parameter declarations])} of every function include/babe_hip.h declares."""
+    hdr = open(os.path.join(ROOT, "include", "babe_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    names = set(re.findall(r"\b(babe_[a-z0-9_]+)\s*\(", hdr))
+    hdr = re.sub(r"typedef\s+struct\s*\{.*?\}\s*\w+\s*;", "", hdr, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(babe_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", hdr):
+        params = params.strip()
+        protos[name] = (ret.strip(), [] if params == "void" else [p.strip() for p in params.split(",")])
+    assert set(protos) == names, sorted(names ^ set(protos))          # a prototype the parser cannot read: reformat it
+    return protos
+
+
+def _agrees(decl, ct, is_param):
+    """Does the ctypes type `ct` of the binding table pass what the C declaration `decl` ('const float* x', 'long') takes?"""
+    from babe_amd import _cabi
+    words = [w for w in re.findall(r"\w+", decl) if w != "const"]
+    if is_param:
+        words = words[:-1]                                            # the parameter's name
+    base = " ".join(words)
+    if "*" in decl:
+        if isinstance(ct, type) and issubclass(ct, ctypes._Pointer):
+            return not issubclass(ct._type_, ctypes.Structure) or _cabi.STRUCTS.get(base) is ct._type_
+        return ct in (ctypes.c_void_p, ctypes.c_char_p)
+    if base in _cabi.STRUCTS:                                         # a struct passed by value
+        return ct is _cabi.STRUCTS[base]
+    if base == "void":
+        return ct is None and not is_param
+    if base in ("long", "size_t"):
+        return ct in (ctypes.c_long, ctypes.c_ulong, ctypes.c_size_t, ctypes.c_ssize_t, ctypes.c_int64, ctypes.c_uint64) \
+            and ctypes.sizeof(ct) == 8
+    return {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double}[base] is ct
+
+
+def test_binding_table_matches_header():
+    """Every entry of the binding table (babe_amd/_cabi.py::SIGS) against the prototype include/babe_hip.h declares: the function
+    exists, takes as many arguments, and each argument and the return value is of the prototype's kind - a pointer where C takes a
+    pointer (to the mirrored struct where the table names one), a 64-bit integer for long, c_int / c_float / c_double for int /
+    float / double.  A wrong entry would truncate a pointer or shift every later argument."""
+    from babe_amd import _cabi
+    protos = _prototypes()
+    assert len(_cabi.SIGS) >= 100
+    for name, (restype, argtypes) in _cabi.SIGS.items():
+        assert name in protos, f"{name}: not declared in the header"
+        ret, params = protos[name]
+        assert len(argtypes) == len(params), (name, len(argtypes), params)
+        assert _agrees(ret, restype, False), (name, "returns", ret, restype)
+        for i, (p, ct) in enumerate(zip(params, argtypes)):
+            assert _agrees(p, ct, True), (name, i, p, ct)
+
+
+def test_nothing_undeclared_is_called():
+    """Every `.babe_<name>(` call in the package, the tools, the entry script and the tests names a function of the binding table,
+    and the bound library has no other babe_* attribute: an undeclared function cannot be called with guessed argument types."""
+    import glob
+    import pytest
+    from babe_amd import _cabi
+    from babe_amd._lib import lib
+    files = glob.glob(os.path.join(ROOT, "babe_amd", "**", "*.py"), recursive=True) + \
+        glob.glob(os.path.join(ROOT, "tools", "**", "*.py"), recursive=True) + \
+        glob.glob(os.path.join(ROOT, "tests", "*.py")) + [os.path.join(ROOT, "__graft_entry__.py")]
+    assert len(files) > 50
+    for f in files:
+        undeclared = set(re.findall(r"\.(babe_\w+)\s*\(", open(f).read())) - set(_cabi.SIGS)
+        assert not undeclared, (f, sorted(undeclared))
+    L = lib()
+    assert isinstance(vars(L)["babe_version"], ctypes._CFuncPtr)      # a plain attribute holding the ctypes function itself
+    with pytest.raises(AttributeError, match="_cabi.py::SIGS"):
+        L.babe_not_a_function
+
+
+def _check_layout(tmp_path, structs):
+    """sizeof and the offsetof of EVERY field of the ctypes mirrors `structs` ({header name: Structure}) against what a C compiler
+    gives the header (a silent mismatch would hand the library garbage pointers).  The probe is generated from _fields_."""
     import shutil
     import subprocess
     import pytest
     if shutil.which("gcc") is None:
         pytest.skip("no C compiler")
-    from babe_amd.networks import unet_c as uc
+    cname = lambda f: "in" if f == "in_" else f
+    exprs, got = [], []
+    for name, st in structs.items():
+        exprs.append(f"sizeof({name})")
+        got.append(ctypes.sizeof(st))
+        for f, _ in st._fields_:
+            exprs.append(f"offsetof({name}, {cname(f)})")
+            got.append(getattr(st, f).offset)
     src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void){printf("%%zu %%zu %%zu %%zu %%zu %%zu %%zu %%zu\\n",'
-                   ' sizeof(babe_packed_conv), sizeof(babe_unet_block), sizeof(babe_unet_plan_desc), offsetof(babe_packed_conv, w_raw),'
-                   ' offsetof(babe_packed_conv, bwd_wino85),'
-                   ' offsetof(babe_unet_block, gamma), offsetof(babe_unet_block, film_gate), offsetof(babe_unet_plan_desc, pyr_conv));return 0;}\n'
-                   % os.path.join(ROOT, "include", "babe_hip.h"))
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void){\n%sreturn 0;}\n'
+                   % (os.path.join(ROOT, "include", "babe_hip.h"), "".join(f'printf("%zu\\n", {e});\n' for e in exprs)))
     exe = tmp_path / "sz"
     subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
     want = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    got = [ctypes.sizeof(uc.CPackedConv), ctypes.sizeof(uc.CBlock), ctypes.sizeof(uc.CPlanDesc), uc.CPackedConv.w_raw.offset,
-           uc.CPackedConv.bwd_wino85.offset, uc.CBlock.gamma.offset, uc.CBlock.film_gate.offset, uc.CPlanDesc.pyr_conv.offset]
-    assert got == want, (got, want)
+    assert got == want, [(e, g, w) for e, g, w in zip(exprs, got, want) if g != w]
+
+
+_UNET_STRUCTS = ("babe_packed_conv", "babe_unet_block", "babe_unet_plan_desc")
+
+
+def test_unet_plan_structs_have_the_headers_layout(tmp_path):
+    """The ctypes mirrors of babe_packed_conv / babe_unet_block / babe_unet_plan_desc (babe_amd/_cabi.py)."""
+    from babe_amd import _cabi
+    _check_layout(tmp_path, {n: _cabi.STRUCTS[n] for n in _UNET_STRUCTS})
 
 
 def test_cqt_bands_struct_has_the_headers_layout(tmp_path):
-    """babe_amd/cqt.py mirrors babe_cqt_bands with ctypes (passed BY VALUE to the band kernels): size and the offsets of the
-    fields round 6 appended (analytic Kaiser window) must be the header's."""
-    import shutil
-    import subprocess
-    import pytest
-    if shutil.which("gcc") is None:
-        pytest.skip("no C compiler")
-    from babe_amd.cqt import _BandsStruct
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "%s"\nint main(void){printf("%%zu %%zu %%zu %%zu %%zu %%zu\\n",'
-                   ' sizeof(babe_cqt_bands), offsetof(babe_cqt_bands, coef), offsetof(babe_cqt_bands, wg_rec), offsetof(babe_cqt_bands, sum_T),'
-                   ' offsetof(babe_cqt_bands, kdeg), offsetof(babe_cqt_bands, kpoly));return 0;}\n'
-                   % os.path.join(ROOT, "include", "babe_hip.h"))
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-o", str(exe), str(src)], check=True)
-    want = [int(v) for v in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()]
-    got = [ctypes.sizeof(_BandsStruct), _BandsStruct.coef.offset, _BandsStruct.wg_rec.offset, _BandsStruct.sum_T.offset,
-           _BandsStruct.kdeg.offset, _BandsStruct.kpoly.offset]
-    assert got == want, (got, want)
+    """The ctypes mirror of babe_cqt_bands (the band kernels get it BY VALUE), the fields round 6 appended included."""
+    from babe_amd import _cabi
+    _check_layout(tmp_path, {"babe_cqt_bands": _cabi.STRUCTS["babe_cqt_bands"]})
+
+
+def test_every_other_struct_mirror_has_the_headers_layout(tmp_path):
+    """... and every remaining struct of the header that babe_amd/_cabi.py mirrors (conv / weight-gradient / denoiser-conv
+    arguments, the fit configuration, the score-evaluation descriptor)."""
+    from babe_amd import _cabi
+    rest = {n: st for n, st in _cabi.STRUCTS.items() if n not in _UNET_STRUCTS + ("babe_cqt_bands",)}
+    assert len(rest) >= 5
+    _check_layout(tmp_path, rest)
 
 
 def test_kaiser_poly_reproduces_the_window_table():
@@ -88,7 +164,6 @@ def test_unet_plan_create_validates_every_block():
     validation only: no GPU call is made."""
     from babe_amd._lib import lib
     from babe_amd.networks import unet_c as uc
-    uc._register()
     L = lib()
     FAKE = 0x1000                                         # never dereferenced by plan_create (pointers stay the caller's)
 
@@ -178,21 +253,11 @@ def test_plan_entry_points_refuse_bad_arguments_without_a_gpu():
     an empty descriptor are refused with a message instead of being dereferenced."""
     from babe_amd._lib import lib
     from babe_amd.testing import eval_c
-    eval_c._register()
     L = lib()
-    L.babe_last_error.restype = ctypes.c_char_p
-    L.babe_cqt_workspace_bytes.restype = ctypes.c_long
-    L.babe_cqt_workspace_bytes.argtypes = [ctypes.c_void_p, ctypes.c_int]
     assert L.babe_cqt_workspace_bytes(None, 4) == -1
     for name in ("babe_cqt_fwd", "babe_cqt_bwd", "babe_cqt_fwd_adjoint", "babe_cqt_bwd_adjoint", "babe_cqt_hpf"):
-        fn = getattr(L, name)
-        fn.restype = ctypes.c_int
-        fn.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_void_p]
-        assert fn(None, None, None, None, 1, None) < 0 and b"bad arguments" in L.babe_last_error()
+        assert getattr(L, name)(None, None, None, None, 1, None) < 0 and b"bad arguments" in L.babe_last_error()
     d = eval_c.EvalDesc()
     assert L.babe_eval_workspace_bytes(ctypes.byref(d), 1) == -1 and b"bad descriptor" in L.babe_last_error()
     assert L.babe_score_eval(ctypes.byref(d), None, 0.1, 1.0, 1.0, 1.0, 0.0, None, None, None, None, None, None, None, 0, 1, None) < 0
-    L.babe_filter_loss_grad.restype = ctypes.c_int
-    L.babe_filter_loss_grad.argtypes = [ctypes.c_void_p, ctypes.c_long, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                        ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
     assert L.babe_filter_loss_grad(None, 0, None, None, 1, 1, 2049, 44100.0, 4096, None, None) < 0

@@ -5,25 +5,17 @@ arguments, and a window is a quotient of two I0 values; 16 ulp on the dual windo
 of ~10^5 squared window samples; the high-pass response 1 - lp / diag to 1e-15 absolute), and the float32 images that reach the device equal
 except where a float64 difference of that size straddles a float32 rounding boundary (< 1e-4 of the entries, 1 float32 ulp)."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [(44100, 368368, 7, 64, 1.0), (22050, 92092, 7, 64, 1.0), (16000, 184184, 7, 64, 1.0), (44100, 46046, 7, 64, 1.0),
          (22050, 65536, 6, 32, 2.0)]
 
 
 def _lib():
-    L = C.CDLL(os.path.join(ROOT, "babe_amd", "libbabe_hip.so"))
-    L.babe_cqt_design_create.restype = C.c_void_p
-    L.babe_cqt_design_create.argtypes = [C.c_double, C.c_int, C.c_int, C.c_int, C.c_double]
-    L.babe_cqt_design_destroy.argtypes = [C.c_void_p]
-    L.babe_cqt_design_get.restype = C.c_long
-    L.babe_cqt_design_get.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_long]
-    L.babe_last_error.restype = C.c_char_p
-    return L
+    from babe_amd._lib import lib
+    return lib()
 
 
 def _get(L, d, name, dtype):

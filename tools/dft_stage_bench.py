@@ -2,11 +2,10 @@
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from babe_amd import ops
-from babe_amd.cqt import RealFFT, _register_sigs
+from babe_amd.cqt import RealFFT
 from babe_amd._lib import lib, check, ptr, stream, dispatch_counts
 B = int(os.environ.get("B", "1"))
 dev = torch.device("cuda", 0)
-_register_sigs()
 f = RealFFT(368368, dev)
 N1, N2, K2 = f.N1, f.N2, f.K2
 print("N1", N1, "N2", N2, "K2", K2)

@@ -2,8 +2,6 @@ import sys, os, math, torch
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, R)
 from babe_amd import ops
-from babe_amd import cqt as _cq
-_cq._register_sigs()
 from babe_amd.cqt import RealFFT
 torch.manual_seed(0)
 L = 368368

@@ -8,9 +8,9 @@ from babe_amd._lib import stream
 so = "/tmp/lds_canary.so"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O2", "-shared", "-fPIC", os.path.join(R, "tools", "lds_canary.hip"), "-o", so])
 lib = C.CDLL(so)
-lib.lds_canary.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p]
-lib.valu_canary.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-lib.pk_canary.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+lds_canary = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_long, C.c_void_p)(("lds_canary", lib))
+valu_canary = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p)(("valu_canary", lib))
+pk_canary = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p)(("pk_canary", lib))
 def mkconv(prec, Cin, Cout, F, T, kh, dil, B=2):
     kw = 3 if kh == 5 else 1
     ww = torch.randn(Cout, Cin, kh, kw, device="cuda") / math.sqrt(Cin * kh * kw); pc = ops.PackedConv(ww, prec)
@@ -27,7 +27,7 @@ for words in words_list:
         for i in range(10):
             with torch.cuda.stream(sB): pf()
             with torch.cuda.stream(sA):
-                rc = lib.lds_canary(out.data_ptr(), 512, 256, words, 200000, stream())
+                rc = lds_canary(out.data_ptr(), 512, 256, words, 200000, stream())
                 assert rc == 0, rc
             with torch.cuda.stream(sB): pf()
         torch.cuda.synchronize()
@@ -45,7 +45,7 @@ for pn, pf in partners.items():
     for i in range(10):
         with torch.cuda.stream(sB): pf()
         with torch.cuda.stream(sA):
-            rc = lib.valu_canary(out.data_ptr(), 1024, 256, 2000, stream())
+            rc = valu_canary(out.data_ptr(), 1024, 256, 2000, stream())
             assert rc == 0, rc
         with torch.cuda.stream(sB): pf()
     torch.cuda.synchronize()
@@ -63,7 +63,7 @@ for pn, pf in partners.items():
     for i in range(10):
         with torch.cuda.stream(sB): pf()
         with torch.cuda.stream(sA):
-            rc = lib.pk_canary(out.data_ptr(), 1024, 256, 3000, stream())
+            rc = pk_canary(out.data_ptr(), 1024, 256, 3000, stream())
             assert rc == 0, rc
         with torch.cuda.stream(sB): pf()
     torch.cuda.synchronize()
