@@ -21,6 +21,7 @@ class ConvArgs(C.Structure):
         ("KH", C.c_int), ("KW", C.c_int), ("dil", C.c_int),
         # optional reduction fused into the F(4,5) kernels' epilogue (include/babe_hip.h; zero = off)
         ("stat_mode", C.c_int), ("stat_cg", C.c_int), ("stat_x", C.c_void_p), ("stat_scale", C.c_void_p), ("stat_part", C.c_void_p),
+        ("fbias", C.c_void_p),                          # [Cout][F] bias per channel and frequency row (the (1,1) fp32 kernels)
     ]
 
 
@@ -45,7 +46,8 @@ class CBlock(C.Structure):
     """babe_unet_block"""
     _fields_ = [("N", C.c_int), ("nd", C.c_int), ("k53", C.c_int),
                 ("proj_in", CPackedConv), ("res_conv", CPackedConv), ("proj_out", CPackedConv), ("H", CPackedConv * 8),
-                ("gamma", C.c_void_p * 8), ("film_aff", C.c_int * 8), ("film_gate", C.c_int * 8)]
+                ("gamma", C.c_void_p * 8), ("film_aff", C.c_int * 8), ("film_gate", C.c_int * 8),
+                ("fb_proj_in", C.c_void_p), ("fb_res_conv", C.c_void_p)]
 
 
 class CPlanDesc(C.Structure):
@@ -235,6 +237,8 @@ SIGS = {
     "babe_gn_param_grad": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P]),
     "babe_linear_bwd_workspace": (_L, [_I, _I, _I]),
     "babe_linear_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
+    "babe_fenc_bias": (_I, [_P, _P, _P, _I, _I, _P]),
+    "babe_fenc_wgrad_rows": (_I, [_P, _L, _L, _P, _F, _P, _L, _I, _I, _I, _I, _I, _P]),
 }
 
 

@@ -30,8 +30,9 @@ struct ConvGeom {
 // its NT MFMAs are contiguous in LDS: channel co0 + nt*32 + l  is stored at  co0 + l*NT + nt.
 // VEC = true: activations are staged as 16-byte loads / ds_write_b128 (needs T % 4 == 0 and 16-byte aligned rows);
 // the LDS row then carries its left halo at index 3 so that the body starts 16-byte aligned.
-template <int NT, int WP, int KC, int KW, bool VEC>
-__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv_mfma_kernel(babe_conv_args a, ConvGeom g) {
+// (the body of both kernels below: conv_mfma_kernel, and conv11_fb_kernel with the frequency bias in its epilogue)
+template <int NT, int WP, int KC, int KW, bool VEC, bool HAS_FB>
+__device__ __forceinline__ void conv_mfma_body(const babe_conv_args& a, const ConvGeom& g) {
     constexpr int BN = NT * 32;
     constexpr int NPOS = 128 * WP;          // output positions per block
     constexpr int TG = 256 / NPOS;          // thread groups that split the KC staged channels
@@ -278,7 +279,20 @@ __global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv_mfma_kernel(babe_
     }
 
     // ---- epilogue
-    conv_epilogue<NT, WP>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
+    if constexpr (HAS_FB) conv_epilogue_fb<NT, WP>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
+    else conv_epilogue<NT, WP>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
+}
+
+template <int NT, int WP, int KC, int KW, bool VEC>
+__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv_mfma_kernel(babe_conv_args a, ConvGeom g) {
+    conv_mfma_body<NT, WP, KC, KW, VEC, false>(a, g);
+}
+
+// out = alpha * oscale * (acc + fbias[co][f]) + rbeta * res (babe_conv_args::fbias, non-NULL): (1,1) convs only (babe_conv2d_nt).
+// A kernel of its own, so that conv_mfma_kernel keeps the registers and scratch it has without the bias epilogues.
+template <int NT, int WP, int KC, bool VEC>
+__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv11_fb_kernel(babe_conv_args a, ConvGeom g) {
+    conv_mfma_body<NT, WP, KC, 1, VEC, true>(a, g);
 }
 
 inline int pick_nt(int CoutP) {
@@ -337,6 +351,12 @@ int launch_conv(const babe_conv_args& a, ConvGeom g, hipStream_t s) {
     const int tiles_f = cdiv(a.F, PR);
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / (NT * 32), a.B);
     size_t lds = 2 * ((size_t)((KC * PR * (PT + (VEC ? 8 : 2)) + 3) & ~3) + (size_t)KW * KC * NT * 32) * sizeof(float);
+    if constexpr (KW == 1) {
+        if (a.fbias) {
+            hipLaunchKernelGGL((conv11_fb_kernel<NT, WP, KC, VEC>), grid, dim3(256), lds, s, a, g);
+            return 0;
+        }
+    }
     hipLaunchKernelGGL((conv_mfma_kernel<NT, WP, KC, KW, VEC>), grid, dim3(256), lds, s, a, g);
     return 0;
 }
@@ -381,6 +401,7 @@ extern "C" int babe_conv2d_nt(const babe_conv_args* ap, int nt, void* stream) {
     BABE_CHECK_ARG((a.KH == 5 || a.KH == 1) && (a.KW == 3 || a.KW == 1) && a.dil >= 1,
                    "conv2d: kernel %dx%d unsupported (need 5x3 or 1x1)", a.KH, a.KW);
     BABE_CHECK_ARG(!a.in2 || (a.cin_split > 0 && a.cin_split < a.Cin), "conv2d: bad cin_split");
+    BABE_CHECK_ARG(!a.fbias || (a.KH == 1 && a.KW == 1), "conv2d: fbias needs a (1,1) kernel (got %dx%d)", a.KH, a.KW);
     ConvGeom g;
     g.CinP = (a.Cin + 7) / 8 * 8;
     g.CoutP = (a.Cout + 31) / 32 * 32;

@@ -57,7 +57,8 @@ struct C11Geom {
 // descriptor's size, so the hardware range check drops it - no per-element branches, no 64-bit address arithmetic, and
 // none of the 132-1228 bytes per lane of scratch the pointer-based shared epilogue (conv_common.h) needed at 256 registers.
 // With four K-slabs per tile (the 64-channel full-resolution layers) the epilogue is a quarter of the kernel.
-template <int NT, int WP>
+// HAS_FB: acc + fbias[co][f] in place of acc (babe_conv_args::fbias, dense [Cout][F]: one more descriptor, 16 loads per group).
+template <int NT, int WP, bool HAS_FB>
 __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16 (&acc)[NT][WP], int b, int co0, int f0,
                                                  int t0, int pt_log2, int wave, int l31, int h) {
 #if __HIP_DEVICE_COMPILE__
@@ -68,9 +69,11 @@ __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16
                                                                          has_res ? (unsigned)(a.Cout * a.res_cs * 4) : 0u, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_ = __builtin_amdgcn_make_buffer_rsrc((void*)(has_os ? a.oscale + (long)b * a.Cout : a.out), 0,
                                                                          has_os ? (unsigned)(a.Cout * 4) : 0u, 0x00020000);
-    const unsigned ocs = (unsigned)a.out_cs * 4u, rcs = (unsigned)a.res_cs * 4u;
+    const __amdgpu_buffer_rsrc_t rf_ = __builtin_amdgcn_make_buffer_rsrc((void*)(HAS_FB ? a.fbias : a.out), 0,
+                                                                         HAS_FB ? (unsigned)(a.Cout * a.F * 4) : 0u, 0x00020000);
+    const unsigned ocs = (unsigned)a.out_cs * 4u, rcs = (unsigned)a.res_cs * 4u, fcs = (unsigned)a.F * 4u;
     // per-position byte offsets of the WP column tiles (out of range when the position is padding)
-    unsigned lo[WP], lr[WP];
+    unsigned lo[WP], lr[WP], lf[WP];
 #pragma unroll
     for (int wp = 0; wp < WP; ++wp) {
         const int p = (wave * WP + wp) * 32 + l31;
@@ -80,6 +83,7 @@ __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16
         const unsigned sp = (unsigned)(f * a.T + t) * 4u;
         lo[wp] = pv ? (unsigned)(co0 + 4 * h) * ocs + sp : 0x80000000u;
         lr[wp] = pv ? (unsigned)(co0 + 4 * h) * rcs + sp : 0x80000000u;
+        lf[wp] = pv ? (unsigned)(co0 + 4 * h) * fcs + (unsigned)f * 4u : 0x80000000u;
     }
     // The residual of group g + 1 (one (row tile, column tile) pair = 16 values per lane) is loaded while group g is scaled and
     // stored: two groups of loads in flight per wave instead of one (the res-carrying layers - every VJP - are bound by this
@@ -111,6 +115,16 @@ __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16
         for (int wp = 0; wp < WP; ++wp) {
             const int gidx = nt * WP + wp;
             if (has_res && gidx + 1 < NT * WP) load_res(gidx + 1, rv[(gidx + 1) & 1]);
+            if constexpr (HAS_FB) {
+                float fb[16];
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int cl = nt * 32 + (r & 3) + 8 * (r >> 2);
+                    fb[r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rf_, lf[wp] + (unsigned)cl * fcs, 0, 0));
+                }
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[nt][wp][r] = __fadd_rn(acc[nt][wp][r], fb[r]);
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int cl = nt * 32 + (r & 3) + 8 * (r >> 2);
@@ -127,8 +141,9 @@ __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16
 
 // NPW = 32-position MFMA column tiles per wave: 2 (256 positions per workgroup, 2 workgroups per CU) or 1 (128 positions,
 // 3 per CU: finer tail quantisation for the launches with only a few hundred workgroups)
-template <int NT, int NPW, bool HAS_ISC>
-__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_kernel(babe_conv_args a, C11Geom g) {
+// (the body of both kernels below: conv11p_kernel, and conv11p_fb_kernel with the frequency bias in its epilogue)
+template <int NT, int NPW, bool HAS_ISC, bool HAS_FB>
+__device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const C11Geom& g) {
 #if __HIP_DEVICE_COMPILE__
     constexpr int KC = 16;
     constexpr int BN = NT * 32;
@@ -289,8 +304,19 @@ __global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_kernel(babe_con
 #if !C11_SYNC_AT_END
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the clamped re-stage of the last slab: nothing lands in LDS after the loop
 #endif
-    conv11p_epilogue<NT, NPW>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
+    conv11p_epilogue<NT, NPW, HAS_FB>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
 #endif
+}
+
+template <int NT, int NPW, bool HAS_ISC>
+__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_kernel(babe_conv_args a, C11Geom g) {
+    conv11p_body<NT, NPW, HAS_ISC, false>(a, g);
+}
+
+// out = alpha * oscale * (acc + fbias[co][f]) + rbeta * res (babe_conv_args::fbias); forward convs only, so no in_scale form
+template <int NT, int NPW>
+__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_fb_kernel(babe_conv_args a, C11Geom g) {
+    conv11p_body<NT, NPW, false, true>(a, g);
 }
 
 template <int NT, int NPW>
@@ -308,10 +334,12 @@ void launch11(const babe_conv_args& a, C11Geom g, hipStream_t s) {
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     static std::atomic<unsigned long long> attr_done{0};
     if (babe_lds_optin(attr_done, {reinterpret_cast<const void*>(&conv11p_kernel<NT, NPW, true>),
-                                   reinterpret_cast<const void*>(&conv11p_kernel<NT, NPW, false>)},
+                                   reinterpret_cast<const void*>(&conv11p_kernel<NT, NPW, false>),
+                                   reinterpret_cast<const void*>(&conv11p_fb_kernel<NT, NPW>)},
                        (int)(3 * (size_t)(16 * 128 * NPW + WJ * 256 * 4) * 4 + 2048 * 4)) != hipSuccess)     // (+ up to 2048 in_scale values)
         return;
-    if (a.in_scale) hipLaunchKernelGGL((conv11p_kernel<NT, NPW, true>), grid, dim3(256), lds, s, a, g);
+    if (a.fbias) hipLaunchKernelGGL((conv11p_fb_kernel<NT, NPW>), grid, dim3(256), lds, s, a, g);       // (never with in_scale: _supported)
+    else if (a.in_scale) hipLaunchKernelGGL((conv11p_kernel<NT, NPW, true>), grid, dim3(256), lds, s, a, g);
     else hipLaunchKernelGGL((conv11p_kernel<NT, NPW, false>), grid, dim3(256), lds, s, a, g);
 }
 
@@ -334,6 +362,7 @@ int babe_conv11p_supported(const babe_conv_args& a, int nt) {
     const long coP = (a.Cout + 31) / 32 * 32;
     if (coP * a.out_cs >= lim || (a.res && coP * a.res_cs >= lim)) return 0;
     if (a.in_scale && a.Cin > 2032) return 0;                 // the LDS copy of the scales
+    if (a.fbias && (a.in_scale || (long)a.Cout * a.F >= lim)) return 0;      // the bias variant has no in_scale form; 32-bit table offsets
     if ((long)a.F * a.T < 4096 && a.Cin < 256) return 0;     // tiny planes AND a short K loop: nothing to pipeline (the
                                                              // dense DFT stages, K ~ 2000 over a few hundred positions, qualify)
     return 1;

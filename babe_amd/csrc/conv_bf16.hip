@@ -365,6 +365,7 @@ extern "C" int babe_conv2d_bf16(const babe_conv_args* ap, const void* w_bf16, in
     BABE_CHECK_ARG(ap && w_bf16, "conv2d_bf16: null args");
     const babe_conv_args& a = *ap;
     BABE_CHECK_ARG(a.in && a.out, "conv2d_bf16: null pointer");
+    BABE_CHECK_ARG(!a.fbias, "conv2d_bf16: fbias is implemented by the fp32 (1,1) kernels only (babe_conv2d)");
     BABE_CHECK_ARG(a.B > 0 && a.Cin > 0 && a.Cout > 0 && a.F > 0 && a.T > 0, "conv2d_bf16: bad shape");
     BABE_CHECK_ARG((a.KH == 5 || a.KH == 1) && (a.KW == 3 || a.KW == 1) && a.dil >= 1, "conv2d_bf16: kernel %dx%d unsupported", a.KH, a.KW);
     BABE_CHECK_ARG(splits == 1 || splits == 2, "conv2d_bf16: splits must be 1 (bf16) or 2 (bf16x3)");

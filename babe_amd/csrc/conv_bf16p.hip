@@ -481,6 +481,7 @@ extern "C" int babe_conv2d_bf16_units_supported(const babe_conv_args* ap) {
     static const char* ov = getenv("BABE_CONV_BF16U");
     if (ov && ov[0] == '0') return 0;
     if (a.KH != 5 || a.KW != 3 || (a.T & 3) || (a.Cin & 7) || a.Cout <= 32 || a.in2 || a.in_scale) return 0;
+    if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (!al16(a.in) || !al16(a.out) || (a.out_bs & 3) || (a.out_cs & 3)) return 0;
     if (a.res && (!al16(a.res) || (a.res_bs & 3) || (a.res_cs & 3))) return 0;

@@ -8,10 +8,11 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// Epilogue shared by all conv kernels: out = alpha*acc*oscale[b,co] + rbeta*res.  The 16 loads of a 32x32 tile are
+// Epilogue shared by all conv kernels: out = alpha*acc*oscale[b,co] + rbeta*res; HAS_FB (the (1,1) kernels): acc + fbias[co][f] in
+// place of acc.  The 16 loads of a 32x32 tile are
 // issued back-to-back inside ONE wave-uniform branch per operand: a per-element "if (ptr) load" makes hipcc branch
 // around every load and wait vmcnt(0) each time (measured: the epilogue then serialises 128 load latencies).
-template <int NT, int WP, bool HAS_OS, bool HAS_RES>
+template <int NT, int WP, bool HAS_OS, bool HAS_RES, bool HAS_FB = false>
 __device__ __forceinline__ void conv_epilogue_impl(const babe_conv_args& a, f32x16 (&acc)[NT][WP], int b, int co0,
                                                    int f0, int t0, int pt_log2, int wave, int l31, int h) {
     const int PT = 1 << pt_log2;
@@ -24,7 +25,7 @@ __device__ __forceinline__ void conv_epilogue_impl(const babe_conv_args& a, f32x
         const long sp = pv ? (long)f * a.T + t : 0;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
-            float os[16], rr[16];
+            float os[16], rr[16], fb[16];
             int cc[16];
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -39,10 +40,17 @@ __device__ __forceinline__ void conv_epilogue_impl(const babe_conv_args& a, f32x
 #pragma unroll
                 for (int r = 0; r < 16; ++r) rr[r] = a.res[(long)b * a.res_bs + (long)cc[r] * a.res_cs + sp];
             }
+            if constexpr (HAS_FB) {
+                const int fr = pv ? f : 0;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) fb[r] = a.fbias[(long)cc[r] * a.F + fr];
+            }
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int co = co0 + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                float v = acc[nt][wp][r] * a.alpha;
+                float v = acc[nt][wp][r];
+                if constexpr (HAS_FB) v = __fadd_rn(v, fb[r]);
+                v *= a.alpha;
                 if constexpr (HAS_OS) v *= os[r];
                 if constexpr (HAS_RES) v += a.rbeta * rr[r];
                 if (pv && co < a.Cout) a.out[(long)b * a.out_bs + (long)co * a.out_cs + sp] = v;
@@ -61,6 +69,19 @@ __device__ __forceinline__ void conv_epilogue(const babe_conv_args& a, f32x16 (&
     } else {
         if (a.res) conv_epilogue_impl<NT, WP, false, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
         else conv_epilogue_impl<NT, WP, false, false>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
+    }
+}
+
+// the same with the frequency bias a.fbias (non-NULL); instantiated by the (1,1) kernels only
+template <int NT, int WP>
+__device__ __forceinline__ void conv_epilogue_fb(const babe_conv_args& a, f32x16 (&acc)[NT][WP], int b, int co0, int f0,
+                                                 int t0, int pt_log2, int wave, int l31, int h) {
+    if (a.oscale) {
+        if (a.res) conv_epilogue_impl<NT, WP, true, true, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
+        else conv_epilogue_impl<NT, WP, true, false, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
+    } else {
+        if (a.res) conv_epilogue_impl<NT, WP, false, true, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
+        else conv_epilogue_impl<NT, WP, false, false, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
     }
 }
 

@@ -149,6 +149,7 @@ extern "C" int babe_conv2d_fewco_supported(const babe_conv_args* ap) {
     const babe_conv_args& a = *ap;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.Cout < 1 || a.Cout > 4 || a.KW != 3 || a.KH < 1 || a.KH > 7 || a.T % 4 || a.in2 || a.in_scale) return 0;
+    if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4 || !al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;
     if (a.res && (!al16(a.res) || a.res_bs % 4 || a.res_cs % 4)) return 0;
     if ((long)a.Cin * a.KH * 4 * 16 > 120 * 1024) return 0;          // weights must fit LDS

@@ -363,6 +363,7 @@ extern "C" int babe_conv2d_wino4_supported(const babe_conv_args* ap) {
     const babe_conv_args& a = *ap;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.KW != 3 || a.KH < 1 || a.T % 4 != 0 || a.T < 16) return 0;
+    if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4) return 0;
     if (a.in2 && (!al16(a.in2) || a.in2_bs % 4 || a.in2_cs % 4)) return 0;
     if (!al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;

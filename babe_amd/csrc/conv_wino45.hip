@@ -1111,6 +1111,7 @@ extern "C" int babe_conv2d_wino45_supported(const babe_conv_args* ap) {
     const babe_conv_args& a = *ap;
     auto al16 = [](const void* p) __attribute__((always_inline)) { return ((uintptr_t)p & 15) == 0; };
     if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;   // (tiles are 64 time steps wide)
+    if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (a.Cin < 16 || a.Cin % 16 != 0 || a.Cout < 33) return 0;   // (the channel part of a load address is a scalar offset,
     // which the buffer range check does not cover: no padded input channels; an even number of 8-channel slabs per pass: the
     // slab loop is unrolled by two; few-channel convs run on conv_fewco / direct)

@@ -1049,6 +1049,7 @@ extern "C" int babe_conv2d_wino85_supported(const babe_conv_args* ap) {
     const babe_conv_args& a = *ap;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;
+    if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (a.Cin < 16 || a.Cin % 16 != 0 || (a.Cout % 128 != 0 && a.Cout % 96 != 0 && a.Cout % 64 != 0)) return 0;
     if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4 || a.in2) return 0;
     if (!al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;

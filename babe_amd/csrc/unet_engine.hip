@@ -20,7 +20,9 @@
  * (babe_amd/ops.py::conv2d calls this too): bf16 images, few-output-channel vector kernel, nested Winograd F(4,5)xF(4,3) /
  * F(2,5)xF(4,3) where their tiles are full, F(4,3), F(2,3), direct / pipelined (1,1); an image left NULL takes its kernel out.
  * The caller fills every field of *a except w_packed, Cin, Cout, KH, KW (taken from pc and transpose).  A requested fused
- * reduction (a->stat_mode) is formed only by the F(4,5) kernels: on return a->stat_mode is 0 if it was NOT produced. */
+ * reduction (a->stat_mode) is formed only by the F(4,5) kernels: on return a->stat_mode is 0 if it was NOT produced.
+ * A frequency bias (a->fbias) is never dropped: every *_supported rule below refuses it, so such a call ends in babe_conv2d_nt,
+ * which adds it ((1,1) kernels) or returns an error; so does babe_conv2d_bf16. */
 extern "C" int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, int transpose, void* stream) {
     BABE_CHECK_ARG(a && pc, "conv2d_auto: null arguments");
     a->Cin = transpose ? pc->Cout : pc->Cin;
@@ -133,7 +135,8 @@ struct Ctx {
     // stat_cg / stat_part: also form the GroupNorm sums of the output in the conv's epilogue (babe_conv_args::stat_mode 1); returns
     // true if the kernel that ran the conv produced them (only the F(4,5) kernels do)
     bool conv(const View& x, const babe_packed_conv& pc, const View& out, int dil, bool transpose, const View* x2, const View* res,
-              const float* in_scale, const float* oscale, float alpha, float rbeta, int stat_cg = 0, double* stat_part = nullptr) {
+              const float* in_scale, const float* oscale, float alpha, float rbeta, int stat_cg = 0, double* stat_part = nullptr,
+              const float* fbias = nullptr) {
         if (dry() || err) return false;
         babe_conv_args a;
         memset(&a, 0, sizeof a);
@@ -141,7 +144,7 @@ struct Ctx {
         if (x2) { a.in2 = x2->p; a.in2_bs = x2->bs; a.in2_cs = x2->cs; a.cin_split = x.C; }
         a.out = out.p; a.out_bs = out.bs; a.out_cs = out.cs;
         if (res) { a.res = res->p; a.res_bs = res->bs; a.res_cs = res->cs; }
-        a.in_scale = in_scale; a.oscale = oscale; a.alpha = alpha; a.rbeta = rbeta;
+        a.in_scale = in_scale; a.oscale = oscale; a.alpha = alpha; a.rbeta = rbeta; a.fbias = fbias;
         a.B = B(); a.F = x.F; a.T = x.T; a.dil = dil;
         if (stat_part) { a.stat_mode = 1; a.stat_cg = stat_cg; a.stat_part = stat_part; }
         ck(babe_conv2d_auto(&a, &pc, transpose ? 1 : 0, st));
@@ -190,7 +193,7 @@ struct Ctx {
         View z;
         if (blk.proj_in.Cout) {
             z = buf(N, Fq, T);
-            conv(x, blk.proj_in, z, 1, false, x2, nullptr, nullptr, nullptr, 1.f, 0.f);
+            conv(x, blk.proj_in, z, 1, false, x2, nullptr, nullptr, nullptr, 1.f, 0.f, 0, nullptr, blk.fb_proj_in);
         } else if (x.dense()) {
             z = x;
         } else {
@@ -240,7 +243,7 @@ struct Ctx {
             conv(z, blk.proj_out, zo, 1, false, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f);
             z = zo;
         }
-        if (blk.res_conv.Cout) conv(x, blk.res_conv, out, 1, false, x2, &z, nullptr, nullptr, RS2, RS2);
+        if (blk.res_conv.Cout) conv(x, blk.res_conv, out, 1, false, x2, &z, nullptr, nullptr, RS2, RS2, 0, nullptr, blk.fb_res_conv);
         else axpby2(z, x, out, RS2, RS2);
         return out;
     }

@@ -9,7 +9,13 @@ sampler code - which calls ``torch.autograd.grad`` through the model - runs on i
 There is no CPU path: device must be a GPU and libbabe_hip.so must be present.
 
 Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run in fp32 on the Python sequencer
-(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them).  Not implemented: frequency encodings (``use_fencoding``).
+(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them).
+
+Frequency encodings (``use_fencoding``, AddFreqEncodingRFF) are never materialised as channels: the 64 encoding channels are
+constant over batch and time and feed only the init blocks' two (1,1) convs, so their share is folded into a bias table per conv
+and octave that the conv kernel adds in its epilogue (csrc/fenc.hip).  ``freq_encodings.{i}.RFF_freq`` and
+``.embeddings`` are non-trainable parameters under the reference's names; the loaded ``embeddings`` is what the network uses.
+Not implemented: ``use_norm=False``.
 """
 import math
 import os
@@ -30,8 +36,22 @@ def attention_options(attention_dict):
             int(g("rel_pos_max_distance", 64)))
 
 
-def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, attention_dict=None, bins_per_oct=64):
-    """[(key, shape, init)] for every parameter/buffer of the reference module, init in {'w','gate','ones','rff','buf','randn'}.
+N_FREQ_ENCODING = 32                     # RFF frequencies per octave (networks/cqtdiff+.py:627): 64 sin / cos encoding channels
+
+
+def freq_embedding(rff_freq, f_dim):
+    """AddFreqEncodingRFF.build_RFF_embedding: [1, 2N, f_dim] = sin | cos of (2 pi n) * freq, every step in float32 as in the
+    reference (the arguments reach 1e4, so the order of the roundings is part of the result)."""
+    n = torch.arange(0, f_dim).unsqueeze(0).unsqueeze(0)
+    table = (2 * np.pi * n) * rff_freq.float().unsqueeze(-1)
+    return torch.cat([torch.sin(table), torch.cos(table)], dim=1)
+
+
+def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, attention_dict=None, bins_per_oct=64,
+                use_fencoding=False):
+    """[(key, shape, init)] for every parameter/buffer of the reference module, init in {'w','gate','ones','rff','buf','randn',
+    'femb'}.  use_fencoding: the per-octave freq_encodings.{i} tables (after the embedding MLP, as in the reference's
+    named_parameters) and 66-input-channel init blocks.
     attention_layers: one flag per octave plus the bottleneck (reference ResnetBlock attention_dict); the attention keys of a
     block come after all of its other keys, so an attention-off net has exactly the keys (and init order) it always had."""
     att = list(attention_layers or [0] * (num_octs + 1))
@@ -39,6 +59,11 @@ def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, at
     out = [("embedding.RFF_freq", (1, 32), "rff")]
     for i, (o, k) in enumerate([(128, 64), (256, 128), (emb_dim, 256)]):
         out += [(f"embedding.MLP.{i}.weight", (o, k), "w"), (f"embedding.MLP.{i}.bias", (o,), "zero")]
+    if use_fencoding:
+        for i in range(num_octs):
+            out += [(f"freq_encodings.{i}.RFF_freq", (1, N_FREQ_ENCODING), "rff"),
+                    (f"freq_encodings.{i}.embeddings", (1, 2 * N_FREQ_ENCODING, bins_per_oct), "femb")]
+    nin = 2 + 2 * N_FREQ_ENCODING if use_fencoding else 2
     out += [("downsamplerT.kernel", (8,), "buf"), ("upsamplerT.kernel", (8,), "buf")]
 
     def block(p, dim, dim_out, nd, k, after, Fdim=0):
@@ -70,7 +95,7 @@ def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, at
 
     for i in range(num_octs):
         din, dout = (Ns[0], Ns[0]) if i == 0 else (Ns[i - 1], Ns[i])
-        out += block(f"downs.{i}.0.", 2, din, 1, (1, 1), False)
+        out += block(f"downs.{i}.0.", nin, din, 1, (1, 1), False)
         out.append((f"downs.{i}.1.weight", (dout, 2, 5, 3), "w"))
         out += block(f"downs.{i}.2.", din, dout, num_dils[i], (5, 3), False, (i + 1) * bins_per_oct if att[i] else 0)
     out += block("middle.0.0.", Ns[-1], 2, 1, (1, 1), True)
@@ -85,14 +110,16 @@ def param_specs(Ns, num_dils, emb_dim=256, num_octs=7, attention_layers=None, at
 CUBIC = [-0.01171875, -0.03515625, 0.11328125, 0.43359375, 0.43359375, 0.11328125, -0.03515625, -0.01171875]
 
 
-def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7, attention_layers=None, attention_dict=None):
+def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7, attention_layers=None, attention_dict=None,
+                    use_fencoding=False):
     """Random weights with the reference's init rule (kaiming_uniform * sqrt(1/3); gates * 1e-7, cqtdiff+.py:599-600).
     gate_scale=1 gives O(1) gates (an untrained net with 1e-7 gates has numerically dead residual branches).
     Attention layers (param_specs) draw after everything else of their block; the relative-position tables are N(0,1)
     (nn.Embedding)."""
     g = torch.Generator().manual_seed(seed)
     sd = {}
-    for key, shape, kind in param_specs(Ns, num_dils, emb_dim, attention_layers=attention_layers, attention_dict=attention_dict):
+    for key, shape, kind in param_specs(Ns, num_dils, emb_dim, attention_layers=attention_layers, attention_dict=attention_dict,
+                                        use_fencoding=use_fencoding):
         if kind in ("w", "gate"):
             fan_in = int(np.prod(shape[1:]))
             w = math.sqrt(3.0 / fan_in) * (torch.rand(shape, generator=g) * 2 - 1)
@@ -105,19 +132,21 @@ def init_state_dict(Ns, num_dils, emb_dim=256, seed=0, gate_scale=1e-7, attentio
             sd[key] = 16 * torch.randn(shape, generator=g)
         elif kind == "randn":
             sd[key] = torch.randn(shape, generator=g)
+        elif kind == "femb":                  # built from the RFF_freq drawn just before it, by the reference's formula
+            sd[key] = freq_embedding(sd[key[:-len("embeddings")] + "RFF_freq"], shape[2])
         else:
             sd[key] = torch.tensor(CUBIC)
     return sd
 
 
-# The reference trains every parameter except embedding.RFF_freq (requires_grad=False, networks/cqtdiff+.py:176); the resampler
-# kernels are buffers.
+# The reference trains every parameter except embedding.RFF_freq (requires_grad=False, networks/cqtdiff+.py:176) and the frequency
+# encodings' RFF_freq / embeddings (:222-228); the resampler kernels are buffers.
 NOT_TRAINABLE = ("embedding.RFF_freq",)
 
 
 def is_trainable(key):
     """True for the parameters the reference's optimizer updates."""
-    return key not in NOT_TRAINABLE
+    return key not in NOT_TRAINABLE and not key.startswith("freq_encodings.")
 
 
 class _Node(nn.Module):
@@ -165,8 +194,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         # conv arithmetic: 'f32' (default, the parity path), 'bf16x3', 'bf16' (csrc/conv_bf16.hip); can also be
         # given as args.network.precision
         self.precision = precision or nw.get("precision", "f32")
-        if nw.get("use_fencoding", False):
-            raise NotImplementedError("use_fencoding=True (disabled in the blind-BWE configs)")
+        self.use_fencoding = bool(nw.get("use_fencoding", False))
         self.attention_layers = [int(bool(v)) for v in (nw.get("attention_layers", None) or [0] * 8)]
         self.attention_dict = nw.get("attention_dict", None) if any(self.attention_layers) else None
         if any(self.attention_layers):
@@ -188,8 +216,10 @@ class Unet_CQT_oct_with_attention(nn.Module):
         win = ("kaiser", nw.cqt.beta) if nw.cqt.window == "kaiser" else nw.cqt.window
         self.CQTransform = CQT_nsgt(self.num_octs, self.bins_per_oct, mode="oct", window=win,
                                     fs=args.exp.sample_rate, audio_len=args.exp.audio_len, device=self.device)
+        if self.use_fencoding and self.bins_per_oct != 64:
+            raise NotImplementedError(f"use_fencoding needs 64 bins per octave (got {self.bins_per_oct}): csrc/fenc.hip")
         for key, t in init_state_dict(self.Ns, self.num_dils, self.emb_dim, attention_layers=self.attention_layers,
-                                      attention_dict=self.attention_dict).items():
+                                      attention_dict=self.attention_dict, use_fencoding=self.use_fencoding).items():
             _attach(self, key, t.to(self.device), is_buffer=key.endswith(".kernel"))
         self._engine = None
         self.register_load_state_dict_post_hook(lambda m, k: m._reset_params())

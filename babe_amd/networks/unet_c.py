@@ -26,6 +26,8 @@ def _blk(dst, b):
         _pc(dst.H[d], b.H[d])
         dst.gamma[d] = ptr(b.gamma[d])
         dst.film_aff[d], dst.film_gate[d] = b.film_off[d]
+    if b.fenc is not None:                                # folded frequency encodings: the tables are rewritten in place by refresh
+        dst.fb_proj_in, dst.fb_res_conv = ptr(b.fb_proj_in), ptr(b.fb_res_conv)
 
 
 class CUnet:

@@ -58,15 +58,32 @@ class _Attn:
 class _Block:
     """One ResnetBlock: packed weights + per-call saved tensors."""
 
-    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32", attn=None):
-        """attn: (Fdim, attention options) if the block carries a time-attention layer."""
+    FOLDED = ("proj_in", "res_conv")      # the convs of an init block with frequency encodings that see all 66 input channels
+
+    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32", attn=None, fenc=None):
+        """attn: (Fdim, attention options) if the block carries a time-attention layer.
+        fenc: the [64, 64] frequency-encoding table of an init block built with use_fencoding.  Its proj_in / res_conv weights
+        are [N, 66, 1, 1] over cat(signal 2, encodings 64): the convs are packed from the 2 signal columns and the encodings'
+        share, constant over batch and time, is the bias table fb_* [N, 64] the conv adds in its epilogue (ops.fenc_bias)."""
         self.p = prefix
         self.nd = num_dils
         self.proj_after = proj_after
         g = lambda k: sd.get(prefix + k)
         PC = lambda w: ops.PackedConv(w, precision)
-        self.proj_in = PC(g("proj_in.weight")) if g("proj_in.weight") is not None else None
-        self.res_conv = PC(g("res_conv.weight")) if g("res_conv.weight") is not None else None
+        self.fenc = fenc
+        if fenc is not None:
+            for name in self.FOLDED:
+                w = g(name + ".weight")
+                assert w is not None and w.shape[1:] == (66, 1, 1), f"{prefix}{name}.weight: expected [N, 66, 1, 1] with frequency encodings"
+                if ops.PackedConv.splits_for((w.shape[0], 2, 1, 1), precision):
+                    raise NotImplementedError(f"use_fencoding with precision={precision!r}: the init block's (1,1) convs would run on "
+                                              "the bf16 kernels, which have no frequency bias")
+                setattr(self, name, PC(w[:, :2].contiguous()))
+                setattr(self, "fb_" + name, ops.fenc_bias(w.reshape(w.shape[0], 66), fenc, torch.empty(w.shape[0], 64, device=w.device)))
+        else:
+            self.fb_proj_in = self.fb_res_conv = None
+            self.proj_in = PC(g("proj_in.weight")) if g("proj_in.weight") is not None else None
+            self.res_conv = PC(g("res_conv.weight")) if g("res_conv.weight") is not None else None
         self.proj_out = PC(g("proj_out.weight")) if (proj_after and g("proj_out.weight") is not None) else None
         self.H = [PC(g(f"H.{d}.weight")) for d in range(num_dils)]
         self.Hw = [g(f"H.{d}.weight").contiguous() for d in range(num_dils)]       # raw weights (the FiLM gate gradient)
@@ -159,7 +176,9 @@ class UnetEngine:
         self.rff_freq = sd["embedding.RFF_freq"].reshape(-1).contiguous()
         self.init_blk, self.main_blk, self.pyr_conv = [], [], []
         for i in range(num_octs):
-            self.init_blk.append(_Block(sd, f"downs.{i}.0.", 1, fi, precision=precision))
+            fe = sd.get(f"freq_encodings.{i}.embeddings")
+            self.init_blk.append(_Block(sd, f"downs.{i}.0.", 1, fi, precision=precision,
+                                        fenc=fe.reshape(64, bins_per_oct).contiguous() if fe is not None else None))
             self.pyr_conv.append(ops.PackedConv(sd[f"downs.{i}.1.weight"], precision))
             self.main_blk.append(_Block(sd, f"downs.{i}.2.", num_dils[i], fi, precision=precision, attn=A(att[i], (i + 1) * bins_per_oct)))
         self.mid_blk = _Block(sd, "middle.0.1.", num_dils[-1], fi, precision=precision, attn=A(att[-1], num_octs * bins_per_oct))
@@ -178,7 +197,8 @@ class UnetEngine:
         for blk in self.blocks():
             for name in ("proj_in", "res_conv", "proj_out"):
                 if getattr(blk, name) is not None:
-                    self._add_grad(blk.p + name + ".weight", getattr(blk, name))
+                    folded = blk.fenc is not None and name != "proj_out"       # the parameter has all 66 input columns
+                    self._add_grad(blk.p + name + ".weight", getattr(blk, name), (blk.N, 66, 1, 1) if folded else None)
             for d in range(blk.nd):
                 self._add_grad(blk.p + f"H.{d}.weight", blk.H[d])
                 self._add_grad(blk.p + f"norm.{d}.gamma", None, (1, blk.N, 1, 1))
@@ -191,7 +211,7 @@ class UnetEngine:
 
     def _add_grad(self, key, pc, shape=None):
         if pc is not None:
-            shape = (pc.Cout, pc.Cin, pc.KH, pc.KW)
+            shape = shape or (pc.Cout, pc.Cin, pc.KH, pc.KW)
             self.packs.append((key, pc))
         n = 1
         for v in shape:
@@ -206,7 +226,15 @@ class UnetEngine:
         """After an optimizer step: repack every conv IN PLACE from sd (the current parameters) and rebuild Wcat / bcat.  The
         GroupNorm gammas and the embedding MLP are views of the parameters already."""
         for key, pc in self.packs:
-            pc.repack(sd[key].reshape(pc.Cout, pc.Cin, pc.KH, pc.KW))
+            w = sd[key]
+            if w.shape[1] == 66 and (pc.Cin, pc.KH, pc.KW) == (2, 1, 1):    # a folded init-block conv: the signal columns of the [N, 66] weight
+                w = w[:, :2].contiguous()
+            pc.repack(w.reshape(pc.Cout, pc.Cin, pc.KH, pc.KW))
+        for i, blk in enumerate(self.init_blk):           # ... and the encoding columns, into the SAME bias tables
+            if blk.fenc is not None:
+                blk.fenc.copy_(sd[f"freq_encodings.{i}.embeddings"].reshape(blk.fenc.shape))
+                for name in blk.FOLDED:
+                    ops.fenc_bias(sd[blk.p + name + ".weight"].reshape(blk.N, 66), blk.fenc, getattr(blk, "fb_" + name))
         self.film_idx.refresh()
 
     def clone_state(self):
@@ -266,7 +294,7 @@ class UnetEngine:
         if self._train:
             blk.inp = (x, x2)
         if blk.proj_in is not None:
-            z = ops.conv2d(x, blk.proj_in, self.buf(B, N, Fq, T), x2=x2)
+            z = ops.conv2d(x, blk.proj_in, self.buf(B, N, Fq, T), x2=x2, fbias=blk.fb_proj_in)
         else:
             assert x2 is None
             z = x if x.is_contiguous() else ops.axpby(x, self.buf(B, N, Fq, T))
@@ -303,7 +331,7 @@ class UnetEngine:
                 blk.zpo = z
             z = ops.conv2d(z, blk.proj_out, self.buf(B, blk.proj_out.Cout, Fq, T))
         if blk.res_conv is not None:
-            ops.conv2d(x, blk.res_conv, out, x2=x2, res=z, alpha=RS2, rbeta=RS2)
+            ops.conv2d(x, blk.res_conv, out, x2=x2, res=z, alpha=RS2, rbeta=RS2, fbias=blk.fb_res_conv)
         else:
             ops.axpby2(z, x, out, RS2, RS2)                  # (x + h)/sqrt2 in one pass
         blk.saved = saved
@@ -343,10 +371,22 @@ class UnetEngine:
         return gz
 
     # ------------------------------------------------------------------ training: parameter gradients
-    def _wg(self, pg, key, x, g, pc, alpha, x2=None, dil=1, **kw):
-        """pg.row(key) <- per-row weight gradient of conv `pc` (input cat(x, x2), output gradient alpha * oscale * g)."""
-        n = ops.conv_wgrad_workspace(x, g, pc.KH, pc.KW, dil, x2)
-        ops.conv_wgrad_rows(x, g, pc.KH, pc.KW, pg.row(key), dil=dil, x2=x2, alpha=alpha, ws=self.scratch("wg", n), **kw)
+    def _wg(self, pg, key, x, g, pc, alpha, x2=None, dil=1, fenc=None, **kw):
+        """pg.row(key) <- per-row weight gradient of conv `pc` (input cat(x, x2), output gradient alpha * oscale * g).
+        fenc: the encoding table of a folded init-block conv, whose rows have the parameter's [N, 66] layout: the 2 signal
+        columns from the ordinary per-row weight gradient on Cin = 2 (into scratch, then a small strided copy), the 64 encoding
+        columns from ops.fenc_wgrad_rows."""
+        ws = self.scratch("wg", ops.conv_wgrad_workspace(x, g, pc.KH, pc.KW, dil, x2))
+        rows = pg.row(key)
+        if fenc is None:
+            assert rows.shape[1] == pc.Cout * pc.Cin * pc.KH * pc.KW, key
+            return ops.conv_wgrad_rows(x, g, pc.KH, pc.KW, rows, dil=dil, x2=x2, alpha=alpha, ws=ws, **kw)
+        assert x2 is None and dil == 1 and not kw and (pc.Cin, pc.KH, pc.KW) == (2, 1, 1) and rows.shape[1] == pc.Cout * 66, key
+        B = g.shape[0]
+        sig = self.scratch("wg2", B * pc.Cout * 2).view(B, pc.Cout * 2)
+        ops.conv_wgrad_rows(x, g, 1, 1, sig, alpha=alpha, ws=ws)
+        ops.copy_cols(sig, rows, 2, 66, 2)
+        ops.fenc_wgrad_rows(g, fenc, rows, alpha)
 
     def _layer_wgrad(self, pg, blk, d, G, c):
         """Dilation layer d, znew = rs2*(gate*H(a) + z), a = gelu(z*scale) recomputed into the "a" scratch (the transposed conv
@@ -371,7 +411,7 @@ class UnetEngine:
         """res_conv / proj_out weight gradients (both see rs2*g_out): before the VJP consumes g_out."""
         x, x2 = blk.inp
         if blk.res_conv is not None:
-            self._wg(pg, blk.p + "res_conv.weight", x, g_out, blk.res_conv, RS2, x2=x2)
+            self._wg(pg, blk.p + "res_conv.weight", x, g_out, blk.res_conv, RS2, x2=x2, fenc=blk.fenc)
         if blk.proj_out is not None:
             self._wg(pg, blk.p + "proj_out.weight", blk.zpo, g_out, blk.proj_out, RS2)
 
@@ -471,7 +511,7 @@ class UnetEngine:
             c = 1.0
         if pg is not None and blk.proj_in is not None:
             x, x2 = blk.inp
-            self._wg(pg, blk.p + "proj_in.weight", x, gz, blk.proj_in, c, x2=x2)
+            self._wg(pg, blk.p + "proj_in.weight", x, gz, blk.proj_in, c, x2=x2, fenc=blk.fenc)
         if blk.proj_in is not None:
             ops.conv2d(gz, blk.proj_in, g_in, transpose=True, res=g_in, alpha=c, rbeta=1.0)
         else:

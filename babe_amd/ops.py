@@ -82,19 +82,24 @@ class PackedConv:
         if nt == 0 and _C11_NT and w.shape[2] * w.shape[3] == 1 and ((w.shape[0] + 31) // 32) % _C11_NT == 0 \
                 and ((w.shape[1] + 31) // 32) % _C11_NT == 0:
             self.nt = _C11_NT
-        self.splits = PRECISIONS[precision]
-        # Shapes that gain nothing from bf16 MFMA run on the fp32 kernels whatever the requested precision (exact AND at
-        # least as fast): convs with <= 4 channels on one side (few-channel kernels), (1,1) kernels with fewer than 32
-        # channels on one side (HBM-bound: all-DMA kernel), and every (1,1) kernel of the bf16x3 mode.  Wide (1,1) kernels are
-        # MFMA-bound in fp32 (up to 85 flop/B) and take the pipelined bf16 kernel under 'bf16'.
-        k11 = w.shape[2] * w.shape[3] == 1
-        if self.splits and BF16_HBM_F32 and (min(w.shape[0], w.shape[1]) <= 4 or
-                                             (k11 and (self.splits == 2 or min(w.shape[0], w.shape[1]) < 32))):
-            self.splits = 0
+        self.splits = self.splits_for(w.shape, precision)
         if self.splits:
             self._init_bf16(w)
             return
         self._init_f32(w)
+
+    @staticmethod
+    def splits_for(shape, precision):
+        """bf16 products per multiply a conv of this weight shape runs with under `precision`; 0 = the fp32 kernels."""
+        splits = PRECISIONS[precision]
+        # Shapes that gain nothing from bf16 MFMA run on the fp32 kernels whatever the requested precision (exact AND at
+        # least as fast): convs with <= 4 channels on one side (few-channel kernels), (1,1) kernels with fewer than 32
+        # channels on one side (HBM-bound: all-DMA kernel), and every (1,1) kernel of the bf16x3 mode.  Wide (1,1) kernels are
+        # MFMA-bound in fp32 (up to 85 flop/B) and take the pipelined bf16 kernel under 'bf16'.
+        k11 = shape[2] * shape[3] == 1
+        if splits and BF16_HBM_F32 and (min(shape[0], shape[1]) <= 4 or (k11 and (splits == 2 or min(shape[0], shape[1]) < 32))):
+            return 0
+        return splits
 
     def __setattr__(self, k, v):
         object.__setattr__(self, k, v)
@@ -168,9 +173,11 @@ FUSE_GN_FWD = os.environ.get("BABE_FUSE_GN_FWD", "1") != "0"
 
 
 def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=None, oscale=None, alpha=1.0, rbeta=0.0,
-           force_nested=False, force_f45=False, vjp_stat=None, fwd_stat=None):
+           force_nested=False, force_f45=False, vjp_stat=None, fwd_stat=None, fbias=None):
     """out = alpha*conv(x[,x2]; W)*oscale + rbeta*res   (transpose=True: input-VJP weights), on the kernel the library picks
     from pc.desc (babe_conv2d_auto).
+    fbias [Cout, F]: out = alpha*oscale*(conv + fbias[co, f]) + rbeta*res, the folded frequency encodings (fp32 (1,1) kernels; any
+    other kernel raises).
     force_nested: take the nested-Winograd F(2,5) x F(4,3) kernel whenever it CAN run the problem (tests), not only when it is
     preferred; force_f45: the same for the F(4,5) x F(4,3) kernel.
     vjp_stat=(z, scale, cg): if the launch takes the F(4,5) kernel, its epilogue also forms the partial sums of the GroupNorm /
@@ -205,6 +212,9 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     if oscale is not None:
         assert oscale.is_contiguous() and oscale.shape == (B, Cout)
     a.in_scale, a.oscale = ptr(in_scale), ptr(oscale)
+    if fbias is not None:
+        assert fbias.is_contiguous() and fbias.dtype == torch.float32 and fbias.shape == (Cout, F)
+        a.fbias = ptr(fbias)
     a.alpha, a.rbeta = alpha, rbeta
     a.B, a.Cin, a.Cout, a.F, a.T = B, Cin, Cout, F, T
     a.KH, a.KW, a.dil = pc.KH, pc.KW, dil
@@ -565,6 +575,36 @@ def conv_wgrad_rows(x, g, KH, KW, rows, *, dil=1, x2=None, oscale=None, alpha=1.
                                      dgate.stride(0) if dgate is not None else 0, galpha, ptr(rows), rows.stride(0), stream()),
           "conv_wgrad_rows")
     return rows
+
+
+def fenc_bias(w, emb, fb):
+    """fb[co, f] <- sum_j w[co, 2 + j] * emb[j, f] (babe_fenc_bias), in place: the frequency encodings' share of a (1,1) conv over
+    cat(signal, encodings) channels, as a bias per channel and frequency row.  w [Cout, 66] (row stride >= 66), emb [64, 64]."""
+    assert w.dim() == 2 and w.shape[1] == 66 and w.stride(1) == 1 and w.dtype == torch.float32
+    assert emb.is_contiguous() and emb.shape == (64, 64) and fb.is_contiguous() and fb.shape == (w.shape[0], 64)
+    check(lib().babe_fenc_bias(ptr(w), ptr(emb), ptr(fb), w.shape[0], w.stride(0), stream()), "fenc_bias")
+    return fb
+
+
+def fenc_wgrad_rows(g, emb, rows, alpha=1.0):
+    """rows[b, co*66 + 2 + j] <- alpha * sum_f emb[j, f] * sum_t g[b, co, f, t] (babe_fenc_wgrad_rows): the encoding columns of the
+    per-row weight gradient of a folded conv; g [B, Cout, 64, T] view with contiguous rows, rows [B, Cout*66] (any row stride)."""
+    B, Cout, F, T = g.shape
+    gp, gbs, gcs = _view(g)
+    assert emb.is_contiguous() and emb.shape == (64, 64)          # (F != 64 is the library's error)
+    assert rows.dim() == 2 and rows.shape == (B, Cout * 66) and rows.stride(1) == 1
+    check(lib().babe_fenc_wgrad_rows(gp, gbs, gcs, ptr(emb), alpha, ptr(rows), rows.stride(0), 66, B, Cout, F, T, stream()),
+          "fenc_wgrad_rows")
+    return rows
+
+
+def copy_cols(src, dst, ld_src, ld_dst, n):
+    """dst[b, r*ld_dst + c] <- src[b, r*ld_src + c] for c < n (babe_axpby4d on [B][rows][1][n] views): a small strided copy."""
+    B = src.shape[0]
+    R = src.shape[1] // ld_src
+    assert src.stride(1) == 1 and dst.stride(1) == 1 and dst.shape[0] == B and dst.shape[1] == R * ld_dst
+    check(lib().babe_axpby4d(ptr(src), src.stride(0), ld_src, ptr(dst), dst.stride(0), ld_dst, B, R, 1, n, 1.0, 0.0, stream()), "copy_cols")
+    return dst
 
 
 def rows_sum(rows, out, beta=0.0):

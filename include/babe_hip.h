@@ -45,6 +45,12 @@ typedef struct {
      * written exactly once (deterministic), in the layout babe_gn_bwd_apply reads with that S. */
     int stat_mode, stat_cg;
     const float* stat_x; const float* stat_scale; double* stat_part;
+    /* Optional bias per output channel and FREQUENCY ROW, dense [Cout][F], NULL = none: out = alpha * oscale * (acc + fbias[co][f]) +
+     * rbeta * res.  The folded frequency encodings of the UNet's init blocks (cqtdiff+.py:213-263, 675: the 64 encoding channels
+     * are constant over batch and time, so their share of a (1,1) conv is this table, babe_fenc_bias).  Implemented by the fp32
+     * (1,1) kernels behind babe_conv2d / babe_conv2d_nt (KH = KW = 1); every other conv entry point returns an error for a
+     * non-NULL fbias, and babe_conv2d_auto never picks one of them for such a call. */
+    const float* fbias;
 } babe_conv_args;
 /* slots per GroupNorm group the fused reduction writes: (row-quad x time tiles of one batch element) * stat_cg / sg, sg = the largest
  * of 16, 8, 4 that divides stat_cg */
@@ -274,6 +280,8 @@ typedef struct {                       /* one ResnetBlock */
     babe_packed_conv proj_in, res_conv, proj_out, H[8];
     const float* gamma[8];             /* BiasFreeGroupNorm gamma of layer d, [N] */
     int film_aff[8], film_gate[8];     /* offsets of layer d's affine / gate vectors in the FiLM row */
+    const float *fb_proj_in, *fb_res_conv;   /* babe_conv_args::fbias [N][bpo] of proj_in / res_conv: an init block with folded
+                                              * frequency encodings (its packed convs hold the 2 signal columns); NULL: none */
 } babe_unet_block;
 typedef struct {
     int nocts, bpo;                    /* octaves (7), bins per octave (64) */
@@ -610,6 +618,18 @@ int babe_gn_param_grad(const float* z, const float* da, const float* scale, cons
 long babe_linear_bwd_workspace(int B, int K, int J);
 int babe_linear_bwd(const float* dy, const float* y, const float* x, const float* W, float* dW, float* db, float* dx, float* ws,
                     int B, int K, int J, float beta, void* stream);
+
+
+/* ---- frequency encodings of the UNet's init blocks (AddFreqEncodingRFF, cqtdiff+.py:213-263) folded into a bias (csrc/fenc.hip).
+ * emb [64][64] = embeddings[j][f] (64 encoding channels x 64 bins of an octave); w [Cout][ld_w] the (1,1) conv weight over
+ * cat(signal 2, encodings 64) channels (ld_w >= 66).
+ *   fb[co*64 + f] = sum_{j<64} w[co*ld_w + 2 + j] * emb[j*64 + f], j ascending (one fused multiply-add chain per entry) */
+int babe_fenc_bias(const float* w, const float* emb, float* fb, int Cout, int ld_w, void* stream);
+/* The encoding columns of that conv's per-row weight gradient, for the output gradient alpha * g (g [B][Cout][F][T] view, rows
+ * contiguous; F must be 64, anything else is an error):  rows[b*rows_bs + co*ld_row + 2 + j] = alpha * sum_f emb[j*64 + f] * (sum_t g[b][co][f][t]).
+ * Fixed-order sums in double, no atomics; every (b, co) is written by one workgroup, so batch rows are independent. */
+int babe_fenc_wgrad_rows(const float* g, long g_bs, long g_cs, const float* emb, float alpha, float* rows, long rows_bs, int ld_row,
+                         int B, int Cout, int F, int T, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,95 @@
+"""use_fencoding on the host side, no GPU: parameter names / shapes / trainable set against the reference's own lists
+(tests/golden/fencoding_a.npz, make_fencoding_golden.py), the embeddings formula, and a state_dict round trip of the module tree."""
+import io
+import os
+
+import numpy as np
+import pytest
+import torch
+
+G = os.path.join(os.path.dirname(__file__), "golden")
+NS, DILS = [8, 8, 8, 8, 16, 16, 16], [2, 3, 4, 5, 6, 7, 7]
+
+
+def golden():
+    return np.load(os.path.join(G, "fencoding_a.npz"))
+
+
+def specs():
+    from babe_amd.networks.cqtdiff_plus import param_specs
+    return param_specs(NS, DILS, use_fencoding=True)
+
+
+def test_parameter_names_shapes_and_trainable_set_equal_the_reference():
+    from babe_amd.networks.cqtdiff_plus import is_trainable
+    f = golden()
+    ours = [f"{k}:{'x'.join(str(s) for s in shape)}" for k, shape, kind in specs() if kind != "buf"]
+    # (as sets of name:shape: inside a ResnetBlock the reference registers its layers in another order than param_specs lists them)
+    assert len(ours) == len(set(ours)) and sorted(ours) == sorted(f["params"].tolist())
+    assert sorted(k for k, _, kind in specs() if kind != "buf" and is_trainable(k)) == sorted(f["trainable"].tolist())
+    fe = [p for p in f["params"].tolist() if p.startswith("freq_encodings.")]
+    assert [p for p in ours if p.startswith("freq_encodings.")] == fe and len(fe) == 14
+    assert "downs.0.0.proj_in.weight:8x66x1x1" in ours and "downs.6.0.res_conv.weight:16x66x1x1" in ours
+    assert not any(k.startswith("freq_encodings.") for k in f["trainable"].tolist())
+
+
+def test_without_fencoding_nothing_changes():
+    from babe_amd.networks.cqtdiff_plus import init_state_dict, param_specs
+    plain = param_specs(NS, DILS)
+    assert not any(k.startswith("freq_encodings.") for k, _, _ in plain)
+    assert dict((k, s) for k, s, _ in plain)["downs.0.0.proj_in.weight"] == (8, 2, 1, 1)
+    a, b = init_state_dict(NS, DILS, seed=3), init_state_dict(NS, DILS, seed=3, use_fencoding=False)
+    assert all(torch.equal(a[k], b[k]) for k in a)
+
+
+def test_init_state_dict_embeddings_equal_the_references():
+    from tests.fencoding_weights import fencoding_sd
+    f = golden()
+    sd = fencoding_sd("a")
+    for i in range(7):
+        e = sd[f"freq_encodings.{i}.embeddings"]
+        assert e.dtype == torch.float32 and tuple(e.shape) == (1, 64, 64)
+        err = float((e[0] - torch.from_numpy(f["embeddings"][i, 0])).abs().max())
+        assert err <= 1e-6, (i, err)
+    assert not torch.equal(sd["freq_encodings.0.RFF_freq"], sd["freq_encodings.1.RFF_freq"])
+
+
+def test_state_dict_round_trip():
+    """The module tree the network builds from the specs (cqtdiff_plus._attach) saves and loads under the reference's names; the
+    loaded embeddings tensor is kept as given, not rebuilt from RFF_freq."""
+    from babe_amd.networks.cqtdiff_plus import _Node, _attach
+    from tests.fencoding_weights import fencoding_sd
+    sd = fencoding_sd("a")
+    sd["freq_encodings.2.embeddings"] = sd["freq_encodings.2.embeddings"] + 0.25          # a checkpoint's table is authoritative
+
+    def tree(fill):
+        root = _Node()
+        for k, t in sd.items():
+            _attach(root, k, fill(t), is_buffer=k.endswith(".kernel"))
+        return root
+
+    src = tree(lambda t: t.clone())
+    buf = io.BytesIO()
+    torch.save(src.state_dict(), buf)
+    buf.seek(0)
+    dst = tree(torch.zeros_like)
+    dst.load_state_dict(torch.load(buf), strict=True)
+    out = dst.state_dict()
+    assert list(out) == list(src.state_dict()) and all(torch.equal(out[k], sd[k]) for k in sd)
+    assert sorted(k for k, _ in dst.named_parameters()) == sorted(p.split(":")[0] for p in golden()["params"].tolist())
+
+
+def test_bf16_modes_keep_the_folded_convs_in_fp32_or_refuse(monkeypatch):
+    """The [N, 2] signal slice of an init-block conv runs on the fp32 kernels (the only ones with a frequency bias) in every
+    precision; with BABE_BF16_HBM_F32=0 it would go to the bf16 kernels, and the block refuses before it packs anything."""
+    from babe_amd import ops
+    from babe_amd.networks.unet_engine import _Block, _FilmIndex
+    from tests.fencoding_weights import fencoding_sd
+    for n in (8, 96, 256):
+        assert ops.PackedConv.splits_for((n, 2, 1, 1), "bf16") == 0 and ops.PackedConv.splits_for((n, 2, 1, 1), "bf16x3") == 0
+    sd = fencoding_sd("a")
+    fenc = sd["freq_encodings.0.embeddings"].reshape(64, 64)
+    monkeypatch.setattr(ops, "BF16_HBM_F32", False)
+    for prec in ("bf16", "bf16x3"):
+        with pytest.raises(NotImplementedError, match="use_fencoding.*" + prec):
+            _Block(sd, "downs.0.0.", 1, _FilmIndex(), precision=prec, fenc=fenc)
