@@ -6,7 +6,8 @@ torch CPU tensors so schedules are bit-identical to the reference; tensors on th
 the babe_hip element-wise kernel."""
 import torch
 
-from ..stft import lincomb
+from ..stft import fir_sqerr, lincomb
+from ..utils.training_utils import FIRFilter
 
 
 class EDM:
@@ -18,8 +19,10 @@ class EDM:
         self.ro, self.ro_train = dp.ro, dp.get("ro_train", dp.ro)
         self.sigma_data = dp.sigma_data
         self.Schurn, self.Stmin, self.Stmax, self.Snoise = dp.Schurn, dp.Stmin, dp.Stmax, dp.Snoise
-        if dp.get("aweighting", {}).get("use_aweighting", False):
-            raise NotImplementedError("A-weighting is a training-only option (edm.py:33-34)")
+        self.AW = None                                   # perceptual weighting of the training error (edm.py:33-34)
+        aw = dp.get("aweighting", None) or {}
+        if aw.get("use_aweighting", False):
+            self.AW = FIRFilter(filter_type="aw", fs=args.exp.sample_rate, ntaps=aw.get("ntaps", 101))
 
     def get_gamma(self, t):
         N = t.shape[0]
@@ -62,10 +65,14 @@ class EDM:
         """(error**2 [B,L], sigma [B,1]) of the denoising objective for clean audio x [B,L]: draws sigma (torch.rand) then the
         noise (torch.randn), like the reference.  The reference's DC correction reads args.net.use_cqt_DC_correction - a key no
         configuration defines (they have exp.use_cqt_DC_correction) - inside a bare except, so it never runs; it is left out
-        here for the same result.  A-weighting is refused at construction."""
+        here for the same result.  With diff_params.aweighting.use_aweighting the error goes through the A-weighting FIR before
+        the square (edm.py:201-203): subtraction, filter and square are one HIP kernel (stft.fir_sqerr), and so is their backward;
+        without it the tail is the two torch operations below, as before."""
         sigma = self.sample_ptrain_safe(x.shape[0]).unsqueeze(-1).to(x.device)
         inp, target, cnoise = self.prepare_train_preconditioning(x, sigma)
         estimate = net(inp, cnoise)
+        if self.AW is not None:
+            return fir_sqerr(estimate, target, self.AW.to(estimate.device).taps), sigma
         error = estimate - target
         return error ** 2, sigma
 

@@ -268,7 +268,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
     def set_trainable(self, flag=True):
         """requires_grad on exactly the reference's trainable set (is_trainable), so torch.optim.Adam(net.parameters()) updates
         what the reference's Adam updates.  Parameter gradients run in fp32 on attention-free networks (others raise on the
-        forward)."""
+        forward), under the plain and the A-weighted EDM loss alike (diff_params/edm.py::loss_fn)."""
         for k, p in self.named_parameters():
             p.requires_grad_(bool(flag) and is_trainable(k))
         return self

@@ -42,6 +42,43 @@ def fir_same(x, taps, adjoint=False):
     return out
 
 
+class _FirSqerr(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, est, tgt, taps):
+        if not (est.is_cuda and tgt.is_cuda and taps.is_cuda):
+            raise RuntimeError("babe_amd.fir_sqerr runs on the GPU only (no CPU fallback)")
+        B, L = est.shape
+        assert tgt.shape == est.shape and est.dtype == tgt.dtype == taps.dtype == torch.float32
+        est = est if est.stride(1) == 1 else est.contiguous()
+        tgt = tgt if tgt.stride(1) == 1 else tgt.contiguous()
+        taps = taps.reshape(-1).contiguous()
+        ew, err2 = torch.empty(B, L, device=est.device), torch.empty(B, L, device=est.device)
+        check(lib().babe_fir_sqerr_fwd(ptr(est), est.stride(0), ptr(tgt), tgt.stride(0), ptr(taps), taps.numel(), ptr(ew),
+                                       ptr(err2), B, L, stream(est)), "fir_sqerr_fwd")
+        ctx.save_for_backward(ew, taps)
+        ctx.mark_non_differentiable(ew)
+        return err2, ew
+
+    @staticmethod
+    def backward(ctx, g, _g_ew):
+        ew, taps = ctx.saved_tensors
+        B, L = ew.shape
+        g = g if g.stride(1) == 1 else g.contiguous()          # (the gradient of .mean() arrives as an expanded scalar)
+        dest = torch.empty_like(ew)
+        check(lib().babe_fir_sqerr_bwd(ptr(g), g.stride(0), ptr(ew), ptr(taps), taps.numel(), ptr(dest), B, L, stream(ew)),
+              "fir_sqerr_bwd")
+        return dest, None, None
+
+
+def fir_sqerr(est, tgt, taps, return_filtered=False):
+    """(taps * (est - tgt))**2 with * the "same" cross-correlation of fir_same, in ONE kernel: the tail of the A-weighted training
+    loss.  est, tgt [B,L] device (rows may be strided), taps [K] device, K odd and <= 255.  Differentiable with respect to est only
+    (one kernel as well: the transposed FIR of 2 g ew, from the filtered error ew the forward saved).  return_filtered: also
+    return ew (not differentiable)."""
+    err2, ew = _FirSqerr.apply(est, tgt, taps)
+    return (err2, ew) if return_filtered else err2
+
+
 def mask_blend(mask, a=None, b=None):
     """mask*a + (1-mask)*b with a/b optional (None = 0); mask [L] (shared) or [B,L]."""
     ref = a if a is not None else b

@@ -458,6 +458,19 @@ int babe_filter_loss_grad(const double* stats, long stats_pstride, const float* 
 int babe_fir_same(const float* x, long x_bs, const float* taps, int ntaps, float* out, long out_bs, int B, int L,
                   int adjoint, void* stream);
 
+/* ---- A-weighted training loss (diff_params/edm.py:201-206: error = AW(estimate - target), then error**2; AW =
+ * utils/training_utils.py FIRFilter :124-138, F.conv1d(padding=K/2), no tap flip): the FIR fused with the subtraction in front
+ * of it and the square behind it, and its transpose fused with the square's derivative - one pass over HBM per direction.
+ * K odd, 1 <= K <= 255 (anything else is refused before a launch); any B >= 1, L >= 1 (L < K included).  est_bs / tgt_bs / g_bs:
+ * row strides in elements; ew, err2 and dest are dense [B][L].  Every output is written exactly once and every sum runs over the
+ * taps in order, without atomics: results are bit-identical from run to run and on any stream. */
+int babe_fir_sqerr_fwd(const float* est, long est_bs, const float* tgt, long tgt_bs, const float* taps, int K,
+                       float* ew, float* err2, int B, int L, void* stream);
+    /* ew[b][n] = sum_k taps[k] * (est - tgt)[b][n + k - K/2]   (zeros outside [0,L));   err2 = ew * ew            */
+int babe_fir_sqerr_bwd(const float* g, long g_bs, const float* ew, const float* taps, int K,
+                       float* dest, int B, int L, void* stream);
+    /* h = 2 * g * ew;   dest[b][m] = sum_k taps[k] * h[b][m - k + K/2]   (the transpose of the forward FIR)       */
+
 /* ---- sampler element-wise steps: testing/blind_bwe_sampler.py:503-516, :125-135, :701-761; edm.py:144-159 */
 /* out = a*x + b*y + c*z (y, z optional) over n elements */
 int babe_lincomb3(float* out, float a, const float* x, float b, const float* y, float c, const float* z, long n,
