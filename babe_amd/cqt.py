@@ -328,9 +328,10 @@ class CQT_nsgt:
         # C host all run on the SAME tables.  BABE_CQT_C=0: this class sequences the kernels from the numpy design (kept as the
         # cross-check of the library's design: tests/test_cqt_plan_cpu.py, tests/test_gpu_cqt.py).
         self._plan = None
-        if os.environ.get("BABE_CQT_C", "1") == "1":
-            # (NULL for a length whose factors the mixed-radix FFT does not cover: this class then sequences the kernels itself,
-            # with the dense-DFT form of the length-L transform)
+        if os.environ.get("BABE_CQT_C", "1") == "1" and self.fft.mixed:
+            # (the plan only has the mixed-radix form of the length-L transform: for a length whose factors that form does not
+            # cover the library returns NULL, and under BABE_FFT_MIXED=0 no plan is asked for; this class then sequences the
+            # kernels itself, with the dense-DFT form)
             self._plan = lib().babe_cqt_plan_create(float(fs), self.Ls, numocts, binsoct, float(window[1])) or None
             self._ws = {}
 

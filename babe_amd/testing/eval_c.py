@@ -15,6 +15,8 @@ def cqt_plan_of(cq):
     itself (BABE_CQT_C=0); None where the library cannot plan the length."""
     if getattr(cq, "_plan", None):
         return cq._plan
+    if not cq.fft.mixed:                                   # BABE_FFT_MIXED=0 / an uncovered length: the plan has no dense form
+        return None
     if getattr(cq, "_plan_eval", None) is None:
         cq._plan_eval = lib().babe_cqt_plan_create(float(cq.fs), cq.Ls, cq.numocts, cq.binsoct, float(cq.design["beta"])) or 0
     return cq._plan_eval or None

@@ -110,13 +110,12 @@ def test_hip_vs_cqt_nsgt_pytorch_library(pair):
 @pytest.mark.parametrize("L", [46046, 184184, 92092, 368368, 441000])
 def test_length_L_fft_and_transpose_other_lengths(L):
     """The mixed-radix four-step FFT (csrc/fft_mixed.hip) picks its radices per length - 46046 = (2 7 13)(11 23), 184184 = (4 7 13)
-    (2 11 23): config #5's segment, ... - and 441000 has a factor the Stockham kernel cannot split into at most six of its radices
-    per stage... or can: either way RealFFT must equal torch.fft.rfft and its transpose must be the adjoint."""
+    (2 11 23): config #5's segment, ... - and 441000 = 630 x 700 = (2 3 3 5 7)(4 5 5 7), the only one with radices 3 and 5.  All
+    five are supported lengths (a ValueError fails): RealFFT must equal torch.fft.rfft and its transpose must be the adjoint.
+    (Small and odd lengths, every bin and the transpose element by element: tests/test_gpu_fft.py.)"""
     from babe_amd.cqt import RealFFT
-    try:
-        fft = RealFFT(L, torch.device("cuda"))
-    except ValueError:
-        pytest.skip(f"L={L}: no balanced factorisation (unsupported length, as before)")
+    fft = RealFFT(L, torch.device("cuda"))
+    assert fft.mixed
     g = torch.Generator().manual_seed(L % 997)
     x = torch.randn(2, L, generator=g)
     spec = fft.rfft(x.cuda())
