@@ -241,6 +241,12 @@ SIGS = {
     "babe_linear_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "babe_fenc_bias": (_I, [_P, _P, _P, _I, _I, _P]),
     "babe_fenc_wgrad_rows": (_I, [_P, _L, _L, _P, _F, _P, _L, _I, _I, _I, _I, _I, _P]),
+    "babe_attn_qk_wgrad_workspace": (_L, [_I, _I, _I]),
+    "babe_attn_qk_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
+    "babe_attn_param_vjp_workspace": (_L, [_I, _I, _I, _I]),
+    "babe_attn_param_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
+    "babe_gn_param_grad_nogelu": (_I, [_P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P]),
+    "babe_scale_channels": (_I, [_P, _P, _P, _I, _I, _L, _P]),
 }
 
 

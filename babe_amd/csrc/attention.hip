@@ -5,7 +5,8 @@
 //   Q[f][n] = qk[b][h*2F + f][n] (+ qb[h*2F + f]),  K[f][m] = qk[b][h*2F + F + f][m] (+ qb[...]),  V[f][m] = a[b][h][f][m]
 //   S[n][m] = (sum_f Q[f][n] K[f][m] + bias_h(m - n)) * scale,    bias_h(d) = emb[bucket[d + T - 1]][h]   (0 without rel-pos)
 //   O[f][n] = sum_m softmax_m(S)[n][m] V[f][m],   lse[n] = log sum_m exp S[n][m]
-// VJP (inputs only: no weight or bias-table gradients), D[n] = sum_f dO[f][n] O[f][n], P recomputed from Q, K and lse:
+// VJP (inputs only; the weight and bias-table gradients are attention_train.hip's), D[n] = sum_f dO[f][n] O[f][n], P recomputed
+// from Q, K and lse:
 //   dS = P o (dP - D), dP[n][m] = sum_f dO[f][n] V[f][m]
 //   dQ = scale dS K,  dK = scale dS^T Q,  dV = P^T dO
 // Two VJP kernels, one over query tiles (dQ) and one over key tiles (dK, dV), each owning the rows it writes: no atomics, the

@@ -1,0 +1,420 @@
+// Parameter gradients of the time-attention branch (csrc/attention.hip is its forward and input-VJP), fp32, gfx950.  Training
+// only: nothing here is launched by the sampler, and the kernels of attention.hip are untouched.
+//
+// No float atomics: every sum has one fixed order, so results are bit-identical run to run; the per-batch-row outputs do not
+// depend on which other rows share the call (the UNet's clip lanes split rows between calls).
+//
+// 1. qk weight gradient  dW[co][ci] = alpha * sum_b sum_t dqk[b][co][t] * a1[b][ci][t] (+ beta * dW), a GEMM with M = 2HF output
+//    rows, N = HF columns and K = (b, t), both operands K-contiguous.  Summed over the batch inside the kernel: a per-row result
+//    would be B x 103 MB at the deepest level.  A workgroup (four waves, 2 x 2, a 64 x 64 block of v_mfma_f32_32x32x2_f32
+//    accumulators each) owns a 128 x 128 output tile and walks K in ascending (b, t) order, 32 time steps per stage through LDS
+//    (row stride 33: the 32 rows a half-wave reads fall in distinct banks), the next stage's global loads in flight under the
+//    MFMAs.  Time steps are loaded one float at a time, so any T works (rows need no alignment); past T they are zero.
+//    The small levels (F = 64: 1024 x 512 = 32 tiles) split K into chunks of whole stages, each chunk's partial tile in the
+//    workspace and a second pass adding the chunks in order; the chunk count depends on (HF, T, B) only.
+//    Operand layout of v_mfma_f32_32x32x2_f32 (lane l): A[i][k] = A[l%32][l/32], B[k][j] = B[l/32][l%32],
+//    D[i][j]: lane l holds D[(r%4) + 8*(r/4) + 4*(l/32)][l%32], r = 0..15.
+//
+// 2. relative-position table gradient  demb[b][k][h] = sum_{n,m: bucket[m-n+T-1] = k} scale * dS[b,h,n,m], dS = P o (dP - D) as in
+//    attention.hip.  A kernel of its own that recomputes S and dP exactly as attn_vjp_q_kernel does (same operands, same MFMA
+//    order, so the same P): a wave owns 16 queries, parks each 16 x 16 dS tile in LDS, one lane per diagonal of the tile adds its
+//    sum (ascending query) into the wave's LDS array of diagonals, key tiles in ascending order; at the end lane k adds the
+//    diagonals of bucket k in ascending offset and writes the query tile's partial; a last pass adds the query tiles in order.
+//    The qk bias gradient is the row sum of dqk over t (double, fixed order).
+//
+// 3. norm2 / affine2: babe_gn_param_grad without the GELU, and the plain per-channel scale pass that rebuilds proj_in's input.
+#include "common.h"
+#include "../../include/babe_hip.h"
+#include <cmath>
+
+namespace {
+
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// ---------------------------------------------------------------- qk weight gradient
+constexpr int QT = 128;            // output tile (rows and columns)
+constexpr int QK = 32;             // time steps per stage
+constexpr int QS = QK + 1;         // LDS row stride
+constexpr int HF_STEP = 512, HF_MAX = 3584;
+
+struct QkPlan {
+    int nst;        // stages per batch row
+    int nsplit;     // K chunks
+    int per;        // stages per chunk
+    int tiles;
+};
+
+inline QkPlan qk_plan(int B, int HF, int T) {
+    QkPlan p;
+    p.nst = cdiv(T, QK);
+    p.tiles = (2 * HF / QT) * (HF / QT);
+    const long total = (long)B * p.nst;
+    long want = 256 / p.tiles;                       // about one workgroup per CU
+    const long cap = total / 8;                      // a chunk is at least 8 stages (256 steps of K)
+    if (want > cap) want = cap;
+    if (want < 1) want = 1;
+    p.per = (int)((total + want - 1) / want);
+    p.nsplit = (int)((total + p.per - 1) / p.per);
+    return p;
+}
+
+inline bool qk_shape_ok(int B, int HF, int T) {
+    return B > 0 && T > 0 && HF >= HF_STEP && HF <= HF_MAX && HF % HF_STEP == 0;
+}
+
+// grid (tiles, nsplit), 256 threads.  direct: the only chunk, out = alpha * acc (+ beta * out); otherwise the raw partial tile
+__global__ __launch_bounds__(256) void qk_wgrad_kernel(const float* __restrict__ dqk, const float* __restrict__ a1,
+                                                       float* __restrict__ out, int M, int N, int T, int B, int nst, int per,
+                                                       float alpha, float beta, int direct) {
+    __shared__ float Gs[QT * QS];
+    __shared__ float Xs[QT * QS];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int tiles_n = N / QT;
+    const int co0 = (blockIdx.x / tiles_n) * QT, ci0 = (blockIdx.x % tiles_n) * QT;
+    const long total = (long)B * nst;
+    const long s0 = (long)blockIdx.y * per;
+    const long s1 = s0 + per < total ? s0 + per : total;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // loader: thread (lt, lr0) fetches time step lt of the rows lr0 + 8 i of both operands
+    const int lt = tid & 31, lr0 = tid >> 5;
+    float gr[16], xr[16];
+    auto load = [&](long s) {
+        const int b = (int)(s / nst);
+        const int t = (int)(s % nst) * QK + lt;
+        const bool in = t < T;
+        const float* gp = dqk + ((long)b * M + co0 + lr0) * T + t;
+        const float* xp = a1 + ((long)b * N + ci0 + lr0) * T + t;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            gr[i] = in ? gp[(long)8 * i * T] : 0.f;
+            xr[i] = in ? xp[(long)8 * i * T] : 0.f;
+        }
+    };
+    if (s0 < s1) load(s0);
+    for (long s = s0; s < s1; ++s) {
+        __syncthreads();                   // the previous stage's reads are done
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            Gs[(lr0 + 8 * i) * QS + lt] = gr[i];
+            Xs[(lr0 + 8 * i) * QS + lt] = xr[i];
+        }
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+#pragma unroll 4
+        for (int kk = 0; kk < QK / 2; ++kk) {
+            const int p = 2 * kk + h;
+            const float a0 = Gs[(wm * 64 + l31) * QS + p];
+            const float a1v = Gs[(wm * 64 + 32 + l31) * QS + p];
+            const float b0 = Xs[(wn * 64 + l31) * QS + p];
+            const float b1 = Xs[(wn * 64 + 32 + l31) * QS + p];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1v, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    float* dst = direct ? out : out + (long)blockIdx.y * M * N;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int ci = ci0 + wn * 64 + j * 32 + l31;
+                const long o = (long)co * N + ci;
+                const float v = acc[i][j][r];
+                if (direct)
+                    dst[o] = beta == 0.f ? alpha * v : alpha * v + beta * dst[o];
+                else
+                    dst[o] = v;
+            }
+}
+
+__global__ __launch_bounds__(256) void qk_wgrad_reduce_kernel(const float* __restrict__ ws, int nsplit, long n,
+                                                              float* __restrict__ out, float alpha, float beta) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = 0.f;
+    for (int s = 0; s < nsplit; ++s) v += ws[(long)s * n + i];
+    out[i] = beta == 0.f ? alpha * v : alpha * v + beta * out[i];
+}
+
+// ---------------------------------------------------------------- table / bias gradients
+constexpr int FMAX = 448;
+constexpr int LDS_LIMIT = 65536;
+
+__device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+__device__ __forceinline__ void stage16(float* dst, const float* src, const float* rb, int F, int T, int c0) {
+    for (int i = threadIdx.x; i < F * 16; i += 64) {
+        const int f = i >> 4, c = c0 + (i & 15);
+        dst[i] = c < T ? src[(long)f * T + c] + (rb ? rb[f] : 0.f) : 0.f;
+    }
+}
+
+// D[b][h][n] = sum_f dO[f][n] O[f][n] (the sum attention.hip's VJP forms); grid (ceil(T/256), H, B), 256 threads
+__global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ dout, const float* __restrict__ out,
+                                                     float* __restrict__ D, int H, int F, int T) {
+    const int n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= T) return;
+    const long base = ((long)blockIdx.z * H + blockIdx.y) * F * T + n;
+    float s = 0.f;
+    for (int f = 0; f < F; ++f) s += dout[base + (long)f * T] * out[base + (long)f * T];
+    D[((long)blockIdx.z * H + blockIdx.y) * T + n] = s;
+}
+
+inline int diag_len(int T) { return ((T + 15) & ~15) + 16; }
+
+// grid (ceil(T/16), H, B), 64 threads, dynamic LDS diag_len(T) floats.  part [B][H][gridDim.x][nbk]
+template <int FB>
+__global__ __launch_bounds__(64) void attn_demb_kernel(const float* __restrict__ qk, const float* __restrict__ qkb,
+                                                       const float* __restrict__ a, const int* __restrict__ bucket,
+                                                       const float* __restrict__ emb, int nbk, const float* __restrict__ dout,
+                                                       const float* __restrict__ lse, const float* __restrict__ D,
+                                                       float* __restrict__ part, int H, int T, float scale) {
+    constexpr int F = FB * 64;
+    __shared__ float Qs[F * 16];
+    __shared__ float dOs[F * 16];
+    __shared__ float emb_lds[64];
+    __shared__ float tile[16 * 17];            // dS[m - m0][n - n0]
+    extern __shared__ float diag[];            // entry j: the sum over the diagonal m - n = j - 15 - n0 of this wave's queries
+    const int lane = threadIdx.x, lr = lane & 15, lg = lane >> 4;
+    const int n0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
+    const float* Q = qk + ((long)b * 2 * H * F + (long)h * 2 * F) * T;
+    const float* K = Q + (long)F * T;
+    const float* qb = qkb ? qkb + h * 2 * F : nullptr;
+    const float* kb = qkb ? qb + F : nullptr;
+    const float* V = a + ((long)b * H + h) * F * T;
+    const float* dO = dout + ((long)b * H + h) * F * T;
+    const int nd = ((T + 15) & ~15) + 16;
+    if (lane < nbk) emb_lds[lane] = emb[lane * H + h];
+    for (int i = lane; i < nd; i += 64) diag[i] = 0.f;
+    stage16(Qs, Q, qb, F, T, n0);
+    stage16(dOs, dO, nullptr, F, T, n0);
+    __syncthreads();
+    const int n = n0 + lr;
+    const bool nin = n < T;
+    const float L = nin ? lse[((long)b * H + h) * T + n] : 0.f;
+    const float Dn = nin ? D[((long)b * H + h) * T + n] : 0.f;
+    for (int m0 = 0; m0 < T; m0 += 16) {
+        floatx4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
+        const int mk = m0 + lr;
+        const bool kin = mk < T;
+#pragma unroll 8
+        for (int f0 = 0; f0 < F; f0 += 4) {
+            const int f = f0 + lg;
+            const float kv = kin ? K[(long)f * T + mk] + (kb ? kb[f] : 0.f) : 0.f;
+            const float vv = kin ? V[(long)f * T + mk] : 0.f;
+            s = mfma(kv, Qs[f * 16 + lr], s);
+            dp = mfma(vv, dOs[f * 16 + lr], dp);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + 4 * lg + r;
+            float ds = 0.f;
+            if (m < T && nin) ds = expf((s[r] + emb_lds[bucket[m - n + T - 1]]) * scale - L) * (dp[r] - Dn);
+            tile[(4 * lg + r) * 17 + lr] = ds;
+        }
+        __syncthreads();
+        if (lane < 31) {                       // diagonal (m - m0) - (n - n0) = lane - 15, queries ascending
+            const int lo = lane < 15 ? 15 - lane : 0, hi = lane > 15 ? 30 - lane : 15;
+            float sum = 0.f;
+            for (int q = lo; q <= hi; ++q) sum += tile[(q + lane - 15) * 17 + q];
+            diag[m0 + lane] += sum;
+        }
+        __syncthreads();
+    }
+    if (lane < nbk) {                          // entry j holds the offset m - n = j - 15 - n0
+        float accb = 0.f;
+        for (int j = 0; j < nd; ++j) {
+            const int idx = j - 15 - n0 + T - 1;
+            if (idx >= 0 && idx <= 2 * T - 2 && bucket[idx] == lane) accb += diag[j];
+        }
+        part[(((long)b * H + h) * gridDim.x + blockIdx.x) * nbk + lane] = accb * scale;
+    }
+}
+
+// demb_rows[b][k][h] = sum over query tiles, ascending; grid (B), 256 threads
+__global__ __launch_bounds__(256) void demb_sum_kernel(const float* __restrict__ part, int nqt, int nbk, int H,
+                                                       float* __restrict__ rows, long rows_bs) {
+    const int b = blockIdx.x;
+    for (int i = threadIdx.x; i < nbk * H; i += 256) {
+        const int k = i / H, h = i % H;
+        const float* p = part + ((long)b * H + h) * nqt * nbk + k;
+        float v = 0.f;
+        for (int q = 0; q < nqt; ++q) v += p[(long)q * nbk];
+        rows[(long)b * rows_bs + i] = v;
+    }
+}
+
+// rows[b][r] = sum_t x[b][r][t]; one wave per row; grid (ceil(R/4), B), 256 threads
+__global__ __launch_bounds__(256) void rowsum_t_kernel(const float* __restrict__ x, int R, int T, float* __restrict__ rows,
+                                                       long rows_bs) {
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = blockIdx.y;
+    if (r >= R) return;
+    const float* p = x + ((long)b * R + r) * T;
+    double s = 0;
+    for (int t = lane; t < T; t += 64) s += (double)p[t];
+    s = wave_sum(s);
+    if (lane == 0) rows[(long)b * rows_bs + r] = (float)s;
+}
+
+#define DEMB_DISPATCH(FB, ...)                                                                           \
+    switch (FB) {                                                                                        \
+        case 1: hipLaunchKernelGGL(attn_demb_kernel<1>, __VA_ARGS__); break;                             \
+        case 2: hipLaunchKernelGGL(attn_demb_kernel<2>, __VA_ARGS__); break;                             \
+        case 3: hipLaunchKernelGGL(attn_demb_kernel<3>, __VA_ARGS__); break;                             \
+        case 4: hipLaunchKernelGGL(attn_demb_kernel<4>, __VA_ARGS__); break;                             \
+        case 5: hipLaunchKernelGGL(attn_demb_kernel<5>, __VA_ARGS__); break;                             \
+        case 6: hipLaunchKernelGGL(attn_demb_kernel<6>, __VA_ARGS__); break;                             \
+        default: hipLaunchKernelGGL(attn_demb_kernel<7>, __VA_ARGS__); break;                            \
+    }
+
+inline bool pv_shape_ok(int B, int H, int F, int T, int nbk) {
+    return B > 0 && H > 0 && T > 0 && F % 64 == 0 && F >= 64 && F <= FMAX && nbk >= 0 && nbk <= 64;
+}
+
+// static LDS of attn_demb_kernel<F/64> + its diagonals
+inline long demb_lds_bytes(int F, int T) { return 4L * (2L * F * 16 + 64 + 16 * 17 + diag_len(T)); }
+
+// ---------------------------------------------------------------- GroupNorm * FiLM without GELU, scale pass
+__device__ double block_sum_d(double v, double* sh) {
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+// grid (C, B)
+__global__ __launch_bounds__(256) void gn_param_nogelu_kernel(const float* __restrict__ z, const float* __restrict__ da,
+                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
+                                                              const float* __restrict__ film, long film_bs, float cs,
+                                                              float* __restrict__ dg, long dg_bs, float* __restrict__ dfilm,
+                                                              long dfilm_bs, int C, int G, long hw) {
+    __shared__ double sh[256];
+    const int c = blockIdx.x, b = blockIdx.y;
+    const long base = ((long)b * C + c) * hw;
+    double s = 0;
+    for (long i = threadIdx.x; i < hw; i += 256) s += (double)da[base + i] * (double)z[base + i];
+    s = block_sum_d(s, sh);
+    if (threadIdx.x == 0) {
+        const double ds = (double)cs * s;
+        const double r = stats[((long)b * G + c / (C / G)) * 3 + 2];
+        dg[(long)b * dg_bs + c] = (float)(ds * ((double)film[(long)b * film_bs + c] + 1.0) * r);
+        dfilm[(long)b * dfilm_bs + c] = (float)(ds * (double)gamma[c] * r);
+    }
+}
+
+// grid (ceil(hw/1024), C, B), 256 threads
+__global__ __launch_bounds__(256) void scale_channels_kernel(const float* __restrict__ x, const float* __restrict__ scale,
+                                                             float* __restrict__ out, int C, long hw) {
+    const float sc = scale[(long)blockIdx.z * C + blockIdx.y];
+    const long base = ((long)blockIdx.z * C + blockIdx.y) * hw;
+    const long i0 = (long)blockIdx.x * 1024 + threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const long i = i0 + 256 * k;
+        if (i < hw) out[base + i] = x[base + i] * sc;
+    }
+}
+
+}  // namespace
+
+extern "C" long babe_attn_qk_wgrad_workspace(int B, int HF, int T) {
+    if (!qk_shape_ok(B, HF, T)) return -1;
+    const QkPlan p = qk_plan(B, HF, T);
+    return p.nsplit > 1 ? (long)p.nsplit * 2 * HF * HF : 0;
+}
+
+extern "C" int babe_attn_qk_wgrad(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha,
+                                  float beta, void* stream) {
+    BABE_CHECK_ARG(dqk && a1 && dW, "attn_qk_wgrad: null pointer");
+    BABE_CHECK_ARG(qk_shape_ok(B, HF, T), "attn_qk_wgrad: unsupported shape B=%d HF=%d T=%d (HF a multiple of %d, at most %d)", B, HF,
+                   T, HF_STEP, HF_MAX);
+    const QkPlan p = qk_plan(B, HF, T);
+    BABE_CHECK_ARG(p.nsplit == 1 || ws, "attn_qk_wgrad: this shape needs a workspace (babe_attn_qk_wgrad_workspace)");
+    hipStream_t s = (hipStream_t)stream;
+    const int M = 2 * HF, N = HF;
+    const int direct = p.nsplit == 1;
+    hipLaunchKernelGGL(qk_wgrad_kernel, dim3(p.tiles, p.nsplit), dim3(256), 0, s, dqk, a1, direct ? dW : ws, M, N, T, B, p.nst, p.per,
+                       alpha, beta, direct);
+    BABE_LAUNCH_CHECK();
+    if (!direct) {
+        const long n = (long)M * N;
+        hipLaunchKernelGGL(qk_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, p.nsplit, n, dW, alpha, beta);
+        BABE_LAUNCH_CHECK();
+    }
+    return BABE_OK;
+}
+
+extern "C" long babe_attn_param_vjp_workspace(int B, int H, int T, int num_buckets) {
+    if (B <= 0 || H <= 0 || T <= 0 || num_buckets < 0 || num_buckets > 64) return -1;
+    return (long)B * H * T + (long)B * H * cdiv(T, 16) * num_buckets;
+}
+
+extern "C" int babe_attn_param_vjp(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
+                                   int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk,
+                                   float* ws, float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H, int F,
+                                   int T, float scale, void* stream) {
+    BABE_CHECK_ARG(!bucket == !emb && !bucket == !demb_rows, "attn_param_vjp: bucket table, embedding and demb_rows go together");
+    const int nbk = bucket ? num_buckets : 0;
+    BABE_CHECK_ARG(pv_shape_ok(B, H, F, T, nbk), "attn_param_vjp: unsupported shape B=%d H=%d F=%d T=%d buckets=%d", B, H, F, T, nbk);
+    BABE_CHECK_ARG(demb_rows || dqkb_rows, "attn_param_vjp: nothing to compute");
+    BABE_CHECK_ARG(!dqkb_rows || (dqk && dqkb_bs >= 2L * H * F), "attn_param_vjp: dqkb_rows needs dqk and dqkb_bs >= 2HF");
+    hipStream_t s = (hipStream_t)stream;
+    if (demb_rows) {
+        BABE_CHECK_ARG(qk && a && out && lse && dout && ws, "attn_param_vjp: null pointer");
+        BABE_CHECK_ARG(nbk > 0 && demb_bs >= (long)nbk * H, "attn_param_vjp: demb_bs %ld < num_buckets*H", demb_bs);
+        BABE_CHECK_ARG(demb_lds_bytes(F, T) <= LDS_LIMIT, "attn_param_vjp: F=%d with T=%d needs %ld bytes of LDS (limit %d)", F, T,
+                       demb_lds_bytes(F, T), LDS_LIMIT);
+        float* D = ws;
+        float* part = ws + (long)B * H * T;
+        const int nqt = cdiv(T, 16);
+        hipLaunchKernelGGL(rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
+        BABE_LAUNCH_CHECK();
+        DEMB_DISPATCH(F / 64, dim3(nqt, H, B), dim3(64), diag_len(T) * sizeof(float), s, qk, qk_bias, a, bucket, emb, nbk, dout,
+                      lse, D, part, H, T, scale);
+        BABE_LAUNCH_CHECK();
+        hipLaunchKernelGGL(demb_sum_kernel, dim3(B), dim3(256), 0, s, part, nqt, nbk, H, demb_rows, demb_bs);
+        BABE_LAUNCH_CHECK();
+    }
+    if (dqkb_rows) {
+        const int R = 2 * H * F;
+        hipLaunchKernelGGL(rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
+        BABE_LAUNCH_CHECK();
+    }
+    return BABE_OK;
+}
+
+extern "C" int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stats, const float* gamma,
+                                         const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
+                                         long dfilm_bs, int B, int C, int G, long hw, void* stream) {
+    BABE_CHECK_ARG(z && da && stats && gamma && film_aff && dgamma_rows && dfilm && B > 0 && C > 0 && G > 0 && C % G == 0 && hw > 0,
+                   "gn_param_grad_nogelu: bad arguments");
+    hipLaunchKernelGGL(gn_param_nogelu_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, z, da, stats, gamma, film_aff, film_bs,
+                       cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, C, G, hw);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
+
+extern "C" int babe_scale_channels(const float* x, const float* scale, float* out, int B, int C, long hw, void* stream) {
+    BABE_CHECK_ARG(x && scale && out && B > 0 && C > 0 && hw > 0 && B <= 65535 && C <= 65535, "scale_channels: bad arguments");
+    hipLaunchKernelGGL(scale_channels_kernel, dim3(cdiv(hw, 1024), C, B), dim3(256), 0, (hipStream_t)stream, x, scale, out, C, hw);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}

@@ -9,7 +9,8 @@ sampler code - which calls ``torch.autograd.grad`` through the model - runs on i
 There is no CPU path: device must be a GPU and libbabe_hip.so must be present.
 
 Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run in fp32 on the Python sequencer
-(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them).
+(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them); their parameter gradients are opt-in
+(``set_trainable(True, attention=True)``, csrc/attention_train.hip).
 
 Frequency encodings (``use_fencoding``, AddFreqEncodingRFF) are never materialised as channels: the 64 encoding channels are
 constant over batch and time and feed only the init blocks' two (1,1) convs, so their share is folded into a bias table per conv
@@ -265,10 +266,16 @@ class Unet_CQT_oct_with_attention(nn.Module):
             self._versions = v
 
     # ---------------------------------------------------------------- training
-    def set_trainable(self, flag=True):
+    def set_trainable(self, flag=True, attention=False):
         """requires_grad on exactly the reference's trainable set (is_trainable), so torch.optim.Adam(net.parameters()) updates
-        what the reference's Adam updates.  Parameter gradients run in fp32 on attention-free networks (others raise on the
-        forward), under the plain and the A-weighted EDM loss alike (diff_params/edm.py::loss_fn)."""
+        what the reference's Adam updates.  Parameter gradients run in fp32, under the plain and the A-weighted EDM loss alike
+        (diff_params/edm.py::loss_fn).
+        attention=True opts in to the parameter gradients of the time-attention branch (norm2 / affine2 / gate2 and attn_block.*,
+        csrc/attention_train.hip); without it a network with attention layers raises on the forward while a parameter requires
+        grad.  The opt-in is about memory: a qk weight is a [16 F, 8 F] matrix per attention block (25.7 M floats at F = 448), and
+        the attention_layers [0,0,0,0,1,1,1,1] layout carries about 141 M of them - weights, gradients and the two Adam moments
+        come to about 2 GB on top of the attention-free network.  On a network without attention layers the flag does nothing."""
+        self._train_attention = bool(flag) and bool(attention)
         for k, p in self.named_parameters():
             p.requires_grad_(bool(flag) and is_trainable(k))
         return self
@@ -278,8 +285,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
         ps = [(k, p) for k, p in self._params if p.requires_grad]
         if not ps:
             return ps
-        if self.has_attention:
-            raise NotImplementedError("parameter gradients of networks with attention layers are not implemented")
+        if self.has_attention and not getattr(self, "_train_attention", False):
+            raise NotImplementedError("parameter gradients of networks with attention layers are not implemented "
+                                      "(opt in with set_trainable(True, attention=True))")
         if self.precision != "f32":
             raise NotImplementedError(f"parameter gradients run in fp32 only (precision={self.precision!r})")
         bad = [k for k, _ in ps if not is_trainable(k)]
@@ -373,7 +381,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
 
     def fwd_nograd(self, x, cnoise, lane=None, train=False):
         """x [B,L], cnoise [B,1] -> [B,L]; keeps what vjp() needs until the next call (of the same lane).
-        train=True: also what the parameter gradients need (_vjp_train); fp32, attention-free, the module's own lanes."""
+        train=True: also what the parameter gradients need (_vjp_train); fp32, the module's own lanes."""
         assert x.device == self.device, f"input on {x.device}, network on {self.device}"
         with torch.cuda.device(self.device):       # every launch below goes to THIS device's current stream
             if lane is None:

@@ -32,14 +32,17 @@ class _Attn:
         z'  = (gate2(emb) * proj_out(o) + z) / sqrt2
     z is the block's proj_in output, z' feeds the dilated conv stack."""
 
-    def __init__(self, g, Fdim, N, film_index, opts):
+    def __init__(self, g, Fdim, N, film_index, opts, prefix=""):
         self.H, self.bias_qkv, self.rel_pos, self.nbk, self.maxd = opts
         self.F = Fdim
+        self.p = prefix
         self.scale = float(Fdim) ** -0.5
         self.gamma = g("norm2.gamma").reshape(-1).contiguous()
-        self.film_off = (film_index.add(g("affine2.weight"), g("affine2.bias")), film_index.add(g("gate2.weight"), g("gate2.bias")))
+        self.film_off = (film_index.add(g("affine2.weight"), g("affine2.bias"), prefix + "affine2"),
+                         film_index.add(g("gate2.weight"), g("gate2.bias"), prefix + "gate2"))
         self.proj_in = ops.PackedConv(g("attn_block.proj_in.weight"))
         self.proj_out = ops.PackedConv(g("attn_block.proj_out.weight"))
+        self.proj_out_w = g("attn_block.proj_out.weight").contiguous()             # raw weights (the gate2 gradient)
         w = g("attn_block.qk.weight")
         self.qk = ops.PackedConv(w.reshape(w.shape[0], w.shape[1], 1, 1))
         self.qk_bias = g("attn_block.qk.bias").contiguous() if self.bias_qkv else None
@@ -94,7 +97,7 @@ class _Block:
         for d in range(num_dils):
             self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias"), prefix + f"affine.{d}"),
                                   film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"), prefix + f"gate.{d}")))
-        self.attn = _Attn(g, attn[0], self.N, film_index, attn[1]) if attn else None
+        self.attn = _Attn(g, attn[0], self.N, film_index, attn[1], prefix) if attn else None
         self.saved = None
         self.attn_saved = None
         self.inp = self.zpo = None    # training: the block's input(s) and proj_out's input, for the weight gradients
@@ -124,29 +127,43 @@ class _FilmIndex:
         self._parts = (self.W, self.b)
         self.W = self.b = None
 
-    def refresh(self):
-        """Rebuild Wcat / bcat in place from the (parameter-aliasing) pieces after an optimizer step."""
-        torch.cat(self._parts[0], 0, out=self.Wcat)
-        torch.cat(self._parts[1], 0, out=self.bcat)
+    def refresh(self, sd=None):
+        """Rebuild Wcat / bcat in place after an optimizer step: from sd (the current parameters) where the pieces have keys,
+        from the (parameter-aliasing) pieces themselves otherwise."""
+        W, b = self._parts
+        if sd is not None:
+            W = [sd[k + ".weight"] if k is not None else w for (k, _, _), w in zip(self.keys, W)]
+            b = [sd[k + ".bias"] if k is not None else v for (k, _, _), v in zip(self.keys, b)]
+        torch.cat(W, 0, out=self.Wcat)
+        torch.cat(b, 0, out=self.bcat)
 
 
 class ParamGrads:
     """Per-call parameter-gradient buffers of a training step, shared by the clip lanes: every lane writes only its own batch
     rows, and one fixed-order reduction over the rows after the join (UnetEngine.param_grads) makes the result independent of
     the lane count.  rows [B, n]: per-row weight gradients of every conv and GroupNorm gamma, flat (layout: key -> (offset,
-    shape)); dfilm [B, J]: gradient w.r.t. the concatenated FiLM Linear output."""
+    shape)); dfilm [B, J]: gradient w.r.t. the concatenated FiLM Linear output.
+    qk {block prefix: (dqk [B, 2HF, T], a1 [B, HF, T])}: the operands of the attention blocks' qk weight gradients.  Those are
+    [2HF, HF] matrices of up to 25.7 M floats, far too large for a per-row copy: the lanes leave their rows of both operands here
+    (allocated on the caller's stream before the lanes fork, so they outlive the lanes' buffer recycling) and param_grads
+    forms each gradient in one batch-summed launch after the join."""
 
-    def __init__(self, layout, rows, dfilm):
-        self.layout, self.rows, self.dfilm = layout, rows, dfilm
+    def __init__(self, layout, rows, dfilm, qk=None):
+        self.layout, self.rows, self.dfilm, self.qk = layout, rows, dfilm, qk or {}
 
     @classmethod
     def new(cls, eng, B):
         rows = torch.zeros(B, eng.grad_numel, device=eng.dev, dtype=torch.float32)
         dfilm = torch.zeros(B, eng.film_idx.J, device=eng.dev, dtype=torch.float32)
-        return cls(eng.grad_layout, rows, dfilm)
+        qk = {}
+        for blk, level in eng.attn_blocks:
+            HF, T = blk.attn.H * blk.attn.F, eng.Ts[level]
+            qk[blk.p] = (torch.empty(B, 2 * HF, T, device=eng.dev, dtype=torch.float32),
+                         torch.empty(B, HF, T, device=eng.dev, dtype=torch.float32))
+        return cls(eng.grad_layout, rows, dfilm, qk)
 
     def lane(self, b0, b1):
-        return ParamGrads(self.layout, self.rows[b0:b1], self.dfilm[b0:b1])
+        return ParamGrads(self.layout, self.rows[b0:b1], self.dfilm[b0:b1], {k: (d[b0:b1], a[b0:b1]) for k, (d, a) in self.qk.items()})
 
     def row(self, key):
         off, shape = self.layout[key]
@@ -206,8 +223,21 @@ class UnetEngine:
                 at = blk.attn
                 self.packs += [(blk.p + "attn_block.proj_in.weight", at.proj_in), (blk.p + "attn_block.proj_out.weight", at.proj_out),
                                (blk.p + "attn_block.qk.weight", at.qk)]
+                # per-row gradients of the attention branch; qk.weight is batch-summed after the join instead (ParamGrads.qk)
+                self._add_grad(blk.p + "norm2.gamma", None, (1, blk.N, 1, 1))
+                self._add_grad(blk.p + "attn_block.proj_in.weight", None, (at.H, blk.N, 1, 1))
+                self._add_grad(blk.p + "attn_block.proj_out.weight", None, (blk.N, at.H, 1, 1))
+                if at.bias_qkv:
+                    self._add_grad(blk.p + "attn_block.qk.bias", None, (2 * at.H * at.F,))
+                if at.rel_pos:
+                    self._add_grad(blk.p + "attn_block.rel_pos.relative_attention_bias.weight", None, (at.nbk, at.H))
         for i, pc in enumerate(self.pyr_conv):
             self._add_grad(f"downs.{i}.1.weight", pc)
+        # (block, level whose time length it runs at) of every block with attention
+        n = num_octs
+        self.attn_blocks = [(b, i) for i, b in enumerate(self.main_blk) if b.attn is not None]
+        self.attn_blocks += [(self.mid_blk, n - 1)] if self.mid_blk.attn is not None else []
+        self.attn_blocks += [(b, n - 1 - i) for i, b in enumerate(self.up_blk) if b.attn is not None]
 
     def _add_grad(self, key, pc, shape=None):
         if pc is not None:
@@ -235,7 +265,17 @@ class UnetEngine:
                 blk.fenc.copy_(sd[f"freq_encodings.{i}.embeddings"].reshape(blk.fenc.shape))
                 for name in blk.FOLDED:
                     ops.fenc_bias(sd[blk.p + name + ".weight"].reshape(blk.N, 66), blk.fenc, getattr(blk, "fb_" + name))
-        self.film_idx.refresh()
+        for blk, _ in self.attn_blocks:                   # the attention branch's plain tensors (no-ops while they alias the parameters)
+            at, p = blk.attn, blk.p
+            pairs = [(at.gamma, sd[p + "norm2.gamma"].reshape(-1)), (at.proj_out_w, sd[p + "attn_block.proj_out.weight"])]
+            if at.qk_bias is not None:
+                pairs.append((at.qk_bias, sd[p + "attn_block.qk.bias"]))
+            if at.emb is not None:
+                pairs.append((at.emb, sd[p + "attn_block.rel_pos.relative_attention_bias.weight"]))
+            for dst, src in pairs:
+                if dst.data_ptr() != src.data_ptr():
+                    dst.copy_(src.reshape(dst.shape))
+        self.film_idx.refresh(sd)
 
     def clone_state(self):
         """A second engine over the SAME packed weights with its own per-call state (saved activations, scratch), so that
@@ -354,18 +394,39 @@ class UnetEngine:
         blk.attn_saved = (z, stats, scale, gate, a1, qk, o, lse)
         return zn
 
-    def attn_vjp(self, blk, gz, c):
-        """gz <- gradient w.r.t. the attention branch's input z, given c*gz = gradient w.r.t. its output z' (in place)."""
+    def attn_vjp(self, blk, gz, c, pg=None):
+        """gz <- gradient w.r.t. the attention branch's input z, given c*gz = gradient w.r.t. its output z' (in place).
+        pg: ParamGrads of a training step: also the branch's parameter gradients (per row into pg.rows / pg.dfilm; the qk weight
+        gradient's operands into pg.qk, for param_grads)."""
         at = blk.attn
         z, stats, scale, gate, a1, qk, o, lse = blk.attn_saved
         B, N, Fq, T = z.shape
         H = at.H
+        p = blk.p
+        if pg is not None:                                   # z' = rs2*(gate2 * proj_out(o) + z), before gz is overwritten
+            goff = at.film_off[1]
+            self._wg(pg, p + "attn_block.proj_out.weight", o, gz, at.proj_out, RS2 * c, oscale=gate, w=at.proj_out_w,
+                     dgate=pg.dfilm[:, goff:goff + N], galpha=RS2 * c)
         do = ops.conv2d(gz, at.proj_out, self.buf(B, H, Fq, T), transpose=True, in_scale=gate, alpha=RS2 * c)
-        dqk = self.buf(B, 2 * H * Fq, 1, T)
+        # training: dqk goes straight into this lane's rows of the buffer the qk weight gradient reads after the join
+        dqk = self.buf(B, 2 * H * Fq, 1, T) if pg is None else pg.qk[p][0].view(B, 2 * H * Fq, 1, T)
         dv = self.buf(B, H, Fq, T)
-        ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=at.buckets(T, self.dev), emb=at.emb)
+        bucket = at.buckets(T, self.dev)
+        ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb)
+        if pg is not None:
+            ops.axpby(a1.view(B, H * Fq, 1, T), pg.qk[p][1].view(B, H * Fq, 1, T))
+            if at.rel_pos or at.bias_qkv:
+                ops.attn_param_vjp(qk, a1, o, lse, do, dqk, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb,
+                                   demb_rows=pg.row(p + "attn_block.rel_pos.relative_attention_bias.weight") if at.rel_pos else None,
+                                   dqkb_rows=pg.row(p + "attn_block.qk.bias") if at.bias_qkv else None)
         da1 = ops.conv2d(dqk, at.qk, self.buf(B, H * Fq, 1, T), transpose=True, res=dv.view(B, H * Fq, 1, T), rbeta=1.0)
         da0 = ops.conv2d(da1.view(B, H, Fq, T), at.proj_in, self.buf(B, N, Fq, T), transpose=True)
+        if pg is not None:                                   # a0 = z * scale2 (no GELU), a1 = proj_in(a0); da0, da1 are unscaled
+            aoff = at.film_off[0]
+            ops.gn_param_grad_nogelu(z, da0, stats, at.gamma, self._film(self._film_saved, aoff, N), pg.row(p + "norm2.gamma"),
+                                     pg.dfilm[:, aoff:aoff + N])
+            a0 = ops.scale_channels(z, scale, self.scratch("a", B * N * Fq * T).view(B, N, Fq, T))
+            self._wg(pg, p + "attn_block.proj_in.weight", a0, da1.view(B, H, Fq, T), at.proj_in, 1.0)
         ops.gn_bwd_nogelu(z, da0, gz, scale, stats, gz, RS2 * c)
         blk.attn_saved = None
         return gz
@@ -425,6 +486,10 @@ class UnetEngine:
             for v in shape:
                 n *= v
             grads[key] = flat[off:off + n].view(shape)
+        for blk, _ in self.attn_blocks:                  # the qk weight gradients: one launch per block over all batch rows
+            dqk, a1 = pg.qk[blk.p]
+            HF = a1.shape[1]
+            grads[blk.p + "attn_block.qk.weight"] = ops.attn_qk_wgrad(dqk, a1, self.buf(2 * HF, HF, 1))
         h0, h1, h2, h3 = emb_keep
         B = h3.shape[0]
         fi = self.film_idx
@@ -507,7 +572,7 @@ class UnetEngine:
                 self._layer_gn_grad(pg, blk, d, da, c)
             ops.gn_bwd(z, da, gz, scale, stats, gz, RS2, fused=fs)
         if blk.attn is not None:
-            self.attn_vjp(blk, gz, c)
+            self.attn_vjp(blk, gz, c, pg)
             c = 1.0
         if pg is not None and blk.proj_in is not None:
             x, x2 = blk.inp

@@ -627,6 +627,66 @@ def gn_param_grad(z, da, scale, stats, gamma, film_aff, dgamma_rows, dfilm, cs=1
           "gn_param_grad")
 
 
+def gn_param_grad_nogelu(z, da, stats, gamma, film_aff, dgamma_rows, dfilm, cs=1.0, G=8):
+    """gn_param_grad for a = z * scale without the GELU (babe_gn_param_grad_nogelu: norm2 / affine2 of the attention branch)."""
+    B, Cc, F, T = z.shape
+    assert z.is_contiguous() and da.is_contiguous() and da.shape == z.shape
+    assert film_aff.stride(1) == 1 and dgamma_rows.stride(1) == 1 and dfilm.stride(1) == 1
+    assert dgamma_rows.shape == (B, Cc) and dfilm.shape == (B, Cc)
+    check(lib().babe_gn_param_grad_nogelu(ptr(z), ptr(da), ptr(stats), ptr(gamma), ptr(film_aff), film_aff.stride(0), cs,
+                                          ptr(dgamma_rows), dgamma_rows.stride(0), ptr(dfilm), dfilm.stride(0), B, Cc, G, F * T,
+                                          stream()), "gn_param_grad_nogelu")
+
+
+def scale_channels(x, scale, out):
+    """out = x * scale[b, c] (babe_scale_channels), dense [B,C,F,T]: scale_gelu without the GELU."""
+    B, Cc, F, T = x.shape
+    assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and scale.is_contiguous() and scale.shape == (B, Cc)
+    check(lib().babe_scale_channels(ptr(x), ptr(scale), ptr(out), B, Cc, F * T, stream()), "scale_channels")
+    return out
+
+
+def attn_qk_wgrad(dqk, a1, dW, alpha=1.0, beta=0.0, ws=None):
+    """dW [2HF, HF] = alpha * sum_b dqk[b] a1[b]^T + beta * dW (babe_attn_qk_wgrad): the qk Conv1d weight gradient, summed over
+    the batch in a fixed order.  dqk [B,2HF,T], a1 [B,HF,T] dense."""
+    B, M, T = dqk.shape
+    HF = a1.shape[1]
+    for t in (dqk, a1, dW):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert a1.shape == (B, HF, T) and M == 2 * HF and dW.numel() == M * HF
+    n = lib().babe_attn_qk_wgrad_workspace(B, HF, T)
+    if n < 0:
+        raise _lib.BabeHipError(f"attn_qk_wgrad: unsupported shape B={B} HF={HF} T={T} (HF a multiple of 512, at most 3584)")
+    if n and ws is None:
+        ws = torch.empty(n, device=dW.device, dtype=torch.float32)
+    assert not n or (ws.numel() >= n and ws.is_contiguous())
+    check(lib().babe_attn_qk_wgrad(ptr(dqk), ptr(a1), ptr(dW), ptr(ws) if n else None, B, HF, T, alpha, beta, stream()), "attn_qk_wgrad")
+    return dW
+
+
+def attn_param_vjp(qk, a, out, lse, dout, dqk, scale, qk_bias=None, bucket=None, emb=None, demb_rows=None, dqkb_rows=None):
+    """Table and bias gradients of attn_fwd per batch row (babe_attn_param_vjp), from the operands of attn_vjp and its dqk:
+    demb_rows [B, nb*H] (with bucket / emb) and dqkb_rows [B, 2HF] (views with any row stride; None: not computed)."""
+    B, H, F, T = a.shape
+    for t in (qk, a, out, lse, dout, dqk):
+        assert t.is_contiguous() and t.dtype == torch.float32
+    assert dout.shape == a.shape and dqk.numel() == qk.numel() == B * 2 * H * F * T
+    nb = 0
+    if bucket is not None:
+        assert bucket.dtype == torch.int32 and bucket.numel() == 2 * T - 1 and emb.is_contiguous() and emb.shape[1] == H
+        nb = emb.shape[0]
+        assert demb_rows is not None and demb_rows.shape == (B, nb * H) and demb_rows.stride(1) == 1
+    else:
+        assert demb_rows is None
+    if dqkb_rows is not None:
+        assert dqkb_rows.shape == (B, 2 * H * F) and dqkb_rows.stride(1) == 1
+    ws = torch.empty(max(1, lib().babe_attn_param_vjp_workspace(B, H, T, nb)), device=a.device, dtype=torch.float32)
+    check(lib().babe_attn_param_vjp(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(dqk),
+                                    ptr(ws), ptr(demb_rows), demb_rows.stride(0) if demb_rows is not None else 0, ptr(dqkb_rows),
+                                    dqkb_rows.stride(0) if dqkb_rows is not None else 0, B, H, F, T, scale, stream()),
+          "attn_param_vjp")
+
+
 def linear_bwd(dy, x, W, dW, db, dx=None, y=None, beta=0.0, ws=None):
     """Backward of linear(x, W, bias, relu=y is not None) with output y: dW (+)= dp^T x, db (+)= sum_b dp, dx = dp W,
     dp = dy * (y > 0) (babe_linear_bwd; fixed-order sums)."""

@@ -644,6 +644,37 @@ int babe_fenc_bias(const float* w, const float* emb, float* fb, int Cout, int ld
 int babe_fenc_wgrad_rows(const float* g, long g_bs, long g_cs, const float* emb, float alpha, float* rows, long rows_bs, int ld_row,
                          int B, int Cout, int F, int T, void* stream);
 
+
+/* ---- training: parameter gradients of the time-attention branch (csrc/attention_train.hip), fp32, fixed-order sums, no float
+ * atomics.  Tensors as for babe_attn_fwd / babe_attn_vjp.
+ *
+ * qk Conv1d weight gradient, summed over the batch:
+ *   dW[co*HF + ci] = alpha * sum_b sum_t dqk[b][co][t] * a1[b][ci][t] + beta * dW[co*HF + ci]     (beta == 0: dW is not read)
+ * dqk [B][2HF][T], a1 [B][HF][T] dense, HF a multiple of 512 up to 3584, any T >= 1 (rows need no alignment).  K = (b, t) is
+ * walked in ascending order; small HF splits it into chunks that a second pass adds in order (chunk count a function of
+ * (B, HF, T) only).  ws: babe_attn_qk_wgrad_workspace floats (0: none needed; -1: unsupported shape). */
+long babe_attn_qk_wgrad_workspace(int B, int HF, int T);
+int babe_attn_qk_wgrad(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha, float beta,
+                       void* stream);
+/* Per batch row, from the inputs of babe_attn_vjp (dS = P o (dP - D) recomputed; dqk is babe_attn_vjp's output):
+ *   demb_rows[b*demb_bs + k*H + h] = sum_{n,m : bucket[m - n + T - 1] = k} scale * dS[b][h][n][m]   every k < num_buckets written,
+ *                                    exactly 0 where no pair reaches the bucket        (NULL with bucket and emb NULL)
+ *   dqkb_rows[b*dqkb_bs + r]       = sum_t dqk[b][r][t], r < 2HF                                    (NULL: not computed)
+ * ws: babe_attn_param_vjp_workspace floats.  The wave's diagonals live in LDS next to its 16 query columns: 4*(32 F + T) bytes
+ * plus 1.5 KB must fit in 64 KB (F = 448: T <= 1300; F = 64: any T up to 15000), anything larger is an argument error. */
+long babe_attn_param_vjp_workspace(int B, int H, int T, int num_buckets);
+int babe_attn_param_vjp(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
+                        int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk, float* ws,
+                        float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H, int F, int T, float scale,
+                        void* stream);
+/* babe_gn_param_grad for a = z * scale WITHOUT the GELU (norm2 / affine2 of the attention branch): dscale = cs * sum_i da*z. */
+int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stats, const float* gamma, const float* film_aff,
+                              long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm, long dfilm_bs, int B, int C,
+                              int G, long hw, void* stream);
+/* out[b][c][i] = x[b][c][i] * scale[b*C + c], dense [B][C][hw] (out may be x): the input of the attention proj_in, rebuilt for
+ * its weight gradient. */
+int babe_scale_channels(const float* x, const float* scale, float* out, int B, int C, long hw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,11 @@
 input-VJP, parameter-gradient work (and the conv weight-gradient calls in it), reductions and repack, plus the conv weight-gradient kernel's rate per level against the 157.3
 TFLOP/s fp32 MFMA peak.  Prints one JSON document (profiles/train_bench.json).
 
-    python tools/train_bench.py [--B 4] [--L 368368] [--reps 3]
+    python tools/train_bench.py [--B 4] [--L 368368] [--reps 3] [--attention-layers 0,0,0,0,1,1,1,1]
+
+--attention-layers: train a network with time-attention layers (set_trainable(True, attention=True)); the report then also has the
+qk weight-gradient launches of one backward (babe_attn_qk_wgrad, one per attention block after the lane join): their summed time
+and share of the step.
 """
 import argparse
 import json
@@ -34,21 +38,28 @@ def main():
     ap.add_argument("--B", type=int, default=4)
     ap.add_argument("--L", type=int, default=368368)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--attention-layers", default=None, help="8 comma-separated flags, e.g. 0,0,0,0,1,1,1,1")
     a = ap.parse_args()
+    att = [int(v) for v in a.attention_layers.split(",")] if a.attention_layers else None
     from babe_amd import ops
     from babe_amd.config import default_args
     from babe_amd.networks.cqtdiff_plus import Unet_CQT_oct_with_attention, init_state_dict
     from tests.golden_weights import FULL_DILS, FULL_NS
 
     args = default_args(sample_rate=44100, audio_len=a.L)
+    adict = None
+    if att:
+        adict = dict(num_heads=8, attn_dropout=0.0, bias_qkv=False, N=0, rel_pos_num_buckets=32, rel_pos_max_distance=64,
+                     use_rel_pos=True, Nproj=8)
+        args.network.attention_layers, args.network.attention_dict = att, adict
     net = Unet_CQT_oct_with_attention(args, "cuda")
-    net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0))
-    net.set_trainable(True)
+    net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0, attention_layers=att, attention_dict=adict))
+    net.set_trainable(True, attention=bool(att))
     gen = torch.Generator().manual_seed(0)
     x = (0.1 * torch.randn(a.B, a.L, generator=gen)).cuda()
     cn = torch.linspace(-1, 0.5, a.B).reshape(a.B, 1).cuda()
     w = torch.randn(a.B, a.L, generator=gen).cuda()
-    res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES)}
+    res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES), "attention_layers": att}
 
     # input-VJP alone (the sampler's path) and the forward without training state
     def fwd_vjp():
@@ -71,6 +82,17 @@ def main():
         e.record()
         wg_ev.append((s, e))
     ue.UnetEngine._wg = wg
+    qk_ev = []
+    orig_qk = ops.attn_qk_wgrad
+
+    def qk_wgrad(*args, **kw):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        out = orig_qk(*args, **kw)
+        e.record()
+        qk_ev.append((s, e))
+        return out
+    ops.attn_qk_wgrad = qk_wgrad
     eng = net.engine()
     red = []
     orig = eng.param_grads
@@ -90,6 +112,7 @@ def main():
     torch.cuda.synchronize()
     eng.param_grads = orig
     ue.UnetEngine._wg = orig_wg
+    ops.attn_qk_wgrad = orig_qk
     res["train_backward_ms"] = sorted(bwd)[len(bwd) // 2]
     res["reductions_ms"] = sorted(s.elapsed_time(e) for s, e in red)[len(red) // 2]
     # everything the parameter gradients add to the backward: conv weight gradients, the recomputed GELU, the GroupNorm / FiLM
@@ -112,6 +135,10 @@ def main():
         opt.step()
     step()
     res["step_ms"] = timed(step, a.reps)
+    if att:                                            # the launches run back to back on one stream: their times add up
+        res["attn_qk_wgrad_calls_per_backward"] = len(qk_ev) // a.reps
+        res["attn_qk_wgrad_ms_sum"] = sum(s.elapsed_time(e) for s, e in qk_ev) / a.reps
+        res["attn_qk_wgrad_share_of_step"] = round(res["attn_qk_wgrad_ms_sum"] / res["step_ms"], 4)
 
     # weight-gradient kernel per level: the (5,3) H convs of the main blocks at this geometry, B rows per call
     Ts = [c.shape[-1] for c in net.CQTransform.fwd_planar(x[:1])][::-1]
