@@ -20,19 +20,13 @@
 
 namespace {
 
-__device__ __forceinline__ float sel_scale(bool has, float loaded) { return has ? loaded : 1.f; }
-
-struct ConvGeom {
-    int CinP, CoutP, pt_log2, pr_log2, tiles_t;
-};
-
 // Packed weights are permuted inside every BN-wide output-channel tile so that the NT values one lane feeds to
 // its NT MFMAs are contiguous in LDS: channel co0 + nt*32 + l  is stored at  co0 + l*NT + nt.
 // VEC = true: activations are staged as 16-byte loads / ds_write_b128 (needs T % 4 == 0 and 16-byte aligned rows);
 // the LDS row then carries its left halo at index 3 so that the body starts 16-byte aligned.
 // (the body of both kernels below: conv_mfma_kernel, and conv11_fb_kernel with the frequency bias in its epilogue)
 template <int NT, int WP, int KC, int KW, bool VEC, bool HAS_FB>
-__device__ __forceinline__ void conv_mfma_body(const babe_conv_args& a, const ConvGeom& g) {
+__device__ __forceinline__ void conv_mfma_body(const babe_conv_args& a, const ConvTileGeom& g) {
     constexpr int BN = NT * 32;
     constexpr int NPOS = 128 * WP;          // output positions per block
     constexpr int TG = 256 / NPOS;          // thread groups that split the KC staged channels
@@ -284,22 +278,15 @@ __device__ __forceinline__ void conv_mfma_body(const babe_conv_args& a, const Co
 }
 
 template <int NT, int WP, int KC, int KW, bool VEC>
-__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv_mfma_kernel(babe_conv_args a, ConvGeom g) {
+__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv_mfma_kernel(babe_conv_args a, ConvTileGeom g) {
     conv_mfma_body<NT, WP, KC, KW, VEC, false>(a, g);
 }
 
 // out = alpha * oscale * (acc + fbias[co][f]) + rbeta * res (babe_conv_args::fbias, non-NULL): (1,1) convs only (babe_conv2d_nt).
 // A kernel of its own, so that conv_mfma_kernel keeps the registers and scratch it has without the bias epilogues.
 template <int NT, int WP, int KC, bool VEC>
-__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv11_fb_kernel(babe_conv_args a, ConvGeom g) {
+__global__ __launch_bounds__(256, (WP == 1 ? 4 : 2)) void conv11_fb_kernel(babe_conv_args a, ConvTileGeom g) {
     conv_mfma_body<NT, WP, KC, 1, VEC, true>(a, g);
-}
-
-inline int pick_nt(int CoutP) {
-    const int n32 = CoutP / 32;
-    for (int c = 4; c >= 1; --c)
-        if (n32 % c == 0) return c;
-    return 1;
 }
 
 __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restrict__ dst, int Cout, int Cin, int KH,
@@ -316,39 +303,16 @@ __global__ void pack_weights_kernel(const float* __restrict__ w, float* __restri
     r /= CinP;
     const int kw = (int)(r % KW);
     const int kh = (int)(r / KW);
-    float v = 0.f;
-    if (!tf) {
-        if (co < Cout && ci < Cin) v = w[(((long)co * Cin + ci) * KH + kh) * KW + kw];
-    } else {
-        // packed "Cout" = reference Cin, packed "Cin" = reference Cout
-        if (co < Cin && ci < Cout) v = w[(((long)ci * Cin + co) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)];
-    }
-    dst[i] = v;
-}
-
-inline int ilog2_floor(int v) {
-    int l = 0;
-    while ((1 << (l + 1)) <= v) ++l;
-    return l;
-}
-inline int ilog2_ceil(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
+    dst[i] = conv_w_tap(w, Cout, Cin, KH, KW, tf, co, ci, kh, kw);
 }
 
 template <int NT, int WP, int KW, bool VEC>
-int launch_conv(const babe_conv_args& a, ConvGeom g, hipStream_t s) {
+int launch_conv(const babe_conv_args& a, hipStream_t s) {
     constexpr int KC = 8;
     constexpr int NPOS = 128 * WP;
-    const int npos_log2 = ilog2_floor(NPOS);
-    g.pt_log2 = ilog2_ceil(a.T);
-    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = npos_log2 - g.pt_log2;
+    int tiles_f;
+    const ConvTileGeom g = conv_tile_geom(a, ilog2_floor(NPOS), 4, &tiles_f);
     const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    const int tiles_f = cdiv(a.F, PR);
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / (NT * 32), a.B);
     size_t lds = 2 * ((size_t)((KC * PR * (PT + (VEC ? 8 : 2)) + 3) & ~3) + (size_t)KW * KC * NT * 32) * sizeof(float);
     if constexpr (KW == 1) {
@@ -364,9 +328,8 @@ int launch_conv(const babe_conv_args& a, ConvGeom g, hipStream_t s) {
 }  // namespace
 
 extern "C" long babe_conv_packed_size(int Cout, int Cin, int KH, int KW, int transpose_flip) {
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    return (long)KH * KW * ((ci + 7) / 8 * 8) * ((co + 31) / 32 * 32);
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    return (long)KH * KW * pad_to(io.ci, 8) * pad_to(io.co, 32);
 }
 
 extern "C" int babe_conv_pack_weights(const float* w, float* dst, int Cout, int Cin, int KH, int KW,
@@ -377,9 +340,8 @@ extern "C" int babe_conv_pack_weights(const float* w, float* dst, int Cout, int 
 extern "C" int babe_conv_pack_weights_nt(const float* w, float* dst, int Cout, int Cin, int KH, int KW,
                                          int transpose_flip, int nt, void* stream) {
     BABE_CHECK_ARG(w && dst && Cout > 0 && Cin > 0 && KH > 0 && KW > 0, "conv_pack_weights: bad arguments");
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    const int CinP = (ci + 7) / 8 * 8, CoutP = (co + 31) / 32 * 32;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    const int CinP = pad_to(io.ci, 8), CoutP = pad_to(io.co, 32);
     const long total = (long)KH * KW * CinP * CoutP;
     BABE_CHECK_ARG(nt == 0 || (nt >= 1 && nt <= 4 && (CoutP / 32) % nt == 0), "conv_pack_weights_nt: nt=%d does not divide %d row tiles", nt, CoutP / 32);
     hipLaunchKernelGGL(pack_weights_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout,
@@ -402,11 +364,9 @@ extern "C" int babe_conv2d_nt(const babe_conv_args* ap, int nt, void* stream) {
                    "conv2d: kernel %dx%d unsupported (need 5x3 or 1x1)", a.KH, a.KW);
     BABE_CHECK_ARG(!a.in2 || (a.cin_split > 0 && a.cin_split < a.Cin), "conv2d: bad cin_split");
     BABE_CHECK_ARG(!a.fbias || (a.KH == 1 && a.KW == 1), "conv2d: fbias needs a (1,1) kernel (got %dx%d)", a.KH, a.KW);
-    ConvGeom g;
-    g.CinP = (a.Cin + 7) / 8 * 8;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
-    const int n32 = g.CoutP / 32;
-    const int NT = nt > 0 ? nt : pick_nt(g.CoutP);
+    const int CoutP = pad_to(a.Cout, 32);
+    const int n32 = CoutP / 32;
+    const int NT = nt > 0 ? nt : pick_nt(CoutP);
     BABE_CHECK_ARG(NT >= 1 && NT <= 4 && n32 % NT == 0, "conv2d_nt: nt=%d does not divide %d row tiles", NT, n32);
     // positions per block: measured on MI355X (tools/conv_shapes_bench.py) 128-position blocks (WP=1, 3-4 blocks/CU)
     // beat 256-position blocks (2/CU) on every wide layer because partial last rounds are cheaper; the
@@ -428,20 +388,19 @@ extern "C" int babe_conv2d_nt(const babe_conv_args* ap, int nt, void* stream) {
         return BABE_OK;
     }
     // vector staging needs 16-byte aligned rows in every source tensor
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    bool vec = (a.T % 4 == 0) && al16(a.in) && (a.in_bs % 4 == 0) && (a.in_cs % 4 == 0) &&
-               (!a.in2 || (al16(a.in2) && a.in2_bs % 4 == 0 && a.in2_cs % 4 == 0));
+    bool vec = (a.T % 4 == 0) && view_aligned(a.in, a.in_bs, a.in_cs) &&
+               (!a.in2 || view_aligned(a.in2, a.in2_bs, a.in2_cs));
     {
         static const char* ov = getenv("BABE_CONV_VEC");
         if (ov && ov[0] == '0') vec = false;
     }
 #define BABE_CONV_CASE(NTv, WPv)                                          \
     if (a.KW == 3) {                                                      \
-        if (vec) launch_conv<NTv, WPv, 3, true>(a, g, s);                 \
-        else launch_conv<NTv, WPv, 3, false>(a, g, s);                    \
+        if (vec) launch_conv<NTv, WPv, 3, true>(a, s);                 \
+        else launch_conv<NTv, WPv, 3, false>(a, s);                    \
     } else {                                                              \
-        if (vec) launch_conv<NTv, WPv, 1, true>(a, g, s);                 \
-        else launch_conv<NTv, WPv, 1, false>(a, g, s);                    \
+        if (vec) launch_conv<NTv, WPv, 1, true>(a, s);                 \
+        else launch_conv<NTv, WPv, 1, false>(a, s);                    \
     }
     if (wp2) {
         switch (NT) {

@@ -48,10 +48,6 @@ __device__ __forceinline__ void c11_dma16(c11_i32x4 rs, const float* lds_dst, un
 #endif
 }
 
-struct C11Geom {
-    int CinP, CoutP, pt_log2, pr_log2, tiles_t;
-};
-
 // Epilogue through buffer descriptors: out = alpha*acc*oscale[b,co] + rbeta*res.  One per-lane byte offset per position
 // (out of range when the position is padding) + one scalar term per output channel; a channel beyond Cout lands beyond the
 // descriptor's size, so the hardware range check drops it - no per-element branches, no 64-bit address arithmetic, and
@@ -143,7 +139,7 @@ __device__ __forceinline__ void conv11p_epilogue(const babe_conv_args& a, f32x16
 // 3 per CU: finer tail quantisation for the launches with only a few hundred workgroups)
 // (the body of both kernels below: conv11p_kernel, and conv11p_fb_kernel with the frequency bias in its epilogue)
 template <int NT, int NPW, bool HAS_ISC, bool HAS_FB>
-__device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const C11Geom& g) {
+__device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const ConvTileGeom& g) {
 #if __HIP_DEVICE_COMPILE__
     constexpr int KC = 16;
     constexpr int BN = NT * 32;
@@ -309,28 +305,24 @@ __device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const C11G
 }
 
 template <int NT, int NPW, bool HAS_ISC>
-__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_kernel(babe_conv_args a, C11Geom g) {
+__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_kernel(babe_conv_args a, ConvTileGeom g) {
     conv11p_body<NT, NPW, HAS_ISC, false>(a, g);
 }
 
 // out = alpha * oscale * (acc + fbias[co][f]) + rbeta * res (babe_conv_args::fbias); forward convs only, so no in_scale form
 template <int NT, int NPW>
-__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_fb_kernel(babe_conv_args a, C11Geom g) {
+__global__ __launch_bounds__(256, NPW == 2 ? 2 : 3) void conv11p_fb_kernel(babe_conv_args a, ConvTileGeom g) {
     conv11p_body<NT, NPW, false, true>(a, g);
 }
 
 template <int NT, int NPW>
-void launch11(const babe_conv_args& a, C11Geom g, hipStream_t s) {
+void launch11(const babe_conv_args& a, hipStream_t s) {
     constexpr int LOGP = NPW == 2 ? 8 : 7;
-    g.pt_log2 = 0;
-    while ((1 << g.pt_log2) < a.T && g.pt_log2 < LOGP) ++g.pt_log2;
-    if (g.pt_log2 < 2) g.pt_log2 = 2;
-    g.pr_log2 = LOGP - g.pt_log2;
-    g.tiles_t = cdiv(a.T, 1 << g.pt_log2);
-    const int tiles_f = cdiv(a.F, 1 << g.pr_log2);
+    int tiles_f;
+    const ConvTileGeom g = conv_tile_geom(a, LOGP, 2, &tiles_f);
     constexpr int BN = NT * 32;
     constexpr int WJ = (16 * BN / 4 + 255) / 256;
-    const size_t lds = 3 * (size_t)(16 * 128 * NPW + WJ * 256 * 4) * 4 + (a.in_scale ? (size_t)((g.CinP + 15) / 16 * 16) * 4 : 0);
+    const size_t lds = 3 * (size_t)(16 * 128 * NPW + WJ * 256 * 4) * 4 + (a.in_scale ? (size_t)(pad_to(g.CinP, 16)) * 4 : 0);
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     static std::atomic<unsigned long long> attr_done{0};
     if (babe_lds_optin(attr_done, {reinterpret_cast<const void*>(&conv11p_kernel<NT, NPW, true>),
@@ -349,32 +341,27 @@ void launch11(const babe_conv_args& a, C11Geom g, hipStream_t s) {
 int babe_conv11p_supported(const babe_conv_args& a, int nt) {
     static const char* ov = getenv("BABE_CONV11P");
     if (ov && ov[0] == '0') return 0;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.KH != 1 || a.KW != 1 || a.T % 4 != 0 || nt < 1 || nt > 4) return 0;
-    if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4) return 0;
-    if (a.in2 && (!al16(a.in2) || a.in2_bs % 4 || a.in2_cs % 4 || a.cin_split % 16)) return 0;
-    if (!al16(a.w_packed)) return 0;
-    const long lim = 0x7fffffffL / 4;
+    if (!view_aligned(a.in, a.in_bs, a.in_cs)) return 0;
+    if (a.in2 && (!view_aligned(a.in2, a.in2_bs, a.in2_cs) || a.cin_split % 16)) return 0;
+    if (!view_aligned(a.w_packed, 0, 0)) return 0;
     const int split = a.in2 ? a.cin_split : a.Cin;
-    if ((long)split * a.in_cs >= lim || (a.in2 && (long)(a.Cin - split) * a.in2_cs >= lim)) return 0;
-    if ((long)((a.Cin + 7) / 8 * 8) * ((a.Cout + 31) / 32 * 32) >= lim) return 0;
+    if (!fits_i32((long)split * a.in_cs) || (a.in2 && !fits_i32((long)(a.Cin - split) * a.in2_cs))) return 0;
+    if (!fits_i32((long)pad_to(a.Cin, 8) * pad_to(a.Cout, 32))) return 0;
     // the epilogue addresses out / res of a batch item through buffer descriptors with 32-bit offsets
-    const long coP = (a.Cout + 31) / 32 * 32;
-    if (coP * a.out_cs >= lim || (a.res && coP * a.res_cs >= lim)) return 0;
+    const long coP = pad_to(a.Cout, 32);
+    if (!fits_i32(coP * a.out_cs) || (a.res && !fits_i32(coP * a.res_cs))) return 0;
     if (a.in_scale && a.Cin > 2032) return 0;                 // the LDS copy of the scales
-    if (a.fbias && (a.in_scale || (long)a.Cout * a.F >= lim)) return 0;      // the bias variant has no in_scale form; 32-bit table offsets
+    if (a.fbias && (a.in_scale || !fits_i32((long)a.Cout * a.F))) return 0;      // the bias variant has no in_scale form; 32-bit table offsets
     if ((long)a.F * a.T < 4096 && a.Cin < 256) return 0;     // tiny planes AND a short K loop: nothing to pipeline (the
                                                              // dense DFT stages, K ~ 2000 over a few hundred positions, qualify)
     return 1;
 }
 
 int babe_conv11p_launch(const babe_conv_args& a, int nt, hipStream_t s) {
-    C11Geom g;
-    g.CinP = (a.Cin + 7) / 8 * 8;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
     // Tile choice by tail quantisation: a launch costs about rounds x (resident workgroups per CU x positions per
     // workgroup); 128-position tiles run 3 per CU, 256-position tiles 2 per CU (measured: tools/conv_shapes_bench.py)
-    const long cot = g.CoutP / (nt * 32);
+    const long cot = pad_to(a.Cout, 32) / (nt * 32);
     const long b128 = (((long)a.F * a.T + 127) / 128) * cot * a.B, b256 = (((long)a.F * a.T + 255) / 256) * cot * a.B;
     const long cost1 = ((b128 + 767) / 768) * 3, cost2 = ((b256 + 511) / 512) * 4;
     // Round 5: on the two-lane job the 128-position tiles win everywhere (2.441 / 2.440 vs 2.434 / 2.430 audio-sec/s with this cost
@@ -383,14 +370,14 @@ int babe_conv11p_launch(const babe_conv_args& a, int nt, hipStream_t s) {
     static const char* ov = getenv("BABE_CONV11P_NPW");
     const bool big = ov ? (ov[0] == '2' || (ov[0] == 'a' && cost2 < cost1)) : false;
     switch (nt * 2 + (big ? 1 : 0)) {
-        case 9: launch11<4, 2>(a, g, s); break;
-        case 8: launch11<4, 1>(a, g, s); break;
-        case 7: launch11<3, 2>(a, g, s); break;
-        case 6: launch11<3, 1>(a, g, s); break;
-        case 5: launch11<2, 2>(a, g, s); break;
-        case 4: launch11<2, 1>(a, g, s); break;
-        case 3: launch11<1, 2>(a, g, s); break;
-        default: launch11<1, 1>(a, g, s); break;
+        case 9: launch11<4, 2>(a, s); break;
+        case 8: launch11<4, 1>(a, s); break;
+        case 7: launch11<3, 2>(a, s); break;
+        case 6: launch11<3, 1>(a, s); break;
+        case 5: launch11<2, 2>(a, s); break;
+        case 4: launch11<2, 1>(a, s); break;
+        case 3: launch11<1, 2>(a, s); break;
+        default: launch11<1, 1>(a, s); break;
     }
     return 0;
 }

@@ -10,71 +10,13 @@
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
+#include "conv_common.h"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-__device__ __forceinline__ float sel_scale(bool has, float loaded) { return has ? loaded : 1.f; }
-
-// Epilogue shared by all conv kernels: out = alpha*acc*oscale[b,co] + rbeta*res.  The 16 loads of a 32x32 tile are
-// issued back-to-back inside ONE wave-uniform branch per operand: a per-element "if (ptr) load" makes hipcc branch
-// around every load and wait vmcnt(0) each time (measured: the epilogue then serialises 128 load latencies).
-template <int NT, int WP, bool HAS_OS, bool HAS_RES>
-__device__ __forceinline__ void conv_epilogue_impl(const babe_conv_args& a, f32x16 (&acc)[NT][WP], int b, int co0,
-                                                   int f0, int t0, int pt_log2, int wave, int l31, int h) {
-    const int PT = 1 << pt_log2;
-#pragma unroll
-    for (int wp = 0; wp < WP; ++wp) {
-        const int p = (wave * WP + wp) * 32 + l31;
-        const int f = f0 + (p >> pt_log2);
-        const int t = t0 + (p & (PT - 1));
-        const bool pv = f < a.F && t < a.T;
-        const long sp = pv ? (long)f * a.T + t : 0;
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            float os[16], rr[16];
-            int cc[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                cc[r] = co < a.Cout ? co : a.Cout - 1;
-            }
-            if constexpr (HAS_OS) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) os[r] = a.oscale[b * a.Cout + cc[r]];
-            }
-            if constexpr (HAS_RES) {
-#pragma unroll
-                for (int r = 0; r < 16; ++r) rr[r] = a.res[(long)b * a.res_bs + (long)cc[r] * a.res_cs + sp];
-            }
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int co = co0 + nt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                float v = acc[nt][wp][r] * a.alpha;
-                if constexpr (HAS_OS) v *= os[r];
-                if constexpr (HAS_RES) v += a.rbeta * rr[r];
-                if (pv && co < a.Cout) a.out[(long)b * a.out_bs + (long)co * a.out_cs + sp] = v;
-            }
-        }
-    }
-}
-
-template <int NT, int WP>
-__device__ __forceinline__ void conv_epilogue(const babe_conv_args& a, f32x16 (&acc)[NT][WP], int b, int co0, int f0,
-                                              int t0, int pt_log2, int wave, int l31, int h) {
-    // four straight-line specialisations behind wave-uniform branches
-    if (a.oscale) {
-        if (a.res) conv_epilogue_impl<NT, WP, true, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
-        else conv_epilogue_impl<NT, WP, true, false>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
-    } else {
-        if (a.res) conv_epilogue_impl<NT, WP, false, true>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
-        else conv_epilogue_impl<NT, WP, false, false>(a, acc, b, co0, f0, t0, pt_log2, wave, l31, h);
-    }
-}
 
 struct ConvGeomB {
     int GP, CoutP, pt_log2, pr_log2, tiles_t;
@@ -289,12 +231,7 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, unsigned s
     const int kw = (int)(r % KW);
     const int kh = (int)(r / KW);
     const int ci = gq * 8 + j;
-    float v = 0.f;
-    if (!tf) {
-        if (co < Cout && ci < Cin) v = w[(((long)co * Cin + ci) * KH + kh) * KW + kw];
-    } else {
-        if (co < Cin && ci < Cout) v = w[(((long)ci * Cin + co) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)];
-    }
+    const float v = conv_w_tap(w, Cout, Cin, KH, KW, tf, co, ci, kh, kw);
     const __bf16 hi = (__bf16)v;
     dst[i] = __builtin_bit_cast(unsigned short, hi);
     if (splits == 2) {
@@ -303,34 +240,13 @@ __global__ void pack_weights_bf16_kernel(const float* __restrict__ w, unsigned s
     }
 }
 
-inline int ilog2_floor(int v) {
-    int l = 0;
-    while ((1 << (l + 1)) <= v) ++l;
-    return l;
-}
-inline int ilog2_ceil(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-inline int pick_nt(int CoutP) {
-    const int n32 = CoutP / 32;
-    for (int c = 4; c >= 1; --c)
-        if (n32 % c == 0) return c;
-    return 1;
-}
-
 template <int NT, int WP, int KW, int SX>
 void launch(const babe_conv_args& a, ConvGeomB g, const unsigned short* wq, hipStream_t s) {
     constexpr int NPOS = 128 * WP;
-    const int npos_log2 = ilog2_floor(NPOS);
-    g.pt_log2 = ilog2_ceil(a.T);
-    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = npos_log2 - g.pt_log2;
+    int tiles_f;
+    const ConvTileGeom t = conv_tile_geom(a, ilog2_floor(NPOS), 4, &tiles_f);
+    g.pt_log2 = t.pt_log2; g.pr_log2 = t.pr_log2; g.tiles_t = t.tiles_t;
     const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    const int tiles_f = cdiv(a.F, PR);
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / (NT * 32), a.B);
     const size_t units = (size_t)SX * 2 * PR * (PT + 2) + (size_t)SX * KW * 2 * NT * 32;
     hipLaunchKernelGGL((conv_bf16_kernel<NT, WP, KW, SX>), grid, dim3(256), 2 * units * 16, s, a, g, wq);
@@ -342,17 +258,15 @@ int babe_conv2d_bf16p_supported(const babe_conv_args& a);       // conv_bf16p.hi
 int babe_conv2d_bf16p_launch(const babe_conv_args& a, const unsigned short* wq, hipStream_t s);
 
 extern "C" long babe_conv_packed_size_bf16(int Cout, int Cin, int KH, int KW, int transpose_flip, int splits) {
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    return (long)splits * KH * KW * ((ci + 15) / 16 * 16) * ((co + 31) / 32 * 32);      // in bf16 elements
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    return (long)splits * KH * KW * pad_to(io.ci, 16) * pad_to(io.co, 32);      // in bf16 elements
 }
 
 extern "C" int babe_conv_pack_weights_bf16(const float* w, void* dst, int Cout, int Cin, int KH, int KW,
                                            int transpose_flip, int splits, void* stream) {
     BABE_CHECK_ARG(w && dst && Cout > 0 && Cin > 0 && (splits == 1 || splits == 2), "conv_pack_weights_bf16: bad arguments");
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    const int GP = (ci + 15) / 16 * 2, CoutP = (co + 31) / 32 * 32;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    const int GP = pad_to(io.ci, 16) / 8, CoutP = pad_to(io.co, 32);
     const long per_split = (long)KH * KW * GP * 8 * CoutP;
     hipLaunchKernelGGL(pack_weights_bf16_kernel, dim3(cdiv(per_split, 256)), dim3(256), 0, (hipStream_t)stream, w,
                        (unsigned short*)dst, Cout, Cin, KH, KW, transpose_flip, GP, CoutP, per_split, splits);
@@ -371,8 +285,8 @@ extern "C" int babe_conv2d_bf16(const babe_conv_args* ap, const void* w_bf16, in
     BABE_CHECK_ARG(splits == 1 || splits == 2, "conv2d_bf16: splits must be 1 (bf16) or 2 (bf16x3)");
     BABE_CHECK_ARG(!a.in2 || (a.cin_split > 0 && a.cin_split < a.Cin), "conv2d_bf16: bad cin_split");
     ConvGeomB g;
-    g.GP = (a.Cin + 15) / 16 * 2;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
+    g.GP = pad_to(a.Cin, 16) / 8;
+    g.CoutP = pad_to(a.Cout, 32);
     g.split_stride = (long)a.KH * a.KW * g.GP * 8 * g.CoutP;
     const int NT = pick_nt(g.CoutP);
     const long npos = (long)a.F * a.T;

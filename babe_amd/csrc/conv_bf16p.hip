@@ -409,22 +409,11 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
 #endif
 }
 
-inline int ilog2_ceil_b(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 template <int G, int KW, bool UNITS = false>
 void launch_bf16p(const babe_conv_args& a, Bf16pGeom g, const unsigned short* wq, hipStream_t s) {
     constexpr int BN = 32 * G, NTH = 128 * G;
-    g.pt_log2 = ilog2_ceil_b(a.T);
-    if (g.pt_log2 > 9) g.pt_log2 = 9;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = 9 - g.pt_log2;
-    const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    g.tiles_f = cdiv(a.F, PR);
+    const ConvTileGeom t = conv_tile_geom(a, 9, 4, &g.tiles_f);       // 512 positions per workgroup
+    g.pt_log2 = t.pt_log2; g.pr_log2 = t.pr_log2; g.tiles_t = t.tiles_t;
     g.ncb = cdiv(g.CoutP, BN);
     g.total = g.tiles_t * g.tiles_f * g.ncb * a.B;
     dim3 grid(8 * ((g.total + 7) / 8));
@@ -446,23 +435,22 @@ int babe_conv2d_bf16p_supported(const babe_conv_args& a) {
     if (ov && ov[0] == '0') return 0;
     if (!((a.KW == 3) || (a.KW == 1 && a.KH == 1)) || (a.T & 3) || (a.Cin & 7) || a.Cout <= 32) return 0;
     if (a.in2 && (a.cin_split % 32 != 0)) return 0;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (!al16(a.out) || (a.out_bs & 3) || (a.out_cs & 3)) return 0;                   // 16-byte epilogue vectors
-    if (a.res && (!al16(a.res) || (a.res_bs & 3) || (a.res_cs & 3))) return 0;
-    const long lim = 0x7fffffffL / 4;
+    if (!view_aligned(a.out, a.out_bs, a.out_cs)) return 0;                           // 16-byte epilogue vectors
+    if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs)) return 0;
     // (the epilogue addresses out / res of a batch item through buffer descriptors with 32-bit byte offsets)
-    if ((long)((a.Cout + 31) / 32 * 32) * a.out_cs >= lim || (a.res && (long)((a.Cout + 31) / 32 * 32) * a.res_cs >= lim)) return 0;
+    const long coP = pad_to(a.Cout, 32);
+    if (!fits_i32(coP * a.out_cs) || (a.res && !fits_i32(coP * a.res_cs))) return 0;
     const int split = a.in2 ? a.cin_split : a.Cin;
-    if ((long)split * a.in_cs >= lim) return 0;
-    if (a.in2 && (long)(a.Cin - split) * a.in2_cs >= lim) return 0;
-    if ((long)a.KH * a.KW * ((a.Cin + 15) / 16 * 2) * ((a.Cout + 31) / 32 * 32) * 16 >= 0x7fffffffL) return 0;
+    if (!fits_i32((long)split * a.in_cs)) return 0;
+    if (a.in2 && !fits_i32((long)(a.Cin - split) * a.in2_cs)) return 0;
+    if (!fits_i32((long)a.KH * a.KW * (pad_to(a.Cin, 16) / 8) * coP * 16, LIM_BYTES_2G)) return 0;
     return 1;
 }
 
 int babe_conv2d_bf16p_launch(const babe_conv_args& a, const unsigned short* wq, hipStream_t s) {
     Bf16pGeom g;
-    g.GP = (a.Cin + 15) / 16 * 2;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
+    g.GP = pad_to(a.Cin, 16) / 8;
+    g.CoutP = pad_to(a.Cout, 32);
     if (a.KW == 3) {
         if (g.CoutP == 64) launch_bf16p<2, 3>(a, g, wq, s);      //  64 co x 512 positions, 4 waves, two workgroups per CU
         else launch_bf16p<4, 3>(a, g, wq, s);                    // 128 co x 512 positions, 8 waves
@@ -482,11 +470,10 @@ extern "C" int babe_conv2d_bf16_units_supported(const babe_conv_args* ap) {
     if (ov && ov[0] == '0') return 0;
     if (a.KH != 5 || a.KW != 3 || (a.T & 3) || (a.Cin & 7) || a.Cout <= 32 || a.in2 || a.in_scale) return 0;
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (!al16(a.in) || !al16(a.out) || (a.out_bs & 3) || (a.out_cs & 3)) return 0;
-    if (a.res && (!al16(a.res) || (a.res_bs & 3) || (a.res_cs & 3))) return 0;
-    if ((long)(a.Cin >> 3) * a.in_cs * 16 >= 0x7fffffffL) return 0;
-    if ((long)a.KH * 3 * ((a.Cin + 15) / 16 * 2) * ((a.Cout + 31) / 32 * 32) * 16 >= 0x7fffffffL) return 0;
+    if (!view_aligned(a.in, 0, 0) || !view_aligned(a.out, a.out_bs, a.out_cs)) return 0;
+    if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs)) return 0;
+    if (!fits_i32((long)(a.Cin >> 3) * a.in_cs * 16, LIM_BYTES_2G)) return 0;
+    if (!fits_i32((long)a.KH * 3 * (pad_to(a.Cin, 16) / 8) * pad_to(a.Cout, 32) * 16, LIM_BYTES_2G)) return 0;
     return 1;
 }
 
@@ -496,8 +483,8 @@ extern "C" int babe_conv2d_bf16_units(const babe_conv_args* ap, const void* w_bf
     const babe_conv_args& a = *ap;
     BABE_CHECK_ARG(a.in_cs == (long)a.F * 4 * (a.T / 4 + 1), "conv2d_bf16_units: in_cs %ld is not F*4*(T/4+1)", a.in_cs);
     Bf16pGeom g;
-    g.GP = (a.Cin + 15) / 16 * 2;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
+    g.GP = pad_to(a.Cin, 16) / 8;
+    g.CoutP = pad_to(a.Cout, 32);
     const double flops = babe_conv_flops(a);
     BabeProfScope prof(BABE_SLOT_CONV_BF16P, babe_conv_bytes(a) - 2.0 * a.B * a.Cin * (double)a.F * a.T, flops, flops, stream);
     if (g.CoutP == 64) launch_bf16p<2, 3, true>(a, g, (const unsigned short*)w_bf16, (hipStream_t)stream);

@@ -1,4 +1,8 @@
-// Pieces shared by the direct conv kernels (conv.hip, conv11p.hip): the fused epilogue and the A-operand fragment read.
+// Pieces shared by the nine conv translation units (conv*.hip).
+//   device: the fused epilogue and sel_scale (conv.hip, conv_bf16.hip; conv11p.hip for the weights' layout), the A-operand fragment
+//           read, and conv_w_tap, the one statement of how a packed image reads the reference weight (every pack_* kernel);
+//   host:   what the launchers, the *_supported rules and the packed_size / pack_weights entry points have in common: padding,
+//           the (co, ci) of the executed op, view alignment, the 32-bit offset limits and the time x frequency split of a tile.
 #pragma once
 #include "common.h"
 #include "../../include/babe_hip.h"
@@ -7,6 +11,17 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
+
+__device__ __forceinline__ float sel_scale(bool has, float loaded) { return has ? loaded : 1.f; }
+
+// Tap (kh, kw) between channels (co, ci) of the op a packed image EXECUTES, read from the reference weight w [Cout][Cin][KH][KW]:
+// tf 0 the conv itself; tf 1 its input-VJP, the transposed conv: packed Cout = reference Cin, packed Cin = reference Cout, taps
+// flipped on both axes.  0 for the padded channels of the image.
+__device__ __forceinline__ float conv_w_tap(const float* __restrict__ w, int Cout, int Cin, int KH, int KW, int tf, int co, int ci,
+                                            int kh, int kw) {
+    if (!tf) return (co < Cout && ci < Cin) ? w[(((long)co * Cin + ci) * KH + kh) * KW + kw] : 0.f;
+    return (co < Cin && ci < Cout) ? w[(((long)ci * Cin + co) * KH + (KH - 1 - kh)) * KW + (KW - 1 - kw)] : 0.f;
+}
 
 // Epilogue shared by all conv kernels: out = alpha*acc*oscale[b,co] + rbeta*res; HAS_FB (the (1,1) kernels): acc + fbias[co][f] in
 // place of acc.  The 16 loads of a 32x32 tile are
@@ -102,5 +117,67 @@ template <> struct AVec<4> {
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     }
 };
+
+// ---- host scaffolding
+
+inline int pad_to(int x, int m) { return (x + m - 1) / m * m; }
+
+inline int ilog2_floor(int v) {
+    int l = 0;
+    while ((1 << (l + 1)) <= v) ++l;
+    return l;
+}
+inline int ilog2_ceil(int v) {
+    int l = 0;
+    while ((1 << l) < v) ++l;
+    return l;
+}
+
+// 32-row output-channel tiles per workgroup of the direct kernels: the largest of 4..1 that divides the tile count
+inline int pick_nt(int CoutP) {
+    const int n32 = CoutP / 32;
+    for (int c = 4; c >= 1; --c)
+        if (n32 % c == 0) return c;
+    return 1;
+}
+
+// (output, input) channels of the op a packed image executes (conv_w_tap): swapped under transpose_flip
+struct ConvIO {
+    int co, ci;
+};
+inline ConvIO conv_exec_io(int Cout, int Cin, int transpose_flip) {
+    return transpose_flip ? ConvIO{Cin, Cout} : ConvIO{Cout, Cin};
+}
+
+// a [B][C][F][T] float view whose rows may be read / written as `bytes`-wide vectors (16: float4, 8: float2)
+inline bool view_aligned(const void* p, long bs, long cs, int bytes = 16) {
+    return ((uintptr_t)p & (uintptr_t)(bytes - 1)) == 0 && bs % (bytes / 4) == 0 && cs % (bytes / 4) == 0;
+}
+
+// Limits of what one buffer descriptor (or a kernel's own 32-bit offset arithmetic) may span: floats below 2 GiB, floats below
+// 1 GiB (the nested Winograd kernels, whose out-of-range marker is bit 30), bytes below 2 GiB.
+constexpr long LIM_F32_2G = 0x7fffffffL / 4, LIM_F32_1G = 0x3fffffffL / 4, LIM_BYTES_2G = 0x7fffffffL;
+inline bool fits_i32(long n, long lim = LIM_F32_2G) { return n < lim; }
+
+// Geometry argument of the kernels that tile (frequency rows x time) into power-of-two tiles.  Kernels with more fields keep a
+// struct of their own (ConvGeomB, Bf16pGeom, Wino45Geom, Wino85Geom).
+struct ConvTileGeom {
+    int CinP, CoutP, pt_log2, pr_log2, tiles_t;
+};
+
+// A tile of 2^npos_log2 positions as 2^pr_log2 rows x 2^pt_log2 time steps: the power of two that covers T, at most the whole
+// tile and at least 2^min_pt_log2.  CinP / CoutP are the 8 / 32 padding of the packed images; *tiles_f = row tiles.
+inline ConvTileGeom conv_tile_geom(const babe_conv_args& a, int npos_log2, int min_pt_log2, int* tiles_f) {
+    ConvTileGeom g;
+    g.CinP = pad_to(a.Cin, 8);
+    g.CoutP = pad_to(a.Cout, 32);
+    g.pt_log2 = ilog2_ceil(a.T);
+    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
+    if (g.pt_log2 < min_pt_log2) g.pt_log2 = min_pt_log2;
+    g.pr_log2 = npos_log2 - g.pt_log2;
+    g.tiles_t = cdiv(a.T, 1 << g.pt_log2);
+    *tiles_f = cdiv(a.F, 1 << g.pr_log2);
+    return g;
+}
 
 }  // namespace

@@ -16,21 +16,16 @@
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
+#include "conv_common.h"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-struct WinoGeom {
-    int CinP, CoutP, pt_log2, pr_log2, tiles_t;
-};
-
 // ABL: compile-time ablation bits for profiling builds (1 no global loads, 2 no LDS stores, 4 no barrier, 8 no MFMA)
 template <int NTW, int WR, int WC, int ABL = 0>
-__global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_args a, WinoGeom g,
+__global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_args a, ConvTileGeom g,
                                                                  const float* __restrict__ wq) {
     constexpr int NTH = 64 * WR * WC;
     constexpr int KC = 8;
@@ -253,7 +248,7 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_ar
 // the block, and the output transform exchanges half of the partial sums through LDS once at the end.  LDS images
 // XQ[pair][8][units][2], WQ[pair][8][BN][2]: one 8-byte read per operand and K-step, 16-byte staging stores.
 template <int NTW, int WC>
-__global__ __launch_bounds__(128 * WC, (NTW <= 3 ? 3 : 2)) void conv_wino_pp_kernel(babe_conv_args a, WinoGeom g,
+__global__ __launch_bounds__(128 * WC, (NTW <= 3 ? 3 : 2)) void conv_wino_pp_kernel(babe_conv_args a, ConvTileGeom g,
                                                                 const float* __restrict__ wq) {
     constexpr int NTH = 128 * WC;
     constexpr int KC = 8;
@@ -506,18 +501,8 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     long r = i / CoutP;
     const int ci = (int)(r % CinP);
     const int kh = (int)(r / CinP);
-    float w0 = 0.f, w1 = 0.f, w2 = 0.f;
-    if (!tf) {
-        if (co < Cout && ci < Cin) {
-            const float* p = w + (((long)co * Cin + ci) * KH + kh) * 3;
-            w0 = p[0]; w1 = p[1]; w2 = p[2];
-        }
-    } else {
-        if (co < Cin && ci < Cout) {      // packed "Cout" = reference Cin; taps flipped in both axes
-            const float* p = w + (((long)ci * Cin + co) * KH + (KH - 1 - kh)) * 3;
-            w0 = p[2]; w1 = p[1]; w2 = p[0];
-        }
-    }
+    const float w0 = conv_w_tap(w, Cout, Cin, KH, 3, tf, co, ci, kh, 0), w1 = conv_w_tap(w, Cout, Cin, KH, 3, tf, co, ci, kh, 1),
+                w2 = conv_w_tap(w, Cout, Cin, KH, 3, tf, co, ci, kh, 2);
     f32x4 v = {w0, 0.5f * (w0 + w1 + w2), 0.5f * (w0 - w1 + w2), w2};
     if (pp) {
         f32x2* d2 = reinterpret_cast<f32x2*>(dst) + ((long)(kh * CinP + ci) * 2) * CoutP + co;
@@ -528,28 +513,11 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     }
 }
 
-inline int ilog2_floor(int v) {
-    int l = 0;
-    while ((1 << (l + 1)) <= v) ++l;
-    return l;
-}
-inline int ilog2_ceil(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 template <int NTW, int WR, int WC, int ABL = 0>
-void launch(const babe_conv_args& a, WinoGeom g, const float* wq, hipStream_t s) {
+void launch(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int NPOS = 64 * WC;
-    const int npos_log2 = ilog2_floor(NPOS);
-    g.pt_log2 = ilog2_ceil(a.T);
-    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = npos_log2 - g.pt_log2;
-    const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    const int tiles_f = cdiv(a.F, PR);
+    int tiles_f;
+    const ConvTileGeom g = conv_tile_geom(a, ilog2_floor(NPOS), 4, &tiles_f);
     constexpr int BN = WR * NTW * 32;
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     const size_t lds = 2 * (size_t)(8 * (WC * 32) + 8 * BN) * 16;
@@ -557,16 +525,10 @@ void launch(const babe_conv_args& a, WinoGeom g, const float* wq, hipStream_t s)
 }
 
 template <int NTW, int WC>
-void launch_pp(const babe_conv_args& a, WinoGeom g, const float* wq, hipStream_t s) {
+void launch_pp(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int NPOS = 64 * WC;
-    const int npos_log2 = ilog2_floor(NPOS);
-    g.pt_log2 = ilog2_ceil(a.T);
-    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = npos_log2 - g.pt_log2;
-    const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    const int tiles_f = cdiv(a.F, PR);
+    int tiles_f;
+    const ConvTileGeom g = conv_tile_geom(a, ilog2_floor(NPOS), 4, &tiles_f);
     constexpr int BN = NTW * 32;
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     size_t lds = 2 * (size_t)(4 * 8 * (WC * 32 + BN)) * 4;
@@ -579,17 +541,15 @@ void launch_pp(const babe_conv_args& a, WinoGeom g, const float* wq, hipStream_t
 
 
 extern "C" long babe_conv_packed_size_wino(int Cout, int Cin, int KH, int transpose_flip) {
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    return (long)KH * ((ci + 7) / 8 * 8) * ((co + 31) / 32 * 32) * 4;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    return (long)KH * pad_to(io.ci, 8) * pad_to(io.co, 32) * 4;
 }
 
 extern "C" int babe_conv_pack_weights_wino(const float* w, float* dst, int Cout, int Cin, int KH, int KW,
                                            int transpose_flip, void* stream) {
     BABE_CHECK_ARG(w && dst && Cout > 0 && Cin > 0 && KH > 0 && KW == 3, "conv_pack_weights_wino: needs KW == 3");
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    const int CinP = (ci + 7) / 8 * 8, CoutP = (co + 31) / 32 * 32;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    const int CinP = pad_to(io.ci, 8), CoutP = pad_to(io.co, 32);
     const long total = (long)KH * CinP * CoutP;
     hipLaunchKernelGGL(pack_wino_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, Cin,
                        KH, transpose_flip, CinP, CoutP, total, wino_use_pp(CoutP / 32) ? 1 : 0);
@@ -601,15 +561,13 @@ extern "C" int babe_conv_pack_weights_wino(const float* w, float* dst, int Cout,
 extern "C" int babe_conv2d_wino_supported(const babe_conv_args* ap) {
     if (!ap) return 0;
     const babe_conv_args& a = *ap;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    auto al8 = [](const void* p) { return ((uintptr_t)p & 7) == 0; };
     if (a.KW != 3 || a.KH < 1 || a.T % 4 != 0 || a.T < 16) return 0;
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
-    if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4) return 0;
-    if (a.in2 && (!al16(a.in2) || a.in2_bs % 4 || a.in2_cs % 4)) return 0;
-    if (!al8(a.out) || a.out_bs % 2 || a.out_cs % 2) return 0;
-    if (a.res && (!al8(a.res) || a.res_bs % 2 || a.res_cs % 2)) return 0;
-    const int n32 = (a.Cout + 31) / 32;
+    if (!view_aligned(a.in, a.in_bs, a.in_cs)) return 0;
+    if (a.in2 && !view_aligned(a.in2, a.in2_bs, a.in2_cs)) return 0;
+    if (!view_aligned(a.out, a.out_bs, a.out_cs, 8)) return 0;          // (the epilogue stores pairs: 8 bytes are enough)
+    if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs, 8)) return 0;
+    const int n32 = pad_to(a.Cout, 32) / 32;
     return (n32 == 1 || n32 == 3 || n32 % 2 == 0) ? 1 : 0;
 }
 
@@ -617,17 +575,14 @@ extern "C" int babe_conv2d_wino(const babe_conv_args* ap, const float* w_wino, v
     BABE_CHECK_ARG(ap && w_wino, "conv2d_wino: null args");
     BABE_CHECK_ARG(babe_conv2d_wino_supported(ap), "conv2d_wino: unsupported problem (use babe_conv2d)");
     const babe_conv_args& a = *ap;
-    WinoGeom g;
-    g.CinP = (a.Cin + 7) / 8 * 8;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
-    const int n32 = g.CoutP / 32;
+    const int n32 = pad_to(a.Cout, 32) / 32;
     hipStream_t s = (hipStream_t)stream;
     const double flops = babe_conv_flops(a);     // F(2,3): 4 multiplies per 2 outputs instead of 6
     BabeProfScope prof(BABE_SLOT_CONV53_WINO2, babe_conv_bytes(a), flops, flops * (2.0 / 3.0), stream);
-    if (n32 == 1) launch<1, 1, 4>(a, g, w_wino, s);            //  32 co x 256 positions
-    else if (wino_use_pp(n32)) launch_pp<3, 2>(a, g, w_wino, s);   //  96 co x 128 positions, phase-pair split
-    else if (n32 == 2) launch<2, 1, 4>(a, g, w_wino, s);       //  64 co x 256 positions
-    else launch<2, 2, 2>(a, g, w_wino, s);                     // 128 co x 128 positions
+    if (n32 == 1) launch<1, 1, 4>(a, w_wino, s);            //  32 co x 256 positions
+    else if (wino_use_pp(n32)) launch_pp<3, 2>(a, w_wino, s);   //  96 co x 128 positions, phase-pair split
+    else if (n32 == 2) launch<2, 1, 4>(a, w_wino, s);       //  64 co x 256 positions
+    else launch<2, 2, 2>(a, w_wino, s);                     // 128 co x 128 positions
     BABE_LAUNCH_CHECK();
     return BABE_OK;
 }

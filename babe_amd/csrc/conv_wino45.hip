@@ -28,10 +28,10 @@
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
+#include "conv_common.h"
 #include <cstdlib>
 #include <type_traits>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ABL: compile-time ablation bits for profiling builds (tools/ab/abl_build.sh conv_wino45 <mask>): 1 no activation loads,
 // 2 no MFMA, 4 no operand LDS reads, 8 no input transform / LDS stores, 16 no barrier, 32 no weight DMA, 64 every slab
@@ -1046,20 +1046,7 @@ __global__ void pack_wino45_kernel(const float* __restrict__ w, float* __restric
 #pragma unroll
     for (int kh = 0; kh < 5; ++kh)
 #pragma unroll
-        for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = 0;
-    if (!tf) {
-        if (co < Cout && ci < Cin) {
-            const float* p = w + ((long)co * Cin + ci) * 15;
-            for (int kh = 0; kh < 5; ++kh)
-                for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = p[kh * 3 + kw];
-        }
-    } else {
-        if (co < Cin && ci < Cout) {      // packed "Cout" = reference Cin; taps flipped in both axes
-            const float* p = w + ((long)ci * Cin + co) * 15;
-            for (int kh = 0; kh < 5; ++kh)
-                for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = p[(4 - kh) * 3 + (2 - kw)];
-        }
-    }
+        for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = conv_w_tap(w, Cout, Cin, 5, 3, tf, co, ci, kh, kw);
     const double G5[6][5] = {{0.25, 0, 0, 0, 0},
                              {-1.0 / 6, -1.0 / 6, -1.0 / 6, -1.0 / 6, -1.0 / 6},
                              {-1.0 / 6, 1.0 / 6, -1.0 / 6, 1.0 / 6, -1.0 / 6},
@@ -1085,17 +1072,15 @@ __global__ void pack_wino45_kernel(const float* __restrict__ w, float* __restric
 }  // namespace
 
 extern "C" long babe_conv_packed_size_wino45(int Cout, int Cin, int transpose_flip) {
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    return 36L * ((ci + 7) / 8 * 8) * ((co + 63) / 64 * 64);
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    return 36L * pad_to(io.ci, 8) * pad_to(io.co, 64);
 }
 
 extern "C" int babe_conv_pack_weights_wino45(const float* w, float* dst, int Cout, int Cin, int KH, int KW,
                                              int transpose_flip, void* stream) {
     BABE_CHECK_ARG(w && dst && Cout > 0 && Cin > 0 && KH == 5 && KW == 3, "conv_pack_weights_wino45: needs a (5,3) kernel");
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    const int CinP = (ci + 7) / 8 * 8, CoutP = (co + 63) / 64 * 64;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    const int CinP = pad_to(io.ci, 8), CoutP = pad_to(io.co, 64);
     const long total = 3L * CinP * CoutP;
     hipLaunchKernelGGL(pack_wino45_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, Cin,
                        transpose_flip, CinP, CoutP, total);
@@ -1109,20 +1094,19 @@ extern "C" int babe_conv2d_wino45_supported(const babe_conv_args* ap) {
     static const char* ov = getenv("BABE_CONV_WINO45");
     if (ov && ov[0] == '0') return 0;
     const babe_conv_args& a = *ap;
-    auto al16 = [](const void* p) __attribute__((always_inline)) { return ((uintptr_t)p & 15) == 0; };
     if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;   // (tiles are 64 time steps wide)
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (a.Cin < 16 || a.Cin % 16 != 0 || a.Cout < 33) return 0;   // (the channel part of a load address is a scalar offset,
     // which the buffer range check does not cover: no padded input channels; an even number of 8-channel slabs per pass: the
     // slab loop is unrolled by two; few-channel convs run on conv_fewco / direct)
-    if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4) return 0;
+    if (!view_aligned(a.in, a.in_bs, a.in_cs)) return 0;
     if (a.in2) return 0;                                     // one source only (csrc/conv_wino45.hip, descriptors)
-    if (!al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;
-    if (a.res && (!al16(a.res) || a.res_bs % 4 || a.res_cs % 4)) return 0;
-    const long lim = 0x3fffffffL / 4;                        // source views below 1 GiB per batch item (OOBH arithmetic)
-    if ((long)a.Cin * a.in_cs >= lim) return 0;
-    if ((long)a.F * a.T >= lim) return 0;
-    if (36L * ((a.Cin + 7) / 8 * 8) * ((a.Cout + 63) / 64 * 64) * 4 >= 0x7fffffffL) return 0;
+    if (!view_aligned(a.out, a.out_bs, a.out_cs)) return 0;
+    if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs)) return 0;
+    // source views below 1 GiB per batch item (OOBH arithmetic)
+    if (!fits_i32((long)a.Cin * a.in_cs, LIM_F32_1G)) return 0;
+    if (!fits_i32((long)a.F * a.T, LIM_F32_1G)) return 0;
+    if (!fits_i32(36L * pad_to(a.Cin, 8) * pad_to(a.Cout, 64) * 4, LIM_BYTES_2G)) return 0;
     return 1;
 }
 
@@ -1162,8 +1146,8 @@ extern "C" int babe_conv2d_wino45(const babe_conv_args* ap, const float* w_wino4
     BABE_CHECK_ARG(babe_conv2d_wino45_supported(ap), "conv2d_wino45: unsupported problem (use babe_conv2d_wino4 / babe_conv2d)");
     const babe_conv_args& a = *ap;
     Wino45Geom g;
-    g.CinP = (a.Cin + 7) / 8 * 8;
-    g.CoutP = (a.Cout + 63) / 64 * 64;
+    g.CinP = pad_to(a.Cin, 8);
+    g.CoutP = pad_to(a.Cout, 64);
     g.tsh = wino45_best_tsh(a);
     g.tiles_t = cdiv(a.T, 64 << g.tsh);
     const int n = cdiv(a.F, a.dil);                  // rows per residue class (at most)

@@ -20,17 +20,12 @@
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
+#include "conv_common.h"
 #include <cstdlib>
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-struct Wino4pGeom {
-    int CinP, CoutP, pt_log2, pr_log2, tiles_t;
-};
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 constexpr unsigned OOB = 0x80000000u;      // beyond every descriptor's num_records: the load returns 0, touches nothing
@@ -39,7 +34,7 @@ constexpr unsigned OOB = 0x80000000u;      // beyond every descriptor's num_reco
 // triple instead of a padded float4), and a B operand is three ds_read_b32: 24 KB instead of 32 KB per slab for 128 units,
 // which is what lets the 96-channel tile (96 co x 512 positions) keep three buffers inside 160 KB of LDS.
 template <int NTW, int WR, int WC, bool HAS_ISC, bool XSOA = false>
-__global__ __launch_bounds__(128 * WR * WC, 1) void conv_wino4p_kernel(babe_conv_args a, Wino4pGeom g,
+__global__ __launch_bounds__(128 * WR * WC, 1) void conv_wino4p_kernel(babe_conv_args a, ConvTileGeom g,
                                                                        const float* __restrict__ wq) {
 #if __HIP_DEVICE_COMPILE__      // the buffer-descriptor builtins exist in the device pass only; the host pass needs just the stub
     constexpr int NTH = 128 * WR * WC;
@@ -340,28 +335,11 @@ __global__ __launch_bounds__(128 * WR * WC, 1) void conv_wino4p_kernel(babe_conv
 #endif
 }
 
-inline int ilog2_floor_p(int v) {
-    int l = 0;
-    while ((1 << (l + 1)) <= v) ++l;
-    return l;
-}
-inline int ilog2_ceil_p(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
 template <int NTW, int WR, int WC, bool XSOA = false>
-void launch4p(const babe_conv_args& a, Wino4pGeom g, const float* wq, hipStream_t s) {
+void launch4p(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int NPOS = 128 * WC;
-    const int npos_log2 = ilog2_floor_p(NPOS);
-    g.pt_log2 = ilog2_ceil_p(a.T);
-    if (g.pt_log2 > npos_log2) g.pt_log2 = npos_log2;
-    if (g.pt_log2 < 4) g.pt_log2 = 4;
-    g.pr_log2 = npos_log2 - g.pt_log2;
-    const int PT = 1 << g.pt_log2, PR = 1 << g.pr_log2;
-    g.tiles_t = cdiv(a.T, PT);
-    const int tiles_f = cdiv(a.F, PR);
+    int tiles_f;
+    const ConvTileGeom g = conv_tile_geom(a, ilog2_floor(NPOS), 4, &tiles_f);
     constexpr int BN = WR * NTW * 32;
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     size_t lds = 3 * (size_t)((XSOA ? 2 * 8 * 3 * (WC * 32) / 4 : 2 * 8 * (WC * 32)) + 2 * 8 * BN) * 16;
@@ -384,23 +362,20 @@ void launch4p(const babe_conv_args& a, Wino4pGeom g, const float* wq, hipStream_
 int babe_conv2d_wino4p_supported(const babe_conv_args& a) {
     static const char* ov = getenv("BABE_CONV_WINO4P");
     if (ov && ov[0] == '0') return 0;
-    const int n32 = (a.Cout + 31) / 32;
+    const int n32 = pad_to(a.Cout, 32) / 32;
     if (n32 % 4 != 0 && n32 != 2 && n32 != 3) return 0;   // 8-wave workgroups: 128 co x 256 pos, 64 / 96 co x 512 pos
     if (a.in2 && (a.cin_split % 8 != 0)) return 0;
-    const long lim = 0x7fffffffL / 4;
     const int split = a.in2 ? a.cin_split : a.Cin;
-    if ((long)split * a.in_cs >= lim) return 0;
-    if (a.in2 && (long)(a.Cin - split) * a.in2_cs >= lim) return 0;
-    if ((long)a.KH * ((a.Cin + 7) / 8 * 8) * 2 * ((a.Cout + 31) / 32 * 32) * 16 >= 0x7fffffffL) return 0;
+    if (!fits_i32((long)split * a.in_cs)) return 0;
+    if (a.in2 && !fits_i32((long)(a.Cin - split) * a.in2_cs)) return 0;
+    if (!fits_i32((long)a.KH * pad_to(a.Cin, 8) * 2 * pad_to(a.Cout, 32) * 16, LIM_BYTES_2G)) return 0;
     return 1;
 }
 
 int babe_conv2d_wino4p_launch(const babe_conv_args& a, const float* w_wino4, hipStream_t s) {
-    Wino4pGeom g;
-    g.CinP = (a.Cin + 7) / 8 * 8;
-    g.CoutP = (a.Cout + 31) / 32 * 32;
-    if (g.CoutP == 64) launch4p<2, 1, 4>(a, g, w_wino4, s);             //  64 co x 512 positions, 8 waves
-    else if (g.CoutP == 96) launch4p<3, 1, 4, true>(a, g, w_wino4, s);  //  96 co x 512 positions, phase-planar activations
-    else launch4p<2, 2, 2>(a, g, w_wino4, s);                           // 128 co x 256 positions, 8 waves
+    const int CoutP = pad_to(a.Cout, 32);
+    if (CoutP == 64) launch4p<2, 1, 4>(a, w_wino4, s);             //  64 co x 512 positions, 8 waves
+    else if (CoutP == 96) launch4p<3, 1, 4, true>(a, w_wino4, s);  //  96 co x 512 positions, phase-planar activations
+    else launch4p<2, 2, 2>(a, w_wino4, s);                           // 128 co x 256 positions, 8 waves
     return 0;
 }

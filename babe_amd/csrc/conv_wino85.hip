@@ -33,11 +33,11 @@
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
+#include "conv_common.h"
 #include "gelu.h"
 #include <atomic>
 #include <cstdlib>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 #ifndef W85_HALFLOAD
 #define W85_HALFLOAD 1 // in the 128-channel kernel waves 0-3 load the rows and transform BOTH phase pairs of their (ci, unit), waves 4-7
@@ -977,20 +977,7 @@ __global__ void pack_wino85_kernel(const float* __restrict__ w, float* __restric
     const int ci = cq * 4 + c4;
     double wk[5][3];
     for (int kh = 0; kh < 5; ++kh)
-        for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = 0;
-    if (!tf) {
-        if (co < Cout && ci < Cin) {
-            const float* p = w + ((long)co * Cin + ci) * 15;
-            for (int kh = 0; kh < 5; ++kh)
-                for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = p[kh * 3 + kw];
-        }
-    } else {
-        if (co < Cin && ci < Cout) {      // packed "Cout" = reference Cin; taps flipped in both axes
-            const float* p = w + ((long)ci * Cin + co) * 15;
-            for (int kh = 0; kh < 5; ++kh)
-                for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = p[(4 - kh) * 3 + (2 - kw)];
-        }
-    }
+        for (int kw = 0; kw < 3; ++kw) wk[kh][kw] = conv_w_tap(w, Cout, Cin, 5, 3, tf, co, ci, kh, kw);
     const double G8[8][5] = {{-1, 0, 0, 0, 0},
                              {-2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9, -2.0 / 9},
                              {-2.0 / 9, 2.0 / 9, -2.0 / 9, 2.0 / 9, -2.0 / 9},
@@ -1023,17 +1010,15 @@ __global__ void pack_wino85_kernel(const float* __restrict__ w, float* __restric
 }  // namespace
 
 extern "C" long babe_conv_packed_size_wino85(int Cout, int Cin, int transpose_flip) {
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    return 48L * ((ci + 15) / 16 * 16) * ((co + 15) / 16 * 16);
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    return 48L * pad_to(io.ci, 16) * pad_to(io.co, 16);
 }
 
 extern "C" int babe_conv_pack_weights_wino85(const float* w, float* dst, int Cout, int Cin, int KH, int KW, int transpose_flip,
                                              void* stream) {
     BABE_CHECK_ARG(w && dst && Cout > 0 && Cin > 0 && KH == 5 && KW == 3, "conv_pack_weights_wino85: needs a (5,3) kernel");
-    const int co = transpose_flip ? Cin : Cout;
-    const int ci = transpose_flip ? Cout : Cin;
-    const int CinP = (ci + 15) / 16 * 16, CoutP = (co + 15) / 16 * 16;
+    const ConvIO io = conv_exec_io(Cout, Cin, transpose_flip);
+    const int CinP = pad_to(io.ci, 16), CoutP = pad_to(io.co, 16);
     const long total = 4L * CinP * CoutP;
     hipLaunchKernelGGL(pack_wino85_kernel, dim3(cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream, w, dst, Cout, Cin,
                        transpose_flip, CinP, CoutP, total);
@@ -1047,18 +1032,16 @@ extern "C" int babe_conv_pack_weights_wino85(const float* w, float* dst, int Cou
 extern "C" int babe_conv2d_wino85_supported(const babe_conv_args* ap) {
     if (!ap) return 0;
     const babe_conv_args& a = *ap;
-    auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
     if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (a.Cin < 16 || a.Cin % 16 != 0 || (a.Cout % 128 != 0 && a.Cout % 96 != 0 && a.Cout % 64 != 0)) return 0;
-    if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4 || a.in2) return 0;
-    if (!al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;
-    if (a.res && (!al16(a.res) || a.res_bs % 4 || a.res_cs % 4)) return 0;
-    const long lim = 0x3fffffffL / 4;
-    if ((long)a.Cin * a.in_cs >= lim || (long)a.F * a.T >= lim || (long)a.Cout * a.out_cs >= lim ||
-        (a.res && (long)a.Cout * a.res_cs >= lim))
+    if (!view_aligned(a.in, a.in_bs, a.in_cs) || a.in2) return 0;
+    if (!view_aligned(a.out, a.out_bs, a.out_cs)) return 0;
+    if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs)) return 0;
+    if (!fits_i32((long)a.Cin * a.in_cs, LIM_F32_1G) || !fits_i32((long)a.F * a.T, LIM_F32_1G) ||
+        !fits_i32((long)a.Cout * a.out_cs, LIM_F32_1G) || (a.res && !fits_i32((long)a.Cout * a.res_cs, LIM_F32_1G)))
         return 0;
-    if (48L * a.Cin * a.Cout * 4 >= 0x7fffffffL) return 0;
+    if (!fits_i32(48L * a.Cin * a.Cout * 4, LIM_BYTES_2G)) return 0;
     return 1;
 }
 

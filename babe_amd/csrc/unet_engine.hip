@@ -134,10 +134,9 @@ struct Ctx {
     // ---- ops (each = one extern "C" call of this library; nothing runs in a dry pass or after an error)
     // stat_cg / stat_part: also form the GroupNorm sums of the output in the conv's epilogue (babe_conv_args::stat_mode 1); returns
     // true if the kernel that ran the conv produced them (only the F(4,5) kernels do)
-    bool conv(const View& x, const babe_packed_conv& pc, const View& out, int dil, bool transpose, const View* x2, const View* res,
-              const float* in_scale, const float* oscale, float alpha, float rbeta, int stat_cg = 0, double* stat_part = nullptr,
-              const float* fbias = nullptr) {
-        if (dry() || err) return false;
+    // the argument block of out = alpha * conv(x[, x2]) * oscale + rbeta * res (babe_conv2d_auto fills in the weight's shape)
+    babe_conv_args conv_args(const View& x, const View& out, int dil, const View* x2, const View* res, const float* in_scale,
+                             const float* oscale, float alpha, float rbeta, const float* fbias = nullptr) const {
         babe_conv_args a;
         memset(&a, 0, sizeof a);
         a.in = x.p; a.in_bs = x.bs; a.in_cs = x.cs;
@@ -146,6 +145,13 @@ struct Ctx {
         if (res) { a.res = res->p; a.res_bs = res->bs; a.res_cs = res->cs; }
         a.in_scale = in_scale; a.oscale = oscale; a.alpha = alpha; a.rbeta = rbeta; a.fbias = fbias;
         a.B = B(); a.F = x.F; a.T = x.T; a.dil = dil;
+        return a;
+    }
+    bool conv(const View& x, const babe_packed_conv& pc, const View& out, int dil, bool transpose, const View* x2, const View* res,
+              const float* in_scale, const float* oscale, float alpha, float rbeta, int stat_cg = 0, double* stat_part = nullptr,
+              const float* fbias = nullptr) {
+        if (dry() || err) return false;
+        babe_conv_args a = conv_args(x, out, dil, x2, res, in_scale, oscale, alpha, rbeta, fbias);
         if (stat_part) { a.stat_mode = 1; a.stat_cg = stat_cg; a.stat_part = stat_part; }
         ck(babe_conv2d_auto(&a, &pc, transpose ? 1 : 0, st));
         return a.stat_mode == 1;
@@ -257,12 +263,7 @@ struct Ctx {
         const int Sp = splits(n);
         *part = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * (Sf > Sp ? Sf : Sp) * 2));     // (floats: 2 per double)
         if (dry() || err) return 0;
-        babe_conv_args a;
-        memset(&a, 0, sizeof a);
-        a.in = src.p; a.in_bs = src.bs; a.in_cs = src.cs;
-        a.out = da.p; a.out_bs = da.bs; a.out_cs = da.cs;
-        a.in_scale = sv.gate; a.alpha = RS2; a.rbeta = 0.f;
-        a.B = B(); a.F = src.F; a.T = src.T; a.dil = dil;
+        babe_conv_args a = conv_args(src, da, dil, nullptr, nullptr, sv.gate, nullptr, RS2, 0.f);
         if (fuse_gn() && blk.k53 && cg % 4 == 0 && z.dense() && da.dense()) {
             a.stat_mode = 2; a.stat_cg = cg; a.stat_x = z.p; a.stat_scale = sv.scale; a.stat_part = *part;
         }

@@ -19,6 +19,23 @@ def _view(t):
     return ptr(t), t.stride(0), t.stride(1)
 
 
+def _fill_out(a, pc, out, Cin, dil, res, oscale, alpha, rbeta):
+    """The output side of a ConvArgs - out, residual, output scale, alpha / rbeta - and the problem's shape."""
+    B, Cout, F, T = out.shape
+    a.out, a.out_bs, a.out_cs = _view(out)
+    if res is not None:
+        assert res.shape == out.shape
+        a.res, a.res_bs, a.res_cs = _view(res)
+    else:
+        a.res, a.res_bs, a.res_cs = None, 0, 0
+    if oscale is not None:
+        assert oscale.is_contiguous() and oscale.shape == (B, Cout)
+    a.oscale = ptr(oscale)
+    a.alpha, a.rbeta = alpha, rbeta
+    a.B, a.Cin, a.Cout, a.F, a.T = B, Cin, Cout, F, T
+    a.KH, a.KW, a.dil = pc.KH, pc.KW, dil
+
+
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2}
 BF16_HBM_F32 = os.environ.get("BABE_BF16_HBM_F32", "1") != "0"
 # debug switch for the (5,3) fp32 convs: 0 = direct kernel only, 2 = Winograd F(2,3) only, 4 (default) = F(4,3) where the
@@ -46,7 +63,7 @@ def _io(pc, tf):
     return (pc.Cout, pc.Cin) if tf else (pc.Cin, pc.Cout)
 
 
-# The Winograd image families of an fp32 PackedConv, which construction and repack() both walk: (suffix of the fwd_ / bwd_
+# The Winograd image families of an fp32 PackedConv: construction allocates them, repack() fills them.  (suffix of the fwd_ / bwd_
 # attribute, size function, pack function, may direction tf be packed?).  Images exist only for the direction(s) their kernel can
 # take (the *_supported rules of include/babe_hip.h, on the executed op's channels):
 #   wino / wino4   F(2,3) / F(4,3) along time: every 3-tap kernel
@@ -83,10 +100,24 @@ class PackedConv:
                 and ((w.shape[1] + 31) // 32) % _C11_NT == 0:
             self.nt = _C11_NT
         self.splits = self.splits_for(w.shape, precision)
+        assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
+        w = w.contiguous()
+        self.Cout, self.Cin, self.KH, self.KW = w.shape
+        L = lib()
+        shp = (self.Cout, self.Cin, self.KH, self.KW)
         if self.splits:
-            self._init_bf16(w)
-            return
-        self._init_f32(w)
+            for tf, d in ((0, "fwd"), (1, "bwd")):
+                setattr(self, d, torch.empty(L.babe_conv_packed_size_bf16(*shp, tf, self.splits), device=w.device, dtype=torch.int16))
+        else:
+            # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip):
+            # the caller's tensor itself
+            self.w_raw = w if (FEWCO and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
+            for tf, d in ((0, "fwd"), (1, "bwd")):
+                setattr(self, d, torch.empty(L.babe_conv_packed_size(*shp, tf), device=w.device, dtype=torch.float32))
+            for name, size, _, eligible in _FAMILIES:
+                for tf, d in ((0, "fwd_"), (1, "bwd_")):
+                    setattr(self, d + name, torch.empty(size(L, self, tf), device=w.device) if eligible(self, tf) else None)
+        self.repack(w)
 
     @staticmethod
     def splits_for(shape, precision):
@@ -109,7 +140,7 @@ class PackedConv:
     def repack(self, w):
         """Pack new weights of the same shape IN PLACE into the existing images, so that every pointer to them (this `desc`, the
         descriptors of the library-side plan, engine states sharing this object) stays valid: the refresh after an optimizer
-        step.  The same pack calls as construction, so the images are exactly those a freshly built PackedConv would hold."""
+        step.  Construction packs through this function too, so the images are exactly those a freshly built PackedConv holds."""
         assert w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (self.Cout, self.Cin, self.KH, self.KW)
         w = w.contiguous()
         L = lib()
@@ -127,40 +158,6 @@ class PackedConv:
                 dst = getattr(self, d + name)
                 if dst is not None:
                     check(pack(L)(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
-
-    def _init_bf16(self, w):
-        assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
-        w = w.contiguous()
-        self.Cout, self.Cin, self.KH, self.KW = w.shape
-        L = lib()
-        nf = L.babe_conv_packed_size_bf16(self.Cout, self.Cin, self.KH, self.KW, 0, self.splits)
-        nb = L.babe_conv_packed_size_bf16(self.Cout, self.Cin, self.KH, self.KW, 1, self.splits)
-        self.fwd = torch.empty(nf, device=w.device, dtype=torch.int16)
-        self.bwd = torch.empty(nb, device=w.device, dtype=torch.int16)
-        for tf, dst in ((0, self.fwd), (1, self.bwd)):
-            check(L.babe_conv_pack_weights_bf16(ptr(w), ptr(dst), self.Cout, self.Cin, self.KH, self.KW, tf, self.splits,
-                                                stream()), "pack_bf16")
-
-    def _init_f32(self, w):
-        assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
-        w = w.contiguous()
-        self.Cout, self.Cin, self.KH, self.KW = w.shape
-        # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip)
-        self.w_raw = w if (FEWCO and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
-        L = lib()
-        nf = L.babe_conv_packed_size(self.Cout, self.Cin, self.KH, self.KW, 0)
-        nb = L.babe_conv_packed_size(self.Cout, self.Cin, self.KH, self.KW, 1)
-        self.fwd = torch.empty(nf, device=w.device, dtype=torch.float32)
-        self.bwd = torch.empty(nb, device=w.device, dtype=torch.float32)
-        check(L.babe_conv_pack_weights_nt(ptr(w), ptr(self.fwd), self.Cout, self.Cin, self.KH, self.KW, 0, self.nt, stream()), "pack")
-        check(L.babe_conv_pack_weights_nt(ptr(w), ptr(self.bwd), self.Cout, self.Cin, self.KH, self.KW, 1, self.nt, stream()), "pack")
-        for name, size, pack, eligible in _FAMILIES:
-            for tf, d in ((0, "fwd_"), (1, "bwd_")):
-                img = None
-                if eligible(self, tf):
-                    img = torch.empty(size(L, self, tf), device=w.device)
-                    check(pack(L)(ptr(w), ptr(img), self.Cout, self.Cin, self.KH, self.KW, tf, stream()), "pack_" + name)
-                setattr(self, d + name, img)
 
 
 # GroupNorm-VJP partial sums formed in the F(4,5) transposed conv's epilogue instead of babe_gn_bwd_partial's own pass: OFF by
@@ -201,23 +198,13 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     wq = pc.bwd if transpose else pc.fwd
     a.w_packed = None if pc.splits else ptr(wq)
     assert out.shape == (B, Cout, F, T), (out.shape, (B, Cout, F, T))
-    a.out, a.out_bs, a.out_cs = _view(out)
-    if res is not None:
-        assert res.shape == out.shape
-        a.res, a.res_bs, a.res_cs = _view(res)
-    else:
-        a.res, a.res_bs, a.res_cs = None, 0, 0
+    _fill_out(a, pc, out, Cin, dil, res, oscale, alpha, rbeta)
     if in_scale is not None:
         assert in_scale.is_contiguous() and in_scale.shape == (B, Cin)
-    if oscale is not None:
-        assert oscale.is_contiguous() and oscale.shape == (B, Cout)
-    a.in_scale, a.oscale = ptr(in_scale), ptr(oscale)
+    a.in_scale = ptr(in_scale)
     if fbias is not None:
         assert fbias.is_contiguous() and fbias.dtype == torch.float32 and fbias.shape == (Cout, F)
         a.fbias = ptr(fbias)
-    a.alpha, a.rbeta = alpha, rbeta
-    a.B, a.Cin, a.Cout, a.F, a.T = B, Cin, Cout, F, T
-    a.KH, a.KW, a.dil = pc.KH, pc.KW, dil
     L = lib()
     w85 = getattr(pc, "bwd_wino85" if transpose else "fwd_wino85", None)
     f45 = w85 is not None and x2 is None and not force_nested         # the F(4,5) kernel may run: it alone fuses the sums
@@ -360,18 +347,8 @@ def units_args(au, pc, out, Cin, dil=1, res=None, oscale=None, alpha=1.0, rbeta=
     a.in_, a.in_bs, a.in_cs = ptr(au), nu, nu // (Cin // 8)
     a.in2, a.in2_bs, a.in2_cs, a.cin_split = None, 0, 0, Cin
     a.w_packed = None
-    a.out, a.out_bs, a.out_cs = _view(out)
-    if res is not None:
-        assert res.shape == out.shape
-        a.res, a.res_bs, a.res_cs = _view(res)
-    else:
-        a.res, a.res_bs, a.res_cs = None, 0, 0
-    if oscale is not None:
-        assert oscale.is_contiguous() and oscale.shape == (B, Cout)
-    a.in_scale, a.oscale = None, ptr(oscale)
-    a.alpha, a.rbeta = alpha, rbeta
-    a.B, a.Cin, a.Cout, a.F, a.T = B, Cin, Cout, F, T
-    a.KH, a.KW, a.dil = pc.KH, pc.KW, dil
+    a.in_scale = None
+    _fill_out(a, pc, out, Cin, dil, res, oscale, alpha, rbeta)
     return a
 
 
