@@ -222,14 +222,18 @@ class Unet_CQT_oct_with_attention(nn.Module):
         for key, t in init_state_dict(self.Ns, self.num_dils, self.emb_dim, attention_layers=self.attention_layers,
                                       attention_dict=self.attention_dict, use_fencoding=self.use_fencoding).items():
             _attach(self, key, t.to(self.device), is_buffer=key.endswith(".kernel"))
-        self._engine = None
+        self._train_attention = False         # set_trainable(True, attention=True)
+        self._grad_keys = None                # keys of the parameters handed to _UnetFn by the last training forward
         self.register_load_state_dict_post_hook(lambda m, k: m._reset_params())
         self._reset_params()
 
     def _reset_params(self):
-        """Drop the engine and re-read the Parameter objects (load_state_dict(assign=True) and _apply may replace them): the
-        version check and the parameters handed to autograd are always the module's current ones."""
+        """Drop the engine, with every state over it, and re-read the Parameter objects (load_state_dict(assign=True) and _apply
+        may replace them): the version check and the parameters handed to autograd are always the module's current ones."""
         self._engine = None
+        self._lanes = None                    # [(stream, engine state)] of the lane=None evaluations (_get_lanes)
+        self._lane_engines = None             # engine states of the lane=k evaluations (lane_engine)
+        self._train_keep = None               # the embedding MLP's activations between a training forward and its backward
         self._params = list(self.named_parameters())
         self._versions = None
 
@@ -247,7 +251,6 @@ class Unet_CQT_oct_with_attention(nn.Module):
             sd = self._engine_sd()
             self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision,
                                       attention_layers=self.attention_layers, attention_dict=self.attention_dict)
-            self._lanes = None
             self._versions = self._param_versions()
         return self._engine
 
@@ -256,7 +259,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
 
     def _refresh_weights(self):
         """The engine packs the weights once; a parameter changed in place since then (optimizer.step(), a no_grad copy_)
-        shows as a new _version: repack every conv IN PLACE (lane clones and the library-side plan keep their pointers) and
+        shows as a new _version: repack every conv IN PLACE (every engine state and the library-side plan share those objects) and
         rebuild the concatenated FiLM matrix.  Costs nothing on the GPU while the parameters stay as they are."""
         if self._engine is None:
             return
@@ -285,7 +288,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         ps = [(k, p) for k, p in self._params if p.requires_grad]
         if not ps:
             return ps
-        if self.has_attention and not getattr(self, "_train_attention", False):
+        if self.has_attention and not self._train_attention:
             raise NotImplementedError("parameter gradients of networks with attention layers are not implemented "
                                       "(opt in with set_trainable(True, attention=True))")
         if self.precision != "f32":
@@ -305,7 +308,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         n = min(B, self.MAX_LANES) if self.concurrent_lanes_ok else 1      # (bf16: one stream if BABE_BF16_LANES=0)
         if n <= 1:
             return None
-        if getattr(self, "_lanes", None) is None or len(self._lanes) != n:
+        if self._lanes is None or len(self._lanes) != n:
             eng = self.engine()
             self._lanes = [(torch.cuda.Stream(device=self.device), eng if i == 0 else eng.clone_state()) for i in range(n)]
         return self._lanes
@@ -334,6 +337,16 @@ class Unet_CQT_oct_with_attention(nn.Module):
         for _, done in results:
             main.wait_event(done)
         return [r for r, _ in results]
+
+    def _run(self, fn, tensors, eng=None):
+        """fn(engine state, tensors, b0, b1) -> list of tensors, for all batch rows of `tensors`.  eng: the state to run on, on the
+        caller's stream (a lane=k evaluation).  None: the module's own stream lanes, each with its rows [b0, b1) of every tensor,
+        the results concatenated; with one lane the engine itself on the caller's stream."""
+        B = tensors[0].shape[0]
+        if eng is not None or self._get_lanes(B) is None:
+            return fn(self.engine() if eng is None else eng, tensors, 0, B)
+        parts = self._run_lanes(B, lambda e, b0, b1: fn(e, [t[b0:b1] for t in tensors], b0, b1))
+        return [torch.cat([p[j] for p in parts], 0) for j in range(len(parts[0]))]
 
     def _apply(self, fn, *a, **k):
         self._engine = None
@@ -373,7 +386,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         library-side evaluation (testing/eval_c.py), so the weight refresh runs here too."""
         self._refresh_weights()
         eng = self.engine()
-        if getattr(self, "_lane_engines", None) is None or self._lane_engines[0] is not eng:
+        if self._lane_engines is None:
             self._lane_engines = [eng]
         while len(self._lane_engines) <= lane:
             self._lane_engines.append(eng.clone_state())
@@ -383,87 +396,46 @@ class Unet_CQT_oct_with_attention(nn.Module):
         """x [B,L], cnoise [B,1] -> [B,L]; keeps what vjp() needs until the next call (of the same lane).
         train=True: also what the parameter gradients need (_vjp_train); fp32, the module's own lanes."""
         assert x.device == self.device, f"input on {x.device}, network on {self.device}"
+        assert lane is None or not train
         with torch.cuda.device(self.device):       # every launch below goes to THIS device's current stream
             if lane is None:
                 self._refresh_weights()            # (the lane path refreshes in lane_engine)
-            if train:
-                assert lane is None
-                return self._fwd_train(x, cnoise)
-            return self._fwd_nograd(x, cnoise, lane)
-
-    def _fwd_train(self, x, cnoise):
-        eng = self.engine()
-        x = x.detach().contiguous().float()
-        assert x.shape[-1] == self.CQTransform.Ls, "input length must equal exp.audio_len (the CQT is built for it)"
-        keep = []
-        film = eng.embed(cnoise.detach().reshape(-1, 1).contiguous().float(), keep=keep)
-        co = self.CQTransform.fwd_planar(x)
-        B = x.shape[0]
-        self._train_keep = keep
-        if self._get_lanes(B) is None:
-            outs = eng.forward(co, film, train=True)
-        else:
-            parts = self._run_lanes(B, lambda e, b0, b1: e.forward([c[b0:b1] for c in co], film[b0:b1], train=True))
-            outs = [torch.cat([p[j] for p in parts], 0) for j in range(len(co))]
-        return self.CQTransform.bwd_planar(outs)
-
-    def _vjp_train(self, g):
-        """(gradient w.r.t. x, {key: gradient of every parameter}) of <net(x), g> for the last fwd_nograd(train=True)."""
-        from .unet_engine import ParamGrads
-        with torch.cuda.device(self.device):
-            eng = self.engine()
-            B = g.shape[0]
-            pg = ParamGrads.new(eng, B)
-            gouts = self.CQTransform.bwd_adjoint(g.contiguous())
-            if self._get_lanes(B) is None:
-                gC = eng.vjp(gouts, pg=pg)
-            else:
-                parts = self._run_lanes(B, lambda e, b0, b1: e.vjp([c[b0:b1] for c in gouts], pg=pg.lane(b0, b1)))
-                gC = [torch.cat([p[j] for p in parts], 0) for j in range(len(gouts))]
-            gx = self.CQTransform.fwd_adjoint(gC)
-            grads = eng.param_grads(pg, self._train_keep)
-            self._train_keep = None
-            return gx, grads
-
-    def _fwd_nograd(self, x, cnoise, lane=None):
-        if lane is not None:
-            eng = self.lane_engine(lane)
+            state = None if lane is None else self.lane_engine(lane)
+            eng = self.engine() if state is None else state
             x = x.detach().contiguous().float()
-            assert x.shape[-1] == self.CQTransform.Ls
-            film = eng.embed(cnoise.detach().reshape(-1, 1).contiguous().float())
-            return self.CQTransform.bwd_planar(eng.forward(self.CQTransform.fwd_planar(x), film))
-        eng = self.engine()
-        x = x.detach().contiguous().float()
-        assert x.shape[-1] == self.CQTransform.Ls, "input length must equal exp.audio_len (the CQT is built for it)"
-        film = eng.embed(cnoise.detach().reshape(-1, 1).contiguous().float())
-        co = self.CQTransform.fwd_planar(x)
-        B = x.shape[0]
-        if self._get_lanes(B) is None:
-            outs = eng.forward(co, film)
-        else:
-            parts = self._run_lanes(B, lambda e, b0, b1: e.forward([c[b0:b1] for c in co], film[b0:b1]))
-            outs = [torch.cat([p[j] for p in parts], 0) for j in range(len(co))]
-        return self.CQTransform.bwd_planar(outs)
+            assert x.shape[-1] == self.CQTransform.Ls, "input length must equal exp.audio_len (the CQT is built for it)"
+            keep = [] if train else None
+            film = eng.embed(cnoise.detach().reshape(-1, 1).contiguous().float(), keep=keep)
+            co = self.CQTransform.fwd_planar(x)
+            if train:
+                self._train_keep = keep
+            outs = self._run(lambda e, t, b0, b1: e.forward(t[:-1], t[-1], train=train), list(co) + [film], state)
+            return self.CQTransform.bwd_planar(outs)
 
     def vjp(self, g, lane=None):
         """Gradient of <net(x), g> w.r.t. x for the last fwd_nograd call (of the same lane)."""
         assert g.device == self.device, f"gradient on {g.device}, network on {self.device}"
-        with torch.cuda.device(self.device):
-            return self._vjp(g, lane)
+        return self._vjp(g, lane)[0]
 
-    def _vjp(self, g, lane=None):
-        if lane is not None:
-            eng = self.lane_engine(lane)
-            return self.CQTransform.fwd_adjoint(eng.vjp(self.CQTransform.bwd_adjoint(g.contiguous())))
-        eng = self.engine()
-        gouts = self.CQTransform.bwd_adjoint(g.contiguous())
-        B = g.shape[0]
-        if self._get_lanes(B) is None:
-            gC = eng.vjp(gouts)
-        else:
-            parts = self._run_lanes(B, lambda e, b0, b1: e.vjp([c[b0:b1] for c in gouts]))
-            gC = [torch.cat([p[j] for p in parts], 0) for j in range(len(gouts))]
-        return self.CQTransform.fwd_adjoint(gC)
+    def _vjp_train(self, g):
+        """(gradient w.r.t. x, {key: gradient of every parameter}) of <net(x), g> for the last fwd_nograd(train=True)."""
+        return self._vjp(g, train=True)
+
+    def _vjp(self, g, lane=None, train=False):
+        from .unet_engine import ParamGrads
+        with torch.cuda.device(self.device):
+            state = None if lane is None else self.lane_engine(lane)
+            eng = self.engine()
+            # training: the buffers the lanes write their rows of, made on the caller's stream before the lanes fork
+            pg = ParamGrads.new(eng, g.shape[0]) if train else None
+            gouts = self.CQTransform.bwd_adjoint(g.contiguous())
+            gC = self._run(lambda e, t, b0, b1: e.vjp(t, pg=pg.lane(b0, b1) if train else None), list(gouts), state)
+            gx = self.CQTransform.fwd_adjoint(gC)
+            if not train:
+                return gx, None
+            grads = eng.param_grads(pg, self._train_keep)
+            self._train_keep = None
+            return gx, grads
 
     # ---------------------------------------------------------------- nn.Module call
     def forward(self, inputs, sigma):

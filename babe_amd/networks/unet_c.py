@@ -1,7 +1,8 @@
 """ctypes binding of the library-side UNet engine (csrc/unet_engine.hip: babe_unet_plan_* / babe_unet_fwd / babe_unet_vjp).
 
-`CUnet(engine)` describes a `UnetEngine`'s packed weights to the library once (a plan handle); `fwd` / `vjp` are then ONE C call per
-direction instead of ~1100 op-level calls from Python.  Results are bit-identical to the Python-sequenced engine
+`CPlan` describes a `UnetEngine`'s packed weights to the library once (a plan handle, owned by the engine); a `CUnet` is one
+library-side state and workspace over it, whose `fwd` / `vjp` are ONE C call per direction instead of ~1100 op-level calls from
+Python.  Results are bit-identical to the Python-sequenced engine
 (tests/test_gpu_unet_c.py).  fp32 convs only.  Workspace and outputs are torch allocations (the library never allocates)."""
 import ctypes as C
 
@@ -30,18 +31,18 @@ def _blk(dst, b):
         dst.fb_proj_in, dst.fb_res_conv = ptr(b.fb_proj_in), ptr(b.fb_res_conv)
 
 
-class CUnet:
-    """Plan (shared, immutable) + one state and workspace per engine state (= per clip lane)."""
+class CPlan:
+    """The library's description of one engine's packed weights (babe_unet_plan): immutable, made on first use, shared by every
+    library-side state over that engine and destroyed with the last of them."""
 
-    def __init__(self, eng, plan=None):
-        assert eng.precision == "f32", "the library-side engine sequences the fp32 network"
-        if getattr(eng, "has_attention", False):
-            raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
-                                      "(such networks run on the Python sequencer)")
-        self.eng = eng
-        self.n = eng.nocts
-        L = lib()
-        if plan is None:
+    handle = None
+
+    def get(self, eng):
+        if self.handle is None:
+            assert eng.precision == "f32", "the library-side engine sequences the fp32 network"
+            if eng.has_attention:
+                raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
+                                          "(such networks run on the Python sequencer)")
             d = CPlanDesc()
             d.nocts, d.bpo = eng.nocts, eng.bpo
             for i, v in enumerate(eng.Ns):
@@ -54,27 +55,36 @@ class CUnet:
                 _pc(d.pyr_conv[i], eng.pyr_conv[i])
             _blk(d.mid_blk, eng.mid_blk)
             _blk(d.mid_out, eng.mid_out)
-            plan = L.babe_unet_plan_create(C.byref(d))
-            if not plan:
-                raise RuntimeError("babe_unet_plan_create: " + L.babe_last_error().decode())
-            self._owns_plan = True
-        else:
-            self._owns_plan = False
-        self.plan = plan
-        self.state = L.babe_unet_state_create()
-        self.ws = None
-        self.key = None
-
-    def clone(self, eng):
-        return CUnet(eng, plan=self.plan)
+            self.handle = lib().babe_unet_plan_create(C.byref(d))
+            if not self.handle:
+                raise RuntimeError("babe_unet_plan_create: " + lib().babe_last_error().decode())
+            self._keep = eng                             # the plan points into the engine's weight buffers
+        return self.handle
 
     def __del__(self):
         try:
-            L = lib()
+            if self.handle:
+                lib().babe_unet_plan_destroy(self.handle)
+        except Exception:
+            pass
+
+
+class CUnet:
+    """One library-side state and workspace over an engine's plan (UnetEngine.c_plan): one per engine state on the BABE_UNET_C
+    path, one per lane for testing/eval_c.py.  Belongs to one stream at a time."""
+
+    def __init__(self, eng):
+        self.plan = eng.c_plan()
+        self._owner = eng._plan                          # keeps the plan alive as long as this state
+        self.n = eng.nocts
+        self.state = lib().babe_unet_state_create()
+        self.ws = None
+        self.key = None
+
+    def __del__(self):
+        try:
             if getattr(self, "state", None):
-                L.babe_unet_state_destroy(self.state)
-            if getattr(self, "_owns_plan", False) and getattr(self, "plan", None):
-                L.babe_unet_plan_destroy(self.plan)
+                lib().babe_unet_state_destroy(self.state)
         except Exception:
             pass
 

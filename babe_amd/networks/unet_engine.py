@@ -10,13 +10,18 @@ never materialised as copies of big tensors: producers write straight into frequ
 sub-views of the consumer's buffer and channel concatenation is a two-source conv input.
 Each dilation layer keeps exactly one tensor (its input) for the VJP; GroupNorm / FiLM /
 GELU are recomputed in the backward kernels.
+
+Plan and state, as in csrc/unet_engine.hip: _Block / _Attn / _FilmIndex hold weights only and are shared by every engine handle;
+what an evaluation leaves between forward and vjp is one _State per handle (UnetEngine.clone_state makes another).
 """
+import copy
 import math
 import os
 
 import torch
 
 from .. import ops
+from .unet_c import CPlan, CUnet
 
 RS2 = 1.0 / math.sqrt(2.0)
 # the library-side sequencer (csrc/unet_engine.hip): one C call per direction.  BABE_UNET_C=1 enables it (fp32 networks).
@@ -30,7 +35,7 @@ class _Attn:
         qk  = Conv1d(a1.view(B, H*F, T))                 a (1,1) conv on the [B, H*F, 1, T] view
         o   = attention(qk, V = a1)                      csrc/attention.hip
         z'  = (gate2(emb) * proj_out(o) + z) / sqrt2
-    z is the block's proj_in output, z' feeds the dilated conv stack."""
+    z is the block's proj_in output, z' feeds the dilated conv stack.  Weights only, shared by every engine handle."""
 
     def __init__(self, g, Fdim, N, film_index, opts, prefix=""):
         self.H, self.bias_qkv, self.rel_pos, self.nbk, self.maxd = opts
@@ -47,27 +52,20 @@ class _Attn:
         self.qk = ops.PackedConv(w.reshape(w.shape[0], w.shape[1], 1, 1))
         self.qk_bias = g("attn_block.qk.bias").contiguous() if self.bias_qkv else None
         self.emb = g("attn_block.rel_pos.relative_attention_bias.weight").contiguous() if self.rel_pos else None
-        self._buckets = {}
-
-    def buckets(self, T, dev):
-        if not self.rel_pos:
-            return None
-        t = self._buckets.get(T)
-        if t is None:
-            t = self._buckets[T] = ops.attn_buckets(T, self.nbk, self.maxd).to(dev)
-        return t
 
 
 class _Block:
-    """One ResnetBlock: packed weights + per-call saved tensors."""
+    """One ResnetBlock: its packed weights, shared by every engine handle and written after __init__ by UnetEngine.refresh alone.
+    idx: the block's position in UnetEngine.blocks(), which is where a _State keeps what an evaluation saves for it."""
 
     FOLDED = ("proj_in", "res_conv")      # the convs of an init block with frequency encodings that see all 66 input channels
 
-    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32", attn=None, fenc=None):
+    def __init__(self, sd, prefix, num_dils, film_index, proj_after=False, precision="f32", attn=None, fenc=None, idx=None):
         """attn: (Fdim, attention options) if the block carries a time-attention layer.
         fenc: the [64, 64] frequency-encoding table of an init block built with use_fencoding.  Its proj_in / res_conv weights
         are [N, 66, 1, 1] over cat(signal 2, encodings 64): the convs are packed from the 2 signal columns and the encodings'
         share, constant over batch and time, is the bias table fb_* [N, 64] the conv adds in its epilogue (ops.fenc_bias)."""
+        self.idx = idx
         self.p = prefix
         self.nd = num_dils
         self.proj_after = proj_after
@@ -98,12 +96,28 @@ class _Block:
             self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias"), prefix + f"affine.{d}"),
                                   film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"), prefix + f"gate.{d}")))
         self.attn = _Attn(g, attn[0], self.N, film_index, attn[1], prefix) if attn else None
-        self.saved = None
-        self.attn_saved = None
-        self.inp = self.zpo = None    # training: the block's input(s) and proj_out's input, for the weight gradients
 
     def dil(self, d):
         return 2 ** d if self.k53 else 1
+
+
+class _State:
+    """What one evaluation leaves between forward and vjp.  Every engine handle has one of its own (UnetEngine.clone_state), so two
+    handles over the same weights can be in flight together.  The per-block records are lists over _Block.idx; all of it lives
+    until vjp consumes it or the next forward of this state replaces it."""
+
+    def __init__(self, nblocks):
+        self.B = self.Ts = None           # batch rows and the time length of every level
+        self.train = False                # forward(train=True): inp / zpo / pyrs / film are kept as well
+        self.film = None                  # training: the FiLM vectors
+        self.hs = self.pyrs = None        # the encoder's skip tensors; training: the pyramid convs' inputs
+        self.saved = [None] * nblocks     # per dilation layer (z, stats, scale, gate)
+        self.attn = [None] * nblocks      # the attention branch's (z, stats, scale, gate, a1, qk, o, lse)
+        self.inp = [None] * nblocks       # training: the block's input(s) ...
+        self.zpo = [None] * nblocks       # ... and proj_out's input, for the weight gradients
+        self.scratch = {}                 # name -> flat buffer, grown on demand
+        self.cunet = None                 # BABE_UNET_C: the library-side state and workspace (unet_c.CUnet) ...
+        self.c_fwd = False                # ... and whether the last forward ran there
 
 
 class _FilmIndex:
@@ -157,7 +171,7 @@ class ParamGrads:
         dfilm = torch.zeros(B, eng.film_idx.J, device=eng.dev, dtype=torch.float32)
         qk = {}
         for blk, level in eng.attn_blocks:
-            HF, T = blk.attn.H * blk.attn.F, eng.Ts[level]
+            HF, T = blk.attn.H * blk.attn.F, eng._state.Ts[level]
             qk[blk.p] = (torch.empty(B, 2 * HF, T, device=eng.dev, dtype=torch.float32),
                          torch.empty(B, HF, T, device=eng.dev, dtype=torch.float32))
         return cls(eng.grad_layout, rows, dfilm, qk)
@@ -189,26 +203,29 @@ class UnetEngine:
         self.Ns, self.num_dils, self.nocts, self.bpo = list(Ns), list(num_dils), num_octs, bins_per_oct
         self.dev = sd["embedding.RFF_freq"].device
         fi = _FilmIndex()
+        n = num_octs                                 # blocks() order: init, main, mid_blk, mid_out, up_out, up_blk
         self.emb_W = [(sd[f"embedding.MLP.{i}.weight"].contiguous(), sd[f"embedding.MLP.{i}.bias"].contiguous()) for i in range(3)]
         self.rff_freq = sd["embedding.RFF_freq"].reshape(-1).contiguous()
         self.init_blk, self.main_blk, self.pyr_conv = [], [], []
         for i in range(num_octs):
             fe = sd.get(f"freq_encodings.{i}.embeddings")
-            self.init_blk.append(_Block(sd, f"downs.{i}.0.", 1, fi, precision=precision,
+            self.init_blk.append(_Block(sd, f"downs.{i}.0.", 1, fi, idx=i, precision=precision,
                                         fenc=fe.reshape(64, bins_per_oct).contiguous() if fe is not None else None))
             self.pyr_conv.append(ops.PackedConv(sd[f"downs.{i}.1.weight"], precision))
-            self.main_blk.append(_Block(sd, f"downs.{i}.2.", num_dils[i], fi, precision=precision, attn=A(att[i], (i + 1) * bins_per_oct)))
-        self.mid_blk = _Block(sd, "middle.0.1.", num_dils[-1], fi, precision=precision, attn=A(att[-1], num_octs * bins_per_oct))
-        self.mid_out = _Block(sd, "middle.0.0.", 1, fi, proj_after=True, precision=precision)
+            self.main_blk.append(_Block(sd, f"downs.{i}.2.", num_dils[i], fi, idx=n + i, precision=precision, attn=A(att[i], (i + 1) * bins_per_oct)))
+        self.mid_blk = _Block(sd, "middle.0.1.", num_dils[-1], fi, idx=2 * n, precision=precision, attn=A(att[-1], num_octs * bins_per_oct))
+        self.mid_out = _Block(sd, "middle.0.0.", 1, fi, idx=2 * n + 1, proj_after=True, precision=precision)
         self.up_out, self.up_blk = [], []
         for i in range(num_octs):
             j = num_octs - 1 - i
-            self.up_out.append(_Block(sd, f"ups.{i}.0.", 1, fi, proj_after=True, precision=precision))
-            self.up_blk.append(_Block(sd, f"ups.{i}.1.", num_dils[j], fi, precision=precision, attn=A(att[j], (j + 1) * bins_per_oct)))
+            self.up_out.append(_Block(sd, f"ups.{i}.0.", 1, fi, idx=2 * n + 2 + i, proj_after=True, precision=precision))
+            self.up_blk.append(_Block(sd, f"ups.{i}.1.", num_dils[j], fi, idx=3 * n + 2 + i, precision=precision, attn=A(att[j], (j + 1) * bins_per_oct)))
         fi.finalize()
         self.film_idx = fi
-        self._scratch = {}
-        self._train = False
+        assert all(b.idx == k for k, b in enumerate(self.blocks()))
+        self._buckets = {}                           # T -> the relative-position bucket table (shape only), every handle's
+        self._plan = CPlan()                         # the library-side plan over these weights, every handle's (c_plan)
+        self._state = _State(len(self.blocks()))
         # training: flat per-row layout of the conv weights and GroupNorm gammas (ParamGrads), the convs the refresh repacks
         self.grad_layout, self.grad_numel, self.packs = {}, 0, []
         for blk in self.blocks():
@@ -234,7 +251,6 @@ class UnetEngine:
         for i, pc in enumerate(self.pyr_conv):
             self._add_grad(f"downs.{i}.1.weight", pc)
         # (block, level whose time length it runs at) of every block with attention
-        n = num_octs
         self.attn_blocks = [(b, i) for i, b in enumerate(self.main_blk) if b.attn is not None]
         self.attn_blocks += [(self.mid_blk, n - 1)] if self.mid_blk.attn is not None else []
         self.attn_blocks += [(b, n - 1 - i) for i, b in enumerate(self.up_blk) if b.attn is not None]
@@ -278,38 +294,31 @@ class UnetEngine:
         self.film_idx.refresh(sd)
 
     def clone_state(self):
-        """A second engine over the SAME packed weights with its own per-call state (saved activations, scratch), so that
-        two batch items can run on two streams at once."""
-        import copy
+        """A second handle over the SAME weight objects (blocks, packed convs, FiLM index, library-side plan) with a fresh _State,
+        so that two batch items can run on two streams at once."""
         c = copy.copy(self)
-        c._scratch = {}
-        c.__dict__.pop("_cunet", None)                   # own state + workspace over the SAME plan
-        if self.__dict__.get("_cunet") is not None:
-            c._cunet_parent = self._cunet
-        elif USE_C and self.precision == "f32":
-            c._cunet_parent = self._c_engine()
-        cp = lambda blks: [copy.copy(b) for b in blks]
-        c.init_blk, c.main_blk, c.up_out, c.up_blk = cp(self.init_blk), cp(self.main_blk), cp(self.up_out), cp(self.up_blk)
-        c.mid_blk, c.mid_out = copy.copy(self.mid_blk), copy.copy(self.mid_out)
+        c._state = _State(len(self._state.saved))
         return c
 
     # ------------------------------------------------------------------ helpers
     def buf(self, *shape):
         return torch.empty(*shape, device=self.dev, dtype=torch.float32)
 
-    def scratch(self, name, numel):
-        t = self._scratch.get(name)
+    def scratch(self, name, numel, dtype=torch.float32):
+        sc = self._state.scratch
+        t = sc.get(name)
         if t is None or t.numel() < numel:
-            t = torch.empty(numel, device=self.dev, dtype=torch.float32)
-            self._scratch[name] = t
+            t = sc[name] = torch.empty(numel, device=self.dev, dtype=dtype)
         return t[:numel]
 
-    def scratch_i16(self, name, numel):
-        t = self._scratch.get(name)
-        if t is None or t.numel() < numel:
-            t = torch.empty(numel, device=self.dev, dtype=torch.int16)
-            self._scratch[name] = t
-        return t[:numel]
+    def _bucket(self, at, T):
+        """The relative-position bucket table of attention branch `at` at time length T (None without rel_pos)."""
+        if not at.rel_pos:
+            return None
+        t = self._buckets.get(T)
+        if t is None:
+            t = self._buckets[T] = ops.attn_buckets(T, at.nbk, at.maxd).to(self.dev)
+        return t
 
     def embed(self, cnoise, keep=None):
         """cnoise [B,1] -> FiLM vectors for every layer [B, J] (RFF_MLP_Block + all affine/gate Linears).
@@ -331,8 +340,9 @@ class UnetEngine:
         """out <- ResnetBlock(cat(x,x2)); out may be a strided frequency sub-view."""
         B, _, Fq, T = x.shape
         N = blk.N
-        if self._train:
-            blk.inp = (x, x2)
+        st = self._state
+        if st.train:
+            st.inp[blk.idx] = (x, x2)
         if blk.proj_in is not None:
             z = ops.conv2d(x, blk.proj_in, self.buf(B, N, Fq, T), x2=x2, fbias=blk.fb_proj_in)
         else:
@@ -344,7 +354,7 @@ class UnetEngine:
         # precision='bf16': the GELU output goes to the conv as bf16 units (half the bytes, both conv operands by LDS-DMA)
         units = blk.nd > 0 and ops.units_ok(blk.H[0], N, N, T) and z.is_contiguous()
         if units:
-            au = self.scratch_i16("au", B * ops.lib().babe_units_size(N, Fq, T) * 8)
+            au = self.scratch("au", B * ops.lib().babe_units_size(N, Fq, T) * 8, torch.int16)
         zsum = None                                          # (part, S): GroupNorm sums of z formed by the conv that wrote it
         for d in range(blk.nd):
             aoff, goff = blk.film_off[d]
@@ -367,18 +377,18 @@ class UnetEngine:
             saved.append((z, stats, scale, gate))
             z = znew
         if blk.proj_out is not None:
-            if self._train:
-                blk.zpo = z
+            if st.train:
+                st.zpo[blk.idx] = z
             z = ops.conv2d(z, blk.proj_out, self.buf(B, blk.proj_out.Cout, Fq, T))
         if blk.res_conv is not None:
             ops.conv2d(x, blk.res_conv, out, x2=x2, res=z, alpha=RS2, rbeta=RS2, fbias=blk.fb_res_conv)
         else:
             ops.axpby2(z, x, out, RS2, RS2)                  # (x + h)/sqrt2 in one pass
-        blk.saved = saved
+        st.saved[blk.idx] = saved
         return out
 
     def attn_fwd(self, blk, z, film):
-        """z' = (gate2 * proj_out(attention(...)) + z)/sqrt2 (class _Attn); keeps what attn_vjp needs in blk.attn_saved."""
+        """z' = (gate2 * proj_out(attention(...)) + z)/sqrt2 (class _Attn); keeps what attn_vjp needs in the state's attention record."""
         at = blk.attn
         B, N, Fq, T = z.shape
         H = at.H
@@ -388,10 +398,10 @@ class UnetEngine:
         qk = ops.conv2d(a1.view(B, H * Fq, 1, T), at.qk, self.buf(B, 2 * H * Fq, 1, T))
         o = self.buf(B, H, Fq, T)
         lse = self.buf(B, H, T)
-        ops.attn_fwd(qk, a1, o, lse, at.scale, qk_bias=at.qk_bias, bucket=at.buckets(T, self.dev), emb=at.emb)
+        ops.attn_fwd(qk, a1, o, lse, at.scale, qk_bias=at.qk_bias, bucket=self._bucket(at, T), emb=at.emb)
         gate = self._film(film, at.film_off[1], N).contiguous()
         zn = ops.conv2d(o, at.proj_out, self.buf(B, N, Fq, T), res=z, oscale=gate, alpha=RS2, rbeta=RS2)
-        blk.attn_saved = (z, stats, scale, gate, a1, qk, o, lse)
+        self._state.attn[blk.idx] = (z, stats, scale, gate, a1, qk, o, lse)
         return zn
 
     def attn_vjp(self, blk, gz, c, pg=None):
@@ -399,7 +409,8 @@ class UnetEngine:
         pg: ParamGrads of a training step: also the branch's parameter gradients (per row into pg.rows / pg.dfilm; the qk weight
         gradient's operands into pg.qk, for param_grads)."""
         at = blk.attn
-        z, stats, scale, gate, a1, qk, o, lse = blk.attn_saved
+        st = self._state
+        z, stats, scale, gate, a1, qk, o, lse = st.attn[blk.idx]
         B, N, Fq, T = z.shape
         H = at.H
         p = blk.p
@@ -411,7 +422,7 @@ class UnetEngine:
         # training: dqk goes straight into this lane's rows of the buffer the qk weight gradient reads after the join
         dqk = self.buf(B, 2 * H * Fq, 1, T) if pg is None else pg.qk[p][0].view(B, 2 * H * Fq, 1, T)
         dv = self.buf(B, H, Fq, T)
-        bucket = at.buckets(T, self.dev)
+        bucket = self._bucket(at, T)
         ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb)
         if pg is not None:
             ops.axpby(a1.view(B, H * Fq, 1, T), pg.qk[p][1].view(B, H * Fq, 1, T))
@@ -423,12 +434,12 @@ class UnetEngine:
         da0 = ops.conv2d(da1.view(B, H, Fq, T), at.proj_in, self.buf(B, N, Fq, T), transpose=True)
         if pg is not None:                                   # a0 = z * scale2 (no GELU), a1 = proj_in(a0); da0, da1 are unscaled
             aoff = at.film_off[0]
-            ops.gn_param_grad_nogelu(z, da0, stats, at.gamma, self._film(self._film_saved, aoff, N), pg.row(p + "norm2.gamma"),
+            ops.gn_param_grad_nogelu(z, da0, stats, at.gamma, self._film(st.film, aoff, N), pg.row(p + "norm2.gamma"),
                                      pg.dfilm[:, aoff:aoff + N])
             a0 = ops.scale_channels(z, scale, self.scratch("a", B * N * Fq * T).view(B, N, Fq, T))
             self._wg(pg, p + "attn_block.proj_in.weight", a0, da1.view(B, H, Fq, T), at.proj_in, 1.0)
         ops.gn_bwd_nogelu(z, da0, gz, scale, stats, gz, RS2 * c)
-        blk.attn_saved = None
+        st.attn[blk.idx] = None
         return gz
 
     # ------------------------------------------------------------------ training: parameter gradients
@@ -452,7 +463,7 @@ class UnetEngine:
     def _layer_wgrad(self, pg, blk, d, G, c):
         """Dilation layer d, znew = rs2*(gate*H(a) + z), a = gelu(z*scale) recomputed into the "a" scratch (the transposed conv
         overwrites it with da next): H's weight gradient and the gate gradient, for the output gradient c*G."""
-        z, stats, scale, gate = blk.saved[d]
+        z, stats, scale, gate = self._state.saved[blk.idx][d]
         B, N, Fq, T = z.shape
         a = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
         ops.scale_gelu(z, scale, a)
@@ -462,19 +473,20 @@ class UnetEngine:
 
     def _layer_gn_grad(self, pg, blk, d, da, c):
         """gamma / affine gradients of layer d from da = (dL/da)/c, the transposed conv's output."""
-        z, stats, scale, gate = blk.saved[d]
+        st = self._state
+        z, stats, scale, gate = st.saved[blk.idx][d]
         N = blk.N
         aoff = blk.film_off[d][0]
-        ops.gn_param_grad(z, da, scale, stats, blk.gamma[d], self._film(self._film_saved, aoff, N), pg.row(blk.p + f"norm.{d}.gamma"),
+        ops.gn_param_grad(z, da, scale, stats, blk.gamma[d], self._film(st.film, aoff, N), pg.row(blk.p + f"norm.{d}.gamma"),
                           pg.dfilm[:, aoff:aoff + N], cs=c)
 
     def _block_out_wgrad(self, pg, blk, g_out):
         """res_conv / proj_out weight gradients (both see rs2*g_out): before the VJP consumes g_out."""
-        x, x2 = blk.inp
+        x, x2 = self._state.inp[blk.idx]
         if blk.res_conv is not None:
             self._wg(pg, blk.p + "res_conv.weight", x, g_out, blk.res_conv, RS2, x2=x2, fenc=blk.fenc)
         if blk.proj_out is not None:
-            self._wg(pg, blk.p + "proj_out.weight", blk.zpo, g_out, blk.proj_out, RS2)
+            self._wg(pg, blk.p + "proj_out.weight", self._state.zpo[blk.idx], g_out, blk.proj_out, RS2)
 
     def param_grads(self, pg, emb_keep):
         """After the (joined) reverse sweep: {state_dict key: gradient} of every trainable parameter.  One fixed-order sum over
@@ -509,6 +521,22 @@ class UnetEngine:
             dh = dx
         return grads
 
+    def _layer_vjp(self, blk, d, g, da, out, c, pg, merge=None):
+        """Dilation layer d backwards: out <- gradient / c w.r.t. the layer's input, given g = gradient / c w.r.t. its output (the
+        chain is linear, the scalar c rides along; out may be g).  da: scratch the transposed conv writes.  With pg the layer's
+        parameter gradients as well.  merge: ops.gn_bwd's, the tail of an N -> N block."""
+        z, stats, scale, gate = self._state.saved[blk.idx][d]
+        if pg is not None:
+            self._layer_wgrad(pg, blk, d, g, c)
+        fs = ops.conv2d(g, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, blk.N // 8))
+        if pg is not None:
+            self._layer_gn_grad(pg, blk, d, da, c)
+        return ops.gn_bwd(z, da, g, scale, stats, out, RS2, merge=merge, fused=fs)
+
+    def _block_done(self, blk):
+        st = self._state
+        st.saved[blk.idx] = st.inp[blk.idx] = st.zpo[blk.idx] = None
+
     def block_vjp(self, blk, g_out, g_in, accumulate=False, consume=False, pg=None):
         """g_in (+)= VJP of the block w.r.t. its (concatenated) input. g_out: [B,Cout,F,T] (may be strided).
         consume=True: g_out is a dense buffer owned by the caller that may be overwritten (saves a full copy).
@@ -528,25 +556,17 @@ class UnetEngine:
             da = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
             src = g_out
             merged = g_in.is_contiguous() and MERGE_TAIL
-            for d in reversed(range(blk.nd)):
-                z, stats, scale, gate = blk.saved[d]
-                if pg is not None:                       # src is the output gradient / rs2 throughout this chain
-                    self._layer_wgrad(pg, blk, d, src, RS2)
-                fs = ops.conv2d(src, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, N // 8))
-                if pg is not None:
-                    self._layer_gn_grad(pg, blk, d, da, RS2)
+            for d in reversed(range(blk.nd)):            # src is the output gradient / rs2 throughout this chain
                 if d == 0 and merged:
                     # the last layer's VJP pass writes g_in = RS2*g_out + RS2*gz itself (gz is never stored)
-                    ops.gn_bwd(z, da, src, scale, stats, g_in, RS2, merge=(g_out, RS2, RS2), fused=fs)
+                    self._layer_vjp(blk, d, src, da, g_in, RS2, pg, merge=(g_out, RS2, RS2))
                 else:
                     if gz is None:
                         gz = self.buf(B, N, Fq, T)
-                    ops.gn_bwd(z, da, src, scale, stats, gz, RS2, fused=fs)
-                    src = gz
+                    src = self._layer_vjp(blk, d, src, da, gz, RS2, pg)
             if not merged:
                 ops.axpby2(g_out, gz, g_in, RS2, RS2)
-            blk.saved = None
-            blk.inp = blk.zpo = None
+            self._block_done(blk)
             return g_in
         # residual path
         if blk.res_conv is not None:
@@ -564,55 +584,50 @@ class UnetEngine:
             gz = ops.axpby(g_out, self.buf(B, N, Fq, T), alpha=RS2)
         da = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
         for d in reversed(range(blk.nd)):
-            z, stats, scale, gate = blk.saved[d]
-            if pg is not None:
-                self._layer_wgrad(pg, blk, d, gz, c)
-            fs = ops.conv2d(gz, blk.H[d], da, dil=blk.dil(d), transpose=True, in_scale=gate, alpha=RS2, vjp_stat=(z, scale, N // 8))
-            if pg is not None:
-                self._layer_gn_grad(pg, blk, d, da, c)
-            ops.gn_bwd(z, da, gz, scale, stats, gz, RS2, fused=fs)
+            self._layer_vjp(blk, d, gz, da, gz, c, pg)
         if blk.attn is not None:
             self.attn_vjp(blk, gz, c, pg)
             c = 1.0
         if pg is not None and blk.proj_in is not None:
-            x, x2 = blk.inp
+            x, x2 = self._state.inp[blk.idx]
             self._wg(pg, blk.p + "proj_in.weight", x, gz, blk.proj_in, c, x2=x2, fenc=blk.fenc)
         if blk.proj_in is not None:
             ops.conv2d(gz, blk.proj_in, g_in, transpose=True, res=g_in, alpha=c, rbeta=1.0)
         else:
             ops.axpby(gz, g_in, alpha=c, beta=1.0)
-        blk.saved = None
-        blk.inp = blk.zpo = None
+        self._block_done(blk)
         return g_in
 
     # ------------------------------------------------------------------ forward
+    def c_plan(self):
+        """The library-side plan over this engine's packed weights (networks/unet_c.py), made on first use.  Every handle and
+        every library-side state - the BABE_UNET_C path's and testing/eval_c.py's - shares this one."""
+        return self._plan.get(self)
+
     def _c_engine(self):
-        """The library-side sequencer for this engine STATE (networks/unet_c.py), or None: fp32 only, BABE_UNET_C=0 switches it
-        off, the measurement hook's per-launch events work with either."""
+        """The library-side sequencer of this handle's state (its own library-side state and workspace over c_plan()), or None:
+        fp32 without attention only, BABE_UNET_C=0 switches it off, the measurement hook's per-launch events work with either."""
         if not USE_C or self.precision != "f32" or self.has_attention:
             return None
-        cu = self.__dict__.get("_cunet")
-        if cu is None:
-            from .unet_c import CUnet
-            parent = self.__dict__.get("_cunet_parent")
-            cu = parent.clone(self) if parent is not None else CUnet(self)
-            self._cunet = cu
-        return cu
+        st = self._state
+        if st.cunet is None:
+            st.cunet = CUnet(self)
+        return st.cunet
 
     def forward(self, C_list, film, train=False):
         """C_list[j]: planar [B,2,bpo,T_j], index 0 = lowest octave. Returns same structure.
         train=True: also keep what the parameter gradients need (vjp(pg=...)); always on this Python sequencer."""
-        self._train = bool(train)
-        self._film_saved = film if train else None
+        st = self._state
+        st.train = bool(train)
+        st.film = film if train else None
         cu = None if train else self._c_engine()
+        st.c_fwd = cu is not None
         if cu is not None:
-            self._c_fwd = True
             return cu.fwd([c.contiguous() for c in C_list], film)
-        self._c_fwd = False
         n, bpo, Ns = self.nocts, self.bpo, self.Ns
         B = C_list[0].shape[0]
         Ts = [C_list[n - 1 - i].shape[-1] for i in range(n)]      # level i time length
-        self.Ts, self.B = Ts, B
+        st.Ts, st.B = Ts, B
         hs, pyrs = [], []
         XC = self.buf(B, Ns[0], bpo, Ts[0])
         for i in range(n):
@@ -634,7 +649,7 @@ class UnetEngine:
                 pyr = pyr_new
             pyrs.append(pyr)
             if train:
-                self.pyrs = pyrs
+                st.pyrs = pyrs
             H = self.block_fwd(self.main_blk[i], XC, film, self.buf(B, Ns[i], Fi, Ts[i]))
             hs.append(H)
             if i < n - 1:
@@ -645,7 +660,7 @@ class UnetEngine:
                 XC = XCn
             else:
                 X = ops.conv2d(pyr, self.pyr_conv[i], self.buf(B, Ns[i], Fi, Ts[i]), res=H, alpha=RS2, rbeta=RS2)
-        self.hs = hs
+        st.hs = hs
         X = self.block_fwd(self.mid_blk, X, film, self.buf(*X.shape))
         Xout = self.block_fwd(self.mid_out, X, film, self.buf(B, 2, bpo * n, Ts[-1]))
         outs = [None] * n
@@ -667,10 +682,11 @@ class UnetEngine:
         """gouts[i]: gradient w.r.t. outs[i] (index 0 = lowest octave). Returns gradients w.r.t. C_list.
         pg: ParamGrads (rows of this call's batch items) after a forward(train=True): also every conv / GroupNorm parameter
         gradient and the FiLM output gradient."""
-        assert pg is None or self._train, "parameter gradients need forward(..., train=True)"
-        if getattr(self, "_c_fwd", False):
-            return self._c_engine().vjp([g.contiguous() for g in gouts])
-        n, bpo, Ns, Ts, B = self.nocts, self.bpo, self.Ns, self.Ts, self.B
+        st = self._state
+        assert pg is None or st.train, "parameter gradients need forward(..., train=True)"
+        if st.c_fwd:
+            return st.cunet.vjp([g.contiguous() for g in gouts])
+        n, bpo, Ns, Ts, B = self.nocts, self.bpo, self.Ns, st.Ts, st.B
         gH = [None] * n
         gX_prev = gXO_prev = None          # gradients w.r.t. X_{j-1}, XO_{j-1} (outputs of the up-samplers)
         for j in range(n):                  # reverse of the decoder order (which ran j = n-1 .. 0)
@@ -707,7 +723,7 @@ class UnetEngine:
         for i in reversed(range(n)):
             Fi = bpo * (i + 1)
             if pg is not None:                 # pyramid conv: its output entered as rs2 * pconv(pyr)
-                self._wg(pg, f"downs.{i}.1.weight", self.pyrs[i], gXm if i == n - 1 else gP, self.pyr_conv[i], RS2)
+                self._wg(pg, f"downs.{i}.1.weight", st.pyrs[i], gXm if i == n - 1 else gP, self.pyr_conv[i], RS2)
             if i == n - 1:
                 gHi = ops.axpby2(gH[i], gXm, self.buf(B, Ns[i], Fi, Ts[i]), 1.0, RS2)
                 gpyr = ops.conv2d(gXm, self.pyr_conv[i], self.buf(B, 2, Fi, Ts[i]), transpose=True, alpha=RS2)
@@ -732,8 +748,8 @@ class UnetEngine:
             else:
                 ops.resample(gpyr, gCi, 2, beta=1.0)
             gC[n - 1 - i] = gCi
-        self.hs = None
+        st.hs = None
         if pg is not None:
-            self.pyrs = self._film_saved = None
-            self._train = False
+            st.pyrs = st.film = None
+            st.train = False
         return gC

@@ -39,10 +39,9 @@ class CEval:
         from ..networks.unet_c import CUnet
         net, st = smp.model, smp._stft
         eng = net.lane_engine(lane or 0)
-        root = net.lane_engine(0)
-        if getattr(root, "_eval_cunet", None) is None:
-            root._eval_cunet = CUnet(root)
-        self.cu = root._eval_cunet if eng is root else root._eval_cunet.clone(eng)
+        # a library-side state of its own over the engine's plan: a score evaluation runs forward and VJP inside one call, and
+        # may fall between a forward and the vjp of the engine state's own
+        self.cu = CUnet(eng)
         cq = net.CQTransform
         self.cq_plan = cqt_plan_of(cq)
         d = EvalDesc()

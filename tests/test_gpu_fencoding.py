@@ -198,7 +198,7 @@ def test_library_side_unet_equals_python_sequencer(monkeypatch, gold_a, B):
     monkeypatch.setattr(ue, "USE_C", True)
     netc = make_net("a")
     y1, g1 = fwd_vjp(netc, x, cn, w)
-    assert netc.engine().__dict__.get("_cunet") is not None, "the library path did not run"
+    assert netc.engine()._c_engine().ws is not None, "the library path did not run"       # its state already holds a workspace
     assert torch.equal(y0, y1) and torch.equal(g0, g1)
 
 
