@@ -134,6 +134,8 @@ class STFTOps:
     def filter_frames(self, spec, H):
         """H: [nbins] (shared) or [B,nbins]."""
         B = spec.shape[0]
+        assert spec.is_contiguous() and spec.shape[1:] == (self.frames, self.nbins, 2)
+        assert H.stride(-1) == 1 and H.shape[-1] == self.nbins and (H.dim() == 1 or H.shape == (B, self.nbins))
         fr = torch.empty(B, self.frames, self.nfft, device=self.dev)
         H_bs = 0 if H.dim() == 1 else H.stride(0)
         check(lib().babe_spec_filter_istft(ptr(spec), ptr(H), H_bs, ptr(fr), B, self.nfft, self.frames,
@@ -173,6 +175,7 @@ class STFTOps:
 
     def mag_stats(self, specX, specY, shared=False):
         B = specX.shape[0]
+        assert specX.is_contiguous() and specY.is_contiguous() and specX.shape == specY.shape == (B, self.frames, self.nbins, 2)
         stats = torch.empty(1 if shared else B, 3, self.nbins, device=self.dev, dtype=torch.float64)
         check(lib().babe_stft_mag_stats(ptr(specX), ptr(specY), ptr(stats), B, self.nbins, self.frames, int(shared),
                                         stream()), "stft_mag_stats")
@@ -212,6 +215,7 @@ class STFTOps:
         2 log-magnitude (utils/blind_bwe_utils.py:148-247); weight [nbins].  STFT^T is the overlap-add of windowed inverse
         FFTs of G * nfft * [1, 1/2, ..., 1/2, 1]."""
         B = rec.shape[0]
+        assert y.shape == rec.shape and weight.is_contiguous() and weight.shape == (self.nbins,)
         X, R = self.stft(rec), self.stft(y)
         part = torch.empty(B, self.NBLK, device=self.dev, dtype=torch.float64)
         check(lib().babe_stft_dist_partial(ptr(X), ptr(R), ptr(weight), ptr(part), self.NBLK, B, self.nbins, self.frames, mode,
