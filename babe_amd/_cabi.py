@@ -235,6 +235,8 @@ SIGS = {
     "babe_attn_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "babe_conv_wgrad_workspace": (_L, [C.POINTER(WgradArgs)]),
     "babe_conv_wgrad_rows": (_I, [C.POINTER(WgradArgs), _P, _P, _F, _P, _P, _L, _F, _P, _L, _P]),
+    "babe_conv_wgrad_bf16_workspace": (_L, [C.POINTER(WgradArgs)]),
+    "babe_conv_wgrad_bf16_rows": (_I, [C.POINTER(WgradArgs), _P, _P, _F, _P, _P, _L, _F, _P, _L, _P]),
     "babe_rows_sum": (_I, [_P, _L, _I, _L, _P, _F, _P]),
     "babe_gn_param_grad": (_I, [_P, _P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P]),
     "babe_linear_bwd_workspace": (_L, [_I, _I, _I]),

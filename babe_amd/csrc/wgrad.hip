@@ -1,4 +1,5 @@
-// Parameter gradients of the CQTDiff+ UNet for training (fp32, gfx950): conv weight gradients on the fp32 MFMA pipe, the FiLM gate
+// Parameter gradients of the CQTDiff+ UNet for training (fp32, gfx950): conv weight gradients on the fp32 MFMA pipe (and, as an
+// opt-in, with bf16 operands on the bf16 MFMA pipe: wgrad_bf16_partial_kernel below), the FiLM gate
 // gradient from the same per-row partials, the per-channel GroupNorm * FiLM reduction and the Linear backward of the FiLM /
 // embedding MLP.  Replaces autograd's convolution_backward (weight), the GroupNorm / Linear parameter backward of
 // the reference's networks/cqtdiff+.py:382-493 and :167-211 in its trainer's loss.backward().
@@ -105,6 +106,254 @@ __global__ __launch_bounds__(256, 2) void wgrad_partial_kernel(babe_wgrad_args a
 #pragma unroll
     for (int j = 0; j < TAPW; ++j) {
         const int tap = NT == 1 ? 0 : tw + 2 * j;
+        if (tap >= NT) continue;
+        for (int r = 0; r < 16; ++r) {
+            const int co = co0 + cw * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (co < a.Cout) dst[(long)co * K + (long)ci * NT + tap] = acc[j][r];
+        }
+    }
+}
+
+// ---- bf16 operands (babe_conv_wgrad_bf16_rows): the same GEMM, tile (64 output x 32 input channels), step (one frequency row of
+// 64 time steps), chunking and workspace layout as above, on v_mfma_f32_32x32x16_bf16.  g and X are read as fp32, rounded once
+// to bf16 (round to nearest even) and kept in LDS as bf16 pairs; positions are the MFMA's k index, so a lane's A fragment is 8
+// consecutive time steps of a g row (one aligned 16-byte LDS read) and its B fragment 8 consecutive time steps of an X row
+// shifted by kw - 1.  An X row sits in LDS with its left neighbour in front and its body 16-byte aligned; the lane reads the 6
+// dwords that cover its 8 steps and both neighbours once per frequency tap and forms the three time taps in registers: kw = 1
+// is the aligned 16-byte read as it is, kw = 0 and kw = 2 are 16-bit funnel shifts (v_alignbit_b32 / v_perm_b32) of it with
+// the dword before and the dword after.  Waves: (output half, taps
+// 0..7 | 8..14) for (5,3) - a wave reads only 3 of the 5 frequency-tap rows -, (output half, position half) for (1,1).
+// Staging: where every row is 16-byte aligned (T % 4 == 0, aligned bases and strides) a thread's float4 loads of step j+1
+// are issued before step j's MFMAs (all addressing precomputed outside the loop), converted and written to the OTHER LDS
+// buffer after them: one barrier per step.  Anything else takes the element-wise staging of the fp32 kernel (into the other
+// buffer as well), which is correct for any alignment and not fast.
+typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 wg_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float wg_f32x2 __attribute__((ext_vector_type(2)));
+typedef float wg_f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned wg_u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int BRW = 36;                  // dwords per LDS row (72 bf16): 16-byte aligned rows, 32 lanes' b128 reads spread over the banks
+
+__device__ __forceinline__ unsigned wg_pack(float lo, float hi) {      // two fp32 -> bf16 pair, round to nearest even (v_cvt_pk_bf16_f32)
+    wg_f32x2 v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, wg_bf16x2));
+}
+__device__ __forceinline__ unsigned short wg_bf16_bits(float v) {
+    return __builtin_bit_cast(unsigned short, (__bf16)v);
+}
+
+// the MFMAs of one staged step for wave (cw, TW); G: [64][BRW] dwords, X: [32][KH][BRW] dwords
+template <int KH, int KW, int TW, int NACC>
+__device__ __forceinline__ void wg_bf16_mma(const unsigned* __restrict__ G, const unsigned* __restrict__ X, int cw, int l31, int h,
+                                            wg_f32x16 (&acc)[NACC]) {
+    constexpr int NT = KH * KW;
+    const unsigned* grow = G + (cw * 32 + l31) * BRW + 4 * h;
+    const unsigned* xrow = X + l31 * (KH * BRW) + 4 * h;
+    if constexpr (NT == 1) {
+#pragma unroll
+        for (int ks = 2 * TW; ks < 2 * TW + 2; ++ks) {
+            const wg_u32x4 av = *(const wg_u32x4*)(grow + 8 * ks);
+            const wg_u32x4 bv = *(const wg_u32x4*)(xrow + 8 * ks);
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(wg_bf16x8, av), __builtin_bit_cast(wg_bf16x8, bv), acc[0],
+                                                            0, 0, 0);
+        }
+    } else {
+        static_assert(KW == 3 || NT == 1, "time taps are formed for KW == 3");
+#pragma unroll 1
+        for (int ks = 0; ks < TT / 16; ++ks) {
+            const wg_u32x4 av = *(const wg_u32x4*)(grow + 8 * ks);
+            const wg_bf16x8 a = __builtin_bit_cast(wg_bf16x8, av);
+#pragma unroll
+            for (int kh = 0; kh < KH; ++kh) {
+                if (kh * KW + KW - 1 < TW * 8 || kh * KW >= TW * 8 + 8) continue;     // no tap of this wave in the row
+                const unsigned* xr = xrow + kh * BRW + 8 * ks;                         // dwords 3 | 4..7 | 8 of the lane's window
+                const unsigned p = xr[3], e = xr[8];
+                const wg_u32x4 d = *(const wg_u32x4*)(xr + 4);
+#pragma unroll
+                for (int kw = 0; kw < KW; ++kw) {
+                    const int j = kh * KW + kw - TW * 8;
+                    if (j < 0 || j >= 8) continue;
+                    wg_u32x4 bv;
+                    if (kw == 0)
+                        bv = wg_u32x4{__builtin_amdgcn_alignbit(d[0], p, 16), __builtin_amdgcn_alignbit(d[1], d[0], 16),
+                                      __builtin_amdgcn_alignbit(d[2], d[1], 16), __builtin_amdgcn_alignbit(d[3], d[2], 16)};
+                    else if (kw == 1)
+                        bv = d;
+                    else
+                        bv = wg_u32x4{__builtin_amdgcn_alignbit(d[1], d[0], 16), __builtin_amdgcn_alignbit(d[2], d[1], 16),
+                                      __builtin_amdgcn_alignbit(d[3], d[2], 16), __builtin_amdgcn_alignbit(e, d[3], 16)};
+                    acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(wg_bf16x8, bv), acc[j], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+template <int KH, int KW, bool ALIGNED>
+__global__ __launch_bounds__(256, 2) void wgrad_bf16_partial_kernel(babe_wgrad_args a, float* __restrict__ ws, int nchunks, int per,
+                                                                     int ntt, int ci_tiles) {
+    constexpr int NT = KH * KW;
+    constexpr int NACC = NT == 1 ? 1 : 8;
+    constexpr int XO = NT == 1 ? 0 : 2;             // an X row in LDS: element jj = t - t0 + XO sits in dword XD + jj / 2 of its row, so
+    constexpr int XD = NT == 1 ? 0 : 3;             // that the body starts 16-byte aligned (dword 4); dword 36 is the next row's unused dword 0
+    constexpr int XCS = KH * BRW;                   // dwords per X channel
+    constexpr int NGQ = CO_T * (TT / 4) / 256;      // float4 loads of g per thread and step (4)
+    constexpr int NXQ = CI_T * KH * (TT / 4) / 256; // ... of X (2 KH: two channels, every tap row)
+    __shared__ __attribute__((aligned(16))) unsigned Gs[2][CO_T * BRW];
+    __shared__ __attribute__((aligned(16))) unsigned Xs[2][CI_T * XCS + 4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    const int cw = wave & 1, tw = wave >> 1;
+    const int co0 = (blockIdx.x / ci_tiles) * CO_T, ci0 = (blockIdx.x % ci_tiles) * CI_T;
+    const int chunk = blockIdx.y, b = blockIdx.z;
+    const long nwork = (long)a.F * ntt;
+    const long w0 = (long)chunk * per;
+    const long w1 = w0 + per < nwork ? w0 + per : nwork;
+    wg_f32x16 acc[NACC];
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    const float* gb = a.g + (long)b * a.g_bs;
+    const float* xb = a.x + (long)b * a.x_bs;
+    const float* x2b = a.x2 ? a.x2 + (long)b * a.x2_bs : nullptr;
+    const int split = a.x2 ? a.cin_split : a.Cin;
+    const int T = a.T, F = a.F;
+
+    // loop-invariant addressing of the aligned staging: thread (r16, quad column q4) loads the g rows r16 + 16 k and every tap
+    // row of the X channels r16 and r16 + 16; what changes with the step, (f + dil (kh - KH/2)) T + t0, is wave-uniform
+    const int q4 = (tid & 15) * 4, r16 = tid >> 4;
+    const float* gsrc = gb + (long)(co0 + r16) * a.g_cs + q4;
+    const long g16 = 16 * a.g_cs;
+    const float* xsrc[2];
+    const float* hsrc = nullptr;                   // halo columns t0 - 1 and t0 + 64: thread i < 32 KH owns (channel, tap row) i
+    int hdf = 0;
+    if constexpr (ALIGNED) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int c = ci0 + r16 + 16 * k;
+            xsrc[k] = c >= a.Cin ? nullptr : (c < split ? xb + (long)c * a.x_cs : x2b + (long)(c - split) * a.x2_cs) + q4;
+        }
+        if (NT > 1 && tid < CI_T * KH) {
+            const int c = ci0 + tid / KH;
+            hdf = a.dil * (tid % KH - KH / 2);
+            hsrc = c >= a.Cin ? nullptr : (c < split ? xb + (long)c * a.x_cs : x2b + (long)(c - split) * a.x2_cs);
+        }
+    }
+    wg_f32x4 gq[NGQ], xq[NXQ];
+    float hl = 0.f, hr = 0.f;
+
+    auto load = [&](int f, int t0) {               // ALIGNED: global -> registers
+        const wg_f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const bool tin = t0 + q4 < T;              // T % 4 == 0: a quad is inside or outside as a whole
+        const long gofs = (long)f * T + t0;
+#pragma unroll
+        for (int k = 0; k < NGQ; ++k)
+            gq[k] = (co0 + r16 + 16 * k < a.Cout && tin) ? *(const wg_f32x4*)(gsrc + k * g16 + gofs) : z;
+#pragma unroll
+        for (int kh = 0; kh < KH; ++kh) {
+            const int fr = f + a.dil * (kh - KH / 2);
+            const bool fin = fr >= 0 && fr < F;
+            const long xofs = (long)fr * T + t0;
+#pragma unroll
+            for (int k = 0; k < 2; ++k) xq[k * KH + kh] = (xsrc[k] && tin && fin) ? *(const wg_f32x4*)(xsrc[k] + xofs) : z;
+        }
+        if (NT > 1) {
+            const int fr = f + hdf;
+            const bool ok = hsrc && fr >= 0 && fr < F;
+            hl = (ok && t0 > 0) ? hsrc[(long)fr * T + t0 - 1] : 0.f;
+            hr = (ok && t0 + TT < T) ? hsrc[(long)fr * T + t0 + TT] : 0.f;
+        }
+    };
+    auto store = [&](int buf) {                    // ALIGNED: registers -> bf16 pairs in LDS
+#pragma unroll
+        for (int k = 0; k < NGQ; ++k) {
+            unsigned* d = &Gs[buf][(r16 + 16 * k) * BRW + (tid & 15) * 2];
+            d[0] = wg_pack(gq[k][0], gq[k][1]);
+            d[1] = wg_pack(gq[k][2], gq[k][3]);
+        }
+#pragma unroll
+        for (int k = 0; k < NXQ; ++k) {
+            unsigned* d = &Xs[buf][(r16 + 16 * (k / KH)) * XCS + (k % KH) * BRW + (tid & 15) * 2 + XD + XO / 2];
+            d[0] = wg_pack(xq[k][0], xq[k][1]);
+            d[1] = wg_pack(xq[k][2], xq[k][3]);
+        }
+        if (NT > 1 && tid < CI_T * KH) {
+            unsigned* d = &Xs[buf][(tid / KH) * XCS + (tid % KH) * BRW + XD];
+            d[0] = wg_pack(0.f, hl);               // jj = 0 (never used), 1 (t0 - 1)
+            d[TT / 2 + 1] = wg_pack(hr, 0.f);      // jj = 66 (t0 + 64), 67 (never used)
+        }
+    };
+    auto stage_any = [&](int buf, int f, int t0) { // element-wise: any alignment, any T
+        unsigned short* G16 = (unsigned short*)Gs[buf];
+        unsigned short* X16 = (unsigned short*)Xs[buf];
+        for (int i = tid; i < CO_T * TT; i += 256) {
+            const int co = i / TT, t = i % TT;
+            float v = 0.f;
+            if (co0 + co < a.Cout && t0 + t < T) v = gb[(long)(co0 + co) * a.g_cs + (long)f * T + t0 + t];
+            G16[co * (2 * BRW) + t] = wg_bf16_bits(v);
+        }
+        constexpr int XW = TT + 2 * XO;            // jj = 0 .. 67 for (5,3): every element a fragment read can touch
+        for (int i = tid; i < CI_T * KH * XW; i += 256) {
+            const int ci = i / (KH * XW);
+            const int r = i % (KH * XW);
+            const int kh = r / XW, jj = r % XW;
+            const int fr = f + a.dil * (kh - KH / 2);
+            const int t = t0 + jj - XO;
+            const int c = ci0 + ci;
+            float v = 0.f;
+            if (c < a.Cin && fr >= 0 && fr < F && t >= 0 && t < T && jj >= XO - KW / 2 && jj < XO + TT + KW / 2) {
+                const float* src = c < split ? xb + (long)c * a.x_cs : x2b + (long)(c - split) * a.x2_cs;
+                v = src[(long)fr * T + t];
+            }
+            X16[ci * (2 * XCS) + kh * (2 * BRW) + 2 * XD + jj] = wg_bf16_bits(v);
+        }
+    };
+
+    int f = (int)(w0 / ntt), tt = (int)(w0 % ntt);
+    if (w0 < w1) {
+        if constexpr (ALIGNED) {
+            load(f, tt * TT);
+            store(0);
+        } else {
+            stage_any(0, f, tt * TT);
+        }
+    }
+    __syncthreads();
+    int buf = 0;
+    for (long w = w0; w < w1; ++w) {
+        if (++tt == ntt) tt = 0, ++f;              // (f, tt) of step w + 1
+        const bool more = w + 1 < w1;
+        if constexpr (ALIGNED)
+            if (more) load(f, tt * TT);
+        if (tw == 0)
+            wg_bf16_mma<KH, KW, 0>(Gs[buf], Xs[buf], cw, l31, h, acc);
+        else
+            wg_bf16_mma<KH, KW, 1>(Gs[buf], Xs[buf], cw, l31, h, acc);
+        if (more) {
+            if constexpr (ALIGNED)
+                store(buf ^ 1);
+            else
+                stage_any(buf ^ 1, f, tt * TT);
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+    if (NT == 1) {                        // (1,1): the two position halves, added in a fixed order
+        float* red = (float*)Xs;
+        if (tw == 1)
+            for (int r = 0; r < 16; ++r) red[(cw * 16 + r) * 64 + lane] = acc[0][r];
+        __syncthreads();
+        if (tw == 1) return;
+        for (int r = 0; r < 16; ++r) acc[0][r] += red[(cw * 16 + r) * 64 + lane];
+    }
+    const long K = (long)a.Cin * NT;
+    float* dst = ws + ((long)b * nchunks + chunk) * a.Cout * K;
+    const int ci = ci0 + l31;
+    if (ci >= a.Cin) return;
+#pragma unroll
+    for (int j = 0; j < NACC; ++j) {
+        const int tap = NT == 1 ? 0 : tw * 8 + j;
         if (tap >= NT) continue;
         for (int r = 0; r < 16; ++r) {
             const int co = co0 + cw * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -275,6 +524,38 @@ extern "C" int babe_conv_wgrad_rows(const babe_wgrad_args* a, float* ws, const f
         hipLaunchKernelGGL((wgrad_partial_kernel<5, 3>), grid, dim3(256), 0, s, *a, ws, nchunks, per, ntt, ci_tiles);
     else
         hipLaunchKernelGGL((wgrad_partial_kernel<1, 1>), grid, dim3(256), 0, s, *a, ws, nchunks, per, ntt, ci_tiles);
+    BABE_LAUNCH_CHECK();
+    hipLaunchKernelGGL(wgrad_rows_kernel, dim3(a->Cout, a->B), dim3(256), 0, s, ws, nchunks, a->Cout, K, oscale, alpha, w, dgate,
+                       dgate_bs, galpha, rows, rows_bs);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
+
+extern "C" long babe_conv_wgrad_bf16_workspace(const babe_wgrad_args* a) { return babe_conv_wgrad_workspace(a); }
+
+extern "C" int babe_conv_wgrad_bf16_rows(const babe_wgrad_args* a, float* ws, const float* oscale, float alpha, const float* w,
+                                         float* dgate, long dgate_bs, float galpha, float* rows, long rows_bs, void* stream) {
+    BABE_CHECK_ARG(wg_args_ok(a), "conv_wgrad_bf16: unsupported arguments (KH x KW must be 5x3 or 1x1, channels <= 512)");
+    BABE_CHECK_ARG(ws && rows && (!dgate || w), "conv_wgrad_bf16: bad pointers");
+    const long K = (long)a->Cin * a->KH * a->KW;
+    BABE_CHECK_ARG(rows_bs >= (long)a->Cout * K, "conv_wgrad_bf16: rows_bs %ld < Cout*Cin*KH*KW", rows_bs);
+    int ntt, ci_tiles, tiles, nchunks, per;
+    wg_plan(*a, ntt, ci_tiles, tiles, nchunks, per);
+    // float4 staging: every row of every view starts on a 16-byte boundary
+    auto al = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+    const bool aligned = a->T % 4 == 0 && al(a->x) && al(a->g) && a->x_cs % 4 == 0 && a->g_cs % 4 == 0 &&
+                         (a->B == 1 || (a->x_bs % 4 == 0 && a->g_bs % 4 == 0)) &&
+                         (!a->x2 || (al(a->x2) && a->x2_cs % 4 == 0 && (a->B == 1 || a->x2_bs % 4 == 0)));
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(tiles, nchunks, a->B);
+#define WG_BF16_LAUNCH(KH, KW, AL) \
+    hipLaunchKernelGGL((wgrad_bf16_partial_kernel<KH, KW, AL>), grid, dim3(256), 0, s, *a, ws, nchunks, per, ntt, ci_tiles)
+    if (a->KH == 5) {
+        if (aligned) WG_BF16_LAUNCH(5, 3, true); else WG_BF16_LAUNCH(5, 3, false);
+    } else {
+        if (aligned) WG_BF16_LAUNCH(1, 1, true); else WG_BF16_LAUNCH(1, 1, false);
+    }
+#undef WG_BF16_LAUNCH
     BABE_LAUNCH_CHECK();
     hipLaunchKernelGGL(wgrad_rows_kernel, dim3(a->Cout, a->B), dim3(256), 0, s, ws, nchunks, a->Cout, K, oscale, alpha, w, dgate,
                        dgate_bs, galpha, rows, rows_bs);

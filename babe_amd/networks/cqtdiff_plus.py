@@ -223,6 +223,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
                                       attention_dict=self.attention_dict, use_fencoding=self.use_fencoding).items():
             _attach(self, key, t.to(self.device), is_buffer=key.endswith(".kernel"))
         self._train_attention = False         # set_trainable(True, attention=True)
+        self._wgrad = None                    # set_trainable(True, wgrad=...): conv weight-gradient arithmetic (None: 'f32')
         self._grad_keys = None                # keys of the parameters handed to _UnetFn by the last training forward
         self.register_load_state_dict_post_hook(lambda m, k: m._reset_params())
         self._reset_params()
@@ -251,6 +252,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
             sd = self._engine_sd()
             self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision,
                                       attention_layers=self.attention_layers, attention_dict=self.attention_dict)
+            self._engine.wgrad = self._wgrad or "f32"
             self._versions = self._param_versions()
         return self._engine
 
@@ -269,7 +271,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
             self._versions = v
 
     # ---------------------------------------------------------------- training
-    def set_trainable(self, flag=True, attention=False):
+    def set_trainable(self, flag=True, attention=False, wgrad=None):
         """requires_grad on exactly the reference's trainable set (is_trainable), so torch.optim.Adam(net.parameters()) updates
         what the reference's Adam updates.  Parameter gradients run in fp32, under the plain and the A-weighted EDM loss alike
         (diff_params/edm.py::loss_fn).
@@ -277,8 +279,21 @@ class Unet_CQT_oct_with_attention(nn.Module):
         csrc/attention_train.hip); without it a network with attention layers raises on the forward while a parameter requires
         grad.  The opt-in is about memory: a qk weight is a [16 F, 8 F] matrix per attention block (25.7 M floats at F = 448), and
         the attention_layers [0,0,0,0,1,1,1,1] layout carries about 141 M of them - weights, gradients and the two Adam moments
-        come to about 2 GB on top of the attention-free network.  On a network without attention layers the flag does nothing."""
+        come to about 2 GB on top of the attention-free network.  On a network without attention layers the flag does nothing.
+        wgrad: arithmetic of the UNet body's conv weight gradients (H.*, res_conv, proj_in / proj_out, the pyramid convs): None,
+        'f32' or 'bf16'.  'bf16' is mixed-precision training: both operands rounded once to bf16, fp32 accumulation, fp32 master
+        weights and gradients (babe_conv_wgrad_bf16_rows).  The signal columns of a folded frequency-encoding conv, the
+        encoding columns, the attention branch and the GroupNorm / FiLM / Linear reductions stay in fp32.  None means 'f32' on a
+        precision='f32' network (bit for bit what it always was); a precision='bf16' / 'bf16x3' network keeps refusing parameter
+        gradients unless wgrad is given: then its forward and input-VJP run on its own conv kernels and the weight gradients
+        on the kernel named here, from the fp32 activations the forward saved."""
+        if wgrad not in (None, "f32", "bf16"):
+            raise ValueError(f"set_trainable: wgrad must be None, 'f32' or 'bf16', got {wgrad!r}")
         self._train_attention = bool(flag) and bool(attention)
+        self._wgrad = wgrad if flag else None
+        eng = getattr(self, "_engine", None)
+        if eng is not None:
+            eng.wgrad = self._wgrad or "f32"
         for k, p in self.named_parameters():
             p.requires_grad_(bool(flag) and is_trainable(k))
         return self
@@ -291,8 +306,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
         if self.has_attention and not self._train_attention:
             raise NotImplementedError("parameter gradients of networks with attention layers are not implemented "
                                       "(opt in with set_trainable(True, attention=True))")
-        if self.precision != "f32":
-            raise NotImplementedError(f"parameter gradients run in fp32 only (precision={self.precision!r})")
+        if self.precision != "f32" and self._wgrad is None:
+            raise NotImplementedError(f"parameter gradients run in fp32 only (precision={self.precision!r}); opt in with "
+                                      "set_trainable(True, wgrad='f32' | 'bf16')")
         bad = [k for k, _ in ps if not is_trainable(k)]
         if bad:
             raise NotImplementedError(f"{bad} is not trainable (fixed in the reference); use set_trainable()")

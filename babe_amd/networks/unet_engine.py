@@ -162,8 +162,9 @@ class ParamGrads:
     (allocated on the caller's stream before the lanes fork, so they outlive the lanes' buffer recycling) and param_grads
     forms each gradient in one batch-summed launch after the join."""
 
-    def __init__(self, layout, rows, dfilm, qk=None):
+    def __init__(self, layout, rows, dfilm, qk=None, wgrad="f32"):
         self.layout, self.rows, self.dfilm, self.qk = layout, rows, dfilm, qk or {}
+        self.wgrad = wgrad                           # conv weight-gradient arithmetic of this step (UnetEngine.wgrad), every lane's
 
     @classmethod
     def new(cls, eng, B):
@@ -174,10 +175,11 @@ class ParamGrads:
             HF, T = blk.attn.H * blk.attn.F, eng._state.Ts[level]
             qk[blk.p] = (torch.empty(B, 2 * HF, T, device=eng.dev, dtype=torch.float32),
                          torch.empty(B, HF, T, device=eng.dev, dtype=torch.float32))
-        return cls(eng.grad_layout, rows, dfilm, qk)
+        return cls(eng.grad_layout, rows, dfilm, qk, eng.wgrad)
 
     def lane(self, b0, b1):
-        return ParamGrads(self.layout, self.rows[b0:b1], self.dfilm[b0:b1], {k: (d[b0:b1], a[b0:b1]) for k, (d, a) in self.qk.items()})
+        return ParamGrads(self.layout, self.rows[b0:b1], self.dfilm[b0:b1], {k: (d[b0:b1], a[b0:b1]) for k, (d, a) in self.qk.items()},
+                          self.wgrad)
 
     def row(self, key):
         off, shape = self.layout[key]
@@ -200,6 +202,9 @@ class UnetEngine:
         opts = attention_options(attention_dict)
         A = lambda flag, Fd: (Fd, opts) if flag else None
         self.precision = precision
+        # training: arithmetic of the UNet body's conv weight gradients, 'f32' or 'bf16' (ops.conv_wgrad_rows).  A training step
+        # reads it once, into its ParamGrads, so the lane clones of this engine always agree
+        self.wgrad = "f32"
         self.Ns, self.num_dils, self.nocts, self.bpo = list(Ns), list(num_dils), num_octs, bins_per_oct
         self.dev = sd["embedding.RFF_freq"].device
         fi = _FilmIndex()
@@ -417,7 +422,7 @@ class UnetEngine:
         if pg is not None:                                   # z' = rs2*(gate2 * proj_out(o) + z), before gz is overwritten
             goff = at.film_off[1]
             self._wg(pg, p + "attn_block.proj_out.weight", o, gz, at.proj_out, RS2 * c, oscale=gate, w=at.proj_out_w,
-                     dgate=pg.dfilm[:, goff:goff + N], galpha=RS2 * c)
+                     dgate=pg.dfilm[:, goff:goff + N], galpha=RS2 * c, precision="f32")
         do = ops.conv2d(gz, at.proj_out, self.buf(B, H, Fq, T), transpose=True, in_scale=gate, alpha=RS2 * c)
         # training: dqk goes straight into this lane's rows of the buffer the qk weight gradient reads after the join
         dqk = self.buf(B, 2 * H * Fq, 1, T) if pg is None else pg.qk[p][0].view(B, 2 * H * Fq, 1, T)
@@ -437,22 +442,24 @@ class UnetEngine:
             ops.gn_param_grad_nogelu(z, da0, stats, at.gamma, self._film(st.film, aoff, N), pg.row(p + "norm2.gamma"),
                                      pg.dfilm[:, aoff:aoff + N])
             a0 = ops.scale_channels(z, scale, self.scratch("a", B * N * Fq * T).view(B, N, Fq, T))
-            self._wg(pg, p + "attn_block.proj_in.weight", a0, da1.view(B, H, Fq, T), at.proj_in, 1.0)
+            self._wg(pg, p + "attn_block.proj_in.weight", a0, da1.view(B, H, Fq, T), at.proj_in, 1.0, precision="f32")
         ops.gn_bwd_nogelu(z, da0, gz, scale, stats, gz, RS2 * c)
         st.attn[blk.idx] = None
         return gz
 
     # ------------------------------------------------------------------ training: parameter gradients
-    def _wg(self, pg, key, x, g, pc, alpha, x2=None, dil=1, fenc=None, **kw):
-        """pg.row(key) <- per-row weight gradient of conv `pc` (input cat(x, x2), output gradient alpha * oscale * g).
+    def _wg(self, pg, key, x, g, pc, alpha, x2=None, dil=1, fenc=None, precision=None, **kw):
+        """pg.row(key) <- per-row weight gradient of conv `pc` (input cat(x, x2), output gradient alpha * oscale * g), in the
+        step's weight-gradient precision pg.wgrad ('f32' | 'bf16') unless `precision` names one (the attention branch: fp32).
         fenc: the encoding table of a folded init-block conv, whose rows have the parameter's [N, 66] layout: the 2 signal
         columns from the ordinary per-row weight gradient on Cin = 2 (into scratch, then a small strided copy), the 64 encoding
-        columns from ops.fenc_wgrad_rows."""
-        ws = self.scratch("wg", ops.conv_wgrad_workspace(x, g, pc.KH, pc.KW, dil, x2))
+        columns from ops.fenc_wgrad_rows; both always in fp32."""
+        prec = "f32" if fenc is not None else (precision or pg.wgrad)
+        ws = self.scratch("wg", ops.conv_wgrad_workspace(x, g, pc.KH, pc.KW, dil, x2, prec))
         rows = pg.row(key)
         if fenc is None:
             assert rows.shape[1] == pc.Cout * pc.Cin * pc.KH * pc.KW, key
-            return ops.conv_wgrad_rows(x, g, pc.KH, pc.KW, rows, dil=dil, x2=x2, alpha=alpha, ws=ws, **kw)
+            return ops.conv_wgrad_rows(x, g, pc.KH, pc.KW, rows, dil=dil, x2=x2, alpha=alpha, ws=ws, precision=prec, **kw)
         assert x2 is None and dil == 1 and not kw and (pc.Cin, pc.KH, pc.KW) == (2, 1, 1) and rows.shape[1] == pc.Cout * 66, key
         B = g.shape[0]
         sig = self.scratch("wg2", B * pc.Cout * 2).view(B, pc.Cout * 2)

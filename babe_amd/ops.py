@@ -525,20 +525,36 @@ def _wgrad_args(x, g, KH, KW, dil=1, x2=None):
     return a
 
 
-def conv_wgrad_workspace(x, g, KH, KW, dil=1, x2=None):
+WGRAD_PRECISIONS = ("f32", "bf16")
+
+
+def _wgrad_fns(precision):
+    """(workspace, rows) entry points of the conv weight gradient: 'f32' (fp32 MFMA) or 'bf16' (operands rounded once to bf16,
+    fp32 accumulation: babe_conv_wgrad_bf16_rows)."""
+    if precision not in WGRAD_PRECISIONS:
+        raise ValueError(f"conv_wgrad: precision must be one of {WGRAD_PRECISIONS}, got {precision!r}")
+    L = lib()
+    return (L.babe_conv_wgrad_workspace, L.babe_conv_wgrad_rows) if precision == "f32" else \
+        (L.babe_conv_wgrad_bf16_workspace, L.babe_conv_wgrad_bf16_rows)
+
+
+def conv_wgrad_workspace(x, g, KH, KW, dil=1, x2=None, precision="f32"):
     """Floats of workspace conv_wgrad_rows needs for these operands."""
-    n = lib().babe_conv_wgrad_workspace(C.byref(_wgrad_args(x, g, KH, KW, dil, x2)))
+    n = _wgrad_fns(precision)[0](C.byref(_wgrad_args(x, g, KH, KW, dil, x2)))
     if n < 0:
         raise _lib.BabeHipError(f"conv_wgrad: unsupported shape x{tuple(x.shape)} g{tuple(g.shape)} k=({KH},{KW})")
     return n
 
 
-def conv_wgrad_rows(x, g, KH, KW, rows, *, dil=1, x2=None, oscale=None, alpha=1.0, w=None, dgate=None, galpha=1.0, ws=None):
+def conv_wgrad_rows(x, g, KH, KW, rows, *, dil=1, x2=None, oscale=None, alpha=1.0, w=None, dgate=None, galpha=1.0, ws=None,
+                    precision="f32"):
     """Per-batch-row conv weight gradient (babe_conv_wgrad_rows): rows[b] (a [B, Cout*Cin*KH*KW] view, any row stride) <-
     alpha * oscale[b, co] * sum_{f,t} g[b, co] * shifted cat(x, x2)[b, ci]; dgate[b, co] <- galpha * <w[co], that sum without
-    oscale>.  x, x2, g: [B, C, F, T] views with contiguous rows (frequency sub-views allowed); ws: workspace (allocated if None)."""
+    oscale>.  x, x2, g: [B, C, F, T] views with contiguous rows (frequency sub-views allowed); ws: workspace (allocated if None).
+    precision='bf16': x and g rounded once to bf16 (nearest even), fp32 accumulation, everything after the sum as in fp32
+    (babe_conv_wgrad_bf16_rows)."""
     a = _wgrad_args(x, g, KH, KW, dil, x2)
-    n = conv_wgrad_workspace(x, g, KH, KW, dil, x2)
+    n = conv_wgrad_workspace(x, g, KH, KW, dil, x2, precision)
     if ws is None:
         ws = torch.empty(n, device=g.device, dtype=torch.float32)
     assert ws.numel() >= n and ws.is_contiguous()
@@ -548,8 +564,8 @@ def conv_wgrad_rows(x, g, KH, KW, rows, *, dil=1, x2=None, oscale=None, alpha=1.
     if dgate is not None:
         assert w is not None and w.is_contiguous() and w.numel() == a.Cout * a.Cin * KH * KW
         assert dgate.shape == (a.B, a.Cout) and dgate.stride(1) == 1
-    check(lib().babe_conv_wgrad_rows(C.byref(a), ptr(ws), ptr(oscale), alpha, ptr(w), ptr(dgate),
-                                     dgate.stride(0) if dgate is not None else 0, galpha, ptr(rows), rows.stride(0), stream()),
+    check(_wgrad_fns(precision)[1](C.byref(a), ptr(ws), ptr(oscale), alpha, ptr(w), ptr(dgate),
+                                   dgate.stride(0) if dgate is not None else 0, galpha, ptr(rows), rows.stride(0), stream()),
           "conv_wgrad_rows")
     return rows
 

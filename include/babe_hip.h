@@ -595,7 +595,8 @@ int babe_attn_vjp(const float* qk, const float* qk_bias, const float* a, const i
                   int T, float scale, void* stream);
 
 
-/* ---- training: parameter gradients of the CQTDiff+ UNet (csrc/wgrad.hip), fp32, no float atomics (every result is a
+/* ---- training: parameter gradients of the CQTDiff+ UNet (csrc/wgrad.hip), fp32 (the conv weight gradient also with bf16
+ * operands: babe_conv_wgrad_bf16_rows), no float atomics (every result is a
  * fixed-order sum: bit-identical run to run and independent of how batch rows are split between calls).
  *
  * Conv weight gradient (autograd's convolution_backward w.r.t. the weight of Conv2d "same", no bias):
@@ -616,6 +617,18 @@ long babe_conv_wgrad_workspace(const babe_wgrad_args* a);
  * gate gradient of znew = rs2*(gate*conv(a) + z) without recomputing the conv (galpha = rs2 * upstream scale). */
 int babe_conv_wgrad_rows(const babe_wgrad_args* a, float* ws, const float* oscale, float alpha, const float* w, float* dgate,
                          long dgate_bs, float galpha, float* rows, long rows_bs, void* stream);
+/* The same weight gradient with bf16 operands (mixed-precision training; v_mfma_f32_32x32x16_bf16).  Arguments, shapes taken,
+ * workspace layout and chunk count (a function of the shape only, not of B) are those of the fp32 pair; -1: shape not taken.
+ * Arithmetic: g and X are read as fp32 and each rounded ONCE to bf16, round to nearest even (v_cvt_pk_bf16_f32), on the way into
+ * LDS; the products of two bf16 values are exact in fp32 (8 x 8 significand bits); sums run in the MFMA's fp32 accumulators; the
+ * chunks' partial tiles are fp32 in ws and are added in a fixed order by the fp32 entry's own tail, so oscale, alpha and the gate
+ * dot galpha * <w, P_b> (w fp32, double sum) are exactly the fp32 entry's.  No float atomics: bit-identical run to run, and row b
+ * does not depend on the other rows of the call.  Outside [0,F) x [0,T) of the VIEW the sum is zero (a sub-view's neighbouring
+ * rows in memory are never read).  Rows that are 16-byte aligned (T % 4 == 0, aligned bases and strides) are staged with
+ * 16-byte loads; anything else takes an element-wise path with the same arithmetic. */
+long babe_conv_wgrad_bf16_workspace(const babe_wgrad_args* a);
+int  babe_conv_wgrad_bf16_rows(const babe_wgrad_args* a, float* ws, const float* oscale, float alpha, const float* w,
+                               float* dgate, long dgate_bs, float galpha, float* rows, long rows_bs, void* stream);
 /* out[i] = beta*out[i] + sum_{b=0..B-1} rows[b*rows_bs + i], b in increasing order, i < n. */
 int babe_rows_sum(const float* rows, long rows_bs, int B, long n, float* out, float beta, void* stream);
 /* Per-channel GroupNorm * FiLM parameter gradient of a = gelu(z * scale), scale[b][c] = gamma[c]*(film_aff[b][c]+1)*r[b][g],

@@ -1,8 +1,13 @@
 """One training step of the full-width CQTDiff+ prior at the reference geometry (B=4, L=368368, 44.1 kHz), split into forward,
-input-VJP, parameter-gradient work (and the conv weight-gradient calls in it), reductions and repack, plus the conv weight-gradient kernel's rate per level against the 157.3
-TFLOP/s fp32 MFMA peak.  Prints one JSON document (profiles/train_bench.json).
+input-VJP, parameter-gradient work (and the conv weight-gradient calls in it), reductions and repack, plus the conv weight-gradient kernel's rate per level against the matching peak: 157.3
+TFLOP/s measured fp32 MFMA peak for --wgrad f32, the 2.5 PFLOP/s dense bf16 SPEC figure for --wgrad bf16.  Prints one JSON
+document (profiles/train_bench.json, profiles/train_bench_wgrad_bf16.json).
 
     python tools/train_bench.py [--B 4] [--L 368368] [--reps 3] [--attention-layers 0,0,0,0,1,1,1,1]
+                                [--wgrad {f32,bf16}] [--precision {f32,bf16}]
+
+--wgrad: arithmetic of the conv weight gradients (set_trainable(True, wgrad=...)); --precision: the network's conv arithmetic
+(forward and input-VJP); --precision bf16 --wgrad bf16 is the full mixed-precision step.
 
 --attention-layers: train a network with time-attention layers (set_trainable(True, attention=True)); the report then also has the
 qk weight-gradient launches of one backward (babe_attn_qk_wgrad, one per attention block after the lane join): their summed time
@@ -16,7 +21,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-PEAK = 157.3e12
+PEAK = {"f32": (157.3e12, "fp32 MFMA peak, measured"), "bf16": (2.5e15, "dense bf16 MFMA, spec")}
 
 
 def timed(fn, reps):
@@ -39,6 +44,8 @@ def main():
     ap.add_argument("--L", type=int, default=368368)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--attention-layers", default=None, help="8 comma-separated flags, e.g. 0,0,0,0,1,1,1,1")
+    ap.add_argument("--wgrad", choices=["f32", "bf16"], default="f32", help="conv weight-gradient arithmetic")
+    ap.add_argument("--precision", choices=["f32", "bf16"], default="f32", help="the network's conv arithmetic")
     a = ap.parse_args()
     att = [int(v) for v in a.attention_layers.split(",")] if a.attention_layers else None
     from babe_amd import ops
@@ -52,14 +59,15 @@ def main():
         adict = dict(num_heads=8, attn_dropout=0.0, bias_qkv=False, N=0, rel_pos_num_buckets=32, rel_pos_max_distance=64,
                      use_rel_pos=True, Nproj=8)
         args.network.attention_layers, args.network.attention_dict = att, adict
-    net = Unet_CQT_oct_with_attention(args, "cuda")
+    net = Unet_CQT_oct_with_attention(args, "cuda", precision=a.precision)
     net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0, attention_layers=att, attention_dict=adict))
-    net.set_trainable(True, attention=bool(att))
+    net.set_trainable(True, attention=bool(att), wgrad=a.wgrad)
     gen = torch.Generator().manual_seed(0)
     x = (0.1 * torch.randn(a.B, a.L, generator=gen)).cuda()
     cn = torch.linspace(-1, 0.5, a.B).reshape(a.B, 1).cuda()
     w = torch.randn(a.B, a.L, generator=gen).cuda()
-    res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES), "attention_layers": att}
+    res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES) if net.concurrent_lanes_ok else 1, "attention_layers": att,
+           "precision": a.precision, "wgrad": a.wgrad}
 
     # input-VJP alone (the sampler's path) and the forward without training state
     def fwd_vjp():
@@ -148,13 +156,14 @@ def main():
         xa = torch.randn(a.B, N, F, T, device="cuda")
         g = torch.randn(a.B, N, F, T, device="cuda")
         rows = torch.empty(a.B, N * N * 15, device="cuda")
-        ws = torch.empty(ops.conv_wgrad_workspace(xa, g, 5, 3, 1), device="cuda")
-        ms = timed(lambda: ops.conv_wgrad_rows(xa, g, 5, 3, rows, dil=2, ws=ws), a.reps + 2)
+        ws = torch.empty(ops.conv_wgrad_workspace(xa, g, 5, 3, 1, precision=a.wgrad), device="cuda")
+        ms = timed(lambda: ops.conv_wgrad_rows(xa, g, 5, 3, rows, dil=2, ws=ws, precision=a.wgrad), a.reps + 2)
         fl = 2.0 * a.B * N * N * 15 * F * T
         lv.append({"level": i, "C": N, "F": F, "T": T, "ms": round(ms, 4), "tflops": round(fl / ms / 1e9, 2),
-                   "frac_peak": round(fl / ms / 1e9 / (PEAK / 1e12), 3)})
+                   "frac_peak": round(fl / ms / 1e9 / (PEAK[a.wgrad][0] / 1e12), 3)})
         del xa, g, rows, ws
     res["wgrad_levels"] = lv
+    res["wgrad_levels_peak_tflops"], res["wgrad_levels_peak_is"] = PEAK[a.wgrad][0] / 1e12, PEAK[a.wgrad][1]
     print(json.dumps(res, indent=1))
 
 
