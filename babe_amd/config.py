@@ -33,6 +33,61 @@ def load_yaml(path):
         return to_attr(yaml.safe_load(f))
 
 
+def parse_value(text):
+    """The value of a `key.sub=value` override, read as YAML reads a scalar or a flow list ('3', '2e-4', 'True', '[1, 2]',
+    'None' stays the string the reference's configurations use), with load_yaml's float coercion."""
+    import yaml
+    return to_attr(yaml.safe_load(text))
+
+
+def apply_overrides(args, overrides):
+    """Apply ['exp.lr=1e-4', 'dset.years=[2017, 2018]', ...] to a nested AttrDict in place; a missing section is created, a
+    path through a non-mapping is an error.  Returns args."""
+    for item in overrides:
+        if "=" not in item:
+            raise ValueError(f"override {item!r} is not of the form key.sub=value")
+        path, text = item.split("=", 1)
+        keys = path.strip().split(".")
+        node = args
+        for k in keys[:-1]:
+            if k not in node:
+                node[k] = AttrDict()
+            node = node[k]
+            if not isinstance(node, dict):
+                raise ValueError(f"override {item!r}: {k!r} is not a section")
+        node[keys[-1]] = parse_value(text)
+    return args
+
+
+def default_train_args(**kw):
+    """default_args(**kw) plus what training reads: the training keys of conf/exp/maestro44k_8s.yaml, conf/dset/maestro_allyears.yaml
+    as `dset`, and a `logging` section (values restated; tests/test_train_conf_cpu.py holds them against the files).
+    Carried but never read, by the reference's loop or by ours: exp.scheduler_step_size / scheduler_gamma (no scheduler is ever
+    built), exp.use_fp16 (precision is the network's and set_trainable's), exp.augmentations (marked TODO there, never applied).
+    exp.model_dir is where checkpoints and the log go; the reference reads a top-level model_dir (conf/conf.yaml), which is set
+    to the same value.  The reference ships no conf/logging file; the logging values are this tree's choice and only the keys
+    the reference's trainer reads are kept (log, log_interval, save_model, save_interval, remove_last_checkpoint,
+    num_sigma_bins, freq_cqt_logging)."""
+    a = default_args(**kw)
+    a.exp.update(to_attr(dict(
+        exp_name="44k_8s", model_dir="None",
+        optimizer=dict(type="adam", beta1=0.9, beta2=0.999, eps=1e-8),
+        lr=2e-4, lr_rampup_it=10000, scheduler_step_size=60000, scheduler_gamma=0.8,
+        batch=4, num_accumulation_rounds=1, use_fp16=False, num_workers=4,
+        seed=42, resume=True, resume_checkpoint="None", resample_factor=1,
+        ema_rate=0.9999, ema_rampup=10000, use_grad_clip=True, max_grad_norm=1,
+        augmentations=dict(rev_polarity=True, pitch_shift=dict(use=False, min_semitones=-6, max_semitones=6),
+                           gain=dict(use=False, min_db=-3, max_db=3)))))
+    a.model_dir = a.exp.model_dir
+    a.dset = to_attr(dict(
+        name="maestro_allyears", callable="datasets.maestro_dataset.MaestroDataset_fs", type="audio",
+        path="/scratch/shareddata/dldata/maestro/v3.0.0/maestro-v3.0.0",
+        years=[2004, 2006, 2008, 2009, 2011, 2013, 2014, 2015, 2017, 2018], years_test=[2009], cache=True, load_len=405000))
+    a.logging = to_attr(dict(log=True, log_interval=1, save_model=True, save_interval=50000, remove_last_checkpoint=False,
+                             num_sigma_bins=20, freq_cqt_logging=50))
+    return a
+
+
 def default_args(sample_rate=44100, audio_len=368368, Ns=(64, 96, 96, 128, 128, 256, 256), T=35, xi=0.2,
                  start_sigma=0.2):
     """The blind-BWE configuration the benchmark is quoted on: conf/tester/blind_bwe_formal_3000_opt_2.yaml,

@@ -441,6 +441,18 @@ class CQT_nsgt:
             return co
         return self.analysis(self.fft.rfft(gx), self.win_bwd_adj)
 
+    def band_energy(self, x):
+        """x [B,L] -> [B, numocts*binsoct]: mean over time of |c|^2 per CQT bin, index 0 = the lowest bin (centre frequencies:
+        self.design["f"]).  fwd_planar, then one reduction launch per octave (stft.plane_bin_energy) into the octaves' slices of
+        one buffer.  The training log's loss-by-frequency (training.Trainer), in place of the reference's CPU librosa CQT."""
+        from .stft import plane_bin_energy
+        co = self.fwd_planar(x)
+        B = co[0].shape[0]
+        buf = torch.empty(self.numocts, B, self.binsoct, device=self.device)
+        for j, c in enumerate(co):
+            plane_bin_energy(c, buf[j])
+        return buf.permute(1, 0, 2).reshape(B, self.numocts * self.binsoct)
+
     # ------------------------------------------------------------------ reference API (complex tensors)
     def fwd(self, x):
         """x [B,1,L] -> list of complex tensors [B,1,binsoct,T_j]."""

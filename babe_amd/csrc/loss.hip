@@ -124,7 +124,54 @@ __global__ __launch_bounds__(256) void fir_sqerr_kernel(const float* __restrict_
     }
 }
 
+// Frequency-resolved error of the training log: out[b][f] = (1/T) sum_t |c[b][.][f][t]|^2 of planar CQT coefficients.  One
+// workgroup of 256 threads per (b, f) row pair.  The sum has ONE order whatever the run: per thread serially over its samples
+// (stride 256, or four consecutive samples at stride 1024 from 16-byte loads when both rows allow them), then down the wave of 64
+// lanes by halving offsets, then the four waves' sums from LDS as (s0 + s1) + (s2 + s3), then one division.  No atomics.
+// Every term is non-negative and no partial sum passes more than ceil(T / 256) + 11 roundings, which bounds the relative error.
+constexpr int BE_THREADS = 256;
+
+__global__ __launch_bounds__(BE_THREADS) void plane_bin_energy_kernel(const float* __restrict__ c, float* __restrict__ out,
+                                                                      int F, int T) {
+    __shared__ float part[BE_THREADS / 64];
+    const long row = blockIdx.x;                         // b * F + f
+    const long b = row / F, f = row - b * F;
+    const float* re = c + ((b * 2) * F + f) * (long)T;
+    const float* im = re + (long)F * T;
+    float acc = 0.f;
+    if ((T & 3) == 0 && aligned16(re) && aligned16(im)) {
+        for (int i = threadIdx.x * 4; i < T; i += BE_THREADS * 4) {
+            const float4 x = *reinterpret_cast<const float4*>(re + i);
+            const float4 y = *reinterpret_cast<const float4*>(im + i);
+            const float t0 = __builtin_fmaf(y.x, y.x, x.x * x.x), t1 = __builtin_fmaf(y.y, y.y, x.y * x.y);
+            const float t2 = __builtin_fmaf(y.z, y.z, x.z * x.z), t3 = __builtin_fmaf(y.w, y.w, x.w * x.w);
+            acc += (t0 + t1) + (t2 + t3);
+        }
+    } else {
+        for (int i = threadIdx.x; i < T; i += BE_THREADS) {
+            const float x = re[i], y = im[i];
+            acc += __builtin_fmaf(y, y, x * x);
+        }
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) out[row] = ((part[0] + part[1]) + (part[2] + part[3])) / (float)T;
+}
+
 }  // namespace
+
+extern "C" int babe_plane_bin_energy(const float* c, float* out, int B, int F, int T, void* stream) {
+    BABE_CHECK_ARG(c && out, "plane_bin_energy: null pointer");
+    BABE_CHECK_ARG(B >= 1 && F >= 1 && T >= 1, "plane_bin_energy: bad shape (B %d, F %d, T %d)", B, F, T);
+    BABE_CHECK_ARG((long)B * F <= 2147483647L, "plane_bin_energy: B * F = %ld rows (at most 2^31 - 1)", (long)B * F);
+    BabeProfScope prof(BABE_SLOT_SAMPLER, 8.0 * B * F * (double)T + 4.0 * B * F, 4.0 * B * F * (double)T, 0, stream);
+    hipLaunchKernelGGL(plane_bin_energy_kernel, dim3((unsigned)((long)B * F)), dim3(BE_THREADS), 0, (hipStream_t)stream, c, out,
+                       F, T);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
 
 extern "C" int babe_fir_sqerr_fwd(const float* est, long est_bs, const float* tgt, long tgt_bs, const float* taps, int K,
                                   float* ew, float* err2, int B, int L, void* stream) {

@@ -61,20 +61,23 @@ class EDM:
         target = (1 / cout) * (x - cskip * (x + noise))
         return cin * (x + noise), target, cnoise
 
-    def loss_fn(self, net, x):
+    def loss_fn(self, net, x, return_residual=False):
         """(error**2 [B,L], sigma [B,1]) of the denoising objective for clean audio x [B,L]: draws sigma (torch.rand) then the
         noise (torch.randn), like the reference.  The reference's DC correction reads args.net.use_cqt_DC_correction - a key no
         configuration defines (they have exp.use_cqt_DC_correction) - inside a bare except, so it never runs; it is left out
         here for the same result.  With diff_params.aweighting.use_aweighting the error goes through the A-weighting FIR before
         the square (edm.py:201-203): subtraction, filter and square are one HIP kernel (stft.fir_sqerr), and so is their backward;
-        without it the tail is the two torch operations below, as before."""
+        without it the tail is the two torch operations below, as before.
+        return_residual: also return the signed error before the square (the A-weighted one where that is on), detached - what
+        the training log's loss-by-frequency transforms (training.Trainer); the other two results are the same tensors either way."""
         sigma = self.sample_ptrain_safe(x.shape[0]).unsqueeze(-1).to(x.device)
         inp, target, cnoise = self.prepare_train_preconditioning(x, sigma)
         estimate = net(inp, cnoise)
         if self.AW is not None:
-            return fir_sqerr(estimate, target, self.AW.to(estimate.device).taps), sigma
+            err2, ew = fir_sqerr(estimate, target, self.AW.to(estimate.device).taps, return_filtered=True)
+            return (err2, sigma, ew) if return_residual else (err2, sigma)
         error = estimate - target
-        return error ** 2, sigma
+        return (error ** 2, sigma, error.detach()) if return_residual else (error ** 2, sigma)
 
     def cskip(self, sigma):
         return self.sigma_data ** 2 * (sigma ** 2 + self.sigma_data ** 2) ** -1

@@ -79,6 +79,24 @@ def fir_sqerr(est, tgt, taps, return_filtered=False):
     return (err2, ew) if return_filtered else err2
 
 
+def plane_bin_energy(c, out=None):
+    """Mean energy per frequency row of planar complex coefficients: c [B,2,F,T] device (re, im planes, contiguous) ->
+    [B,F] with out[b,f] = mean_t (re^2 + im^2), one HIP launch (babe_plane_bin_energy, csrc/loss.hip), bit-identical from run to
+    run.  `out`: where to write, a contiguous [B,F] float32 device tensor (CQT_nsgt.band_energy passes the octaves' slices of
+    one [numocts,B,F] buffer)."""
+    if not c.is_cuda:
+        raise RuntimeError("babe_amd.plane_bin_energy runs on the GPU only (no CPU fallback)")
+    if c.dim() != 4 or c.shape[1] != 2 or c.dtype != torch.float32 or not c.is_contiguous():
+        raise ValueError(f"plane_bin_energy: c must be a contiguous float32 [B,2,F,T] tensor (got {tuple(c.shape)}, {c.dtype})")
+    B, _, F, T = c.shape
+    if out is None:
+        out = torch.empty(B, F, device=c.device)
+    elif not (out.is_cuda and out.dtype == torch.float32 and out.shape == (B, F) and out.is_contiguous()):
+        raise ValueError("plane_bin_energy: out must be a contiguous float32 [B,F] device tensor")
+    check(lib().babe_plane_bin_energy(ptr(c), ptr(out), B, F, T, stream(c)), "plane_bin_energy")
+    return out
+
+
 def mask_blend(mask, a=None, b=None):
     """mask*a + (1-mask)*b with a/b optional (None = 0); mask [L] (shared) or [B,L]."""
     ref = a if a is not None else b

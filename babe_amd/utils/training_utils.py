@@ -1,6 +1,7 @@
 """Pre-emphasis filters of the training loss.  Mirrors the call surface of the reference's utils/training_utils.py FIRFilter
 (:55-138, after auraloss.perceptual; Wright & Valimaki 2019): the filter design is host-side scipy exactly like the reference, the
-filtering itself is the HIP FIR (babe_fir_same) instead of F.conv1d.  Device tensors only, no CPU fallback."""
+filtering itself is the HIP FIR (babe_fir_same) instead of F.conv1d.  Device tensors only, no CPU fallback.
+resample_batch (:140-221) is the trainer's batch resampler on the HIP sinc resampler."""
 import numpy as np
 import scipy.signal
 import torch
@@ -20,6 +21,50 @@ def aweighting_taps(fs, ntaps):
     b, a = scipy.signal.bilinear(num, den, fs=fs)
     w, h = scipy.signal.freqz(b, a, worN=512, fs=fs)
     return scipy.signal.firls(ntaps, w, abs(h), fs=fs)
+
+
+def _rate_rule(fs, fs_target):
+    """(orig, new) handed to the resampler for one source rate - the table of reference training_utils.py:140-221 - or None
+    where the row passes through as it is."""
+    fs, fs_target = int(fs), int(fs_target)
+    if fs_target == 22050:
+        rule = {44100: (2, 1), 48000: (160 * 2, 147)}
+    elif fs_target == 44100:
+        rule = {44100: None, 48000: (160, 147), 22050: (1, 2)}
+    else:
+        rule = {44100: (44100, fs_target), 48000: (48000, fs_target)}
+    if fs not in rule:
+        raise ValueError(f"resample_batch: no rule for a {fs} Hz row and target {fs_target} Hz (known: {sorted(rule)})")
+    return rule[fs]
+
+
+def resample_batch(audio, fs, fs_target, length_target):
+    """audio [B,L] on the GPU, fs one rate per row (tensor or list) -> [B, length_target] at fs_target: the reference's rule
+    table (utils/training_utils.py:140-221; 48000 -> 44100 is its approximation 160/147, 48000 -> 22050 is 320/147) on
+    babe_amd.resample.resample, the HIP sinc resampler.  A batch at one rate is one launch; mixed rates go row by row.  The
+    result is cropped to [..., :length_target].
+    Two deliberate departures: a rate without a rule raises ValueError (the reference prints a warning and copies the row
+    unresampled, i.e. trains on audio at the wrong pitch), and so does a resampled row shorter than length_target (the
+    reference returns the short batch, or fails on the row assignment)."""
+    from ..resample import resample
+    rates = [int(r) for r in (fs.tolist() if torch.is_tensor(fs) else fs)]
+    if audio.dim() != 2 or len(rates) != audio.shape[0]:
+        raise ValueError(f"resample_batch: audio {tuple(audio.shape)} needs one rate per row, got {len(rates)}")
+    rules = [_rate_rule(r, fs_target) for r in rates]
+
+    def one(x, rule, what):
+        y = x if rule is None else resample(x, rule[0], rule[1])
+        if y.shape[-1] < length_target:
+            raise ValueError(f"resample_batch: {what} gives {y.shape[-1]} samples at {fs_target} Hz, fewer than "
+                             f"length_target = {length_target}")
+        return y[..., :length_target]
+
+    if len(set(rates)) == 1:
+        return one(audio, rules[0], f"{audio.shape[-1]} samples at {rates[0]} Hz")
+    out = torch.empty(audio.shape[0], length_target, device=audio.device, dtype=torch.float32)
+    for i, rule in enumerate(rules):
+        out[i] = one(audio[i], rule, f"row {i} ({audio.shape[-1]} samples at {rates[i]} Hz)")
+    return out
 
 
 class _Fir(torch.autograd.Function):

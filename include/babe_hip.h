@@ -471,6 +471,13 @@ int babe_fir_sqerr_bwd(const float* g, long g_bs, const float* ew, const float* 
                        float* dest, int B, int L, void* stream);
     /* h = 2 * g * ew;   dest[b][m] = sum_k taps[k] * h[b][m - k + K/2]   (the transpose of the forward FIR)       */
 
+/* ---- frequency-resolved error of the training log (stands in for training/trainer.py:329-334, a librosa CQT on the CPU): mean
+ * energy per CQT bin of planar coefficients, one workgroup per (b, f).  Any T >= 1; B, F or T <= 0 or a NULL pointer return
+ * BABE_ERR_ARG before a launch.  fp32 sums in one fixed order (per thread, within the wave, across the waves through LDS) and no
+ * atomics: bit-identical from run to run; relative error at most (ceil(T / 256) + 11) * 2^-24, every term being non-negative. */
+int babe_plane_bin_energy(const float* c, float* out, int B, int F, int T, void* stream);
+    /* c [B][2][F][T] planar (re, im), out[b][f] = (1/T) * sum_t (re^2 + im^2) */
+
 /* ---- sampler element-wise steps: testing/blind_bwe_sampler.py:503-516, :125-135, :701-761; edm.py:144-159 */
 /* out = a*x + b*y + c*z (y, z optional) over n elements */
 int babe_lincomb3(float* out, float a, const float* x, float b, const float* y, float c, const float* z, long n,
