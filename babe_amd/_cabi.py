@@ -212,6 +212,8 @@ SIGS = {
     "babe_fir_sqerr_fwd": (_I, [_P, _L, _P, _L, _P, _I, _P, _P, _I, _I, _P]),
     "babe_fir_sqerr_bwd": (_I, [_P, _L, _P, _P, _I, _P, _I, _I, _P]),
     "babe_plane_bin_energy": (_I, [_P, _P, _I, _I, _I, _P]),
+    "babe_lsd_num_frames": (_L, [_I, _I, _I]),
+    "babe_lsd_frames": (_I, [_P, _L, _P, _L, _I, _I, _I, _I, _I, _I, _F, _P, _P, _P]),
     "babe_lincomb3": (_I, [_P, _F, _P, _F, _P, _F, _P, _L, _P]),
     "babe_add_obs_noise": (_I, [_P, _L, _P, _L, _F, _I, _L, _P]),
     "babe_mask_blend": (_I, [_P, _P, _L, _P, _P, _I, _L, _P]),

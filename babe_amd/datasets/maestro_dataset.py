@@ -6,13 +6,17 @@ import os
 from .segments import SegmentStream
 
 
-def maestro_train_files(path, years):
-    """Paths of the rows of <path>/maestro-v3.0.0.csv with year in `years` and split == "train", in the file's order
-    (maestro_dataset.py:44-54)."""
+def maestro_files(path, years, split):
+    """Paths of the rows of <path>/maestro-v3.0.0.csv with year in `years` and the given split, in the file's order."""
     years = {int(y) for y in years}
     with open(os.path.join(path, "maestro-v3.0.0.csv"), newline="") as f:
         return [os.path.join(path, r["audio_filename"]) for r in csv.DictReader(f)
-                if int(r["year"]) in years and r["split"] == "train" and r["audio_filename"]]
+                if int(r["year"]) in years and r["split"] == split and r["audio_filename"]]
+
+
+def maestro_train_files(path, years):
+    """The training split, in the file's order (maestro_dataset.py:44-54)."""
+    return maestro_files(path, years, "train")
 
 
 class MaestroDataset(SegmentStream):

@@ -54,9 +54,9 @@ def assemble(preds, plan, L, segL, discard_end=200, ola=256):
     return out
 
 
-def restore_file(sampler, y, batch_size=8, blind=True, filt=None):
+def restore_file(sampler, y, batch_size=8, blind=True, filt=None, filt_type="fc_A"):
     """y [L] device tensor -> (restored [L], [(start, end, filter_params)]) using sampler.predict_blind_bwe
-    (or predict_bwe(filt, 'fc_A') when blind=False) on batches of segments."""
+    (or predict_bwe(filt, filt_type) when blind=False) on batches of segments."""
     segL = sampler.args.exp.audio_len
     ola = sampler.args.tester.get("formal_test", {}).get("OLA", 256) if hasattr(sampler.args.tester, "get") else 256
     L = y.shape[-1]
@@ -70,7 +70,7 @@ def restore_file(sampler, y, batch_size=8, blind=True, filt=None):
             fp = fp if fp.dim() == 3 else fp.unsqueeze(0).expand(chunk.shape[0], -1, -1)
             filters += [fp[j] for j in range(chunk.shape[0])]
         else:
-            x = sampler.predict_bwe(chunk, filt, "fc_A")
+            x = sampler.predict_bwe(chunk, filt, filt_type)
         preds.append(x)
     preds = torch.cat(preds, 0)
     out = assemble(preds, plan, L, segL, 200, ola)

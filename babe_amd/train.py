@@ -17,7 +17,6 @@ keeps the EMA, the checkpoints and the log.  exp.seed_per_rank=False gives every
 the averaged gradient is then the single-rank one.
 """
 import argparse
-import importlib
 import os
 
 import numpy as np
@@ -48,11 +47,8 @@ def load_config(path, overrides=()):
 def build_dataset(args, seed):
     """The dataset object of dset.callable, with the arguments utils/setup.py:10-34 passes: the _fs class gets the dset section
     alone, the others the file rate and length before exp.resample_factor."""
-    name = args.dset.callable
-    if name.startswith("datasets."):
-        name = "babe_amd." + name
-    mod, cls = name.rsplit(".", 1)
-    cls = getattr(importlib.import_module(mod), cls)
+    from .datasets import resolve
+    cls = resolve(args.dset.callable)
     overfit = bool(args.dset.get("overfit", False))
     if args.dset.name == "maestro_allyears":
         return cls(args.dset, overfit=overfit, seed=seed)

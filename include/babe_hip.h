@@ -478,6 +478,20 @@ int babe_fir_sqerr_bwd(const float* g, long g_bs, const float* ew, const float* 
 int babe_plane_bin_energy(const float* c, float* out, int B, int F, int T, void* stream);
     /* c [B][2][F][T] planar (re, im), out[b][f] = (1/T) * sum_t (re^2 + im^2) */
 
+/* ---- evaluation metric: log-spectral distance (LSD) of an estimate against a reference, this project's own definition (the
+ * reference computes none; INTEGRATION.md "Evaluating a prior").  Full frames only, T = 1 + (L - nfft) / hop, no centring and no
+ * padding; periodic Hann window; P = |rfft(w frame)|^2 (unnormalised), floored at floor_pow; d[t][k] = log10 Pref - log10 Pest;
+ * frame_lsd[b][t] = sqrt(mean over k in [k_lo, k_hi) of d^2); clip_lsd[b] = mean over t of frame_lsd[b][t].
+ * nfft a power of two in 256..4096, 1 <= hop <= nfft, L >= nfft, 0 <= k_lo < k_hi <= nfft/2 + 1, floor_pow > 0, 1 <= B <= 65535,
+ * non-NULL pointers (clip_lsd may be NULL: the second launch is left out); anything else returns BABE_ERR_ARG before a launch.
+ * ref_bs / est_bs: row strides in elements (the signals may live in different buffers, any 4-byte alignment); nothing outside
+ * [0, L) of a row is read, nothing but the outputs is written.  One workgroup per (frame, clip), one complex FFT for both
+ * signals, sums in one fixed order without atomics: bit-identical from run to run. */
+long babe_lsd_num_frames(int L, int nfft, int hop);                       /* host only; -1 on bad arguments */
+int babe_lsd_frames(const float* ref, long ref_bs, const float* est, long est_bs, int L, int B, int nfft, int hop,
+                    int k_lo, int k_hi, float floor_pow, float* frame_lsd /* [B][T] */, float* clip_lsd /* [B], may be NULL */,
+                    void* stream);
+
 /* ---- sampler element-wise steps: testing/blind_bwe_sampler.py:503-516, :125-135, :701-761; edm.py:144-159 */
 /* out = a*x + b*y + c*z (y, z optional) over n elements */
 int babe_lincomb3(float* out, float a, const float* x, float b, const float* y, float c, const float* z, long n,
