@@ -1,4 +1,5 @@
-"""HIP CQT (four-step DFT on the MFMA conv kernel + LDS band FFTs) vs the oracle NSGT.  Needs a MI355X."""
+"""HIP CQT (four-step DFT on the MFMA conv kernel + LDS band FFTs) vs the oracle NSGT.  Needs a MI355X.
+(The band, gather and spec_scale kernels per band and per clip on small designs, every band length and path: tests/test_gpu_cqt_bands.py.)"""
 import pytest
 import torch
 
