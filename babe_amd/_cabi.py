@@ -179,6 +179,8 @@ SIGS = {
     "babe_unet_workspace_bytes": (_L, [_P, _I, C.POINTER(_I)]),
     "babe_unet_fwd": (_I, [_P, _P, C.POINTER(_P), _P, _L, _I, C.POINTER(_I), _P, _L, C.POINTER(_P), _P]),
     "babe_unet_vjp": (_I, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P]),
+    "babe_unet_form_get": (_I, [_I]),
+    "babe_unet_form_set": (_I, [_I, _I]),
     "babe_axpby4d": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),
     "babe_axpby2_4d": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),
     "babe_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -12,6 +12,7 @@
 // over one plan.  Host code only: every tensor operation is one of this library's extern "C" functions.
 #include "common.h"
 #include "../../include/babe_hip.h"
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -50,6 +51,28 @@ extern "C" int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, i
     if (pc->fwd_wino4 && babe_conv2d_wino4_supported(a)) return babe_conv2d_wino4(a, transpose ? pc->bwd_wino4 : pc->fwd_wino4, stream);
     if (pc->fwd_wino && babe_conv2d_wino_supported(a)) return babe_conv2d_wino(a, transpose ? pc->bwd_wino : pc->fwd_wino, stream);
     return babe_conv2d_nt(a, pc->nt, stream);
+}
+
+/* The two forms BOTH sequencers of the UNet layer path act on (this file's and babe_amd/networks/unet_engine.py's), one value
+ * per process: the environment is read here, once, and nowhere else; babe_unet_form_set changes a form at run time and
+ * babe_amd/forms.py (FORMS.fuse_gn_fwd / FORMS.fuse_gn) is a view of these values.
+ *   BABE_FORM_FUSE_GN_FWD  the next layer's GroupNorm sums from the forward F(4,5) conv's epilogue (babe_conv_args::stat_mode 1);
+ *                          on by default, BABE_FUSE_GN_FWD=0: babe_gn_partial's own pass
+ *   BABE_FORM_FUSE_GN      the GroupNorm-VJP partial sums from the transposed F(4,5) conv's epilogue (stat_mode 2); off by default
+ *                          (measured slower, profiles/r06_gn_fusion_experiment.txt), BABE_FUSE_GN=1 turns it on */
+static std::atomic<int>& unet_form(int which) {
+    static std::atomic<int> fwd{[] { const char* e = getenv("BABE_FUSE_GN_FWD"); return (e && atoi(e) == 0) ? 0 : 1; }()};
+    static std::atomic<int> vjp{[] { const char* e = getenv("BABE_FUSE_GN"); return (e && atoi(e) != 0) ? 1 : 0; }()};
+    return which == BABE_FORM_FUSE_GN ? vjp : fwd;
+}
+extern "C" int babe_unet_form_get(int which) {
+    if (which != BABE_FORM_FUSE_GN_FWD && which != BABE_FORM_FUSE_GN) return -1;
+    return unet_form(which).load(std::memory_order_relaxed);
+}
+extern "C" int babe_unet_form_set(int which, int on) {
+    BABE_CHECK_ARG(which == BABE_FORM_FUSE_GN_FWD || which == BABE_FORM_FUSE_GN, "unet_form_set: no form %d", which);
+    unet_form(which).store(on ? 1 : 0, std::memory_order_relaxed);
+    return BABE_OK;
 }
 
 namespace {
@@ -234,11 +257,13 @@ struct Ctx {
             const int dil = blk.k53 ? (1 << d) : 1, cg = N / G_GROUPS;
             double* npart = nullptr;
             int nS = 0;
-            if (fuse_gn_fwd() && d + 1 < blk.nd && blk.k53 && cg % 4 == 0) {
+            // (carved whatever the form is, so that babe_unet_workspace_bytes does not depend on it: a form may change between
+            // the dry pass that sized the workspace and the evaluation)
+            if (d + 1 < blk.nd && blk.k53 && cg % 4 == 0) {
                 nS = stat_slots(cg, Fq, T, dil);
                 npart = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * nS * 2 * 2));
             }
-            const bool made = conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, npart);
+            const bool made = conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, form(BABE_FORM_FUSE_GN_FWD) ? npart : nullptr);
             zS = made ? nS : 0;
             zpart = npart;
             saved[d] = Saved{z, stats, scale, gate};
@@ -264,20 +289,13 @@ struct Ctx {
         *part = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * (Sf > Sp ? Sf : Sp) * 2));     // (floats: 2 per double)
         if (dry() || err) return 0;
         babe_conv_args a = conv_args(src, da, dil, nullptr, nullptr, sv.gate, nullptr, RS2, 0.f);
-        if (fuse_gn() && blk.k53 && cg % 4 == 0 && z.dense() && da.dense()) {
+        if (form(BABE_FORM_FUSE_GN) && blk.k53 && cg % 4 == 0 && z.dense() && da.dense()) {
             a.stat_mode = 2; a.stat_cg = cg; a.stat_x = z.p; a.stat_scale = sv.scale; a.stat_part = *part;
         }
         ck(babe_conv2d_auto(&a, &blk.H[d], 1, st));
         return a.stat_mode == 2 ? Sf : 0;
     }
-    static bool fuse_gn_fwd() {
-        static const bool on = [] { const char* e = getenv("BABE_FUSE_GN_FWD"); return !(e && atoi(e) == 0); }();   // (on by default: ops.py FUSE_GN_FWD)
-        return on;
-    }
-    static bool fuse_gn() {
-        static const bool on = [] { const char* e = getenv("BABE_FUSE_GN"); return e && atoi(e) != 0; }();   // (off by default: ops.py FUSE_GN)
-        return on;
-    }
+    static bool form(int which) { return unet_form(which).load(std::memory_order_relaxed) != 0; }
     void gn_bwd(const Saved& sv, const View& da, const View& gy, const View& gx, float rbeta, const View* acc, double* part, int Sf) {
         const View& z = sv.z;
         const long n = (long)(z.C / G_GROUPS) * z.F * z.T;

@@ -16,17 +16,14 @@ what an evaluation leaves between forward and vjp is one _State per handle (Unet
 """
 import copy
 import math
-import os
 
 import torch
 
 from .. import ops
+from ..forms import FORMS
 from .unet_c import CPlan, CUnet
 
 RS2 = 1.0 / math.sqrt(2.0)
-# the library-side sequencer (csrc/unet_engine.hip): one C call per direction.  BABE_UNET_C=1 enables it (fp32 networks).
-USE_C = os.environ.get("BABE_UNET_C", "0") == "1"
-MERGE_TAIL = os.environ.get("BABE_MERGE_TAIL", "1") != "0"      # 0: N -> N block VJP stores gz and merges with axpby2 (A/B switch)
 
 
 class _Attn:
@@ -554,7 +551,7 @@ class UnetEngine:
         if pg is not None:
             self._block_out_wgrad(pg, blk, g_out)
         if (blk.res_conv is None and blk.proj_out is None and blk.proj_in is None and not accumulate and blk.nd > 0
-                and g_out.is_contiguous() and ops.AXPBY2 and blk.attn is None):
+                and g_out.is_contiguous() and FORMS.axpby2 and blk.attn is None):
             # N -> N block (every main block of the encoder, the middle block): the residual path's RS2*g_out and the main path's
             # c*gz are merged in ONE pass at the end (12 instead of 8 + 12 bytes per element).  For that g_out has to survive the
             # chain: the first layer's gn_bwd reads it as its residual input and writes into a buffer of its own (same traffic),
@@ -562,7 +559,7 @@ class UnetEngine:
             gz = self.buf(B, N, Fq, T) if blk.nd > 1 else None
             da = self.scratch("a", B * N * Fq * T).view(B, N, Fq, T)
             src = g_out
-            merged = g_in.is_contiguous() and MERGE_TAIL
+            merged = g_in.is_contiguous() and FORMS.merge_tail
             for d in reversed(range(blk.nd)):            # src is the output gradient / rs2 throughout this chain
                 if d == 0 and merged:
                     # the last layer's VJP pass writes g_in = RS2*g_out + RS2*gz itself (gz is never stored)
@@ -614,7 +611,7 @@ class UnetEngine:
     def _c_engine(self):
         """The library-side sequencer of this handle's state (its own library-side state and workspace over c_plan()), or None:
         fp32 without attention only, BABE_UNET_C=0 switches it off, the measurement hook's per-launch events work with either."""
-        if not USE_C or self.precision != "f32" or self.has_attention:
+        if not FORMS.unet_c or self.precision != "f32" or self.has_attention:
             return None
         st = self._state
         if st.cunet is None:

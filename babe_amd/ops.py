@@ -1,12 +1,12 @@
 """Python views of the babe_hip C-ABI ops (UNet building blocks).  Device tensors only."""
 import ctypes as C
 import math
-import os
 
 import torch
 
 from . import _lib
 from ._cabi import ConvArgs, CPackedConv, WgradArgs
+from .forms import FORMS
 from ._lib import check, lib, ptr, stream
 
 RSQRT2 = 1.0 / math.sqrt(2.0)
@@ -37,25 +37,6 @@ def _fill_out(a, pc, out, Cin, dil, res, oscale, alpha, rbeta):
 
 
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2}
-BF16_HBM_F32 = os.environ.get("BABE_BF16_HBM_F32", "1") != "0"
-# debug switch for the (5,3) fp32 convs: 0 = direct kernel only, 2 = Winograd F(2,3) only, 4 (default) = F(4,3) where the
-# problem qualifies, F(2,3) otherwise
-_W = os.environ.get("BABE_CONV_WINO", "4")
-# BABE_CONV_FEWCO=0: no raw-weight image, so the few-output-channel kernel never runs
-FEWCO = os.environ.get("BABE_CONV_FEWCO", "1") != "0"
-WINOGRAD = _W != "0"
-WINOGRAD4 = _W not in ("0", "2", "1")
-# nested Winograd F(2,5) x F(4,3) (csrc/conv_wino45.hip) for the (5,3) layers it supports; BABE_CONV_WINO45=0 switches it off
-WINOGRAD45 = WINOGRAD4 and os.environ.get("BABE_CONV_WINO45", "1") != "0"
-# nested Winograd F(4,5) x F(4,3) (csrc/conv_wino85.hip) for the (5,3) layers with 128-channel output tiles whose row quads are
-# at least 80 % full (the rule babe_conv2d_auto applies); BABE_CONV_F45=0 leaves them to the F(2,5) x F(4,3) kernel
-WINOGRAD85 = WINOGRAD45 and os.environ.get("BABE_CONV_F45", "1") != "0"
-
-
-# (1,1) convs: 64-channel output tiles per workgroup (two 32-row tiles) wherever both directions' tile counts are even, instead of
-# the library default of up to 128: more workgroups on the small planes of the deep levels, where a launch has a few hundred
-# (whole-job A/B, same box: 2.431 / 2.432 vs 2.423 / 2.424 audio-sec/s; one tile: 2.399 / 2.395).  0 = library default.
-_C11_NT = int(os.environ.get("BABE_CONV11_NT", "2"))
 
 
 def _io(pc, tf):
@@ -71,13 +52,13 @@ def _io(pc, tf):
 #   wino85         nested F(4,5) x F(4,3): input channels % 16 == 0, output channels a multiple of a tile width (128, 96 or 64)
 _FAMILIES = (
     ("wino", lambda L, pc, tf: L.babe_conv_packed_size_wino(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino,
-     lambda pc, tf: pc.KW == 3 and WINOGRAD),
+     lambda pc, tf: pc.KW == 3 and FORMS.winograd),
     ("wino4", lambda L, pc, tf: L.babe_conv_packed_size_wino4(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino4,
-     lambda pc, tf: pc.KW == 3 and WINOGRAD4),
+     lambda pc, tf: pc.KW == 3 and FORMS.winograd4),
     ("wino45", lambda L, pc, tf: L.babe_conv_packed_size_wino45(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino45,
-     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and WINOGRAD45 and _io(pc, tf)[0] % 16 == 0 and _io(pc, tf)[1] > 32),
+     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and FORMS.winograd45 and _io(pc, tf)[0] % 16 == 0 and _io(pc, tf)[1] > 32),
     ("wino85", lambda L, pc, tf: L.babe_conv_packed_size_wino85(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino85,
-     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and WINOGRAD85 and _io(pc, tf)[0] % 16 == 0
+     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and FORMS.winograd85 and _io(pc, tf)[0] % 16 == 0
      and any(_io(pc, tf)[1] % tile == 0 for tile in (128, 96, 64))),
 )
 
@@ -89,16 +70,19 @@ class PackedConv:
     """Conv2d weights packed for babe_conv2d, forward and input-VJP (flipped/transposed) versions.
     precision: 'f32' (exact fp32 MFMA), 'bf16' or 'bf16x3' (bf16 MFMA, see csrc/conv_bf16.hip).
     `desc` is the C descriptor (babe_packed_conv) babe_conv2d_auto picks the kernel from: every shape and image attribute is
-    written through to it, so assigning None to an image after construction takes its kernel out of the dispatch."""
+    written through to it, so assigning None to an image after construction takes its kernel out of the dispatch.
+    The forms that decide which images exist (forms.py: the Winograd families of _FAMILIES, fewco for w_raw, conv11_nt for nt,
+    bf16_hbm_f32 for splits_for) are read when the object is CONSTRUCTED: selecting another form later does not repack it."""
 
     def __init__(self, w, precision="f32", nt=0):
         """nt: row tiles (x32 output channels) per workgroup of the direct kernel, 0 = default (include/babe_hip.h)."""
         self.desc = CPackedConv()
         self.precision = precision
         self.nt = nt
-        if nt == 0 and _C11_NT and w.shape[2] * w.shape[3] == 1 and ((w.shape[0] + 31) // 32) % _C11_NT == 0 \
-                and ((w.shape[1] + 31) // 32) % _C11_NT == 0:
-            self.nt = _C11_NT
+        c11 = FORMS.conv11_nt
+        if nt == 0 and c11 and w.shape[2] * w.shape[3] == 1 and ((w.shape[0] + 31) // 32) % c11 == 0 \
+                and ((w.shape[1] + 31) // 32) % c11 == 0:
+            self.nt = c11
         self.splits = self.splits_for(w.shape, precision)
         assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
         w = w.contiguous()
@@ -111,7 +95,7 @@ class PackedConv:
         else:
             # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip):
             # the caller's tensor itself
-            self.w_raw = w if (FEWCO and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
+            self.w_raw = w if (FORMS.fewco and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
             for tf, d in ((0, "fwd"), (1, "bwd")):
                 setattr(self, d, torch.empty(L.babe_conv_packed_size(*shp, tf), device=w.device, dtype=torch.float32))
             for name, size, _, eligible in _FAMILIES:
@@ -128,7 +112,7 @@ class PackedConv:
         # channels on one side (HBM-bound: all-DMA kernel), and every (1,1) kernel of the bf16x3 mode.  Wide (1,1) kernels are
         # MFMA-bound in fp32 (up to 85 flop/B) and take the pipelined bf16 kernel under 'bf16'.
         k11 = shape[2] * shape[3] == 1
-        if splits and BF16_HBM_F32 and (min(shape[0], shape[1]) <= 4 or (k11 and (splits == 2 or min(shape[0], shape[1]) < 32))):
+        if splits and FORMS.bf16_hbm_f32 and (min(shape[0], shape[1]) <= 4 or (k11 and (splits == 2 or min(shape[0], shape[1]) < 32))):
             return 0
         return splits
 
@@ -160,15 +144,6 @@ class PackedConv:
                     check(pack(L)(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
 
 
-# GroupNorm-VJP partial sums formed in the F(4,5) transposed conv's epilogue instead of babe_gn_bwd_partial's own pass: OFF by
-# default - measured 0.5 % slower than the separate pass (profiles/r06_gn_fusion_experiment.txt: the GELU' arithmetic runs on the
-# multiply waves with nothing to overlap it); BABE_FUSE_GN=1 turns it on (tests/test_gpu_ops.py keeps it parity-checked)
-FUSE_GN = os.environ.get("BABE_FUSE_GN", "0") != "0"
-# The NEXT layer's GroupNorm sums (sum, sum of squares of the output) formed in the forward F(4,5) conv's epilogue instead of
-# babe_gn_partial's pass over the freshly written output: two double additions per output, no extra loads.  BABE_FUSE_GN_FWD=0: own pass.
-FUSE_GN_FWD = os.environ.get("BABE_FUSE_GN_FWD", "1") != "0"
-
-
 def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=None, oscale=None, alpha=1.0, rbeta=0.0,
            force_nested=False, force_f45=False, vjp_stat=None, fwd_stat=None, fbias=None):
     """out = alpha*conv(x[,x2]; W)*oscale + rbeta*res   (transpose=True: input-VJP weights), on the kernel the library picks
@@ -181,7 +156,7 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     FiLM / GELU input-VJP for the gradient `out` it writes (z: the layer's saved input, dense like out; scale [B,C]; cg channels
     per group) and (part, S) is RETURNED for gn_bwd(part=, S=); otherwise None is returned and gn_bwd runs its own pass.
     fwd_stat=cg: likewise the sums of the output itself - the next layer's GroupNorm partial sums - for gn_scale_gelu(fused=);
-    (part, S) or None is returned."""
+    (part, S) or None is returned.  Either only under its form (FORMS.fuse_gn / FORMS.fuse_gn_fwd, forms.py)."""
     a = ConvArgs()
     B, C1, F, T = x.shape
     Cin = pc.Cout if transpose else pc.Cin
@@ -208,11 +183,11 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     L = lib()
     w85 = getattr(pc, "bwd_wino85" if transpose else "fwd_wino85", None)
     f45 = w85 is not None and x2 is None and not force_nested         # the F(4,5) kernel may run: it alone fuses the sums
-    if f45 and vjp_stat is not None and FUSE_GN:
+    if f45 and vjp_stat is not None and FORMS.fuse_gn:
         z, scale, cg = vjp_stat
         assert z.is_contiguous() and out.is_contiguous() and z.shape == out.shape and scale.is_contiguous()
         a.stat_mode, a.stat_cg, a.stat_x, a.stat_scale = 2, cg, ptr(z), ptr(scale)
-    elif f45 and fwd_stat is not None and FUSE_GN_FWD and out.is_contiguous():
+    elif f45 and fwd_stat is not None and FORMS.fuse_gn_fwd and out.is_contiguous():
         a.stat_mode, a.stat_cg = 1, fwd_stat
     if a.stat_mode:                                                     # (mode 1: two sums per slot, mode 2: one)
         S = L.babe_conv2d_wino85_stat_slots(C.byref(a))
@@ -240,10 +215,6 @@ def _splits(n, B, G):
 
 
 _GN_TICKETS = {}
-# Measured (round 4, same box, A/B/A/B): the one-launch form is SLOWER on the whole job - 1.992 / 1.991 vs 2.080 / 2.079 audio-sec/s -
-# every workgroup of a 10 us streaming kernel pays a device-scope fence + an atomic before it retires, and the last one a
-# serial tail; the separate 3.5 us finalize launch overlaps the other lane's kernels instead.  Off by default (BABE_GN_FUSED=1).
-GN_FUSED = os.environ.get("BABE_GN_FUSED", "0") == "1"
 
 
 def _gn_ticket(dev, n):
@@ -260,7 +231,7 @@ def _gn_ticket(dev, n):
 def gn_scale(x, gamma, film, G=8, eps=1e-7):
     """Returns (stats [B,G,3], scale [B,C]) with scale = gamma*(film+1)/(std+eps).  x dense [B,C,F,T].
     Two launches (partial sums, finalize); BABE_GN_FUSED=1 = one launch (csrc/norm.hip gn_partial_kernel<true>: the last
-    workgroup of a group finalises it; bit-identical, measured slower on the whole job - see GN_FUSED above)."""
+    workgroup of a group finalises it; bit-identical, measured slower on the whole job - see gn_fused in forms.py)."""
     assert x.is_contiguous()
     B, Cc, F, T = x.shape
     n = (Cc // G) * F * T
@@ -270,7 +241,7 @@ def gn_scale(x, gamma, film, G=8, eps=1e-7):
     scale = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
     L = lib()
     assert film.stride(1) == 1
-    if GN_FUSED:
+    if FORMS.gn_fused:
         check(L.babe_gn_stats(ptr(x), ptr(part), ptr(_gn_ticket(x.device, B * G)), ptr(gamma), ptr(film), film.stride(0),
                               ptr(stats), ptr(scale), B, Cc, G, n, S, eps, stream()), "gn_stats")
         return stats, scale
@@ -278,9 +249,6 @@ def gn_scale(x, gamma, film, G=8, eps=1e-7):
     check(L.babe_gn_finalize(ptr(part), ptr(gamma), ptr(film), film.stride(0), ptr(stats), ptr(scale), B, Cc, G, n, S,
                              eps, stream()), "gn_finalize")
     return stats, scale
-
-
-GELU_FIN = os.environ.get("BABE_GELU_FIN", "1") != "0"
 
 
 def gn_scale_gelu(x, gamma, film, out, G=8, eps=1e-7, fused=None):
@@ -296,7 +264,7 @@ def gn_scale_gelu(x, gamma, film, out, G=8, eps=1e-7, fused=None):
         check(lib().babe_scale_gelu_fin(ptr(x), ptr(part), ptr(gamma), ptr(film), film.stride(0), ptr(stats), ptr(scale), ptr(out),
                                         B, Cc, G, F * T, S, eps, stream()), "scale_gelu_fin")
         return stats, scale
-    if not GELU_FIN:
+    if not FORMS.gelu_fin:
         stats, scale = gn_scale(x, gamma, film, G, eps)
         scale_gelu(x, scale, out)
         return stats, scale
@@ -321,12 +289,9 @@ def scale_gelu(x, scale, out):
     return out
 
 
-UNITS = os.environ.get("BABE_CONV_BF16U", "1") != "0"
-
-
 def units_ok(pc, Cin, Cout, T):
     """True if the forward of this (5,3) conv can take its input as bf16 units (csrc/conv_bf16p.hip, UNITS variant)."""
-    return UNITS and pc.splits == 1 and pc.KH == 5 and pc.KW == 3 and T % 4 == 0 and Cin % 8 == 0 and Cout > 32
+    return FORMS.units and pc.splits == 1 and pc.KH == 5 and pc.KW == 3 and T % 4 == 0 and Cin % 8 == 0 and Cout > 32
 
 
 def scale_gelu_units(x, scale, au):
@@ -388,9 +353,6 @@ def gn_bwd(x, da, gy, scale, stats, gx, rbeta, G=8, eps=1e-7, merge=None, fused=
     return gx
 
 
-AXPBY2 = os.environ.get("BABE_AXPBY2", "1") != "0"          # 0: the two-pass forms of the merged element-wise passes (A/B switch)
-
-
 def resample(x, out, mode, alpha=1.0, beta=0.0, res=None):
     """mode 0 down, 1 up, 2 down^T, 3 up^T. T argument is the forward op's input length.
     out = alpha*R(x) + beta*out, or with res: out = alpha*R(x) + beta*res (one pass; unaligned views: copy, then accumulate)."""
@@ -403,7 +365,7 @@ def resample(x, out, mode, alpha=1.0, beta=0.0, res=None):
     if res is not None:
         assert res.shape == out.shape
         rp, rbs, rcs = _view(res)
-        if AXPBY2 and all(v % 4 == 0 for v in (rbs, rcs, obs, ocs)) and res.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
+        if FORMS.axpby2 and all(v % 4 == 0 for v in (rbs, rcs, obs, ocs)) and res.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0:
             check(lib().babe_resample_res(xp, xbs, xcs, rp, rbs, rcs, op, obs, ocs, B, Cc, F, T, mode, alpha, beta, stream()),
                   "resample_res")
             return out
@@ -430,7 +392,7 @@ def axpby2(x, y, out, alpha, beta):
     op, obs, ocs = _view(out)
     aligned = (F * T) % 4 == 0 and all(v % 4 == 0 for v in (xbs, xcs, ybs, ycs, obs, ocs)) and \
         all(t.data_ptr() % 16 == 0 for t in (x, y, out))
-    if not (aligned and AXPBY2):
+    if not (aligned and FORMS.axpby2):
         axpby(x, out, alpha=alpha)
         return axpby(y, out, alpha=beta, beta=1.0)
     check(lib().babe_axpby2_4d(xp, xbs, xcs, yp, ybs, ycs, op, obs, ocs, B, Cc, F, T, alpha, beta, stream()), "axpby2_4d")

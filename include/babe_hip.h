@@ -297,6 +297,15 @@ long babe_unet_workspace_bytes(const void* plan, int B, const int* T_oct);
 int babe_unet_fwd(const void* plan, void* state, const float* const* C_in, const float* film, long film_bs, int B,
                   const int* T_oct, void* workspace, long workspace_bytes, float* const* outs, void* stream);
 int babe_unet_vjp(const void* plan, void* state, const float* const* gouts, float* const* gC, void* stream);
+/* The two forms of the layer path that babe_unet_fwd / babe_unet_vjp AND a host sequencing the same layers itself (babe_amd/
+ * networks/unet_engine.py) act on, one value per process.  FUSE_GN_FWD: the next layer's GroupNorm sums come out of the forward
+ * F(4,5) conv's epilogue (stat_mode 1; on unless BABE_FUSE_GN_FWD=0).  FUSE_GN: the GroupNorm-VJP partial sums come out of the
+ * transposed F(4,5) conv's epilogue (stat_mode 2; off unless BABE_FUSE_GN is a non-zero number).  The environment is read once,
+ * here and nowhere else; _set changes a form for every later call of either sequencer.  babe_unet_workspace_bytes does not depend
+ * on them.  _get: 0 / 1, or -1 for a bad index. */
+enum { BABE_FORM_FUSE_GN_FWD = 0, BABE_FORM_FUSE_GN = 1 };
+int babe_unet_form_get(int which);
+int babe_unet_form_set(int which, int on);
 
 /* ---- strided copy / axpby: out = alpha*in + beta*out on [B][C][F][T] views (torch.cat / slicing /
  * (a+b)/sqrt2 residual merges, cqtdiff+.py:769-774,794,814-822) */

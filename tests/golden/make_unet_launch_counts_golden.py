@@ -8,6 +8,7 @@ another's: tests/test_gpu_unet_state.py imports this module for the configuratio
 the table.  Regenerate the table only when the launch stream is MEANT to change.  No reference import: weights come from
 tests/golden/unet_small.npz and from seeds.
 """
+import contextlib
 import json
 import os
 import sys
@@ -86,13 +87,25 @@ def attention():
 CASES = {"small_b1": small_b1, "small_b2_two_lanes": small_b2_two_lanes, "training_step": training_step, "attention": attention}
 
 
+@contextlib.contextmanager
+def selected_forms(**select):
+    """Run the body under these forms (babe_amd/forms.py) and put back what was selected before, whatever the body does."""
+    from babe_amd.forms import FORMS
+    keep = {name: getattr(FORMS, name) for name in select}
+    try:
+        for name, value in select.items():
+            setattr(FORMS, name, value)
+        yield
+    finally:
+        for name, value in keep.items():
+            setattr(FORMS, name, value)
+
+
 if __name__ == "__main__":
-    from babe_amd import ops
-    from babe_amd.networks import unet_engine
-    unet_engine.USE_C = False               # the table is the Python sequencer's ...
-    ops.GN_FUSED = False                    # ... with the default two-launch GroupNorm statistics
     out = sys.argv[1] if len(sys.argv) > 1 else OUT
-    table = {name: fn() for name, fn in CASES.items()}
+    # the table is the Python sequencer's, with the default two-launch GroupNorm statistics
+    with selected_forms(unet_c=False, gn_fused=False):
+        table = {name: fn() for name, fn in CASES.items()}
     with open(out, "w") as fh:
         json.dump(table, fh, indent=0, sort_keys=True)
         fh.write("\n")

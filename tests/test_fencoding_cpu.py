@@ -83,13 +83,14 @@ def test_bf16_modes_keep_the_folded_convs_in_fp32_or_refuse(monkeypatch):
     """The [N, 2] signal slice of an init-block conv runs on the fp32 kernels (the only ones with a frequency bias) in every
     precision; with BABE_BF16_HBM_F32=0 it would go to the bf16 kernels, and the block refuses before it packs anything."""
     from babe_amd import ops
+    from babe_amd.forms import FORMS
     from babe_amd.networks.unet_engine import _Block, _FilmIndex
     from tests.fencoding_weights import fencoding_sd
     for n in (8, 96, 256):
         assert ops.PackedConv.splits_for((n, 2, 1, 1), "bf16") == 0 and ops.PackedConv.splits_for((n, 2, 1, 1), "bf16x3") == 0
     sd = fencoding_sd("a")
     fenc = sd["freq_encodings.0.embeddings"].reshape(64, 64)
-    monkeypatch.setattr(ops, "BF16_HBM_F32", False)
+    monkeypatch.setattr(FORMS, "bf16_hbm_f32", False)
     for prec in ("bf16", "bf16x3"):
         with pytest.raises(NotImplementedError, match="use_fencoding.*" + prec):
             _Block(sd, "downs.0.0.", 1, _FilmIndex(), precision=prec, fenc=fenc)

@@ -190,12 +190,12 @@ def test_network_with_attention_and_encodings_vs_reference_golden():
 
 @pytest.mark.parametrize("B", [1, 2])
 def test_library_side_unet_equals_python_sequencer(monkeypatch, gold_a, B):
-    from babe_amd.networks import unet_engine as ue
+    from babe_amd.forms import FORMS
     x, cn, w = golden_inputs(gold_a, 2)
     x, cn, w = x[:B].contiguous(), cn[:B].contiguous(), w[:B].contiguous()
-    monkeypatch.setattr(ue, "USE_C", False)
+    monkeypatch.setattr(FORMS, "unet_c", False)
     y0, g0 = fwd_vjp(make_net("a"), x, cn, w)
-    monkeypatch.setattr(ue, "USE_C", True)
+    monkeypatch.setattr(FORMS, "unet_c", True)
     netc = make_net("a")
     y1, g1 = fwd_vjp(netc, x, cn, w)
     assert netc.engine()._c_engine().ws is not None, "the library path did not run"       # its state already holds a workspace

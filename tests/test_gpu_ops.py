@@ -283,10 +283,11 @@ def test_groupnorm_film_gelu_fwd_bwd(ops, B, C, Fq, T):
     ops.gn_bwd(xc, dac, gx, scale, stats, gx, 0.5)
     assert rel(gx, gref) < 5e-6
 
-def test_gn_stats_one_launch_equals_two_launches(ops):
+def test_gn_stats_one_launch_equals_two_launches(ops, monkeypatch):
     """gn_partial_kernel<true> (the last workgroup of a group finalises it: one launch) against babe_gn_partial +
     babe_gn_finalize: bit-identical statistics and scales, over shapes with different split counts on the SAME ticket buffer
     (every call must leave its tickets at zero), and from two streams at once."""
+    from babe_amd.forms import FORMS
     g = torch.Generator().manual_seed(77)
     shapes = [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64), (2, 64, 16, 256)]
     for rep in range(2):
@@ -294,11 +295,11 @@ def test_gn_stats_one_launch_equals_two_launches(ops):
             x = torch.randn(B, C, F, T, generator=g).cuda()
             gamma = (torch.rand(C, generator=g) + 0.5).cuda()
             film = torch.randn(B, C, generator=g).cuda()
-            ops.GN_FUSED = True
+            monkeypatch.setattr(FORMS, "gn_fused", True)
             st1, sc1 = ops.gn_scale(x, gamma, film)
-            ops.GN_FUSED = False
+            monkeypatch.setattr(FORMS, "gn_fused", False)
             st0, sc0 = ops.gn_scale(x, gamma, film)
-            ops.GN_FUSED = True
+            monkeypatch.setattr(FORMS, "gn_fused", True)
             assert torch.equal(st1, st0) and torch.equal(sc1, sc0), (B, C, F, T)
     assert all(int(t.abs().sum()) == 0 for t in ops._GN_TICKETS.values())
     sA, sB = torch.cuda.Stream(), torch.cuda.Stream()
@@ -315,8 +316,10 @@ def test_gn_stats_one_launch_equals_two_launches(ops):
     torch.cuda.synchronize()
     assert all(torch.equal(o[0], ref[0]) and torch.equal(o[1], ref[1]) for o in outs)
 
-def test_scale_gelu_with_folded_finalize_is_bit_identical(ops):
+def test_scale_gelu_with_folded_finalize_is_bit_identical(ops, monkeypatch):
     """babe_scale_gelu_fin (gn_finalize's work in the GELU kernel's prologue) against gn_scale + scale_gelu."""
+    from babe_amd.forms import FORMS
+    monkeypatch.setattr(FORMS, "gelu_fin", True)
     g = torch.Generator().manual_seed(78)
     for (B, C, F, T) in [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64)]:
         x = torch.randn(B, C, F, T, generator=g).cuda()
@@ -325,9 +328,7 @@ def test_scale_gelu_with_folded_finalize_is_bit_identical(ops):
         st0, sc0 = ops.gn_scale(x, gamma, film)
         a0 = ops.scale_gelu(x, sc0, torch.empty_like(x))
         a1 = torch.empty_like(x)
-        keep, ops.GELU_FIN = ops.GELU_FIN, True
         st1, sc1 = ops.gn_scale_gelu(x, gamma, film, a1)
-        ops.GELU_FIN = keep
         assert torch.equal(st1, st0) and torch.equal(sc1, sc0) and torch.equal(a1, a0), (B, C, F, T)
 
 
@@ -847,7 +848,8 @@ def test_f45_epilogue_forms_the_next_groupnorm_sums(ops, monkeypatch):
     against float64 sums of the output, and gn_scale_gelu on the fused sums against its own pass (statistics to float rounding,
     the activation to 1e-5)."""
     from babe_amd._lib import dispatch_counts, lib
-    monkeypatch.setattr(ops, "FUSE_GN_FWD", True)
+    from babe_amd.forms import FORMS
+    monkeypatch.setattr(FORMS, "fuse_gn_fwd", True)
     RS2 = 1.0 / math.sqrt(2.0)
     for Cc, Fq, T, dil, waves in ((128, 48, 128, 2, 12), (128, 48, 128, 2, 8), (96, 40, 192, 1, 12), (64, 36, 100, 3, 12), (256, 28, 64, 4, 12),
                                   (128, 5, 64, 1, 12)):
@@ -896,7 +898,8 @@ def test_f45_epilogue_forms_the_groupnorm_vjp_partial_sums(ops, monkeypatch):
     (both sum in double, in different orders), da bit-identical with and without the reduction, and gn_bwd on either set of partial
     sums to float rounding."""
     from babe_amd._lib import dispatch_counts, lib
-    monkeypatch.setattr(ops, "FUSE_GN", True)
+    from babe_amd.forms import FORMS
+    monkeypatch.setattr(FORMS, "fuse_gn", True)
     for Cc, Fq, T, dil, waves in ((128, 48, 128, 2, 12), (128, 48, 128, 2, 8), (96, 40, 192, 1, 12), (64, 36, 100, 3, 12), (256, 28, 64, 4, 12)):
         assert lib().babe_conv2d_wino85_set_waves(waves) == 0
         g = torch.Generator().manual_seed(Cc + Fq + T)

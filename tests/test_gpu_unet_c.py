@@ -26,17 +26,18 @@ def _run(eng, C_list, film, gouts):
 
 @pytest.mark.parametrize("B,T0", [(2, 16), (1, 64)])
 def test_c_engine_equals_python_engine_small(monkeypatch, B, T0):
+    from babe_amd.forms import FORMS
     from babe_amd.networks import unet_engine as ue
     sd, Ns, nd = _small()
     gen = torch.Generator().manual_seed(5 + B)
     C_list = [torch.randn(B, 2, 64, T0 * 2 ** j, generator=gen).cuda() for j in range(7)]
     gouts = [torch.randn(c.shape, generator=gen).cuda() for c in C_list]
     cn = torch.linspace(-1.2, -0.3, B).reshape(B, 1).cuda()
-    monkeypatch.setattr(ue, "USE_C", False)
+    monkeypatch.setattr(FORMS, "unet_c", False)
     eng = ue.UnetEngine(sd, Ns, nd)
     film = eng.embed(cn)
     o_py, g_py = _run(eng, C_list, film, gouts)
-    monkeypatch.setattr(ue, "USE_C", True)
+    monkeypatch.setattr(FORMS, "unet_c", True)
     eng_c = ue.UnetEngine(sd, Ns, nd)
     assert eng_c._c_engine() is not None
     o_c, g_c = _run(eng_c, C_list, film, gouts)
@@ -44,9 +45,9 @@ def test_c_engine_equals_python_engine_small(monkeypatch, B, T0):
         assert torch.equal(a, b)
     # a second evaluation through the same state and workspace (other inputs), then two states over one plan on two streams
     C2 = [c * 0.5 + 0.1 for c in C_list]
-    monkeypatch.setattr(ue, "USE_C", False)
+    monkeypatch.setattr(FORMS, "unet_c", False)
     o_py2, g_py2 = _run(eng, C2, film, gouts)
-    monkeypatch.setattr(ue, "USE_C", True)
+    monkeypatch.setattr(FORMS, "unet_c", True)
     o_c2, g_c2 = _run(eng_c, C2, film, gouts)
     for a, b in zip(o_py2 + g_py2, o_c2 + g_c2):
         assert torch.equal(a, b)
@@ -70,6 +71,7 @@ def test_c_engine_equals_python_engine_small(monkeypatch, B, T0):
 def test_c_engine_equals_python_engine_full_width(monkeypatch):
     """Benchmark width (Ns = [64, 96, 96, 128, 128, 256, 256]) on a 46046-sample segment's octave lengths: every nested-Winograd,
     (1,1), few-channel and pyramid dispatch goes through babe_conv2d_auto."""
+    from babe_amd.forms import FORMS
     from babe_amd.networks import unet_engine as ue
     from babe_amd.networks.cqtdiff_plus import init_state_dict
     Ns, nd = [64, 96, 96, 128, 128, 256, 256], [2, 3, 4, 5, 6, 7, 7]
@@ -79,11 +81,11 @@ def test_c_engine_equals_python_engine_full_width(monkeypatch):
     C_list = [torch.randn(1, 2, 64, T, generator=gen).cuda() for T in Ts]
     gouts = [torch.randn(c.shape, generator=gen).cuda() for c in C_list]
     cn = torch.tensor([[-0.7]]).cuda()
-    monkeypatch.setattr(ue, "USE_C", False)
+    monkeypatch.setattr(FORMS, "unet_c", False)
     eng = ue.UnetEngine(sd, Ns, nd)
     film = eng.embed(cn)
     o_py, g_py = _run(eng, C_list, film, gouts)
-    monkeypatch.setattr(ue, "USE_C", True)
+    monkeypatch.setattr(FORMS, "unet_c", True)
     eng_c = ue.UnetEngine(sd, Ns, nd)
     o_c, g_c = _run(eng_c, C_list, film, gouts)
     for a, b in zip(o_py + g_py, o_c + g_c):
@@ -95,8 +97,8 @@ def test_groupnorm_sums_from_the_conv_epilogue_leave_the_network_unchanged(monke
     sums (babe_conv_args::stat_mode 1) instead of a pass of babe_gn_partial over the tensor: fewer statistics launches, and the
     network's outputs and input-VJP equal to the own-pass form to float rounding of the statistics (the sums are the same numbers
     added in another order, in double)."""
-    from babe_amd import ops
     from babe_amd._lib import dispatch_counts
+    from babe_amd.forms import FORMS
     from babe_amd.networks import unet_engine as ue
     from babe_amd.networks.cqtdiff_plus import init_state_dict
     Ns, nd = [64, 96, 96, 128, 128, 256, 256], [2, 3, 4, 5, 6, 7, 7]
@@ -106,10 +108,10 @@ def test_groupnorm_sums_from_the_conv_epilogue_leave_the_network_unchanged(monke
     C_list = [torch.randn(1, 2, 64, T, generator=gen).cuda() for T in Ts]
     gouts = [torch.randn(c.shape, generator=gen).cuda() for c in C_list]
     cn = torch.tensor([[-0.7]]).cuda()
-    monkeypatch.setattr(ue, "USE_C", False)
+    monkeypatch.setattr(FORMS, "unet_c", False)
     res, launches = [], []
     for fuse in (False, True):
-        monkeypatch.setattr(ops, "FUSE_GN_FWD", fuse)
+        monkeypatch.setattr(FORMS, "fuse_gn_fwd", fuse)
         eng = ue.UnetEngine(sd, Ns, nd)
         film = eng.embed(cn)
         dispatch_counts(reset=True)
@@ -119,6 +121,55 @@ def test_groupnorm_sums_from_the_conv_epilogue_leave_the_network_unchanged(monke
     assert launches[1] < launches[0], launches
     for a, b in zip(*res):
         assert float((a - b).abs().max()) <= 2e-5 * float(a.abs().max()), float((a - b).abs().max() / a.abs().max())
+
+
+def test_both_sequencers_follow_the_two_forms_the_library_owns(monkeypatch):
+    """fuse_gn_fwd and fuse_gn (babe_unet_form_get / _set, FORMS.fuse_gn_fwd / FORMS.fuse_gn) selected through FORMS reach the Python
+    sequencer AND the library-side one: under either value the two stay bit-identical and launch the same number of statistics
+    passes, and the form on launches fewer than the form off.  The smallest network on which the F(4,5) kernel runs at all: one
+    64-channel level with F = 448, T = 64, dilations 1 and 2, full row quads."""
+    from babe_amd._lib import dispatch_counts
+    from babe_amd.forms import FORMS
+    from babe_amd.networks import unet_engine as ue
+    from babe_amd.networks.cqtdiff_plus import init_state_dict
+    Ns, nd = [8, 8, 8, 8, 8, 8, 64], [1, 1, 1, 1, 1, 1, 2]
+    sd = {k: v.cuda() for k, v in init_state_dict(Ns, nd, seed=3, gate_scale=1.0).items()}
+    gen = torch.Generator().manual_seed(13)
+    C_list = [torch.randn(1, 2, 64, 64 * 2 ** j, generator=gen).cuda() for j in range(7)]
+    gouts = [torch.randn(c.shape, generator=gen).cuda() for c in C_list]
+    cn = torch.tensor([[-0.7]]).cuda()
+
+    def run(unet_c, fuse_gn_fwd, fuse_gn):
+        for name, value in (("unet_c", unet_c), ("fuse_gn_fwd", fuse_gn_fwd), ("fuse_gn", fuse_gn)):
+            monkeypatch.setattr(FORMS, name, value)
+        eng = ue.UnetEngine(sd, Ns, nd)                      # a fresh engine for every run
+        assert (eng._c_engine() is not None) == unet_c
+        film = eng.embed(cn)
+        dispatch_counts(reset=True)
+        o, g = _run(eng, C_list, film, gouts)
+        counts = dispatch_counts()
+        assert counts["conv53_wino85"] > 0, "the F(4,5) kernel never ran: nothing here depends on the two forms"
+        return [t.clone() for t in o + g], counts
+
+    stats = {}
+    for fwd in (True, False):
+        (r_py, n_py), (r_c, n_c) = run(False, fwd, False), run(True, fwd, False)
+        for a, b in zip(r_py, r_c):
+            assert torch.equal(a, b), fwd
+        assert n_py["gn_stats"] == n_c["gn_stats"], (fwd, n_py["gn_stats"], n_c["gn_stats"])
+        stats[fwd] = n_py["gn_stats"]
+        if fwd:
+            own_pass, n_own = r_py, n_py["gn_bwd_partial"]
+    assert stats[True] < stats[False], stats
+    # fuse_gn: the GroupNorm-VJP sums from the transposed conv's epilogue
+    (r_py, n_py), (r_c, n_c) = run(False, True, True), run(True, True, True)
+    for a, b in zip(r_py, r_c):
+        assert torch.equal(a, b)
+    assert n_py["gn_bwd_partial"] == n_c["gn_bwd_partial"] < n_own, (n_py["gn_bwd_partial"], n_c["gn_bwd_partial"], n_own)
+    for a, b in zip(own_pass, r_py):                         # across the forms: the tolerance of the fusion's own test (test_gpu_ops.py)
+        err = float((a - b).abs().max() / a.abs().max())
+        print(f"fuse_gn on / off: {err:.3e}")
+        assert err < 1e-6, err
 
 
 def test_workspace_too_small_fails_loudly():

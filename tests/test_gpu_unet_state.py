@@ -27,12 +27,11 @@ REC = _recorder()
 
 @pytest.fixture(autouse=True)
 def python_sequencer(monkeypatch):
-    """The switches the table was recorded with, whatever the environment or an earlier test of the session left in the modules
-    (tests/test_gpu_ops.py leaves ops.GN_FUSED on: one launch per GroupNorm statistic where the default takes two)."""
-    from babe_amd import ops
-    from babe_amd.networks import unet_engine
-    monkeypatch.setattr(unet_engine, "USE_C", False)
-    monkeypatch.setattr(ops, "GN_FUSED", False)
+    """The forms the table was recorded with, whatever the environment selects: the Python sequencer, two launches per GroupNorm
+    statistic."""
+    from babe_amd.forms import FORMS
+    monkeypatch.setattr(FORMS, "unet_c", False)
+    monkeypatch.setattr(FORMS, "gn_fused", False)
 
 
 def network(attention):

@@ -135,8 +135,8 @@ def test_two_lanes_and_c_sequencer_give_bit_identical_grads(monkeypatch):
     assert torch.equal(y1, y2)
     for k in g1:
         assert torch.equal(g1[k], g2[k]), k
-    from babe_amd.networks import unet_engine
-    monkeypatch.setattr(unet_engine, "USE_C", True)
+    from babe_amd.forms import FORMS
+    monkeypatch.setattr(FORMS, "unet_c", True)
     netc = make_net()
     yc, gc = hip_grads(netc, x, cn, w)
     for k in g1:
