@@ -89,6 +89,17 @@ class EvalDesc(C.Structure):
                 ("xi", C.c_float), ("score_mode", C.c_int), ("audio_len_norm", C.c_float)]
 
 
+class SampleStep(C.Structure):
+    """babe_sample_step"""
+    _fields_ = [("t_hat", C.c_float), ("inject", C.c_float), ("t_next", C.c_float), ("h", C.c_float), ("heun", C.c_int),
+                ("c1", C.c_float * 4), ("c2", C.c_float * 4)]
+
+
+class SampleDesc(C.Structure):
+    """babe_sample_desc"""
+    _fields_ = [("eval", EvalDesc), ("T", C.c_int), ("steps", C.POINTER(SampleStep)), ("t0", C.c_float), ("warm_start", C.c_int)]
+
+
 class DnConvArgs(C.Structure):
     """babe_dnconv_args"""
     _fields_ = [("in_", C.c_void_p), ("in_bs", C.c_long), ("in_cs", C.c_long), ("IH", C.c_int), ("IW", C.c_int),
@@ -104,7 +115,7 @@ class DnConvArgs(C.Structure):
 # header struct name -> mirror (the layout test compiles a probe for each of them)
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv, "babe_unet_block": CBlock,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
-           "babe_dnconv_args": DnConvArgs}
+           "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
 _P, _L, _I, _F, _D, _S = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double, C.c_char_p
@@ -227,6 +238,12 @@ SIGS = {
     "babe_score_direction": (_I, [_P, _P, _P, _P, _I, _P, _F, _F, _F, _I, _I, _I, _L, _P]),
     "babe_eval_workspace_bytes": (_L, [C.POINTER(EvalDesc), _I]),
     "babe_score_eval": (_I, [C.POINTER(EvalDesc), _P, _F, _F, _F, _F, _F, _P, _P, _P, _P, _P, _P, _P, _L, _I, _P]),
+    "babe_philox4x32": (_I, [_P, _P, _P]),
+    "babe_randn": (_I, [_P, _L, _I, _L, _L, _L, _L, _P]),
+    "babe_rand_bits": (_I, [_P, _L, _I, _L, _L, _L, _L, _P]),
+    "babe_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I]),
+    "babe_sample_bwe": (_I, [C.POINTER(SampleDesc), _P, _P, _P, _P, _L, _L, _P, _P, _P, _L, _I, _P]),
+    "babe_edm_steps": (_I, [C.POINTER(SampleStep), _P, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
     "babe_dn_conv2d": (_I, [C.POINTER(DnConvArgs), _P, _P]),
     "babe_dn_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "babe_dn_packed_size": (_L, [_I, _I, _I, _I]),

@@ -1,0 +1,168 @@
+// One whole SAMPLING RUN of the blind bandwidth-extension sampler from plan handles - the loop BlindSampler._sample -> step ->
+// _heun_first / _heun_second (babe_amd/testing/blind_bwe_sampler.py) sequences from Python, as ONE C-ABI call for a non-Python
+// host: STFT of the observations, the initial state, and per step the noise injection (move_timestep :509-516), the score
+// evaluation (babe_score_eval, csrc/score_eval.hip) and the Euler or second-order Heun update (:687-761), with the filter
+// parameters handed from evaluation to evaluation on the device.
+// Scope: that of babe_score_eval.  Like it, the run contains no schedule formula: the caller passes one babe_sample_step per
+// step (babe_edm_steps below fills the table for a host without the Python EDM class).  Same kernels, same order, same scalars
+// as the Python loop, so the two agree bit for bit (tests/test_gpu_sample_c.py).  Nothing allocates, nothing synchronises.
+#include <cmath>
+#include "common.h"
+#include "../../include/babe_hip.h"
+
+namespace {
+
+inline long round256(long bytes) { return (bytes + 255) / 256 * 256; }
+
+// the run's own buffers (everything but babe_score_eval's workspace): specY and seven [B][L] signals
+long own_bytes(const babe_eval_desc* e, int B) {
+    const int hop = e->nfft / 2, frames = 1 + e->L / hop, nbins = hop + 1;
+    return round256(4L * B * 2 * frames * nbins) + 7 * round256(4L * B * e->L);
+}
+
+bool eval_dims_ok(const babe_eval_desc* e) { return e->nfft >= 256 && e->L >= e->nfft; }
+
+}  // namespace
+
+extern "C" long babe_sample_workspace_bytes(const babe_sample_desc* d, int B) {
+    if (!d || B < 1) {
+        babe_set_error("sample_workspace_bytes: bad arguments");
+        return -1;
+    }
+    const long ev = babe_eval_workspace_bytes(&d->eval, B);
+    if (ev < 0) return -1;
+    return round256(ev) + own_bytes(&d->eval, B);
+}
+
+extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, float* x_out, const float* noise, long seed,
+                               long clip0, float* rec_x_den, float* rec_params, void* ws, long ws_bytes, int B, void* stream) {
+    // ---- host-side validation, all of it before the first launch
+    BABE_CHECK_ARG(d, "sample_bwe: NULL descriptor");
+    BABE_CHECK_ARG(d->T >= 1, "sample_bwe: T = %d steps", d->T);
+    BABE_CHECK_ARG(d->steps, "sample_bwe: NULL step table");
+    BABE_CHECK_ARG(B >= 1 && B <= 65535, "sample_bwe: B = %d", B);
+    const babe_eval_desc* e = &d->eval;
+    BABE_CHECK_ARG(eval_dims_ok(e), "sample_bwe: nfft = %d, L = %d", e->nfft, e->L);
+    BABE_CHECK_ARG(ws && ws_bytes >= own_bytes(e, B), "sample_bwe: workspace of %ld bytes, the run's own buffers alone need %ld",
+                   ws ? ws_bytes : 0L, own_bytes(e, B));
+    BABE_CHECK_ARG(y && params && x_out, "sample_bwe: NULL y, params or x_out");
+    BABE_CHECK_ARG(e->unet_plan && e->unet_state && e->cqt_plan && e->rff_freq && e->film_W && e->film_b && e->env_inv && e->tw4096,
+                   "sample_bwe: incomplete evaluation descriptor");
+    BABE_CHECK_ARG(e->K >= 1 && e->K <= 8 && e->rff_n > 0 && e->emb_dim[0] == 2 * e->rff_n, "sample_bwe: K = %d, rff_n = %d, emb_dim[0] = %d",
+                   e->K, e->rff_n, e->emb_dim[0]);
+    const long need = babe_sample_workspace_bytes(d, B);
+    BABE_CHECK_ARG(need >= 0, "sample_bwe: bad evaluation descriptor");
+    BABE_CHECK_ARG(ws_bytes >= need, "sample_bwe: workspace of %ld bytes, need %ld", ws_bytes, need);
+    BABE_CHECK_ARG(std::isfinite(d->t0), "sample_bwe: t0 is not finite");
+    for (int i = 0; i < d->T; ++i) {
+        const babe_sample_step& s = d->steps[i];
+        BABE_CHECK_ARG(s.t_hat > 0.f && std::isfinite(s.t_hat) && std::isfinite(s.inject) && std::isfinite(s.h) &&
+                           (s.heun == 0 || (s.heun == 1 && s.t_next > 0.f && std::isfinite(s.t_next))),
+                       "sample_bwe: step %d: t_hat = %g, inject = %g, t_next = %g, h = %g, heun = %d", i, s.t_hat, s.inject, s.t_next, s.h,
+                       s.heun);
+    }
+    if (!noise)
+        BABE_CHECK_ARG(clip0 >= 0 && clip0 + B <= 0x100000000L && d->T + 1L < 0x100000000L, "sample_bwe: clip0 = %ld outside the counter word", clip0);
+    // ---- carve
+    const long L = e->L, n = (long)B * L;
+    const int P = e->shared ? 1 : B, hop = e->nfft / 2, frames = 1 + e->L / hop, nbins = hop + 1;
+    const long ev_bytes = need - own_bytes(e, B);
+    char* p = static_cast<char*>(ws);
+    void* ev_ws = p;
+    p += ev_bytes;
+    float* specY = reinterpret_cast<float*>(p);
+    p += round256(4L * B * 2 * frames * nbins);
+    float* buf[7];
+    for (int k = 0; k < 7; ++k) {
+        buf[k] = reinterpret_cast<float*>(p);
+        p += round256(4L * n);
+    }
+    float *x = x_out, *x_hat = buf[0], *dd = buf[1], *x_den = buf[2], *x_prime = buf[3], *d2 = buf[4], *x_den2 = buf[5], *eps_ws = buf[6];
+    hipStream_t st = (hipStream_t)stream;
+#define EV(call)                          \
+    do {                                  \
+        const int rc__ = (call);          \
+        if (rc__ != BABE_OK) return rc__; \
+    } while (0)
+#define COPY(dst, src, bytes)                                                                          \
+    do {                                                                                               \
+        const hipError_t e__ = hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st);     \
+        if (e__ != hipSuccess) {                                                                       \
+            babe_set_error("%s:%d hipMemcpyAsync: %s", __FILE__, __LINE__, hipGetErrorString(e__));   \
+            return BABE_ERR_HIP;                                                                       \
+        }                                                                                              \
+    } while (0)
+    // draw k: rows of the caller's buffer, or the device generator into the one workspace buffer
+    auto draw = [&](long k, const float** eps) -> int {
+        if (noise) {
+            *eps = noise + k * n;
+            return BABE_OK;
+        }
+        *eps = eps_ws;
+        return babe_randn(eps_ws, L, B, L, seed, clip0, k, stream);
+    };
+    const float* eps = nullptr;
+    EV(babe_stft_fwd(y, L, (int)L, nullptr, specY, B, e->nfft, frames, e->tw4096, stream));
+    // ---- initial state (:311 / :314): t0 eps, or y + t0 eps with a warm start
+    EV(draw(0, &eps));
+    if (d->warm_start) EV(babe_lincomb3(x, 1.f, y, d->t0, eps, 0.f, nullptr, n, stream));
+    else EV(babe_lincomb3(x, d->t0, eps, 0.f, nullptr, 0.f, nullptr, n, stream));
+    for (int i = 0; i < d->T; ++i) {
+        const babe_sample_step& s = d->steps[i];
+        EV(draw(i + 1L, &eps));
+        EV(babe_lincomb3(x_hat, 1.f, x, s.inject, eps, 0.f, nullptr, n, stream));
+        EV(babe_score_eval(e, x_hat, s.t_hat, s.c1[0], s.c1[1], s.c1[2], s.c1[3], y, specY, params, dd, x_den, nullptr, ev_ws, ev_bytes, B,
+                           stream));
+        if (rec_x_den) COPY(rec_x_den + (long)i * n, x_den, 4L * n);
+        if (rec_params) COPY(rec_params + (long)i * P * 2 * e->K, params, 4L * P * 2 * e->K);
+        if (!s.heun) {
+            EV(babe_lincomb3(x, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
+        } else {
+            EV(babe_lincomb3(x_prime, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
+            EV(babe_score_eval(e, x_prime, s.t_next, s.c2[0], s.c2[1], s.c2[2], s.c2[3], y, specY, params, d2, x_den2, nullptr, ev_ws, ev_bytes,
+                               B, stream));
+            EV(babe_lincomb3(x, 1.f, x_hat, 0.5f * s.h, dd, 0.5f * s.h, d2, n, stream));
+        }
+    }
+#undef COPY
+#undef EV
+    return BABE_OK;
+}
+
+/* The tester's schedule in double (diff_params/edm.py:38-75, :108-139; blind_bwe_sampler.py:509-516): t_i = (s0^(1/ro) +
+ * i/(T-1) (sigma_min^(1/ro) - s0^(1/ro)))^ro for i < T, t_T = 0, s0 = start_sigma or sigma_max; gamma_i = min(Schurn/(T+1),
+ * sqrt 2 - 1) where Stmin < t_i < Stmax (the reference divides by the T + 1 entries of the schedule). */
+extern "C" int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double sigma_min, double sigma_max, double ro,
+                              double sigma_data, double Schurn, double Stmin, double Stmax, double Snoise, double start_sigma) {
+    BABE_CHECK_ARG(steps && t0 && T >= 2 && (order == 1 || order == 2), "edm_steps: bad arguments (T >= 2, order 1 or 2)");
+    BABE_CHECK_ARG(sigma_min > 0 && sigma_max > sigma_min && ro > 0 && sigma_data > 0 && Schurn >= 0 && Snoise >= 0,
+                   "edm_steps: sigma_min = %g, sigma_max = %g, ro = %g, sigma_data = %g, Schurn = %g, Snoise = %g", sigma_min, sigma_max, ro,
+                   sigma_data, Schurn, Snoise);
+    const double s0 = start_sigma > 0 ? start_sigma : sigma_max;
+    const double a = std::pow(s0, 1.0 / ro), b = std::pow(sigma_min, 1.0 / ro);
+    auto t_at = [&](int i) { return i >= T ? 0.0 : std::pow(a + (double)i / (T - 1) * (b - a), ro); };
+    const double g = std::fmin(Schurn / (T + 1), std::sqrt(2.0) - 1.0);
+    const double sd2 = sigma_data * sigma_data;
+    auto precond = [&](double s, float c[4]) {
+        c[0] = (float)(sd2 / (s * s + sd2));
+        c[1] = (float)(s * sigma_data / std::sqrt(sd2 + s * s));
+        c[2] = (float)(1.0 / std::sqrt(sd2 + s * s));
+        c[3] = (float)(0.25 * std::log(s));
+    };
+    *t0 = (float)t_at(0);
+    for (int i = 0; i < T; ++i) {
+        const double t = t_at(i), tn = t_at(i + 1);
+        const double gamma = (t > Stmin && t < Stmax) ? g : 0.0;
+        const double t_hat = t + gamma * t;
+        babe_sample_step& s = steps[i];
+        memset(&s, 0, sizeof s);
+        s.t_hat = (float)t_hat;
+        s.inject = (float)(std::sqrt(t_hat * t_hat - t * t) * Snoise);
+        s.t_next = (float)tn;
+        s.h = (float)(tn - t_hat);
+        s.heun = (tn != 0.0 && order == 2) ? 1 : 0;
+        precond(t_hat, s.c1);
+        if (s.heun) precond(tn, s.c2);
+    }
+    return BABE_OK;
+}

@@ -1,12 +1,15 @@
 """Command line: blind bandwidth extension of one wav file on the MI355X path.
 
     python -m babe_amd.restore in.wav out_dir [--ckpt weights.pt] [--precision f32|bf16x3|bf16] [--T 35]
-                               [--denoise [--denoiser-ckpt denoiser.pt]]
+                               [--denoise [--denoiser-ckpt denoiser.pt]] [--loop python|library] [--seed N]
 
 Follows the reference's file-level flow (testing/blind_bwe_tester.py:321-577 formal_test_bwe, blind mode):
 read -> resample to exp.sample_rate (:410, babe_amd/resample.py = torchaudio.functional.resample as published; a 48 kHz file is
 accepted) -> normalise to sigma_norm std -> segments + blind restoration + cross-fade (babe_amd/testing/long_file.py) -> write wav
 (at exp.sample_rate, like the reference) + filter pickle.
+--loop library runs every batch of segments as one library call (babe_sample_bwe); --seed N draws the noise from the library's
+counter-based generator, segment j of the file as clip j: the output is then a function of (weights, file, N) alone, whatever
+--batch is (with --loop python the Python loop draws from the same generator).  Without either, the Python loop on torch's draws.
 Without --ckpt the network has random weights (useful only to exercise the path).
 --denoise runs the denoiser pre-pass first (testing/denoise_and_bwe_tester.py:279-289: file rate -> --denoiser-rate (22050) ->
 apply_denoiser on the whole file -> exp.sample_rate, then the BWE on its output).
@@ -32,6 +35,8 @@ def main():
     ap.add_argument("--denoise", action="store_true", help="denoiser pre-pass before the bandwidth extension")
     ap.add_argument("--denoiser-ckpt", help="state_dict of networks.denoiser.MultiStage_denoise")
     ap.add_argument("--denoiser-rate", type=int, default=22050, help="tester.denoiser.sample_rate_denoiser")
+    ap.add_argument("--loop", default="python", choices=["python", "library"], help="who sequences the sampling loop")
+    ap.add_argument("--seed", type=int, default=None, help="draw the noise from the library's generator under this seed")
     a = ap.parse_args()
     from .config import default_args
     from .diff_params.edm import EDM
@@ -69,7 +74,8 @@ def main():
             y = resample(y, step[0], step[1])
     std = float(y.std())
     y = y * (a.sigma_norm / std)
-    sampler = BlindSampler(net, EDM(args), args, batch_semantics="per_clip")
+    kw = {} if a.seed is None else dict(seed=a.seed, noise_device="philox")
+    sampler = BlindSampler(net, EDM(args), args, batch_semantics="per_clip", loop=a.loop, **kw)
     out, filt = restore_file(sampler, y, batch_size=a.batch)
     name = os.path.splitext(os.path.basename(a.wav))[0]
     p = write_audio_file(out * (std / a.sigma_norm), a.sample_rate, name, a.out_dir)

@@ -41,14 +41,27 @@ class BlindSampler:
 
     obs_snr, sigma_den = None, 0.0        # (class defaults: testing/edm_sampler.Sampler has no observation-noise options)
     _lane_streams, fc_s, A_s = None, None, None        # (made on first use: _sample_lanes, compute_sweep)
+    loop, seed, _csample = "python", None, None        # (class defaults: testing/edm_sampler.Sampler has no library loop)
+    _clip0, _draw = 0, 0                               # noise_device='philox': first clip of the running call, next draw number
 
     def __init__(self, model, diff_params, args, rid=False, batch_semantics="per_clip", noise_device="cpu",
-                 max_segments_in_flight=32):
-        """max_segments_in_flight: with per-clip semantics a larger batch is restored in sub-batches of at most this many
+                 max_segments_in_flight=32, loop="python", seed=None):
+        """loop: "python" (the default) - this class sequences the sampling loop; "library" - predict_blind_bwe and
+        predict_bwe(..., 'fc_A') run as ONE babe_sample_bwe call (csrc/sample.hip through testing/sample_c.py) where
+        sample_c.supported holds, and on the Python loop otherwise.  seed: None - the library run is fed torch's draws (_randn) as
+        a [T+1][B][L] buffer; an integer - it draws from the library's counter-based generator (csrc/randn.hip), clip clip0 + b,
+        draw 0 for the initial state and i + 1 for step i: a function of (weights, y, seed) alone, whatever the batching.
+        noise_device="philox" (needs a seed) makes the Python loop's _randn draw from the same generator with the same numbering.
+        max_segments_in_flight: with per-clip semantics a larger batch is restored in sub-batches of at most this many
         segments, one after the other (clips are independent; the UNet keeps 3.6 GB of activations per 368368-sample
         segment between forward and VJP, so 32 in flight = 115 GB of the 288 GB).  Ignored for 'reference' semantics,
         where the clips of a batch are coupled through the shared filter."""
         self.max_in_flight = int(max_segments_in_flight)
+        if loop not in ("python", "library"):
+            raise ValueError(f"loop must be 'python' or 'library', not {loop!r}")
+        if noise_device == "philox" and seed is None:
+            raise ValueError("noise_device='philox' needs a seed")
+        self.loop, self.seed = loop, (None if seed is None else int(seed))
         self._init_common(model, diff_params, args, batch_semantics, noise_device)
         ps = args.tester.posterior_sampling
         bb = args.tester.blind_bwe
@@ -128,6 +141,13 @@ class BlindSampler:
     def _randn(self, shape, device):
         if self.noise_device == "cpu":
             return torch.randn(shape).to(device)          # reference: CPU draw then copy (:513, edm.py:105)
+        if self.noise_device == "philox":
+            # the library's generator (csrc/randn.hip): draw number = position of this draw in the running _sample call
+            B, n = shape
+            out = torch.empty((B, n), device=device)
+            check(lib().babe_randn(ptr(out), n, B, n, self.seed, self._clip0, self._draw, stream(out)), "randn")
+            self._draw += 1
+            return out
         return torch.randn(shape, device=device)
 
     def _seed(self, r, y, part, post):
@@ -281,8 +301,35 @@ class BlindSampler:
             d2, _, s["fp"] = ev(x_prime, float(t_next), s["fp"])
             s["x"] = lincomb(torch.empty_like(x_prime), 1.0, s["x_hat"], 0.5 * h, s["d"], 0.5 * h, d2)
 
-    def _sample(self, y, filter_params, blind, rid, snoise=1.0, shape=None, device=None, diag=(False, False)):
-        """y None: unconditional sampling of `shape` on `device` (predict_unconditional :366-374).
+    def _sample_library(self, y, filter_params, blind, rid, snoise, clip0):
+        """The whole run as one babe_sample_bwe call (loop="library"); returns what _sample returns."""
+        from . import sample_c
+        B, L = y.shape
+        T = self.nb_steps
+        with torch.cuda.device(y.device):
+            st = self.stft_ops(L, y.device)
+            cs = self._csample
+            if cs is None or cs.ce._keep[1] is not st:
+                cs = self._csample = sample_c.CSample(self)
+            rows, t0, t = sample_c.steps_from(self.diff_params, T, self.order, self.start_sigma, snoise)
+            if not blind and self.batch_semantics == "per_clip" and filter_params.shape[0] == 1 and B > 1:
+                filter_params = filter_params.expand(B, -1, -1)        # the library reads one (known) filter per clip
+            noise = None
+            if self.seed is None:           # torch's draws in the loop's order: the initial state, then one per step
+                noise = torch.stack([self._randn((B, L), y.device) for _ in range(T + 1)]).contiguous()
+            res = cs(self, y, filter_params, blind, rows, t0, self.start_sigma is not None, noise, self.seed or 0, clip0, rid)
+        x, fp = res[0], res[1]
+        if not blind:
+            return (x,)
+        P = fp.shape[0]
+        fp_out = fp[0] if P == 1 else fp
+        if not rid:
+            return x, fp_out
+        return x, fp_out, res[2].cpu(), t, (res[3][:, 0] if P == 1 else res[3]).cpu()
+
+    def _sample(self, y, filter_params, blind, rid, snoise=1.0, shape=None, device=None, diag=(False, False), clip0=0):
+        """clip0: number of the first clip of y within the caller's job (seeded noise only: clip b draws as clip0 + b).
+        y None: unconditional sampling of `shape` on `device` (predict_unconditional :366-374).
         diag = (test_filter_fit, compute_sweep): the two diagnostics of the known-degradation loop (predict :419-466) - per step, on
         the guided Tweedie estimate: a filter fit from the INITIAL conditions (the reference never feeds the estimate back) and
         the fit objective + gradient on a (fc, A) grid.  They do not touch the trajectory; with rid their records are appended."""
@@ -294,6 +341,11 @@ class BlindSampler:
             if self.obs_snr is not None:
                 y = y.clone()                  # the observation noise is added in place: never to the caller's tensor
             shape = y.shape if shape is None else tuple(shape)      # (resample / decimate: the state is longer than y)
+            if self.loop == "library" and tuple(shape) == tuple(y.shape) and not (test_fit or sweep):
+                from . import sample_c
+                if sample_c.supported(self, y, blind, rid):
+                    return self._sample_library(y, filter_params, blind, rid, snoise, clip0)
+        self._clip0, self._draw = int(clip0), 0
         B, L = shape
         with torch.cuda.device(device):
             st = self.stft_ops(L, device)
@@ -431,7 +483,8 @@ class BlindSampler:
     # driver's command in round 5, same box: 2.129 (graphs) vs 2.140 / 2.140 (eager) audio-sec/s - the eager loop has no host
     # sync and enqueues an evaluation in 17 ms of Python against 34 ms of GPU time per evaluation and lane, so there is no launch
     # gap for a graph to close.  Removed, with its pointer-lifetime bookkeeping: one way to sequence the sampler from Python -
-    # this loop - and one for a non-Python host, the library-side UNet sequencer csrc/unet_engine.hip.)
+    # this loop - and one for a non-Python host, the library-side UNet sequencer csrc/unet_engine.hip.  The non-Python host's whole
+    # run is babe_sample_bwe, csrc/sample.hip: BlindSampler(loop="library") takes it.)
     def _sample_lanes(self, x, y, specY, filter_params, blind, snoise, t, gamma):
         B, L = x.shape
         T = self.nb_steps
@@ -484,17 +537,19 @@ class BlindSampler:
         P = 1 if self.batch_semantics == "reference" else B
         return p.unsqueeze(0).repeat(P, 1, 1).contiguous().to(device)
 
-    def predict_blind_bwe(self, y, rid=False, compute_sweep=False):
-        """y [B,L] observations on the GPU -> (x, filter_params[, data_denoised, t, data_filters])  (:619-769)."""
+    def predict_blind_bwe(self, y, rid=False, compute_sweep=False, clip0=0):
+        """y [B,L] observations on the GPU -> (x, filter_params[, data_denoised, t, data_filters])  (:619-769).
+        clip0: with a seed, clip b of y draws its noise as clip number clip0 + b (a caller that restores a file in several
+        calls passes the number of each call's first segment)."""
         # (compute_sweep is accepted and ignored, as in the reference: its blind loop :619-769 never reads the flag)
         B = y.shape[0]
         if self.batch_semantics == "per_clip" and B > self.max_in_flight and not rid:
             outs = [self._sample(y[i:i + self.max_in_flight], self._init_params(min(self.max_in_flight, B - i), y.device),
-                                 blind=True, rid=False) for i in range(0, B, self.max_in_flight)]
+                                 blind=True, rid=False, clip0=clip0 + i) for i in range(0, B, self.max_in_flight)]
             return torch.cat([o[0] for o in outs], 0), torch.cat([o[1].reshape(-1, *o[1].shape[-2:]) for o in outs], 0)
-        return self._sample(y, self._init_params(B, y.device), blind=True, rid=rid)
+        return self._sample(y, self._init_params(B, y.device), blind=True, rid=rid, clip0=clip0)
 
-    def predict_bwe(self, ylpf, filt, filt_type, rid=False, test_filter_fit=False, compute_sweep=False):
+    def predict_bwe(self, ylpf, filt, filt_type, rid=False, test_filter_fit=False, compute_sweep=False, clip0=0):
         """Known-degradation variant (:306-364 -> predict_conditional :387-404 -> predict :406-498).
         filt_type 'fc_A' (filt = [2,K] breakpoints), 'firwin' / 'firwin_hpf' (filt = FIR taps applied with
         conv1d(padding="same"), :211-218), 'cheby1' (filt = (b, a): lfilter, clamp=False, :219-221), 'biquad' (filt = the six
@@ -504,7 +559,7 @@ class BlindSampler:
         (:376-385): state of shape (B, audio_len), y shorter, x returned alone whatever rid is."""
         L = int(self.args.exp.audio_len)
         deg, params = make_degradation(filt, filt_type, ylpf.device, L)
-        kw = dict(diag=(bool(test_filter_fit), bool(compute_sweep)))
+        kw = dict(diag=(bool(test_filter_fit), bool(compute_sweep)), clip0=clip0)
         if filt_type in ("resample", "decimate"):
             # predict_resample (:376-385) -> predict(shape, device): rid, test_filter_fit and compute_sweep are not passed on there.
             # The reference adds y to the initial noise with start_sigma and to A(x0) with data_consistency - shapes that differ
@@ -518,7 +573,7 @@ class BlindSampler:
             if ylpf.shape[-1] != deg.out_length():
                 raise ValueError(f"predict_bwe(..., {filt_type!r}): y has {ylpf.shape[-1]} samples, the degradation of audio_len = {L} "
                                  f"yields {deg.out_length()}")
-            rid, kw = False, dict(shape=(ylpf.shape[0], L))
+            rid, kw = False, dict(shape=(ylpf.shape[0], L), clip0=clip0)
         with self._guiding(deg):
             res = self._sample(ylpf, params, blind=False, rid=rid, snoise=self.diff_params.Snoise, **kw)
         return res if rid else res[0]

@@ -66,11 +66,14 @@ def restore_file(sampler, y, batch_size=8, blind=True, filt=None, filt_type="fc_
     for i in range(0, segs.shape[0], batch_size):
         chunk = segs[i:i + batch_size].contiguous()
         if blind:
-            x, fp = sampler.predict_blind_bwe(chunk)
+            # (a seeded sampler numbers the file's segments: segment j draws as clip j however the batches are cut)
+            seeded = getattr(sampler, "seed", None) is not None
+            x, fp = sampler.predict_blind_bwe(chunk, clip0=i) if seeded else sampler.predict_blind_bwe(chunk)
             fp = fp if fp.dim() == 3 else fp.unsqueeze(0).expand(chunk.shape[0], -1, -1)
             filters += [fp[j] for j in range(chunk.shape[0])]
         else:
-            x = sampler.predict_bwe(chunk, filt, filt_type)
+            seeded = getattr(sampler, "seed", None) is not None
+            x = sampler.predict_bwe(chunk, filt, filt_type, clip0=i) if seeded else sampler.predict_bwe(chunk, filt, filt_type)
         preds.append(x)
     preds = torch.cat(preds, 0)
     out = assemble(preds, plan, L, segL, 200, ola)

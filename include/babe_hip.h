@@ -571,6 +571,61 @@ int babe_score_eval(const babe_eval_desc* desc, const float* x, float t, float c
                     long ws_bytes, int B, void* stream);
 int babe_fill(float* out, float v, int n, void* stream);            /* out[0..n) = v (the [B][1] cnoise input of the embedding) */
 
+/* ---- counter-based Gaussian noise (csrc/randn.hip): Philox4x32-10 with the Random123 constants (multipliers 0xD2511F53,
+ * 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; 10 rounds).  Element i of clip c, draw k, under seed s has ONE definition,
+ * whatever the grid, the block size or the batch it is produced in:
+ *   counter = (q & 0xffffffff, q >> 32, c, k) with q = i / 4;  key = (s & 0xffffffff, s >> 32);  output word i % 4
+ *   u1 = ((r >> 9) + 0.5) * 2^-23 in (0, 1),  u2 = (r' >> 9) * 2^-23   (both exact in float32; r, r' = words (0,1) and (2,3))
+ *   z  = sqrt(-2 ln u1) * (cospi(2 u2), sinpi(2 u2))                     (Box-Muller; |z| <= 5.78)
+ * with logf / sqrtf / sincospif (not the fast intrinsics).  out rows may start at any 4-byte boundary (16-byte stores where a
+ * row starts on a 16-byte one); out_bs >= n for B > 1; 1 <= B <= 65535; 0 <= clip0, clip0 + B <= 2^32; 0 <= draw < 2^32;
+ * anything else returns BABE_ERR_ARG before a launch. */
+/* host, no GPU: out[4] = philox4x32-10(ctr[4], key[2]) - the definition the kernel implements */
+int babe_philox4x32(const int* ctr, const int* key, int* out);
+/* out[b][i] (row stride out_bs) = draw `draw` of clip clip0 + b under `seed`, i in [0, n) */
+int babe_randn(float* out, long out_bs, int B, long n, long seed, long clip0, long draw, void* stream);
+/* the raw 32-bit words behind the same elements (tests pin these bit for bit) */
+int babe_rand_bits(int* out, long out_bs, int B, long n, long seed, long clip0, long draw, void* stream);
+
+/* ---- one whole SAMPLING RUN from plan handles (csrc/sample.hip): what BlindSampler._sample -> step -> _heun_first /
+ * _heun_second sequence from Python (testing/blind_bwe_sampler.py:619-769, :509-516), as one call for a non-Python host:
+ * specY = babe_stft_fwd(y) -> initial state -> per step: noise injection babe_lincomb3(1, x, inject, eps), babe_score_eval at
+ * t_hat, then the Euler update x_hat + h d or the Heun pair (x' = x_hat + h d, babe_score_eval at t_next, x_hat + h/2 d + h/2 d').
+ * Scope: exactly babe_score_eval's (blind or known fc_A filter, L2 guidance, no observation noise / data consistency / AR mask /
+ * FIR or IIR degradation, fp32 network without attention).  Like babe_score_eval the run contains no schedule formula: the
+ * caller passes one row per step (babe_edm_steps fills them for a host without the Python EDM class).  Same kernels, order and
+ * scalars as the Python loop: bit-identical to it (tests/test_gpu_sample_c.py).  No allocation, no synchronisation; a failing
+ * inner call returns its code; every argument is checked on the host before the first launch.  Two runs on two streams, each
+ * with its own unet_state and workspace over one plan, are legal.  Lanes are the caller's: two runs, two calls. */
+typedef struct {
+    float t_hat;              /* t_i + gamma_i t_i: noise level of the first evaluation                         */
+    float inject;             /* sqrt(t_hat^2 - t_i^2) * Snoise:  x_hat = x + inject * eps_i                    */
+    float t_next, h;          /* h = t_next - t_hat                                                             */
+    int   heun;               /* 1: second evaluation at t_next + trapezoidal update; 0: Euler (t_next == 0 or order 1) */
+    float c1[4], c2[4];       /* cskip, cout, cin, cnoise at t_hat / at t_next                                  */
+} babe_sample_step;
+typedef struct {
+    babe_eval_desc eval;      /* as for babe_score_eval; K and blind are read from here                        */
+    int T; const babe_sample_step* steps;   /* host memory, T rows                                             */
+    float t0; int warm_start; /* x_0 = (warm_start ? y : 0) + t0 * eps_init                                    */
+} babe_sample_desc;
+long babe_sample_workspace_bytes(const babe_sample_desc* d, int B);
+/* y [B][L] observations; params [P][2][K] (P = B, or 1 with eval.shared): in the initial filter parameters, out the final ones
+ * (updated in place on the device by every evaluation when eval.blind); x_out [B][L] the restored signal (it carries the state
+ * during the run).  noise [T+1][B][L]: draw 0 is the initial state, draw i + 1 step i; NULL: the draws come from
+ * babe_randn(seed, clip0, draw) into one workspace buffer, so that the run is a function of (weights, y, seed) alone.
+ * rec_x_den [T][B][L] / rec_params [T][P][2][K] (each may be NULL): the FIRST evaluation's denoised estimate of every step and the
+ * parameters after it - what predict_blind_bwe(rid=True) keeps -, copied device to device on the stream. */
+int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, float* x_out, const float* noise, long seed, long clip0,
+                    float* rec_x_den, float* rec_params, void* ws, long ws_bytes, int B, void* stream);
+/* host helper for hosts without the Python EDM class: fills steps[T] and *t0 from the tester's diff_params in double arithmetic
+ * (diff_params/edm.py:38-75, :108-139): t_i = (s0^(1/ro) + i/(T-1) (sigma_min^(1/ro) - s0^(1/ro)))^ro, t_T = 0, s0 = start_sigma
+ * (<= 0: sigma_max); gamma_i = min(Schurn/(T+1), sqrt 2 - 1) where Stmin < t_i < Stmax.  T >= 2, order 1 or 2.  Snoise scales the
+ * injected noise (predict_blind_bwe injects with 1, predict_bwe with diff_params.Snoise: pass what the run you mirror uses).
+ * The Python class evaluates the same formulas in float32, so its rows differ in the last bits ((ro + 4) 2^-23 relative). */
+int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double sigma_min, double sigma_max, double ro,
+                   double sigma_data, double Schurn, double Stmin, double Stmax, double Snoise, double start_sigma);
+
 /* ---- Denoiser pre-pass: networks/denoiser.py:232-321 (MultiStage_denoise, inference only) and
  * testing/denoise_and_bwe_tester.py:146-165 (STFT 1024/256 -> network -> inverse STFT).  csrc/denoiser.hip --------- */
 /* General small-kernel Conv2d on [B][C][H][W] tensors with contiguous rows (replaces nn.Conv2d with
