@@ -64,7 +64,7 @@ class CqtBands(C.Structure):
                 ("oct", C.c_void_p), ("binoct", C.c_void_p), ("tw4096", C.c_void_p),
                 ("nocts", C.c_int), ("binsoct", C.c_int), ("coef", C.c_void_p * 8),
                 ("wg_first", C.c_void_p), ("wg_count", C.c_void_p), ("nwg", C.c_int),
-                ("wg_rec", C.c_void_p), ("band_rec", C.c_void_p), ("abl", C.c_int),
+                ("wg_rec", C.c_void_p), ("band_rec", C.c_void_p), ("reserved", C.c_int),
                 ("max_wg_count", C.c_int), ("min_log2T", C.c_int), ("max_log2T", C.c_int),
                 ("sum_T", C.c_long), ("sum_M", C.c_long), ("sum_TlogT", C.c_double),
                 ("kdeg", C.c_int), ("kpoly", C.c_float * 12)]

@@ -20,10 +20,6 @@
 #include "conv_common.h"
 #include <cstdlib>
 
-#ifndef C11_SYNC_AT_END
-#define C11_SYNC_AT_END 0          // 1: the round-2 form (one __syncthreads() = vmcnt(0) + barrier at the end of every slab)
-#endif
-
 namespace {
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
@@ -257,17 +253,15 @@ __device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const Conv
 #pragma unroll
         for (int st = 0; st < KC / 2; ++st) {
             const int c = st & 1;
-#if !C11_SYNC_AT_END
             if (st == KC / 2 - 1) {
                 // COUNTED wait (round 4): the workgroup synchronises before the LAST K-step of slab j, and each wave waits only for
                 // its part of slab j+1 (vmcnt(n) with n = the XJ + WJ DMA instructions of slab j+2, the youngest in the queue), so
-                // slab j+2 stays in flight across the barrier: two slabs of prefetch distance instead of the one that
-                // __syncthreads()' vmcnt(0) left.  Safe for the ring: the operands of this last step are already in registers
+                // slab j+2 stays in flight across the barrier: two slabs of prefetch distance instead of the one that the round-2
+                // form (one __syncthreads() = vmcnt(0) + barrier at the end of every slab) left.  Safe for the ring: the operands of this last step are already in registers
                 // (read during step KC/2 - 2, complete at lgkmcnt(0)), so after the barrier nobody reads slab j's buffer again,
                 // and the reads of slab j+1 below come after every wave's part of it has landed.
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(XJ + WJ) : "memory");
             }
-#endif
             if (st + 1 < KC / 2) {
                 AVec<NT>::ld(Xs + aoff + 2 * (st + 1) * BN, av[c ^ 1]);
 #pragma unroll
@@ -288,18 +282,13 @@ __device__ __forceinline__ void conv11p_body(const babe_conv_args& a, const Conv
                 for (int wp = 0; wp < NPW; ++wp)
                     acc[nt][wp] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][nt], bv[c][wp], acc[nt][wp], 0, 0, 0);
         }
-#if C11_SYNC_AT_END
-        __syncthreads();                                   // slab j+2 landed (vmcnt(0)), slab j's buffer free
-#endif
         if (HAS_ISC) {
 #pragma unroll
             for (int st = 0; st < KC / 2; ++st) scur[st] = snext[st];
         }
         rb = rn;
     }
-#if !C11_SYNC_AT_END
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // the clamped re-stage of the last slab: nothing lands in LDS after the loop
-#endif
     conv11p_epilogue<NT, NPW, HAS_FB>(a, acc, b, co0, f0, t0, g.pt_log2, wave, l31, h);
 #endif
 }

@@ -41,10 +41,6 @@ struct Bf16pGeom {
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 constexpr unsigned OOB = 0x80000000u;      // beyond every descriptor's num_records: the load returns 0, touches nothing
 
-#ifndef ABL
-#define ABL 0
-#endif
-
 template <int G, int KW, bool HAS_ISC, bool UNITS = false>
 __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(babe_conv_args a, Bf16pGeom g,
                                                                                const unsigned short* __restrict__ wq) {
@@ -182,7 +178,7 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
     float xh[8], xsc[8];
 
     auto issue_act = [&](int kh, int ci0) {
-        if ((ABL & 1) || UNITS) return;
+        if (UNITS) return;
         const int foff = (kh - khc) * a.dil;
         const bool s2 = ci0 >= split;
         const int nch = s2 ? a.Cin - split : split;
@@ -220,7 +216,7 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
         return o;
     };
     auto store_main = [&](bf16x8* buf, int k0, int k1) {
-        if ((ABL & 8) || UNITS) return;
+        if (UNITS) return;
 #pragma unroll
         for (int k = k0; k < k1; ++k) {
             float v[8];
@@ -229,9 +225,8 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
             buf[xslot + (k == 3 ? 1 : (k + 1) * PI)] = pack8(v);           // unit 4*i4 + 1 + k
         }
     };
-    auto store_halo = [&](bf16x8* buf) { if (KW == 3 && !(ABL & 8) && !UNITS) buf[hslot] = pack8(xh); };
+    auto store_halo = [&](bf16x8* buf) { if (KW == 3 && !UNITS) buf[hslot] = pack8(xh); };
     auto dma_w = [&](int kh, int ci0, bf16x8* buf) {
-        if (ABL & 32) return;
         const int so = ((kh * KW) * g.GP + (ci0 >> 3)) * g.CoutP * 16;     // bytes, scalar
 #pragma unroll
         for (int jj = 0; jj < WJ; ++jj)
@@ -294,16 +289,14 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
     for (int j = 0; j < nslab; ++j) {
         const bf16x8* Xs = smem + cur * BUF;
         bf16x8* Xw = smem + (cur ^ 1) * BUF;
-#define READ_A(c, gp, kw) if (!(ABL & 4) || j == 0) \
+#define READ_A(c, gp, kw) \
     _Pragma("unroll") for (int nt = 0; nt < NT; ++nt) av[c][nt] = Xs[aoff + ((kw) * G + 2 * (gp)) * BN + nt * 32];
-#define READ_S(gp, m) if (!(ABL & 4) || j == 0) sv[(gp) & 1][m] = Xs[boff[m] + (gp) * gpo];
+#define READ_S(gp, m) sv[(gp) & 1][m] = Xs[boff[m] + (gp) * gpo];
 #define MFMA_TAP(c, gp, kw)                                                                                   \
-    if (!(ABL & 2)) {                                                                                         \
-        _Pragma("unroll") for (int q = 0; q < NP; ++q)                                                        \
-            acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], sv[(gp) & 1][q + (kw)], acc[0][q], 0, 0, 0); \
-        if (both) _Pragma("unroll") for (int q = 0; q < NP; ++q)                                              \
-            acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], sv[(gp) & 1][q + (kw)], acc[1][q], 0, 0, 0); \
-    }                                                                                                         \
+    _Pragma("unroll") for (int q = 0; q < NP; ++q)                                                            \
+        acc[0][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][0], sv[(gp) & 1][q + (kw)], acc[0][q], 0, 0, 0); \
+    if (both) _Pragma("unroll") for (int q = 0; q < NP; ++q)                                                  \
+        acc[1][q] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(av[c][1], sv[(gp) & 1][q + (kw)], acc[1][q], 0, 0, 0); \
     __builtin_amdgcn_sched_barrier(0);
         if (KW == 3) { READ_S(0, 0) }
         READ_S(0, 1) READ_A(0, 0, 0) READ_S(0, 2) READ_S(0, 3)
@@ -347,7 +340,7 @@ __global__ __launch_bounds__(128 * G, (G == 4 ? 1 : 2)) void conv_bf16p_kernel(b
         if (UNITS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         else if (KW == 3) asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        if (!(ABL & 16)) __syncthreads();
+        __syncthreads();
         cur ^= 1;
     }
 #undef READ_A

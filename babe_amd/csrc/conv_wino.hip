@@ -23,8 +23,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-// ABL: compile-time ablation bits for profiling builds (1 no global loads, 2 no LDS stores, 4 no barrier, 8 no MFMA)
-template <int NTW, int WR, int WC, int ABL = 0>
+template <int NTW, int WR, int WC>
 __global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_args a, ConvTileGeom g,
                                                                  const float* __restrict__ wq) {
     constexpr int NTH = 64 * WR * WC;
@@ -161,7 +160,7 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_ar
             while (nkh < a.KH && !kh_valid(nkh)) ++nkh;
         }
         const bool has_next = nkh < a.KH;
-        if (has_next && (!(ABL & 1) || ci0 == 0)) load_chunk(nkh, nci);
+        if (has_next) load_chunk(nkh, nci);
         const f32x4* Xs = smem + cur * BUF;
         f32x4 av[2][NTW], bv[2];
 #pragma unroll
@@ -176,21 +175,14 @@ __global__ __launch_bounds__(64 * WR * WC, 2) void conv_wino_kernel(babe_conv_ar
                 bv[c ^ 1] = Xs[boff + 2 * (st + 1) * NPAIR];
             }
             __builtin_amdgcn_sched_barrier(0);
-            if (!(ABL & 8)) {
 #pragma unroll
             for (int nt = 0; nt < NTW; ++nt)
 #pragma unroll
                 for (int p = 0; p < 4; ++p)
                     acc[nt][p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][nt][p], bv[c][p], acc[nt][p], 0, 0, 0);
-            } else {
-#pragma unroll
-            for (int nt = 0; nt < NTW; ++nt)
-#pragma unroll
-                for (int p = 0; p < 4; ++p) acc[nt][p][0] += av[c][nt][p] * bv[c][p];
-            }
         }
-        if (has_next && !(ABL & 2)) store_chunk(smem + (cur ^ 1) * BUF);
-        if (!(ABL & 4)) __syncthreads();
+        if (has_next) store_chunk(smem + (cur ^ 1) * BUF);
+        __syncthreads();
         if (!has_next) break;
         kh = nkh;
         ci0 = nci;
@@ -513,7 +505,7 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, float* __restrict_
     }
 }
 
-template <int NTW, int WR, int WC, int ABL = 0>
+template <int NTW, int WR, int WC>
 void launch(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int NPOS = 64 * WC;
     int tiles_f;
@@ -521,7 +513,7 @@ void launch(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int BN = WR * NTW * 32;
     dim3 grid(g.tiles_t * tiles_f, g.CoutP / BN, a.B);
     const size_t lds = 2 * (size_t)(8 * (WC * 32) + 8 * BN) * 16;
-    hipLaunchKernelGGL((conv_wino_kernel<NTW, WR, WC, ABL>), grid, dim3(64 * WR * WC), lds, s, a, g, wq);
+    hipLaunchKernelGGL((conv_wino_kernel<NTW, WR, WC>), grid, dim3(64 * WR * WC), lds, s, a, g, wq);
 }
 
 template <int NTW, int WC>

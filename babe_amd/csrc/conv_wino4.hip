@@ -31,8 +31,7 @@
 
 namespace {
 
-// ABL: compile-time ablation bits for profiling builds (1 no global loads, 2 no LDS stores, 4 no barrier)
-template <int NTW, int WR, int WC, int ABL = 0>
+template <int NTW, int WR, int WC>
 __global__ __launch_bounds__(128 * WR * WC, (WR * WC <= 2 ? 2 : 1)) void conv_wino4_kernel(babe_conv_args a, ConvTileGeom g,
                                                                                         const float* __restrict__ wq) {
     constexpr int NTH = 128 * WR * WC;
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(128 * WR * WC, (WR * WC <= 2 ? 2 : 1)) void conv_wi
             while (nkh < a.KH && !kh_valid(nkh)) ++nkh;
         }
         const bool has_next = nkh < a.KH;
-        if (has_next && (!(ABL & 1) || ci0 == 0)) load_chunk(nkh, nci, smem + (cur ^ 1) * BUF);
+        if (has_next) load_chunk(nkh, nci, smem + (cur ^ 1) * BUF);
         const f32x4* Xs = smem + cur * BUF;
         f32x4 av[2][NTW], bv[2];
 #pragma unroll
@@ -196,8 +195,8 @@ __global__ __launch_bounds__(128 * WR * WC, (WR * WC <= 2 ? 2 : 1)) void conv_wi
                 for (int p = 0; p < 3; ++p)
                     acc[nt][p] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[c][nt][p], bv[c][p], acc[nt][p], 0, 0, 0);
         }
-        if (has_next && !(ABL & 2)) store_chunk(smem + (cur ^ 1) * BUF);
-        if (!(ABL & 4)) __syncthreads();
+        if (has_next) store_chunk(smem + (cur ^ 1) * BUF);
+        __syncthreads();
         if (!has_next) break;
         kh = nkh;
         ci0 = nci;
@@ -287,7 +286,7 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, float* __restrict
     d[CoutP] = f32x4{(float)(w0 / 24 + w1 / 12 + w2 / 6), (float)(w0 / 24 - w1 / 12 + w2 / 6), (float)w2, 0.f};
 }
 
-template <int NTW, int WR, int WC, int ABL = 0>
+template <int NTW, int WR, int WC>
 void launch4(const babe_conv_args& a, const float* wq, hipStream_t s) {
     constexpr int NPOS = 128 * WC;
     int tiles_f;
@@ -297,7 +296,7 @@ void launch4(const babe_conv_args& a, const float* wq, hipStream_t s) {
     size_t lds = 2 * (size_t)(2 * 8 * (WC * 32) + 2 * 8 * BN) * 16;
     const size_t ex = (size_t)WR * WC * 3072 * 4;
     if (ex > lds) lds = ex;
-    hipLaunchKernelGGL((conv_wino4_kernel<NTW, WR, WC, ABL>), grid, dim3(128 * WR * WC), lds, s, a, g, wq);
+    hipLaunchKernelGGL((conv_wino4_kernel<NTW, WR, WC>), grid, dim3(128 * WR * WC), lds, s, a, g, wq);
 }
 
 }  // namespace

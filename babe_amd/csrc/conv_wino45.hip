@@ -30,16 +30,6 @@
 #include "prof.h"
 #include "conv_common.h"
 #include <cstdlib>
-#include <type_traits>
-
-
-// ABL: compile-time ablation bits for profiling builds (tools/ab/abl_build.sh conv_wino45 <mask>): 1 no activation loads,
-// 2 no MFMA, 4 no operand LDS reads, 8 no input transform / LDS stores, 16 no barrier, 32 no weight DMA, 64 every slab
-// loads channel 0 (cache-resident loads: same instructions, no memory-side traffic).  NB: with the loads or the transform
-// removed hipcc also removes whatever became dead (ablation 1 drops the transform arithmetic too) (cache-resident loads: same instructions, no memory-side traffic)
-#ifndef ABL
-#define ABL 0
-#endif
 
 namespace {
 
@@ -68,16 +58,13 @@ static inline int wino45_best_tsh(const babe_conv_args& a) {
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 constexpr unsigned OOBH = 0xC0000000u;     // invalid offsets start here: +-(a source view < 1 GiB) stays >= 2^31
 
-// Optional register cap (-DBABE_W45_NUM_VGPR=112; the attribute counts in halves of the unified file on gfx90a+, so 112 means
-// 224 registers per wave).  Idea: two waves of this kernel per SIMD would then leave 64 of the SIMD's 512 registers, room
-// for one wave of an element-wise kernel (GroupNorm, GELU, axpby, resample: 8..62 VGPRs) of the sampler's other lane.
+// amdgpu_num_vgpr counts in halves of the unified file on gfx90a+: 128 is no cap (248 / 243 registers, no spills).  A cap of
+// 112 (224 registers per wave) was tried: two waves of this kernel per SIMD would then leave 64 of the SIMD's 512 registers,
+// room for one wave of an element-wise kernel (GroupNorm, GELU, axpby, resample: 8..62 VGPRs) of the sampler's other lane.
 // Measured (round 3, same box, same session): 25 spilled registers, kernels 1 % slower, headline 1.636 vs 1.640 - the
-// two-lane overlap is not limited by registers.  Default: no cap (248 / 243 registers, no spills).
-#ifndef BABE_W45_NUM_VGPR
-#define BABE_W45_NUM_VGPR 128
-#endif
+// two-lane overlap is not limited by registers.
 template <bool HAS_ISC, bool PADC>
-__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM_VGPR))) void conv_wino45_kernel(babe_conv_args a, Wino45Geom g, const float* __restrict__ wq) {
+__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(128))) void conv_wino45_kernel(babe_conv_args a, Wino45Geom g, const float* __restrict__ wq) {
 #if __HIP_DEVICE_COMPILE__
     constexpr int NTH = 512, KC = 8, BN = 64, NU = 64;
     constexpr int XSZ = KC * NU * 3;                    // float4 per activation image (12 floats per (ci, unit))
@@ -180,8 +167,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
     // issued back to back by all eight waves they queue up in front of the CU's one address unit and every wave sits in
     // its load-issue phase at the same time (ablation: 240 of 750 us on the 256-channel layers).
     auto issue_rows = [&](int set, int ps, int ci0, int r0, int r1) __attribute__((always_inline)) {
-        if (ABL & 1) return;
-        const int so = (ABL & 64) ? 0 : (ci0 + wave) * cs1 * 4;       // scalar: channel of this wave
+        const int so = (ci0 + wave) * cs1 * 4;          // scalar: channel of this wave
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
             if (r < r0 || r >= r1) continue;
@@ -192,8 +178,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
         }
     };
     auto issue_halo = [&](int set, int ci0) __attribute__((always_inline)) {
-        if (ABL & 1) return;
-        const int so = (ABL & 64) ? 0 : (ci0 + wave) * cs1 * 4;
+        const int so = (ci0 + wave) * cs1 * 4;
         xhls[set] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, ehalo, so, 0));
     };
     auto issue_isc = [&](int set, int ci0) __attribute__((always_inline)) {
@@ -209,8 +194,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
     // but no traffic: behind a branch hipcc cannot count the outstanding loads any more and waits for vmcnt(0) at the next
     // transform, i.e. for the loads of the OTHER register set too.
     auto issue_edge = [&](int ps, int ci0) __attribute__((always_inline)) {
-        if (ABL & 1) return;
-        const int so = (ABL & 64) ? 0 : (ci0 + wave) * cs1 * 4;
+        const int so = (ci0 + wave) * cs1 * 4;
         const unsigned edge = ps == 2 ? 0u : OOBH;
         xve[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[0] | edge, so, 0));
         xve[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[5] | edge, so, 0));
@@ -247,7 +231,6 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
         U[5] = 4.f * E[1] + (E[5] - 5.f * E[3]);
     };
     auto store_act = [&](int set, f32x4* buf) __attribute__((always_inline)) {
-        if (ABL & 8) return;
         const int ps = pSs[set];
         const f32x4 xv[6] = {xve[0], xvs[set][0], xvs[set][1], xvs[set][2], xvs[set][3], xve[1]};
         const float xhl = xhls[set], xsc = xscs[set];
@@ -309,7 +292,6 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
     // weight slab [8 ci][64 co][12] = 24 chunks of 1 KB (one wave instruction each), 3 per input channel; wave w moves chunks
     // w, w + 8, w + 16: the chunk part of the address is scalar, the LDS image is the slab as it lies in memory
     auto dma_w = [&](int ps, int ci0, f32x4* buf, int j0, int j1) __attribute__((always_inline)) {
-        if (ABL & 32) return;
 #pragma unroll
         for (int jj = j0; jj < j1; ++jj) {
             const int c = wave + 8 * jj;
@@ -360,12 +342,12 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
     int rb = 0;                                   // ring slot of the slab being multiplied
     int pM = 0, cM = 0;                           // slab being multiplied (for the pass boundaries)
 #define MFMA_GRP(c, pg)                                                                                               \
-    if (!(ABL & 2) && mact) _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                            \
+    if (mact) _Pragma("unroll") for (int i = 0; i < 4; ++i) {                                                          \
         acc[0][4 * (pg) + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][0][i], acc[0][4 * (pg) + i], 0, 0, 0); \
         acc[1][4 * (pg) + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][1][i], acc[1][4 * (pg) + i], 0, 0, 0); \
     }
 #define READ_GRP(c, base, ks, pg)                                                   \
-    if ((!(ABL & 4) || j == 0) && mact) {                                           \
+    if (mact) {                                                                     \
         av[c] = (base)[aoff + (ks) * 4 * BN * 3 + (pg)];                            \
         bv[c][0] = (base)[boff + (ks) * 4 * NU * 3 + (pg)];                         \
         bv[c][1] = (base)[boff + (ks) * 4 * NU * 3 + 16 * 3 + (pg)];                \
@@ -409,13 +391,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
         /* i.e. for the loads of slab j+3 issued during this slab.  Memory operations complete in order, so the slab      */ \
         /* issues: rows 0 / 5 of slab j+3, the three weight DMAs, then its 4 rows + halo: vmcnt(5) leaves those five in    */ \
         /* flight.                                                                                                         */ \
-        if (ABL & 16) {                                                                                    \
-        } else if (ABL & 1) {                                                                              \
-            __syncthreads();                                                                               \
-        } else {                                                                                           \
-            asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)");                                                 \
-            __builtin_amdgcn_s_barrier();                                                                  \
-        }                                                                                                  \
+        asm volatile("s_waitcnt vmcnt(5) lgkmcnt(0)");                                                     \
+        __builtin_amdgcn_s_barrier();                                                                      \
         rb = rn;                                                                                           \
     }
     // pass boundary: carry the finished phases into the accumulators of the next pass (see the header)
@@ -527,15 +504,12 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45_NUM
 // slot are issued in the last group of the previous one: slot 1 at g2 (its last chunk was issued at g8 of the previous
 // super-slab: 11 younger operations without the edge rows), slot 2 at g5 (g11 of the previous one: 11), slot 3 at g8 (g2: 7), slot 0 of the next
 // super-slab at g11 (g5: 6).
-// (-DBABE_W45X_NUM_VGPR=96 caps the kernel at 192 registers - the attribute counts halves of the unified file - so that two
-// 64-register waves of the other lane's element-wise kernels would fit beside the two conv waves of a SIMD.  Measured, round 4,
-// same box: 76-136 spilled registers, a few of them inside the loop, whole-job throughput 1.44 instead of 2.06 audio-sec/s.
-// Default 128 = no cap.)
-#ifndef BABE_W45X_NUM_VGPR
-#define BABE_W45X_NUM_VGPR 128
-#endif
+// (amdgpu_num_vgpr(128) = no cap.  96 would cap the kernel at 192 registers - the attribute counts halves of the unified file -
+// so that two 64-register waves of the other lane's element-wise kernels would fit beside the two conv waves of a SIMD.
+// Measured, round 4, same box: 76-136 spilled registers, a few of them inside the loop, whole-job throughput 1.44 instead of
+// 2.06 audio-sec/s.)
 template <bool HAS_ISC, int BN>
-__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NUM_VGPR))) void conv_wino45x_kernel(babe_conv_args a, Wino45Geom g, const float* __restrict__ wq) {
+__global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(128))) void conv_wino45x_kernel(babe_conv_args a, Wino45Geom g, const float* __restrict__ wq) {
 #if __HIP_DEVICE_COMPILE__
     constexpr int KS = 16, KQ = 4, NU = 32;
     static_assert(BN == 128 || BN == 96, "tile width");
@@ -613,25 +587,9 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
         sW = sW < sWend ? sW : sWend;
     };
     f32x4* const Ww = Wb + wave * WWV;                   // this wave's part of ring position 0
-    // (ablation bits of this kernel, profiling builds only - results are wrong: 0x2000 no weight DMA, 0x4000 no row / edge / halo
-    // loads, 0x8000 no transform (halo permutes, vector work, LDS stores), 0x10000 no barrier)
-#define X_DMA(rp, j) \
-    if (!(ABL & 0x2000)) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, LDS_PTR(Ww + (rp) * WSL + (j) * 64), 16, wvl[j], sW, 0, 0);
+#define X_DMA(rp, j) __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, LDS_PTR(Ww + (rp) * WSL + (j) * 64), 16, wvl[j], sW, 0, 0);
 #define X_FENCE0 __builtin_amdgcn_sched_barrier(0);
-#if (ABL & 0x100000)
-#define X_WAITVM(n)                                      /* (ablation: no counted waits at all - racy, timing only) */
-#elif (ABL & 256)
-#define X_WAITVM(n) asm volatile("s_waitcnt vmcnt(0)");
-#elif (ABL & 512)
-#define X_WAITVM(n) asm volatile("s_waitcnt vmcnt(0)"); __builtin_amdgcn_s_barrier();
-#else
 #define X_WAITVM(n) asm volatile("s_waitcnt vmcnt(" #n ")");
-#endif
-#if (ABL & 0x20000)
-#define X_WAITVM13 X_WAITVM(13)
-#else
-#define X_WAITVM13 X_WAITVM(11)
-#endif
 
     f32x4 xvm[4], xve[2];
     float xhl = 0.f, xsc = 1.f;
@@ -639,7 +597,6 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
     int pS = 0;
     xve[0] = xve[1] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto issue_rows = [&](int ci0, int r0, int r1) __attribute__((always_inline)) {
-        if (ABL & 0x4000) return;
         const int so = (ci0 + 2 * wave) * cs1 * 4;
 #pragma unroll
         for (int r = 1; r < 5; ++r) {
@@ -648,7 +605,6 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
         }
     };
     auto issue_halo = [&](int ci0) __attribute__((always_inline)) {
-        if (ABL & 0x4000) return;
         const int so = (ci0 + 2 * wave) * cs1 * 4;
         xhl = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, ehalo, so, 0));
     };
@@ -659,21 +615,15 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
         }
     };
     auto issue_edge = [&](int ps, int ci0) __attribute__((always_inline)) {
-        if (ABL & 0x4000) return;
         const int so = (ci0 + 2 * wave) * cs1 * 4;
-#if !(ABL & 0x20000)
         // the two edge-row loads only in the pass that uses them (a wave-uniform branch; the hand-counted waits assume they are
-        // absent: 11 where the always-issued form - ABL bit 0x20000 - has 13).  A vector-memory instruction costs this kernel
-        // 1-2 % of its time whether it moves data or not (ablations): +2 % over all layers, +5 % on the 96-channel ones.
+        // absent: 11 where a form that always issued them, out of range outside pass 2, had 13).  A vector-memory instruction
+        // costs this kernel 1-2 % of its time whether it moves data or not (ablations): +2 % over all layers, +5 % on the
+        // 96-channel ones.
         if (ps == 2) {
             xve[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[0], so, 0));
             xve[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[5], so, 0));
         }
-#else
-        const unsigned edge = ps == 2 ? 0u : OOBH;
-        xve[0] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[0] | edge, so, 0));
-        xve[1] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs1, er[5] | edge, so, 0));
-#endif
     };
     auto dpp_shr1 = [](float old, float src) __attribute__((always_inline)) {
         asm("s_nop 1\n\tv_mov_b32_dpp %0, %1 row_shr:1 row_mask:0xf bank_mask:0xf" : "+v"(old) : "v"(src));
@@ -700,14 +650,12 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
     // statement that consumes them waits).  Rows 0 / 5 are used by pass 2 only; their two bpermutes are issued in every pass
     // (an LDS instruction does not cost matrix-pipe time, a branch here would cost hipcc's register shuffling)
     auto halo_permute = [&]() __attribute__((always_inline)) {
-        if (ABL & 0x8000) return;
 #pragma unroll
         for (int r = 0; r < 6; ++r)
             asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "=v"(xh[r]) : "v"(hsrc), "v"(xhl), "n"(32 * r));
     };
     // (same arithmetic, in the same order, as conv_wino45_kernel::store_act: bit-identical products)
     auto store_act = [&](f32x4* buf) __attribute__((always_inline)) {
-        if (ABL & 0x8000) return;
         const int ps = pS;
         const f32x4 xv[6] = {xve[0], xvm[0], xvm[1], xvm[2], xvm[3], xve[1]};
         const float k2 = fsel(ps, 0x40800000u, 0x3f800000u, 0x40a00000u);
@@ -722,8 +670,7 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
             float d[6];
 #pragma unroll
             for (int r = 1; r < 5; ++r)
-                d[r] = (ABL & 0x80000) ? xv[r][j == 0 ? 0 : (j == 5 ? 3 : j - 1)]
-                                        : (j == 0 ? dpp_shr1(xh[r], xv[r][3]) : (j == 5 ? dpp_shl1(xh[r], xv[r][0]) : xv[r][j - 1]));
+                d[r] = j == 0 ? dpp_shr1(xh[r], xv[r][3]) : (j == 5 ? dpp_shl1(xh[r], xv[r][0]) : xv[r][j - 1]);
             const float e = d[4] - k2 * d[2];
             const float o = k3 * d[3] - k1 * d[1];
             Ea[j] = za * o + e;
@@ -746,16 +693,8 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
             }
         }
         float Ua[6], Ub[6];
-        if (ABL & 0x80000) {                              // (ablation: no time transform, no halo assembly - what a producer-side
-#pragma unroll                                            //  time transform would leave in this kernel; results are wrong)
-            for (int j = 0; j < 6; ++j) {
-                Ua[j] = Ea[j];
-                Ub[j] = Eb[j];
-            }
-        } else {
-            tt(Ea, Ua);
-            tt(Eb, Ub);
-        }
+        tt(Ea, Ua);
+        tt(Eb, Ub);
         buf[xlds] = f32x4{Ua[0], Ua[1], Ua[2], Ua[3]};
         buf[xlds + 1] = f32x4{Ua[4], Ua[5], Ub[0], Ub[1]};
         buf[xlds + 2] = f32x4{Ub[2], Ub[3], Ub[4], Ub[5]};
@@ -820,41 +759,37 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
         acc[0][4 * (pg) + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][0][i], acc[0][4 * (pg) + i], 0, 0, 0); \
         if (two) acc[1][4 * (pg) + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][1][i], acc[1][4 * (pg) + i], 0, 0, 0); \
     }
-#define X_MFMA1(c, pg, i)                                                                            \
-    acc[0][4 * (pg) + (i)] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][0][i], acc[0][4 * (pg) + (i)], 0, 0, 0); \
-    if (two) acc[1][4 * (pg) + (i)] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[c][i], bv[c][1][i], acc[1][4 * (pg) + (i)], 0, 0, 0);
 #define X_READ(c, Xp, sl, pg)                                       \
     av[c] = Ww[(sl) * WSL + aoff + (pg)];                           \
     bv[c][0] = (Xp)[boff + (sl) * KQ * NU * 3 + (pg)];              \
     if (two) bv[c][1] = (Xp)[boff + (sl) * KQ * NU * 3 + 16 * 3 + (pg)];
 #define X_FENCE __builtin_amdgcn_sched_barrier(0);
     // group g: [weight DMA chunk] [staging loads] [wait for a new slot's weights] [reads of group g + 1 into the other operand
-    // set] [transform] [8 MFMAs of group g].  STAGGER: the two waves of a SIMD (w, w + 4) do their staging work - transform
-    // (~90 vector instructions and two LDS round trips during which the wave issues no MFMA) and row loads - half a super-slab
-    // apart: waves 0-3 in groups 0-2 (EARLY), waves 4-7 in groups 6-8 (LATE), so that one partner multiplies while the other
-    // transforms - OPTIONAL, see below.  Two copies of the loop (generic lambda): every count is a compile-time constant.
-    //   vmcnt, EARLY (see the header): 13, 13, 6, 6 at g2, g5, g8, g11;
-    //   LATE issues  g0-g5: D | g6: D E E R R | g7: D R R | g8: D H | g9-g11: D  ->  6, 6, 13, 13.
+    // set] [transform] [8 MFMAs of group g].  Every wave does its staging work - transform (~90 vector instructions and two LDS
+    // round trips during which the wave issues no MFMA) and row loads - in groups 0-2.
+    //   vmcnt (see the header): 11, 11, 6, 6 at g2, g5, g8, g11.
+    // A STAGGERED form, in which waves 4-7 staged half a super-slab after their SIMD partners (groups 6-8) so that one partner
+    // multiplies while the other transforms, was measured (round 4, same box, six layer shapes): staggered 2.42 ms, not staggered
+    // 2.40 ms - no gain, as round 3 found for the first wide kernel (the vector work costs matrix-pipe time whichever wave does it,
+    // and the LDS round trips it exposes are short).
 #define X_G(g, rp, j, cr, sl, pgr, cm, pgm)                                                                     \
     X_DMA(rp, j)                                                                                                \
     X_FENCE                                                                                                     \
-    if constexpr ((g) == SA + 1) {                                                                              \
+    if constexpr ((g) == 1) {                                                                                   \
         issue_rows(cA, 3, 5);                                                                                   \
         X_FENCE                                                                                                 \
     }                                                                                                           \
-    if constexpr ((g) == SA + 2) {                                                                              \
+    if constexpr ((g) == 2) {                                                                                   \
         issue_halo(cA);                                                                                         \
         X_FENCE                                                                                                 \
     }                                                                                                           \
     if constexpr ((j) == 2) {                                                                                   \
         w_next();                                                                                               \
-        if constexpr (((g) < 6) != LATE) { X_WAITVM13 } else { X_WAITVM(6) }                                    \
+        if constexpr ((g) < 6) { X_WAITVM(11) } else { X_WAITVM(6) }                                            \
     }                                                                                                           \
-    if constexpr (!SPREAD || (g) == SA) {                                                                       \
-        X_READ(cr, Xs, sl, pgr)                                                                                 \
-        X_FENCE                                                                                                 \
-    }                                                                                                           \
-    if constexpr ((g) == SA) {                                                                                  \
+    X_READ(cr, Xs, sl, pgr)                                                                                     \
+    X_FENCE                                                                                                     \
+    if constexpr ((g) == 0) {                                                                                   \
         /* transform of super-slab S + 1 (rows loaded one super-slab ago), then the loads of super-slab S + 2 */ \
         store_act(Xw);                                                                                          \
         advance(pA, cA);                                                                                        \
@@ -865,36 +800,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
         issue_rows(cA, 1, 3);                                                                                   \
         X_FENCE                                                                                                 \
     }                                                                                                           \
-    if constexpr (LATE && (g) == 5) {                                                                           \
-        halo_permute();                                                                                         \
-        X_FENCE                                                                                                 \
-    }                                                                                                           \
-    if constexpr (!SPREAD || (g) == SA) {                                                                       \
-        X_MFMA(cm, pgm)                                                                                         \
-    } else {                                                                                                    \
-        /* the three operand reads of group g + 1 one at a time BETWEEN the MFMA pairs of group g (tools/mfma_feed.hip: the */ \
-        /* bare loop runs at 0.991 of the peak this way, 0.969 with the reads clustered in front of the eight MFMAs) */ \
-        X_MFMA1(cm, pgm, 0)                                                                                     \
-        X_FENCE                                                                                                 \
-        av[cr] = Ww[(sl) * WSL + aoff + (pgr)];                                                                 \
-        X_FENCE                                                                                                 \
-        X_MFMA1(cm, pgm, 1)                                                                                     \
-        X_FENCE                                                                                                 \
-        bv[cr][0] = Xs[boff + (sl) * KQ * NU * 3 + (pgr)];                                                      \
-        X_FENCE                                                                                                 \
-        X_MFMA1(cm, pgm, 2)                                                                                     \
-        X_FENCE                                                                                                 \
-        if (two) bv[cr][1] = Xs[boff + (sl) * KQ * NU * 3 + 16 * 3 + (pgr)];                                    \
-        X_FENCE                                                                                                 \
-        X_MFMA1(cm, pgm, 3)                                                                                     \
-    }                                                                                                           \
+    X_MFMA(cm, pgm)                                                                                             \
     X_FENCE
-    auto run = [&](auto late_c) __attribute__((always_inline)) {
-        constexpr bool LATE = decltype(late_c)::value;
-        constexpr int SA = LATE ? 6 : 0;
-        constexpr bool SPREAD = (ABL & 0x40000) != 0;
+    // The loop stays a lambda, called once, and captures cA ahead of pA: both are left from the two-copy (staggered) form, and
+    // hipcc orders instructions of the loop differently without them (checked on the assembly; nothing else depends on either).
+    auto run = [&]() __attribute__((always_inline)) {
+        (void)cA;
         X_READ(0, Xb, 0, 0)
-        if constexpr (!LATE) halo_permute();              // (super-slab 1's halo: waits for its load)
+        halo_permute();                                   // (super-slab 1's halo: waits for its load)
         int cM = 0, pM = 0;
         for (int S = 0; S < NS; ++S) {
             const f32x4* Xs = Xb + (S & 1) * XSZ;
@@ -911,17 +824,17 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
             X_G(9, 2, 0, 0, 3, 1, 1, 0)
             X_G(10, 2, 1, 1, 3, 2, 0, 1)
             // g11: X[(S + 1) & 1] is complete and nobody reads X[S & 1] any more (the operands of this group are in
-            // registers): barrier, then the first operand reads of the next super-slab (+ the EARLY waves' halo permutes of
-            // super-slab S + 2) run behind this group's MFMAs
+            // registers): barrier, then the first operand reads of the next super-slab (+ the halo permutes of super-slab S + 2)
+            // run behind this group's MFMAs
             X_DMA(2, 2)
             w_next();
             X_FENCE
-            if constexpr (LATE) { X_WAITVM13 } else { X_WAITVM(6) }
+            X_WAITVM(6)
             asm volatile("s_waitcnt lgkmcnt(0)");
-            if (!(ABL & 0x10000)) __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_s_barrier();
             X_FENCE
             X_READ(0, Xw, 0, 0)
-            if constexpr (!LATE) halo_permute();
+            halo_permute();
             X_FENCE
             X_MFMA(1, 2)
             X_FENCE
@@ -967,24 +880,14 @@ __global__ __launch_bounds__(512, 1) __attribute__((amdgpu_num_vgpr(BABE_W45X_NU
             }
         }
     };
-    // Measured (round 4, same box, six layer shapes): staggered 2.42 ms, not staggered 2.40 ms - no gain, as round 3 found for
-    // the first wide kernel (the vector work costs matrix-pipe time whichever wave does it, and the LDS round trips it
-    // exposes are short).  Default: every wave EARLY (one copy of the loop); -DABL=1024 builds the staggered form.
-#if (ABL & 1024)
-    if (wave >= 4) run(std::true_type{});
-    else run(std::false_type{});
-#else
-    run(std::false_type{});
-#endif
+    run();
 #undef X_G
 #undef X_MFMA
-#undef X_MFMA1
 #undef X_READ
 #undef X_FENCE
 #undef X_DMA
 #undef X_FENCE0
 #undef X_WAITVM
-#undef X_WAITVM13
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)");          // (the tail's clamped loads / out-of-range DMAs: nothing may land after the exit)
 
     // ---- output

@@ -18,11 +18,11 @@
 // half-slots (4 ci x 16 co x 12 of the pass's 24 phases) = 24 MFMA groups of 4.  The WEIGHT operand never touches LDS: the 96
 // accumulators leave room for a ring of 12 operand registers sets, loaded straight from global memory (L2-resident packed image, one
 // coalesced 1 KB load per wave and group, 12 groups ahead); LDS holds only the transformed activations (2 x 24 KB).  The first build
-// of this kernel staged the weights through a wave-private LDS-DMA ring like conv_wino45x_kernel: its ablations (tools/f45_ablate.py,
-// profiles/r05_f45_ablate.txt) charged 20 % of the time to the DMA and 18 % to the operand reads - LDS bandwidth was the limit.
+// of this kernel staged the weights through a wave-private LDS-DMA ring like conv_wino45x_kernel: its timing ablations
+// (profiles/r05_f45_ablate.txt) charged 20 % of the time to the DMA and 18 % to the operand reads - LDS bandwidth was the limit.
 // Transform (128-channel kernel): thread = (ci, unit) in waves 0-3 (wave w and w + 4 share a SIMD): they load the rows once and compute
-// both phase pairs of the pass, coefficients wave-uniform; waves 4-7 only multiply (W85_HALFLOAD; the first form - every wave one
-// pair from its own copy of the rows - is the 0 setting).
+// both phase pairs of the pass, coefficients wave-uniform; waves 4-7 only multiply (the first form - every wave one pair from its
+// own copy of the rows, twice the row loads - was 0.6 % slower on the whole job).
 // 96- and 64-channel tiles: conv_wino85s_kernel below - waves 0 .. NW-1 only multiply, waves NW .. 7 only load and transform, which
 // balances the four SIMDs where six (four) multiplying waves alone cannot.  All three produce the same sums in the same order for a
 // given (co, output): a conv run as 64-channel tiles equals the same conv run as one 128-channel tile bit for bit.
@@ -39,54 +39,6 @@
 #include <cstdlib>
 
 
-#ifndef W85_HALFLOAD
-#define W85_HALFLOAD 1 // in the 128-channel kernel waves 0-3 load the rows and transform BOTH phase pairs of their (ci, unit), waves 4-7
-#endif                 // only multiply (0: every wave loads and transforms one pair - twice the row loads; -0.6 % on the whole job)
-#ifndef W85_RD
-#define W85_RD 12      // weight register ring: groups in flight (a multiple of 3 that divides 24)
-#endif
-#ifndef W85_TFIRST
-#define W85_TFIRST 1    // specialised-wave kernels: the transform waves are the OLDEST waves of the workgroup (0: the youngest, round 5 - 6a)
-#endif
-// W85_FLAGS (round 6, the default): no barrier inside the main loop of the specialised-wave kernels.  THREE X buffers; every transform
-// wave publishes the number of super-slabs it has finished (prog[t]), every multiplying wave the number it has consumed (cons[w]), in
-// LDS words of their own (no atomics); a consumer polls the words of the other side (one ds_read_b128 per side and super-slab when
-// nothing is late).  A wave then waits only for data it needs, not for the slowest wave of the workgroup: the first multiplying wave
-// of a SIMD, which the oldest-first issue order lets through a super-slab in half its time, goes on into the next one and fills the
-// matrix pipe while its partner waits for weights.  Same arithmetic in the same order: bit-identical to the barrier form
-// (-DW85_FLAGS=0, which the s_memtime probe needs).  +1.0 ... 1.25 % on the job, profiles/r06_f45_flags_ab.txt.
-#ifndef W85_FLAGS
-#define W85_FLAGS 1
-#endif
-#ifndef W85_NXB
-#define W85_NXB 3       // X buffers of the flag-synchronised form (3 or 4)
-#endif
-#ifndef W85_SLEEP
-#define W85_SLEEP 1     // s_sleep argument inside its polling loops (0: none)
-#endif
-#ifndef W85_TPRIO
-#define W85_TPRIO 0
-#endif
-// timing probe (ablation bit 16384, tools/f45_barrier_probe.py): cycles a wave spends at the per-super-slab barrier and in total,
-// written by lane 0 of the first multiplying and the first transform wave to stat_part[tile * 4 ..] (stat_mode 99)
-#define W85_PROBE (W85_ABL & 16384)
-#if W85_PROBE && W85_FLAGS
-#error "the barrier probe instruments the barrier form: build with -DW85_FLAGS=0"
-#endif
-#if W85_PROBE
-#define W85_BARRIER(acc_)                                              \
-    {                                                                  \
-        const unsigned long long tb_ = __builtin_amdgcn_s_memtime();   \
-        __builtin_amdgcn_s_barrier();                                  \
-        acc_ += __builtin_amdgcn_s_memtime() - tb_;                    \
-    }
-#else
-#define W85_BARRIER(acc_) __builtin_amdgcn_s_barrier();
-#endif
-#ifndef W85_ABL
-#define W85_ABL 0      // timing ablations only (tools/f45_ablate.py): 1 no transform arithmetic, 2 no row loads, 4 no weight loads,
-#endif                 // 8 no X reads, 16 no MFMA, 32 rows loaded by waves 0-3 only, 64 / 128 row loads that always hit L2 / L1, 512 no epilogue, 1024 no pass carry - results are wrong
-
 namespace {
 
 struct Wino85Geom {
@@ -96,6 +48,15 @@ struct Wino85Geom {
 
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 constexpr unsigned OOBH = 0xC0000000u;
+// Synchronisation of the specialised-wave kernels (round 6): no barrier inside the main loop.  THREE X buffers; every transform
+// wave publishes the number of super-slabs it has finished (prog[t]), every multiplying wave the number it has consumed (cons[w]), in
+// LDS words of their own (no atomics); a consumer polls the words of the other side (one ds_read_b128 per side and super-slab when
+// nothing is late).  A wave then waits only for data it needs, not for the slowest wave of the workgroup: the first multiplying wave
+// of a SIMD, which the oldest-first issue order lets through a super-slab in half its time, goes on into the next one and fills the
+// matrix pipe while its partner waits for weights.  Same arithmetic in the same order as the form it replaced (two X buffers, one
+// barrier per super-slab): bit-identical, +1.0 ... 1.25 % on the job, profiles/r06_f45_flags_ab.txt.
+constexpr int NXB = 3;                 // X buffers of the specialised-wave kernels
+constexpr int POLL_SLEEP = 1;          // s_sleep argument inside their polling loops
 
 // ---- arithmetic shared by the two kernels, written with explicit fused multiply-adds and contraction off, so that the 128-channel
 // kernel and the specialised-wave kernel round identically (tests/test_gpu_ops.py::test_f45_tile_widths_are_bit_identical)
@@ -244,11 +205,6 @@ __device__ __forceinline__ void w85_epilogue(const babe_conv_args& a, const f32x
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
             float m[6];
-            if (W85_ABL & 4096) {                       // (no output transform: raw accumulators stored)
-                const f32x4 y = {acc[0][row][kk], acc[0][6 + row][kk], acc[1][row][kk], acc[1][6 + row][kk]};
-                if (pv) *reinterpret_cast<f32x4*>(outb + ((co0 + kk) * ocs + sp)) = y;
-                continue;
-            }
 #pragma unroll
             for (int tp = 0; tp < 6; ++tp) {
                 const float M5 = acc[0][tp][kk], M6 = acc[0][6 + tp][kk], M0 = acc[1][tp][kk], M7 = acc[1][6 + tp][kk];
@@ -264,9 +220,7 @@ __device__ __forceinline__ void w85_epilogue(const babe_conv_args& a, const f32x
             y[1] = __builtin_fmaf(y1, sc, a.rbeta * r4[1]);
             y[2] = __builtin_fmaf(y2, sc, a.rbeta * r4[2]);
             y[3] = __builtin_fmaf(y3, sc, a.rbeta * r4[3]);
-            if (W85_ABL & 2048) {                       // (no stores: the arithmetic stays)
-                if (y[0] == 12345.f && y[1] == 5.f) *reinterpret_cast<f32x4*>(a.out) = y;
-            } else if (pv) *reinterpret_cast<f32x4*>(outb + ((co0 + kk) * ocs + sp)) = y;
+            if (pv) *reinterpret_cast<f32x4*>(outb + ((co0 + kk) * ocs + sp)) = y;
             if (smode == 1 && pv) {
                 // babe_gn_partial's sums of the output this conv writes (csrc/norm.hip: sum and sum of squares in double)
 #pragma unroll
@@ -327,7 +281,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
 #if __HIP_DEVICE_COMPILE__
     constexpr int KS = 16, KQ = 4, NU = 16, BN = 128;
     constexpr int XSZ = KS * NU * 6;                    // float4 per activation super-slab (16 ci x 16 units x 24 floats)
-    constexpr int RD = W85_RD;                          // weight register ring: groups in flight (a multiple of 3 that divides 24)
+    constexpr int RD = 12;                              // weight register ring: groups in flight (a multiple of 3 that divides 24)
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
     f32x4* smem = reinterpret_cast<f32x4*>(smem_f);
     f32x4* const Xb = smem;                             // X[2]
@@ -372,7 +326,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
         const int fr = fa + (r - 2) * a.dil;
         const bool ok = fr >= 0 && fr < a.F && s_t < a.T;
         er[r] = ok ? (unsigned)((fr * a.T + s_t) * 4) + chb : OOBH;
-        if (W85_ABL & 128) er[r] = (unsigned)((r * 64 + 4 * s_tu) * 4) + chb;       // (always the same 8 KB: L1 hits)
     }
     unsigned ehalo = OOBH;
     {
@@ -391,7 +344,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
     int sW = ((co0 >> 4) + wave) * 3072;
     const unsigned wvo = (unsigned)(lane * 16);
     auto w_next = [&]() __attribute__((always_inline)) {
-        if (W85_ABL & 256) return;                      // (always the first half-slot: L1 hits)
         sW += wstep;
         sW = sW < sWend ? sW : sWend;
     };
@@ -404,9 +356,10 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
     int pS = 0;
     // the patch rows of super-slab (ps, ci0): rows 1..6 always, rows 0 and 7 in pass B only (a wave-uniform branch; pass A's phases
     // +-1, +-2 do not touch them).  (hipcc counts the vmcnt of every wait from the loads it sees: nothing here is hand-counted.)
+    // Waves 4-7 (half = 1) neither load nor transform: every staging step below returns at once for them.
     auto issue_rows = [&](int ps, int ci0, int r0, int r1) __attribute__((always_inline)) {
-        const int so = (W85_ABL & (64 | 128)) ? 0 : (ci0 + 4 * wq4) * cs1 * 4;       // (64: always the first 4 channels: L2 hits)
-        if ((W85_ABL & 2) || ((W85_ABL & 32) && half) || (W85_HALFLOAD && half)) return;
+        const int so = (ci0 + 4 * wq4) * cs1 * 4;
+        if (half) return;
 #pragma unroll
         for (int r = 1; r < 7; ++r) {
             if (r < r0 || r >= r1) continue;
@@ -419,45 +372,30 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
     };
     auto issue_halo = [&](int ci0) __attribute__((always_inline)) {
         const int so = (ci0 + 4 * wq4) * cs1 * 4;
-        if ((W85_ABL & 2) || ((W85_ABL & 32) && half) || (W85_HALFLOAD && half)) return;
+        if (half) return;
         xhl = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs1, ehalo, so, 0));
     };
     auto issue_isc = [&](int ci0) __attribute__((always_inline)) {
-        if (W85_HALFLOAD && half) return;
+        if (half) return;
         if (HAS_ISC) xsc = a.in_scale[(long)b * a.Cin + ci0 + 4 * wq4 + s_ch];
     };
     auto halo_permute = [&]() __attribute__((always_inline)) {
-        if (W85_HALFLOAD && half) return;
+        if (half) return;
 #pragma unroll
         for (int r = 0; r < 8; ++r)
             asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "=v"(xh[r]) : "v"(hsrc), "v"(xhl), "n"(32 * r));
     };
-    auto store_act = [&](f32x4* buf) __attribute__((always_inline)) {
-        if (W85_ABL & 1) {
-            buf[xlds] = xv[1] + xv[0];
-            buf[xlds + 1] = xv[2] + xv[7];
-            buf[xlds + 2] = xv[3] + f32x4{xh[1], xh[2], xh[0], xh[7]};
-            return;
-        }
-        if (W85_HALFLOAD) {                                  // waves 0-3: both phase pairs of their (ci, unit) from one set of rows
-            if (half) return;
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xh[4]), "+v"(xh[5]), "+v"(xh[6]), "+v"(xh[7]));
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                f32x4 o0, o1, o2;
-                w85_transform<HAS_ISC>(xv, xh, pS * 2 + hf, xsc, o0, o1, o2);
-                buf[xlds + 3 * hf] = o0;
-                buf[xlds + 3 * hf + 1] = o1;
-                buf[xlds + 3 * hf + 2] = o2;
-            }
-            return;
-        }
+    auto store_act = [&](f32x4* buf) __attribute__((always_inline)) {    // waves 0-3: both phase pairs of their (ci, unit) from one set of rows
+        if (half) return;
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xh[4]), "+v"(xh[5]), "+v"(xh[6]), "+v"(xh[7]));
-        f32x4 o0, o1, o2;
-        w85_transform<HAS_ISC>(xv, xh, pS * 2 + half, xsc, o0, o1, o2);      // (the selector is wave-uniform)
-        buf[xlds] = o0;
-        buf[xlds + 1] = o1;
-        buf[xlds + 2] = o2;
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf) {
+            f32x4 o0, o1, o2;
+            w85_transform<HAS_ISC>(xv, xh, pS * 2 + hf, xsc, o0, o1, o2);
+            buf[xlds + 3 * hf] = o0;
+            buf[xlds + 3 * hf + 1] = o1;
+            buf[xlds + 3 * hf + 2] = o2;
+        }
     };
     auto advance = [&](int& ps, int& ci0) __attribute__((always_inline)) {    // next super-slab, clamped at the last one
         int nc = ci0 + KS, np = ps;
@@ -483,7 +421,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
     f32x4 aw[RD];
 #pragma unroll
     for (int i = 0; i < RD; ++i) {
-        aw[i] = (W85_ABL & 4) ? f32x4{1.f, 2.f, 3.f, 4.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + (i % 3) * 1024, 0));
+        aw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + (i % 3) * 1024, 0));
         if (i % 3 == 2) w_next();
     }
     Y_FENCE
@@ -510,23 +448,13 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
     // group G = 3 hs + pg of a super-slab (hs = half-slot 0..7 = (ci quad hs >> 1, phase half hs & 1), pg = 4 of its 12 phases):
     //   [row / halo loads] [X read of group G + 1 into the other operand set] [transform at G = 0] [4 MFMAs of group G]
     //   [weight load of group G + RD into the ring entry the MFMAs just read]
-#if W85_ABL & 8
-#define Y_READ(c, Xp, hs, pg) asm volatile("" : "+v"(bv[c]));
-#else
 #define Y_READ(c, Xp, hs, pg) bv[c] = (Xp)[boff + ((hs) >> 1) * KQ * NU * 6 + ((hs) & 1) * 3 + (pg)];
-#endif
-#ifdef W85_PRIO
-#define Y_PRIO(n) __builtin_amdgcn_s_setprio(n);
-#else
-#define Y_PRIO(n)
-#endif
 #define Y_MFMA(c, GN)                                                  \
-    if (!(W85_ABL & 16))                                               \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                      \
         acc[((GN) / 3) & 1][4 * ((GN) % 3) + i] =                      \
             __builtin_amdgcn_mfma_f32_16x16x4f32(aw[(GN) % RD][i], bv[c][i], acc[((GN) / 3) & 1][4 * ((GN) % 3) + i], 0, 0, 0);
 #define Y_WLOAD(GN)                                                                                                          \
-    if (!(W85_ABL & 4)) aw[(GN) % RD] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + ((GN) % 3) * 1024, 0)); \
+    aw[(GN) % RD] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + ((GN) % 3) * 1024, 0));   \
     if constexpr ((GN) % 3 == 2) w_next();
 #define Y_G(GN)                                                                                                 \
     if constexpr ((GN) == 1) {                                                                                  \
@@ -551,10 +479,8 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
         Y_FENCE                                                                                                 \
     }                                                                                                           \
     if constexpr ((GN) < 23) {                                                                                  \
-        Y_PRIO(1)                                                                                               \
         Y_MFMA((GN) & 1, GN)                                                                                    \
-        Y_PRIO(0)                                                                                               \
-        Y_FENCE                                                                                                 \
+        Y_FENCE                                                                                                \
         Y_WLOAD(GN)                                                                                             \
         Y_FENCE                                                                                                 \
     }
@@ -583,9 +509,7 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
         cM += KS;
         if (cM >= g.CinP) {
             cM = 0;
-            if (pM == 0 && !(W85_ABL & 1024)) {
-                w85_carry(acc);
-            }
+            if (pM == 0) w85_carry(acc);
             ++pM;
         }
     }
@@ -595,15 +519,6 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
 #undef Y_WLOAD
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)");
 
-    if (W85_ABL & 512) {                                 // (no output transform: one store keeps the accumulators alive)
-        f32x4 sacc = acc[0][0];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 12; ++p) sacc += acc[i][p];
-        if (sacc[0] == 12345.f) *reinterpret_cast<f32x4*>(a.out) = sacc;
-        return;
-    }
     w85_epilogue(a, acc, b, co0 + wave * 16, fa, t0, lk, l15, g.xcd ? bx : Q * g.tiles_t + tile_t, g.tiles_t * nQ);
 #endif
 }
@@ -614,31 +529,29 @@ __global__ __launch_bounds__(512, 1) void conv_wino85_kernel(babe_conv_args a, W
 // quads per wave, both phase pairs per thread from ONE set of row loads.  NW = 6: SIMDs 0 and 1 host two multiplying waves, SIMDs 2
 // and 3 one multiplying wave plus a transform wave carrying four wave-shares of transform: about the same time.  NW = 4: every SIMD
 // hosts one of each.  The multiplying waves' memory queue holds weights only, the transform waves' rows only (two register sets: the
-// rows of super-slab S + 2 are in flight while S + 1 is transformed).  One barrier per super-slab, as in the 128-channel kernel.
+// rows of super-slab S + 2 are in flight while S + 1 is transformed).  No barrier in the main loop: the two kinds of wave meet
+// through the progress words in LDS (NXB above).
 // NWV = 12 (round 6, BABE_W85_12W=1): the 128-channel tile as 8 multiplying + 4 transform waves, three waves per SIMD at <= 168
 // registers - the multiplying waves never carry the transform in their own instruction stream.
 template <bool HAS_ISC, int NW, int NWV = 8>
 __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_args a, Wino85Geom g, const float* __restrict__ wq) {
 #if __HIP_DEVICE_COMPILE__
-    constexpr int KS = 16, KQ = 4, NU = 16, BN = 16 * NW, RD = W85_RD;
+    constexpr int KS = 16, KQ = 4, NU = 16, BN = 16 * NW, RD = 12;
     constexpr int TW = NWV - NW, PPL = 4 / TW;          // transform waves; channel quads per transform wave
     static_assert((NWV == 8 && (NW == 6 || NW == 4)) || (NWV == 12 && NW == 8), "tile width");
     constexpr int XSZ = KS * NU * 6;
     extern __shared__ __attribute__((aligned(16))) float smem_f[];
-    f32x4* const Xb = reinterpret_cast<f32x4*>(smem_f);  // X[2]
+    f32x4* const Xb = reinterpret_cast<f32x4*>(smem_f);  // X[NXB]
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     // The hardware issues oldest wave first: with the transform waves as the workgroup's LAST waves their instructions got what the
     // two multiplying waves of their SIMD left over, most of a super-slab's transform ran alone after the MFMAs, and the multiplying
-    // waves stood at the barrier for 53 % (first wave of a SIMD) / 20 % (second) of the main loop (s_memtime probe, ablation bit 16384,
-    // profiles/r06_f45_barrier_probe.txt).  The FIRST TW hardware waves transform; `wave` stays the logical index the rest of the
-    // kernel uses: 0 .. NW-1 multiply, NW .. NWV-1 transform.
+    // waves stood at the barrier for 53 % (first wave of a SIMD) / 20 % (second) of the main loop (s_memtime probe of the barrier
+    // form, profiles/r06_f45_barrier_probe.txt).  The FIRST TW hardware waves transform; `wave` stays the logical index the rest of
+    // the kernel uses: 0 .. NW-1 multiply, NW .. NWV-1 transform.
     const int wave_hw = __builtin_amdgcn_readfirstlane(tid >> 6);
-    // (W85_TFIRST == 2, experiment, 12-wave form only: the transform wave between the two multiplying waves of its SIMD in age)
-    const int wave = (W85_TFIRST == 2 && NWV == 12) ? (wave_hw < 4 ? wave_hw : (wave_hw < 8 ? NW + wave_hw - 4 : wave_hw - 4))
-                     : W85_TFIRST                   ? (wave_hw < NWV - NW ? NW + wave_hw : wave_hw - (NWV - NW))
-                                                    : wave_hw;
+    const int wave = wave_hw < NWV - NW ? NW + wave_hw : wave_hw - (NWV - NW);
     const int l15 = lane & 15, lk = lane >> 4;
     const int b = blockIdx.z;
     int bx = blockIdx.x, by = blockIdx.y;
@@ -656,9 +569,8 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
     const int cls = Q / g.nquads;
     const int fa = Q < a.dil * g.nquads ? cls + 4 * (Q - cls * g.nquads) * a.dil : a.F + 8 * a.dil;
     const int NS = 2 * (g.CinP / KS);                   // super-slabs (even)
-#if W85_FLAGS
-    // flags behind X[W85_NXB]: prog[0..3] (transform waves; unused words stay at "infinity"), cons[0..7] (multiplying waves)
-    unsigned* const flg = reinterpret_cast<unsigned*>(Xb + W85_NXB * XSZ);
+    // flags behind X[NXB]: prog[0..3] (transform waves; unused words stay at "infinity"), cons[0..7] (multiplying waves)
+    unsigned* const flg = reinterpret_cast<unsigned*>(Xb + NXB * XSZ);
     const unsigned flg_a = (unsigned)(unsigned long long)flg;     // LDS byte address of the flags (low word of the flat address)
     if (tid < 12) flg[tid] = (tid < 4 ? tid < TW : tid - 4 < NW) ? 0u : 0x7fffffffu;
     __syncthreads();
@@ -673,15 +585,9 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
     auto flag_set = [&](unsigned ad, unsigned val) __attribute__((always_inline)) {
         asm volatile("s_waitcnt lgkmcnt(0)\n\tds_write_b32 %0, %1" ::"v"(ad), "v"(val) : "memory");
     };
-#endif
 
     if (wave >= NW) {
         // ================= transform waves =================
-#if W85_TPRIO            // (experiment: the transform waves above the multiplying waves of their SIMD)
-        __builtin_amdgcn_s_setprio(W85_TPRIO);
-#endif
-        unsigned long long pb_wait = 0;
-        const unsigned long long pb_t0 = W85_PROBE ? __builtin_amdgcn_s_memtime() : 0ull;
         const float* p1 = a.in + (long)b * a.in_bs;
         const int cs1 = (int)a.in_cs;
         const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc((void*)p1, 0, a.Cin * cs1 * 4, 0x00020000);
@@ -715,7 +621,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
             }
         // the rows of super-slab (ps, ci0) into register set `st` (rows 0 and 7 in pass B only), its halo and input scale
         auto issue = [&](int st, int ps, int ci0) __attribute__((always_inline)) {
-            if (W85_ABL & 2) return;
 #pragma unroll
             for (int p = 0; p < PPL; ++p) {
                 const int so = (ci0 + 4 * (vw0 + p)) * cs1 * 4;
@@ -731,15 +636,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
         };
         // register set `st` (rows of a pass-`ps` super-slab) -> X buffer `buf`: both phase pairs of the pass for this thread's
         // (ci, unit) pairs; the arithmetic of conv_wino85_kernel's store_act, term for term
-        unsigned long long pb_vm = 0;                      // (probe: time waiting for the rows of the set about to be transformed)
         auto transform = [&](int st, int ps, f32x4* buf) __attribute__((always_inline)) {
-#if W85_PROBE
-            {
-                const unsigned long long tv_ = __builtin_amdgcn_s_memtime();
-                asm volatile("s_waitcnt vmcnt(9)" ::: "memory");     // (at most 9 loads per channel quad are younger than this set's)
-                pb_vm += __builtin_amdgcn_s_memtime() - tv_;
-            }
-#endif
 #pragma unroll
             for (int p = 0; p < PPL; ++p) {
                 float xh[8];
@@ -748,11 +645,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
                     asm volatile("ds_bpermute_b32 %0, %1, %2 offset:%3" : "=v"(xh[r]) : "v"(hsrc), "v"(xhl[st][p]), "n"(32 * r));
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xh[0]), "+v"(xh[1]), "+v"(xh[2]), "+v"(xh[3]), "+v"(xh[4]), "+v"(xh[5]), "+v"(xh[6]), "+v"(xh[7]));
                 const int xl = (((vw0 + p) * 4 + s_ch) * NU + s_tu) * 6;
-                if (W85_ABL & 1) {
-                    buf[xl] = xv[st][p][1] + xv[st][p][0];
-                    buf[xl + 3] = xv[st][p][2] + xv[st][p][7] + f32x4{xh[1], xh[2], xh[0], xh[7]};
-                    continue;
-                }
 #pragma unroll
                 for (int hf = 0; hf < 2; ++hf) {
                     f32x4 o0, o1, o2;
@@ -776,7 +668,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
         };
         // super-slab s lives in register set s & 1; (pT, cT) = the slab transformed next, (pL, cL) = the slab loaded next
         int pT = 0, cT = 0, pL = 0, cL = 0;
-#if W85_FLAGS
         issue(0, pL, cL);
         advance(pL, cL);
         issue(1, pL, cL);
@@ -785,11 +676,11 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
         const unsigned my_prog = flg_a + (unsigned)(wave - NW) * 4;
         auto slab = [&](int st, int k) __attribute__((always_inline)) {
             // buffer k mod NXB last held slab k - NXB: every multiplying wave must have consumed it (cons >= k - NXB + 1)
-            if (k >= W85_NXB) {
+            if (k >= NXB) {
                 while (true) {
                     const unsigned c0 = flag_min4(flg_a + 16), c1 = flag_min4(flg_a + 32);
-                    if ((int)(c0 < c1 ? c0 : c1) >= k - W85_NXB + 1) break;
-                    if (W85_SLEEP) __builtin_amdgcn_s_sleep(W85_SLEEP);
+                    if ((int)(c0 < c1 ? c0 : c1) >= k - NXB + 1) break;
+                    __builtin_amdgcn_s_sleep(POLL_SLEEP);
                 }
             }
             transform(st, pT, Xb + kb * XSZ);
@@ -797,50 +688,17 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
             flag_set(my_prog, (unsigned)(k + 1));          // (behind this wave's LDS writes: s_waitcnt lgkmcnt(0) first)
             issue(st, pL, cL);                             // the set just transformed is free: rows of slab k + 2 (clamped at the end)
             advance(pL, cL);
-            kb = kb == W85_NXB - 1 ? 0 : kb + 1;
+            kb = kb == NXB - 1 ? 0 : kb + 1;
         };
         for (int S = 0; S < NS; S += 2) {
             slab(0, S);
             slab(1, S + 1);
         }
         return;
-#endif
-        issue(0, pL, cL);
-        advance(pL, cL);
-        issue(1, pL, cL);
-        advance(pL, cL);
-        transform(0, pT, Xb);                              // super-slab 0 -> X[0]
-        advance(pT, cT);
-        asm volatile("s_waitcnt lgkmcnt(0)");
-        W85_BARRIER(pb_wait)
-        for (int S = 0; S < NS; S += 2) {
-            // iteration S (even): set 0 is free (slab S was transformed last time): rows of slab S + 2; transform slab S + 1 (set 1)
-            issue(0, pL, cL);
-            advance(pL, cL);
-            transform(1, pT, Xb + XSZ);
-            advance(pT, cT);
-            asm volatile("s_waitcnt lgkmcnt(0)");
-            W85_BARRIER(pb_wait)
-            // iteration S + 1: rows of slab S + 3 into set 1; transform slab S + 2 (set 0) -> X[0]
-            issue(1, pL, cL);
-            advance(pL, cL);
-            transform(0, pT, Xb);
-            advance(pT, cT);
-            asm volatile("s_waitcnt lgkmcnt(0)");
-            W85_BARRIER(pb_wait)
-        }
-        if (W85_PROBE && a.stat_mode == 99 && wave == NW && lane == 0) {
-            double* dbg = a.stat_part + 4 * ((long)b * g.total + (g.xcd ? blockIdx.x : blockIdx.x + gridDim.x * blockIdx.y));
-            dbg[2] = (double)pb_wait + 1e-9 * (double)pb_vm;     // (the row wait rides in the fraction: 1e-9 x ticks)
-            dbg[3] = (double)(__builtin_amdgcn_s_memtime() - pb_t0);
-        }
-        return;
     }
 
     // ================= multiplying waves =================
     // (a static s_setprio 1 / 3 for these waves over the transform wave of their SIMD: no effect, profiles/r06_12wave_ab.txt)
-    unsigned long long pb_wait = 0;
-    const unsigned long long pb_t0 = W85_PROBE ? __builtin_amdgcn_s_memtime() : 0ull;
     const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc((void*)wq, 0, 4 * g.CinP * g.CoutP * 48, 0x00020000);
     const int NT = g.CoutP >> 4;
     const int wstep = NT * 3072;
@@ -848,7 +706,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
     int sW = ((co0 >> 4) + wave) * 3072;
     const unsigned wvo = (unsigned)(lane * 16);
     auto w_next = [&]() __attribute__((always_inline)) {
-        if (W85_ABL & 256) return;                      // (timing ablation: always the first half-slot - L1 hits)
         sW += wstep;
         sW = sW < sWend ? sW : sWend;
     };
@@ -856,7 +713,7 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
     f32x4 aw[RD];
 #pragma unroll
     for (int i = 0; i < RD; ++i) {
-        aw[i] = (W85_ABL & 4) ? f32x4{1.f, 2.f, 3.f, 4.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + (i % 3) * 1024, 0));
+        aw[i] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + (i % 3) * 1024, 0));
         if (i % 3 == 2) w_next();
     }
     f32x4 acc[2][12];
@@ -866,65 +723,40 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
         for (int p = 0; p < 12; ++p) acc[i][p] = f32x4{0.f, 0.f, 0.f, 0.f};
     f32x4 bv[2];
     bv[0] = bv[1] = f32x4{1.f, 2.f, 3.f, 4.f};
-#if W85_FLAGS
     const unsigned my_cons = flg_a + 16 + (unsigned)wave * 4;
     auto wait_prog = [&](int need) __attribute__((always_inline)) {
-        while ((int)flag_min4(flg_a) < need)
-            if (W85_SLEEP) __builtin_amdgcn_s_sleep(W85_SLEEP);
+        while ((int)flag_min4(flg_a) < need) __builtin_amdgcn_s_sleep(POLL_SLEEP);
     };
     wait_prog(1);                                          // X[0] is complete
     int kb = 0;
-#else
-    W85_BARRIER(pb_wait)                          // X[0] is complete
-#endif
     Y_FENCE
-#if W85_ABL & 8
-#define Z_READ(c, Xp, hs, pg) asm volatile("" : "+v"(bv[c]));
-#else
 #define Z_READ(c, Xp, hs, pg) bv[c] = (Xp)[boff + ((hs) >> 1) * KQ * NU * 6 + ((hs) & 1) * 3 + (pg)];
-#endif
 #define Z_MFMA(c, GN)                                                  \
-    if (!(W85_ABL & 16))                                               \
     _Pragma("unroll") for (int i = 0; i < 4; ++i)                      \
         acc[((GN) / 3) & 1][4 * ((GN) % 3) + i] =                      \
             __builtin_amdgcn_mfma_f32_16x16x4f32(aw[(GN) % RD][i], bv[c][i], acc[((GN) / 3) & 1][4 * ((GN) % 3) + i], 0, 0, 0);
 #define Z_WLOAD(GN)                                                                                                          \
-    if (!(W85_ABL & 4)) aw[(GN) % RD] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + ((GN) % 3) * 1024, 0)); \
+    aw[(GN) % RD] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsw, wvo, sW + ((GN) % 3) * 1024, 0));   \
     if constexpr ((GN) % 3 == 2) w_next();
-#if W85_ABL & 8192        // (timing probe: waves 4, 5 of the 96-channel tile do half their MFMAs - the balance a K-split would give)
-#define Z_SKIP(GN) (NW == 6 && wave >= 4 && (GN) >= 12)
-#else
-#define Z_SKIP(GN) false
-#endif
 #define Z_G(GN)                                                        \
     Z_READ(((GN) + 1) & 1, Xs, ((GN) + 1) / 3, ((GN) + 1) % 3)         \
     Y_FENCE                                                            \
-    if (!Z_SKIP(GN)) Z_MFMA((GN) & 1, GN)                              \
+    Z_MFMA((GN) & 1, GN)                                               \
     Y_FENCE                                                            \
     Z_WLOAD(GN)                                                        \
     Y_FENCE
     Z_READ(0, Xb, 0, 0)
     int cM = 0, pM = 0;
     for (int S = 0; S < NS; ++S) {
-#if W85_FLAGS
-        const int kbn = kb == W85_NXB - 1 ? 0 : kb + 1;
+        const int kbn = kb == NXB - 1 ? 0 : kb + 1;
         const f32x4* Xs = Xb + kb * XSZ;
         const f32x4* Xw = Xb + kbn * XSZ;
         kb = kbn;
-#else
-        const f32x4* Xs = Xb + (S & 1) * XSZ;
-        const f32x4* Xw = Xb + ((S + 1) & 1) * XSZ;
-#endif
         Z_G(0) Z_G(1) Z_G(2) Z_G(3) Z_G(4) Z_G(5) Z_G(6) Z_G(7) Z_G(8) Z_G(9) Z_G(10) Z_G(11)
         Z_G(12) Z_G(13) Z_G(14) Z_G(15) Z_G(16) Z_G(17) Z_G(18) Z_G(19) Z_G(20) Z_G(21) Z_G(22)
-        // G23: its operands are in registers; barrier (X[(S + 1) & 1] complete, nobody reads X[S & 1] any more)
-#if W85_FLAGS
+        // G23: its operands are in registers; this wave is done with slab S, and slab S + 1 must be complete before its first read
         flag_set(my_cons, (unsigned)(S + 1));              // (behind this wave's reads of slab S: s_waitcnt lgkmcnt(0) first)
         if (S + 1 < NS) wait_prog(S + 2);                  // slab S + 1 is complete
-#else
-        asm volatile("s_waitcnt lgkmcnt(0)");
-        W85_BARRIER(pb_wait)
-#endif
         Y_FENCE
         Z_READ(0, Xw, 0, 0)
         Y_FENCE
@@ -944,16 +776,6 @@ __global__ __launch_bounds__(64 * NWV, 1) void conv_wino85s_kernel(babe_conv_arg
 #undef Z_READ
 #undef Z_WLOAD
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)");
-    if (W85_PROBE && a.stat_mode == 99 && lane == 0) {
-        double* dbg = a.stat_part + 4 * ((long)b * g.total + (g.xcd ? blockIdx.x : blockIdx.x + gridDim.x * blockIdx.y));
-        if (wave == 0) {
-            dbg[0] = (double)pb_wait;
-            dbg[1] = (double)(__builtin_amdgcn_s_memtime() - pb_t0);
-        }
-        // every multiplying wave's barrier share, behind the per-tile records (tools/f45_barrier_probe.py: offset 4 * (tiles + 64))
-        a.stat_part[4 * ((long)g.total + 64) + 8 * (g.xcd ? blockIdx.x : blockIdx.x + gridDim.x * blockIdx.y) + wave] =
-            (double)pb_wait / (double)(__builtin_amdgcn_s_memtime() - pb_t0);
-    }
 
     w85_epilogue(a, acc, b, co0 + wave * 16, fa, t0, lk, l15, g.xcd ? bx : Q * g.tiles_t + tile_t, g.tiles_t * nQ);
 #endif
@@ -1082,7 +904,7 @@ extern "C" int babe_conv2d_wino85(const babe_conv_args* ap, const float* w_wino8
     BABE_CHECK_ARG(babe_conv2d_wino85_supported(ap), "conv2d_wino85: unsupported problem");
     const babe_conv_args& a = *ap;
     if (a.stat_mode) {
-        BABE_CHECK_ARG((a.stat_mode == 1 || a.stat_mode == 2 || (W85_PROBE && a.stat_mode == 99)) && a.stat_part && a.stat_cg >= 4 && a.stat_cg % 4 == 0 && a.Cout % a.stat_cg == 0,
+        BABE_CHECK_ARG((a.stat_mode == 1 || a.stat_mode == 2) && a.stat_part && a.stat_cg >= 4 && a.stat_cg % 4 == 0 && a.Cout % a.stat_cg == 0,
                        "conv2d_wino85: fused reduction: mode %d, group size %d (Cout %d)", a.stat_mode, a.stat_cg, a.Cout);
         BABE_CHECK_ARG(a.stat_mode != 2 || (a.stat_x && a.stat_scale && ((uintptr_t)a.stat_x & 15) == 0 && a.res == nullptr),
                        "conv2d_wino85: fused reduction, mode 2: stat_x (16-byte aligned) and stat_scale are needed, res is not taken");
@@ -1094,8 +916,7 @@ extern "C" int babe_conv2d_wino85(const babe_conv_args* ap, const float* w_wino8
     g.nquads = cdiv(cdiv(a.F, a.dil), 4);
     const double flops = babe_conv_flops(a);         // 48 multiplies per 16 outputs instead of 240: 0.2 of the direct count
     BabeProfScope prof(BABE_SLOT_CONV53_WINO85, babe_conv_bytes(a), flops, flops * 0.2, stream);
-#if W85_FLAGS
-    const size_t lds = (size_t)(W85_NXB * 16 * 16 * 6) * 16 + 64;             // X[NXB] + the progress words: 72 KB at 3
+    const size_t lds = (size_t)(NXB * 16 * 16 * 6) * 16 + 64;                 // X[NXB] + the progress words: 72 KB
     {
         static std::atomic<unsigned long long> attr_done{0};
         if (babe_lds_optin(attr_done, {reinterpret_cast<const void*>(&conv_wino85s_kernel<true, 8, 12>), reinterpret_cast<const void*>(&conv_wino85s_kernel<false, 8, 12>),
@@ -1106,9 +927,6 @@ extern "C" int babe_conv2d_wino85(const babe_conv_args* ap, const float* w_wino8
             return BABE_ERR_HIP;
         }
     }
-#else
-    const size_t lds = (size_t)(2 * 16 * 16 * 6) * 16;                        // X[2]: 48 KB
-#endif
     static const int xcd_order = [] { const char* e = getenv("BABE_W85_XCD"); return e ? atoi(e) : 1; }();
     const int bn = a.Cout % 128 == 0 ? 128 : (a.Cout % 96 == 0 ? 96 : 64);
     g.xcd = xcd_order;

@@ -19,18 +19,10 @@ namespace {
 // is bit-reversed.  One LDS buffer between passes: write - barrier - read - barrier.
 // Element i of the workgroup's image lives at i + (i >> 4) (the first pass writes with stride 16: without the pad all lanes
 // of a wave hit two banks).
-#ifndef ABL
-#define ABL 0     // timing ablations of band_fft_kernel<0> (tools/ab/abl_build.sh cqt <bits>; results are WRONG with any bit set):
-#endif            // 1 wide (16-byte) loads of the same bytes, 2 wide stores, 4 no window loads, 8 no FFT (copy only),
-                  // 16 half the LDS image (indices wrap: more workgroups per CU), 32 register cap for 6 waves per SIMD,
-                  // 128 non-temporal spectrum loads (slower: 41 -> 50 us)
-#if ABL & 16
-#define CQ_AT(i) (((i) + ((i) >> 4)) & 2047)
-#else
+// (Timing ablations of band_fft_kernel<0>: profiles/r06_cqt_ablations.txt.  Non-temporal spectrum loads were slower, 41 -> 50 us.)
 #define CQ_AT(i) ((i) + ((i) >> 4))
-#endif
 constexpr int CQ_PTS = 4096;                           // points per workgroup
-constexpr int CQ_LDS = (ABL & 16) ? 2048 : CQ_PTS + (CQ_PTS >> 4);         // float2 elements
+constexpr int CQ_LDS = CQ_PTS + (CQ_PTS >> 4);         // float2 elements
 
 // Complex values are 2-vectors (register pairs): hipcc turns the arithmetic below into packed fp32 instructions
 // (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32) plus some moves of the halves.  (Round 3 tried the same operations as inline
@@ -293,23 +285,7 @@ __device__ __forceinline__ void cq_run(const babe_cqt_bands& bd, f2* a, int k0, 
         const unsigned im = (unsigned)bd.KX * 4;
         float vr[R0], vi[R0], vw[R0];
         // the band's window covers spectrum bins c - half .. c + M - half - 1; almost every band lies inside 0 .. L/2
-        if ((ABL & 1) && R0 == 16) {
-            typedef float f32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-            for (int t4 = 0; t4 < 4; ++t4) {
-                const unsigned so = active ? (unsigned)(c + 4 * u + t4 * 4 * TB) * 4 : OOB;
-                const unsigned wv = active ? (unsigned)(wo + 4 * u + t4 * 4 * TB) * 4 : OOB;
-                const f32x4 a0 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, so, 0, 0));
-                const f32x4 a1 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, so, im, 0));
-                const f32x4 a2 = (ABL & 4) ? f32x4{1.f, 1.f, 1.f, 1.f} : __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, wv, 0, 0));
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    vr[4 * t4 + i] = a0[i];
-                    vi[4 * t4 + i] = a1[i];
-                    vw[4 * t4 + i] = a2[i];
-                }
-            }
-        } else if (c - half >= 0 && c + M - half - 1 <= bd.L / 2) {
+        if (c - half >= 0 && c + M - half - 1 <= bd.L / 2) {
 #pragma unroll
             for (int t = 0; t < R0; ++t) {
                 const int pos = u + t * TB;
@@ -318,10 +294,10 @@ __device__ __forceinline__ void cq_run(const babe_cqt_bands& bd, f2* a, int k0, 
                 const int m = hi ? pos - T : pos;
                 const unsigned so = in ? (unsigned)(c + m) * 4 : OOB;
                 const unsigned wv = in ? (unsigned)(wo + half + m) * 4 : OOB;
-                vr[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, so, 0, (ABL & 128) ? 2 : 0));
-                vi[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, so, im, (ABL & 128) ? 2 : 0));
+                vr[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, so, 0, 0));
+                vi[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, so, im, 0));
                 if (analytic) vw[t] = cq_kaiser<LT>(kz, m);       // (outside the window the spectrum loads return 0)
-                else vw[t] = (ABL & 4) ? 1.f : __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, wv, 0, 0));
+                else vw[t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, wv, 0, 0));
             }
         } else {                                          // bands that wrap around bin 0 or reach past L/2 (mirror: conjugate)
 #pragma unroll
@@ -355,19 +331,8 @@ __device__ __forceinline__ void cq_run(const babe_cqt_bands& bd, f2* a, int k0, 
 #pragma unroll
         for (int t = 0; t < R0; ++t) v[t] = f2{vr[t], vi[t]};
     }
-    if (!(ABL & 8) || MODE != 0) cq_band_fft_regs<LT, (MODE == 0 ? +1 : -1)>(v, a, tw, s << LT, u, active);
-    if (MODE == 0 && (ABL & 2) && R0 == 16) {
-        typedef float f32x4 __attribute__((ext_vector_type(4)));
-        typedef int i32x4 __attribute__((ext_vector_type(4)));
-#pragma unroll
-        for (int t4 = 0; t4 < 4; ++t4) {
-            const unsigned o0 = cfo + (unsigned)(4 * u + t4 * 4 * TB) * 4;
-            const f32x4 yr = {v[4 * t4].x, v[4 * t4 + 1].x, v[4 * t4 + 2].x, v[4 * t4 + 3].x};
-            const f32x4 yi = {v[4 * t4].y, v[4 * t4 + 1].y, v[4 * t4 + 2].y, v[4 * t4 + 3].y};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, yr), rc, o0, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, yi), rc, o0, plane, 0);
-        }
-    } else if (MODE == 0) {
+    cq_band_fft_regs<LT, (MODE == 0 ? +1 : -1)>(v, a, tw, s << LT, u, active);
+    if (MODE == 0) {
 #pragma unroll
         for (int c = 0; c < PL::CNT; ++c) {
             const unsigned o0 = cfo + (unsigned)PL::out_index(u, c, 0) * 4;                // (cq_perm(0) = 0)
@@ -401,11 +366,7 @@ __device__ __forceinline__ void cq_run(const babe_cqt_bands& bd, f2* a, int k0, 
 }
 
 template <int MODE, bool AN, bool NT>
-__global__ __launch_bounds__(256)
-#if ABL & 32
-__attribute__((amdgpu_waves_per_eu(6, 6)))
-#endif
-void band_fft_kernel(babe_cqt_bands bd, const float* __restrict__ spec,
+__global__ __launch_bounds__(256) void band_fft_kernel(babe_cqt_bands bd, const float* __restrict__ spec,
                                                        float* __restrict__ bs, long bs_stride,
                                                        const float* __restrict__ win) {
     __shared__ f2 a[CQ_LDS];
@@ -416,11 +377,7 @@ void band_fft_kernel(babe_cqt_bands bd, const float* __restrict__ spec,
     if (nb > 64 || (nb << lt) > 4096 || oc >= 8) __builtin_trap();      // a table that contradicts its own summary fields: fail loudly
     switch (lt) {
 #define CQ_CASE(L_) case L_: cq_run<L_, MODE, AN, NT>(bd, a, k0, nb, oc, bin0, b, spec, bs, bs_stride, win); break;
-#ifdef CQ_ONLY                    // (instruction counting: one band length per build)
-        CQ_CASE(CQ_ONLY)
-#else
         CQ_CASE(12) CQ_CASE(11) CQ_CASE(10) CQ_CASE(9) CQ_CASE(8) CQ_CASE(7) CQ_CASE(6) CQ_CASE(5) CQ_CASE(4) CQ_CASE(3) CQ_CASE(2)
-#endif
 #undef CQ_CASE
         default: __builtin_trap();
     }

@@ -440,16 +440,8 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
 
 }  // namespace
 
-// (timing probe only, results wrong: BABE_ABL_GN bit 1 skips the forward statistics pass, bit 2 the VJP's partial-sum pass - the upper
-// bound of what producing those sums inside the convolutions' epilogues could save)
-static int abl_gn() {
-    static const int v = [] { const char* e = getenv("BABE_ABL_GN"); return e ? atoi(e) : 0; }();
-    return v;
-}
-
 extern "C" int babe_gn_partial(const float* x, double* part, int B, int G, long n, int S, void* stream) {
     BABE_CHECK_ARG(x && part && B > 0 && G > 0 && n > 1 && S > 0, "gn_partial: bad arguments");
-    if (abl_gn() & 1) return BABE_OK;
     BABE_CHECK_ARG(n % 4 == 0, "gn_partial: group size %ld not a multiple of 4", n);
     BabeProfScope prof(BABE_SLOT_GN_STATS, 4.0 * B * G * (double)n, 0, 0, stream);
     hipLaunchKernelGGL(gn_partial_kernel<false>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, part, n, S,
@@ -533,7 +525,6 @@ extern "C" int babe_gn_bwd_partial(const float* x, const float* da, const float*
                                    int G, long hw, int S, void* stream) {
     BABE_CHECK_ARG(x && da && scale && part, "gn_bwd_partial: null pointer");
     BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_partial: hw=%ld C=%d G=%d unsupported", hw, C, G);
-    if (abl_gn() & 2) return BABE_OK;
     BabeProfScope prof(BABE_SLOT_GN_BWD_PARTIAL, 8.0 * B * C * (double)hw, 0, 0, stream);
     hipLaunchKernelGGL(gn_bwd_partial_kernel<true>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
                        part, C, G, hw, S);

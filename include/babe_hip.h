@@ -359,7 +359,7 @@ typedef struct {
      * workgroup lives ~6 us and spent a third of that fetching its own description):
      * wg_rec[w] = {wg_first, wg_count, log2T, oct | binoct << 8},  band_rec[k] = {c, M, woff, 0}   (int4 each) */
     const int* wg_rec; const int* band_rec;
-    int abl;             /* timing-only ablation bits (1: skip the FFT passes); read only by -DBABE_CQT_ABL builds */
+    int reserved;        /* must be 0 */
     /* host-side summary of the DEVICE tables above, validated by the entry points (the kernel keeps wg_count bands of
      * 3 ints in LDS and dispatches on log2T): max of wg_count (<= 64), min / max of log2T (2..12) */
     int max_wg_count, min_log2T, max_log2T;
