@@ -203,9 +203,11 @@ SIGS = {
     "babe_cqt_gather": (_I, [_P, _L, _P, _P, _P, _P, _I, _I, _F, _P, _I, _P]),
     "babe_spec_scale": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _I, _P]),
     "babe_cqt_design_create": (_P, [_D, _I, _I, _I, _D]),
+    "babe_cqt_design_create_ex": (_P, [_D, _I, _I, _I, _D, _I]),
     "babe_cqt_design_destroy": (None, [_P]),
     "babe_cqt_design_get": (_L, [_P, _S, _P, _L]),
     "babe_cqt_plan_create": (_P, [_D, _I, _I, _I, _D]),
+    "babe_cqt_plan_create_ex": (_P, [_D, _I, _I, _I, _D, _I]),
     "babe_cqt_plan_destroy": (None, [_P]),
     "babe_cqt_workspace_bytes": (_L, [_P, _I]),
     "babe_cqt_fwd": (_I, [_P, _P, _P, _P, _I, _P]),

@@ -27,6 +27,9 @@ from ._lib import check, lib, ptr, stream
 
 
 # ----------------------------------------------------------------------------- band design
+MAX_BAND = 8192     # longest band transform of csrc/cqt.hip (band_fft13_kernel); the max_band every plan here is created with
+
+
 def _next_pow2(v):
     return 1 << int(math.ceil(math.log2(max(int(v), 1))))
 
@@ -61,7 +64,7 @@ def design_bands(fs, L, numocts=7, binsoct=64, beta=1.0):
     for j in range(numocts):
         sl = slice(j * binsoct, (j + 1) * binsoct)
         T[sl] = _next_pow2(M[sl].max())
-    assert T.max() <= 4096, "band longer than the LDS FFT supports"
+    assert T.max() <= MAX_BAND, "band longer than the LDS FFT supports"
     woff = np.concatenate(([0], np.cumsum(M)[:-1]))
     nwin = int(M.sum())
     g = np.zeros(nwin)
@@ -277,7 +280,8 @@ class CQT_nsgt:
         self.T_oct = [int(d["T"][j * binsoct]) for j in range(numocts)]
         self._tabs = dict(c=ti(d["c"]), M=ti(d["M"]), woff=ti(d["woff"]), log2T=ti(np.log2(d["T"]).astype(np.int64)),
                           oct=ti(np.arange(d["nb"]) // binsoct), binoct=ti(np.arange(d["nb"]) % binsoct))
-        # workgroup table of the band-FFT kernels: 4096 points (4096/T bands of one octave, at most the whole octave) each
+        # workgroup table of the band-FFT kernels: 4096 points (4096/T bands of one octave, at most the whole octave) each; a band
+        # of T = 8192 (the top octave of a segment above 8.5 s) gets a workgroup of its own, at the end of the table
         wgf, wgc = [], []
         for j in range(numocts):
             bpw = int(min(binsoct, max(1, 4096 // self.T_oct[j])))
@@ -332,7 +336,7 @@ class CQT_nsgt:
             # (the plan only has the mixed-radix form of the length-L transform: for a length whose factors that form does not
             # cover the library returns NULL, and under BABE_FFT_MIXED=0 no plan is asked for; this class then sequences the
             # kernels itself, with the dense-DFT form)
-            self._plan = lib().babe_cqt_plan_create(float(fs), self.Ls, numocts, binsoct, float(window[1])) or None
+            self._plan = lib().babe_cqt_plan_create_ex(float(fs), self.Ls, numocts, binsoct, float(window[1]), MAX_BAND) or None
             self._ws = {}
 
     def __del__(self):

@@ -1,7 +1,8 @@
 // Constant-Q (NSGT, "oct") analysis / synthesis kernels.  Definition: oracle/nsgt.py header and
 // babe_amd/cqt_plan.py; call sites in the reference: networks/cqtdiff+.py:743,841,
 // testing/blind_bwe_sampler.py:156 (cqt_nsgt_pytorch.CQT_nsgt.fwd/.bwd/.apply_hpf_DC).
-// HBM/latency-bound: a workgroup owns 4096 complex points of one octave (4096/T bands) in LDS.
+// HBM/latency-bound: a workgroup owns 4096 complex points of one octave (4096/T bands) in LDS, or one band of 8192 points
+// (band_fft13_kernel: the top octave of a segment above 8.5 s).
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include "prof.h"
@@ -93,10 +94,12 @@ __device__ __forceinline__ constexpr int cq_perm(int r) {       // register r of
     }
 }
 
-// ---- pass plan of a T = 2^LT point band: radices 16,16,16 / 16,16,8 / 16,16,4 / 16,8,4 / 16,16 / 16,8 / 16,4 / 16,2 / 16 / 8 / 4
-__host__ __device__ constexpr int cq_npass(int LT) { return LT >= 9 ? 3 : (LT >= 5 ? 2 : 1); }
+// ---- pass plan of a T = 2^LT point band: radices 16,16,16 / 16,16,8 / 16,16,4 / 16,8,4 / 16,16 / 16,8 / 16,4 / 16,2 / 16 / 8 / 4;
+// the long band (LT = 13, band_fft13_kernel below): 16,16,16,2
+__host__ __device__ constexpr int cq_npass(int LT) { return LT >= 13 ? 4 : (LT >= 9 ? 3 : (LT >= 5 ? 2 : 1)); }
 __host__ __device__ constexpr int cq_radix(int LT, int p) {
     if (LT <= 3) return 1 << LT;
+    if (LT == 13) return p < 3 ? 16 : 2;
     if (p == 0) return 16;
     if (LT >= 10) return p == 1 ? 16 : (1 << (LT - 8));
     if (LT == 9) return p == 1 ? 8 : 4;
@@ -153,6 +156,18 @@ struct CqPass {
     // the transform (round 5) - issued right after the band's input loads, so that their global-memory latency runs behind those
     // and pass 0 instead of being paid after every inter-pass barrier (hipcc does not move a load across __syncthreads()).
     static __device__ __forceinline__ void load_tw(f2 (&pre)[CNT * NTW], const f2* __restrict__ tw, int u) {
+        if constexpr (Ns * R == 8192) {
+            // last pass of the long band (radix 2, Ns = 4096): W = exp(-2 pi i k/8192), k = j < 4096.  Even k is table entry k/2;
+            // odd k is that entry times exp(-2 pi i/8192) - one complex product, no chain.  k = u + c*512 has the parity of u.
+            static_assert(R == 2 && NTW == 1 && TB % 2 == 0, "pass plan");
+            const f2 w1 = (u & 1) ? f2{0x1.fffff62161a34p-1f, -0x1.921fb2aecb360p-11f} : f2{1.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < CNT; ++c) {
+                const f2 e = cq_tw(tw, (u + c * TB) >> 1);
+                pre[c] = (u & 1) ? cq_mul<false>(e, w1) : e;
+            }
+            return;
+        }
 #pragma unroll
         for (int c = 0; c < CNT; ++c) {
             const int j = u + c * TB;
@@ -201,9 +216,11 @@ __device__ __forceinline__ void cq_band_fft_regs(f2* v, f2* a, const f2* __restr
     using P0 = CqPass<LT, 0>;
     using P1 = CqPass<LT, (NP >= 2 ? 1 : 0)>;
     using P2 = CqPass<LT, (NP >= 3 ? 2 : 0)>;
-    f2 tw1[P1::CNT * P1::NTW], tw2[P2::CNT * P2::NTW];
+    using P3 = CqPass<LT, (NP >= 4 ? 3 : 0)>;
+    f2 tw1[P1::CNT * P1::NTW], tw2[P2::CNT * P2::NTW], tw3[P3::CNT * P3::NTW];
     if constexpr (NP >= 2) P1::load_tw(tw1, tw, u);
     if constexpr (NP >= 3) P2::load_tw(tw2, tw, u);
+    if constexpr (NP >= 4) P3::load_tw(tw3, tw, u);
     cq_fft<P0::R, S>(v);
     if constexpr (NP >= 2) {
         if (active) P0::scatter(v, a, base, u);
@@ -214,6 +231,12 @@ __device__ __forceinline__ void cq_band_fft_regs(f2* v, f2* a, const f2* __restr
             if (active) P1::scatter(v, a, base, u);
             __syncthreads();
             if (active) P2::template gather_bfly<S>(v, a, tw2, base, u);
+            if constexpr (NP >= 4) {
+                __syncthreads();
+                if (active) P2::scatter(v, a, base, u);
+                __syncthreads();
+                if (active) P3::template gather_bfly<S>(v, a, tw3, base, u);
+            }
         }
     }
 }
@@ -381,6 +404,27 @@ __global__ __launch_bounds__(256) void band_fft_kernel(babe_cqt_bands bd, const 
 #undef CQ_CASE
         default: __builtin_trap();
     }
+}
+
+// The long band: ONE band of T = 8192 points per workgroup of 512 threads (segments above 8.5 s: the top octave's bands have
+// about 0.01086 L samples).  The same register transform with a fourth pass, radices 16,16,16,2: a thread still holds 16 values,
+// the last pass runs its 8 radix-2 butterflies on elements j and j + 4096 (j = u + 512 c) with W = exp(-2 pi i j/8192) from the
+// 4096-table (CqPass::load_tw), and its outputs leave the registers as runs of 512 consecutive samples per instruction.  LDS:
+// 8192 + 8192/16 float2 = 69632 bytes, dynamic (above the 64 KB a kernel gets without the opt-in; two workgroups fit a CU's 160 KB),
+// crossed three times, write - barrier - read - barrier as in the short bands.  Launched over workgroups wg0 .. of the table only:
+// the instantiations of band_fft_kernel above are the ones a design without long bands has always run.
+constexpr int CQ13_LDS_BYTES = (8192 + (8192 >> 4)) * (int)sizeof(f2);
+template <int MODE, bool AN, bool NT>
+__global__ __launch_bounds__(512) void band_fft13_kernel(babe_cqt_bands bd, int wg0, const float* __restrict__ spec,
+                                                         float* __restrict__ bs, long bs_stride,
+                                                         const float* __restrict__ win) {
+    extern __shared__ f2 a13[];
+    const int wg = wg0 + blockIdx.x, b = blockIdx.y;
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    const i32x4 wr = reinterpret_cast<const i32x4*>(bd.wg_rec)[wg];           // {first band, bands, log2 T, oct | binoct << 8}
+    const int k0 = wr[0], nb = wr[1], lt = wr[2], oc = wr[3] & 255, bin0 = wr[3] >> 8;
+    if (nb != 1 || lt != 13 || oc >= 8 || k0 != bd.nbands - bd.binsoct + (int)blockIdx.x) __builtin_trap();      // as above: fail loudly
+    cq_run<13, MODE, AN, NT>(bd, a13, k0, 1, oc, bin0, b, spec, bs, bs_stride, win);
 }
 
 // overlap-add in frequency as a gather (deterministic: fixed summation order, no atomics).  A thread owns bin n of GB
@@ -570,12 +614,34 @@ static int check_bands(const babe_cqt_bands* bd) {
     BABE_CHECK_ARG(bd && bd->nbands > 0 && bd->c && bd->M && bd->woff && bd->log2T && bd->oct && bd->binoct &&
                        bd->tw4096 && bd->nocts <= 8 && bd->wg_first && bd->wg_count && bd->nwg > 0 && bd->wg_rec && bd->band_rec,
                    "cqt: bad band table");
-    // what the band-FFT kernel relies on: <= 64 bands per workgroup (thread = band slot x butterfly), T in 4..4096 (its dispatch)
+    // what the band-FFT kernels rely on: <= 64 bands per workgroup (thread = band slot x butterfly), T in 4..4096 (band_fft_kernel's
+    // dispatch) or 8192 (band_fft13_kernel).  Only the host-side summary can be checked here; a device table that contradicts it
+    // makes the kernels trap.
     BABE_CHECK_ARG(bd->max_wg_count >= 1 && bd->max_wg_count <= 64, "cqt: wg_count must be in 1..64 (got %d)", bd->max_wg_count);
-    BABE_CHECK_ARG(bd->min_log2T >= 2 && bd->max_log2T <= 12 && bd->min_log2T <= bd->max_log2T,
-                   "cqt: band lengths must be 2^2..2^12 (got 2^%d..2^%d)", bd->min_log2T, bd->max_log2T);
+    BABE_CHECK_ARG(bd->min_log2T >= 2 && bd->max_log2T <= 13 && bd->min_log2T <= bd->max_log2T,
+                   "cqt: band lengths must be 2^2..2^13 (got 2^%d..2^%d)", bd->min_log2T, bd->max_log2T);
     BABE_CHECK_ARG(bd->binsoct >= 1 && bd->nwg <= bd->nbands, "cqt: workgroup table inconsistent with the band table");
+    // long bands (2^13): the top octave's, one band per workgroup, the last binsoct workgroups of the table (babe_hip.h)
+    if (bd->max_log2T == 13) {
+        BABE_CHECK_ARG(bd->min_log2T < 13 || (bd->max_wg_count == 1 && bd->nwg == bd->binsoct && bd->nbands == bd->binsoct),
+                       "cqt: a 2^13-point band needs a workgroup of its own (wg_count up to %d, %d workgroups for %d bands)", bd->max_wg_count,
+                       bd->nwg, bd->nbands);
+        BABE_CHECK_ARG(bd->nwg >= bd->binsoct && bd->nbands >= bd->binsoct,
+                       "cqt: a table with 2^13-point bands needs a workgroup per band of the top octave (nwg = %d, binsoct = %d)", bd->nwg, bd->binsoct);
+    }
     return 0;
+}
+// workgroups of band_fft13_kernel (the last ones of the table); the others belong to band_fft_kernel
+static int long_wgs(const babe_cqt_bands* bd) { return bd->max_log2T == 13 ? bd->binsoct : 0; }
+#define CQ13_FN(MODE_, AN_, NT_) reinterpret_cast<const void*>(&band_fft13_kernel<MODE_, AN_, NT_>)
+static int long_optin() {
+    static std::atomic<unsigned long long> attr{0};
+    if (babe_lds_optin(attr, {CQ13_FN(0, false, true), CQ13_FN(0, false, false), CQ13_FN(0, true, true), CQ13_FN(0, true, false),
+                              CQ13_FN(1, false, false), CQ13_FN(1, true, false)}, CQ13_LDS_BYTES) != hipSuccess) {
+        babe_set_error("cqt: cannot opt the 8192-point band kernel in to %d bytes of LDS", CQ13_LDS_BYTES);
+        return BABE_ERR_HIP;
+    }
+    return BABE_OK;
 }
 
 extern "C" int babe_cqt_band_analysis(const babe_cqt_bands* bd, const float* spec, const float* win, int B,
@@ -584,13 +650,25 @@ extern "C" int babe_cqt_band_analysis(const babe_cqt_bands* bd, const float* spe
     BABE_CHECK_ARG(spec && B > 0, "cqt_band_analysis: bad arguments");
     BABE_CHECK_ARG(win || (bd->kdeg > 0 && bd->kdeg <= 11), "cqt_band_analysis: no window table and no analytic window (kdeg = %d)", bd->kdeg);
     BabeProfScope prof(BABE_SLOT_CQT_ANALYSIS, (double)B * (8.0 * (bd->L / 2 + 1) + 8.0 * bd->sum_T + (win ? 4.0 : 0.0) * bd->sum_M), 5.0 * B * bd->sum_TlogT, 0, stream);
-    const dim3 grid(bd->nwg, B);
+    const int nlong = long_wgs(bd), nshort = bd->nwg - nlong;
     const hipStream_t st = (hipStream_t)stream;
-    if (win && B >= 8) hipLaunchKernelGGL((band_fft_kernel<0, false, true>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
-    else if (win) hipLaunchKernelGGL((band_fft_kernel<0, false, false>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
-    else if (B >= 8) hipLaunchKernelGGL((band_fft_kernel<0, true, true>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
-    else hipLaunchKernelGGL((band_fft_kernel<0, true, false>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
-    BABE_LAUNCH_CHECK();
+    if (nlong && long_optin() != BABE_OK) return BABE_ERR_HIP;
+    if (nshort > 0) {
+        const dim3 grid(nshort, B);
+        if (win && B >= 8) hipLaunchKernelGGL((band_fft_kernel<0, false, true>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
+        else if (win) hipLaunchKernelGGL((band_fft_kernel<0, false, false>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
+        else if (B >= 8) hipLaunchKernelGGL((band_fft_kernel<0, true, true>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
+        else hipLaunchKernelGGL((band_fft_kernel<0, true, false>), grid, dim3(256), 0, st, *bd, spec, (float*)nullptr, 0L, win);
+        BABE_LAUNCH_CHECK();
+    }
+    if (nlong) {
+        const dim3 grid(nlong, B);
+        if (win && B >= 8) hipLaunchKernelGGL((band_fft13_kernel<0, false, true>), grid, dim3(512), CQ13_LDS_BYTES, st, *bd, nshort, spec, (float*)nullptr, 0L, win);
+        else if (win) hipLaunchKernelGGL((band_fft13_kernel<0, false, false>), grid, dim3(512), CQ13_LDS_BYTES, st, *bd, nshort, spec, (float*)nullptr, 0L, win);
+        else if (B >= 8) hipLaunchKernelGGL((band_fft13_kernel<0, true, true>), grid, dim3(512), CQ13_LDS_BYTES, st, *bd, nshort, spec, (float*)nullptr, 0L, win);
+        else hipLaunchKernelGGL((band_fft13_kernel<0, true, false>), grid, dim3(512), CQ13_LDS_BYTES, st, *bd, nshort, spec, (float*)nullptr, 0L, win);
+        BABE_LAUNCH_CHECK();
+    }
     return BABE_OK;
 }
 
@@ -600,9 +678,18 @@ extern "C" int babe_cqt_band_synthesis(const babe_cqt_bands* bd, float* bs, cons
     BABE_CHECK_ARG(bs && B > 0, "cqt_band_synthesis: bad arguments");
     BABE_CHECK_ARG(win || (bd->kdeg > 0 && bd->kdeg <= 11), "cqt_band_synthesis: no window table and no analytic window (kdeg = %d)", bd->kdeg);
     BabeProfScope prof(BABE_SLOT_CQT_SYNTHESIS, (double)B * (8.0 * bd->sum_T + (win ? 12.0 : 8.0) * bd->sum_M), 5.0 * B * bd->sum_TlogT, 0, stream);
-    if (win) hipLaunchKernelGGL((band_fft_kernel<1, false, false>), dim3(bd->nwg, B), dim3(256), 0, (hipStream_t)stream, *bd, (const float*)nullptr, bs, bs_stride, win);
-    else hipLaunchKernelGGL((band_fft_kernel<1, true, false>), dim3(bd->nwg, B), dim3(256), 0, (hipStream_t)stream, *bd, (const float*)nullptr, bs, bs_stride, win);
-    BABE_LAUNCH_CHECK();
+    const int nlong = long_wgs(bd), nshort = bd->nwg - nlong;
+    if (nlong && long_optin() != BABE_OK) return BABE_ERR_HIP;
+    if (nshort > 0) {
+        if (win) hipLaunchKernelGGL((band_fft_kernel<1, false, false>), dim3(nshort, B), dim3(256), 0, (hipStream_t)stream, *bd, (const float*)nullptr, bs, bs_stride, win);
+        else hipLaunchKernelGGL((band_fft_kernel<1, true, false>), dim3(nshort, B), dim3(256), 0, (hipStream_t)stream, *bd, (const float*)nullptr, bs, bs_stride, win);
+        BABE_LAUNCH_CHECK();
+    }
+    if (nlong) {
+        if (win) hipLaunchKernelGGL((band_fft13_kernel<1, false, false>), dim3(nlong, B), dim3(512), CQ13_LDS_BYTES, (hipStream_t)stream, *bd, nshort, (const float*)nullptr, bs, bs_stride, win);
+        else hipLaunchKernelGGL((band_fft13_kernel<1, true, false>), dim3(nlong, B), dim3(512), CQ13_LDS_BYTES, (hipStream_t)stream, *bd, nshort, (const float*)nullptr, bs, bs_stride, win);
+        BABE_LAUNCH_CHECK();
+    }
     return BABE_OK;
 }
 

@@ -6,6 +6,8 @@
 //   babe_cqt_design_create / _get / _destroy   host only (no GPU call): the tables, float64 / int64, the same arithmetic in the same
 //                                              order as design_bands (tests/test_cqt_plan_cpu.py compares them with the numpy tables)
 //   babe_cqt_plan_create / _destroy            design + float32 device tables + the mixed-radix plan of the length-L real FFT
+//   babe_cqt_design_create_ex / babe_cqt_plan_create_ex     the same with the longest band transform the host takes as an argument
+//                                              (4096: what the five-argument entries keep; 8192: segments up to about 754 000 samples)
 //   babe_cqt_fwd / _bwd / _fwd_adjoint / _bwd_adjoint / _hpf     the transforms (rfft_L -> band kernels, band kernels -> gather -> rfft_L^T)
 // The definition itself (NSGT LogScale, band lengths, Kaiser windows, painless-case dual frame with the mirrored bands, octave-wise
 // power-of-two rasterisation) is stated in oracle/nsgt.py and DESIGN.md; the dependency is absent from the reference tree (parity
@@ -84,7 +86,7 @@ struct CqtDesign {
     // the length-L real FFT (four-step N1 x N2, csrc/fft_mixed.hip)
     long N1 = 0, N2 = 0, K2 = 0, KX = 0;
     std::vector<int> rad1, rad2;
-    // workgroup table of the band kernels: 4096 points (4096 / T bands of one octave) each
+    // workgroup table of the band kernels: 4096 points (4096 / T bands of one octave) each, an 8192-point band alone
     std::vector<int> wg_first, wg_count;
     std::vector<int> T_oct;
     int kdeg = 0;
@@ -123,9 +125,14 @@ std::vector<int> small_radices(long N) {
 }
 
 // babe_amd/cqt.py::design_bands, operation for operation (float64; sums in the same order)
-CqtDesign* design(double fs, long L, int numocts, int binsoct, double beta) {
+// max_band: the longest band transform the caller takes, 4096 or 8192 points
+CqtDesign* design(double fs, long L, int numocts, int binsoct, double beta, int max_band) {
     CqtDesign* d = new CqtDesign;
     d->fs = fs, d->L = L, d->numocts = numocts, d->binsoct = binsoct, d->beta = beta;
+    if (max_band != 4096 && max_band != 8192) {
+        d->error = "cqt design: max_band must be 4096 or 8192 (got " + std::to_string(max_band) + ")";
+        return d;
+    }
     if (L < 16 || L % 2 != 0 || numocts < 1 || numocts > 8 || binsoct < 2 || binsoct > 255 || !(fs > 0) || !(beta >= 0)) {
         d->error = "cqt design: need an even audio length, 1..8 octaves, 2..255 bins per octave";
         return d;
@@ -159,8 +166,9 @@ CqtDesign* design(double fs, long L, int numocts, int binsoct, double beta) {
         const long T = next_pow2(mx);
         for (int k = j * binsoct; k < (j + 1) * binsoct; ++k) d->T[k] = T;
         d->T_oct[j] = (int)T;
-        if (T > 4096 || T < 4) {
-            d->error = "cqt design: a band is longer than the 4096-point band FFT supports";
+        if (T > max_band || T < 4) {
+            d->error = max_band == 4096 ? "cqt design: a band is longer than the 4096-point band FFT supports"
+                                        : "cqt design: a band is longer than the 8192-point band FFT supports";
             return d;
         }
     }
@@ -305,8 +313,8 @@ int ilog2(long v) {
 
 }  // namespace
 
-extern "C" void* babe_cqt_design_create(double fs, int audio_len, int numocts, int binsoct, double beta) {
-    CqtDesign* d = design(fs, (long)audio_len, numocts, binsoct, beta);
+extern "C" void* babe_cqt_design_create_ex(double fs, int audio_len, int numocts, int binsoct, double beta, int max_band) {
+    CqtDesign* d = design(fs, (long)audio_len, numocts, binsoct, beta, max_band);
     if (!d->error.empty()) {
         babe_set_error("%s (fs = %g, audio_len = %d, numocts = %d, binsoct = %d, beta = %g)", d->error.c_str(), fs, audio_len, numocts,
                        binsoct, beta);
@@ -314,6 +322,9 @@ extern "C" void* babe_cqt_design_create(double fs, int audio_len, int numocts, i
         return nullptr;
     }
     return d;
+}
+extern "C" void* babe_cqt_design_create(double fs, int audio_len, int numocts, int binsoct, double beta) {
+    return babe_cqt_design_create_ex(fs, audio_len, numocts, binsoct, beta, 4096);
 }
 extern "C" void babe_cqt_design_destroy(void* design) { delete static_cast<CqtDesign*>(design); }
 
@@ -357,7 +368,10 @@ extern "C" long babe_cqt_design_get(const void* design, const char* name, void* 
 }
 
 extern "C" void* babe_cqt_plan_create(double fs, int audio_len, int numocts, int binsoct, double beta) {
-    CqtDesign* d = static_cast<CqtDesign*>(babe_cqt_design_create(fs, audio_len, numocts, binsoct, beta));
+    return babe_cqt_plan_create_ex(fs, audio_len, numocts, binsoct, beta, 4096);
+}
+extern "C" void* babe_cqt_plan_create_ex(double fs, int audio_len, int numocts, int binsoct, double beta, int max_band) {
+    CqtDesign* d = static_cast<CqtDesign*>(babe_cqt_design_create_ex(fs, audio_len, numocts, binsoct, beta, max_band));
     if (!d) return nullptr;
     CqtPlan* p = new CqtPlan;
     p->d = d;

@@ -8,6 +8,7 @@ import torch
 
 from .._cabi import EvalDesc
 from .._lib import check, lib, ptr, stream
+from ..cqt import MAX_BAND
 
 
 def cqt_plan_of(cq):
@@ -18,7 +19,7 @@ def cqt_plan_of(cq):
     if not cq.fft.mixed:                                   # BABE_FFT_MIXED=0 / an uncovered length: the plan has no dense form
         return None
     if getattr(cq, "_plan_eval", None) is None:
-        cq._plan_eval = lib().babe_cqt_plan_create(float(cq.fs), cq.Ls, cq.numocts, cq.binsoct, float(cq.design["beta"])) or 0
+        cq._plan_eval = lib().babe_cqt_plan_create_ex(float(cq.fs), cq.Ls, cq.numocts, cq.binsoct, float(cq.design["beta"]), MAX_BAND) or 0
     return cq._plan_eval or None
 
 

@@ -353,7 +353,10 @@ typedef struct {
     int nocts; int binsoct;
     float* coef[8];      /* per octave planar [B][2][binsoct][T_oct]          */
     /* workgroup table: workgroup w transforms bands wg_first[w] .. wg_first[w]+wg_count[w]-1, all of one octave
-     * (same T), wg_count[w] * T <= 4096 points */
+     * (same T), wg_count[w] * T <= 4096 points - or ONE band of T = 8192 points (a "long" workgroup, its own kernel).
+     * Long bands are those of the HIGHEST octave only (an octave below has bands half as long): with max_log2T == 13 the last
+     * binsoct bands of the table are the long ones and the last binsoct workgroups hold one of them each, in order; every
+     * workgroup before them is a short one. */
     const int* wg_first; const int* wg_count; int nwg;
     /* the same tables packed for the kernel (one 16-byte load each instead of chains of dependent 4-byte loads - a
      * workgroup lives ~6 us and spent a third of that fetching its own description):
@@ -361,7 +364,9 @@ typedef struct {
     const int* wg_rec; const int* band_rec;
     int reserved;        /* must be 0 */
     /* host-side summary of the DEVICE tables above, validated by the entry points (the kernel keeps wg_count bands of
-     * 3 ints in LDS and dispatches on log2T): max of wg_count (<= 64), min / max of log2T (2..12) */
+     * 3 ints in LDS and dispatches on log2T): max of wg_count (<= 64), min / max of log2T (2..13; 13 as described at the
+     * workgroup table: then nwg >= binsoct and nbands >= binsoct, and a table of long bands alone - min_log2T == 13 - has
+     * max_wg_count == 1 and nwg == nbands == binsoct) */
     int max_wg_count, min_log2T, max_log2T;
     long sum_T, sum_M;   /* sum over bands of T_k and M_k (for the measurement hook's algorithmic bytes) */
     double sum_TlogT;    /* sum over bands of T_k*log2(T_k) (algorithmic FFT flops = 5*that)            */
@@ -403,11 +408,17 @@ int babe_spec_scale(const float* spec_in, const float* spec2, float* spec_out, c
  *   plan: design + device tables (one allocation on the current device).  Coefficients are planar, one tensor per octave:
  *   coef[j] = [B][2][binsoct][T_oct[j]], j = 0 the LOWEST octave (the [B,2,64,T] tensors the UNet consumes).  ws: device scratch of
  *   babe_cqt_workspace_bytes(plan, B) bytes, owned by the caller (one per concurrent stream).  NULL / negative on failure
- *   (babe_last_error()). */
+ *   (babe_last_error()).
+ *   max_band (the _ex entries): the longest band transform the host is prepared for, 4096 or 8192 points (anything else: NULL).  A
+ *   design whose longest band needs more is refused ("cqt design: ..." naming the limit); the top octave's bands have about
+ *   0.01086 * audio_len samples whatever fs is, so 4096 reaches audio_len = 368368 (and not 384000) and 8192 about 754000.  The
+ *   five-argument entries are the _ex entries with max_band = 4096: a host that sized its tables by that limit keeps it. */
 void* babe_cqt_design_create(double fs, int audio_len, int numocts, int binsoct, double beta);
+void* babe_cqt_design_create_ex(double fs, int audio_len, int numocts, int binsoct, double beta, int max_band);
 void babe_cqt_design_destroy(void* design);
 long babe_cqt_design_get(const void* design, const char* name, void* out, long capacity_bytes);
 void* babe_cqt_plan_create(double fs, int audio_len, int numocts, int binsoct, double beta);
+void* babe_cqt_plan_create_ex(double fs, int audio_len, int numocts, int binsoct, double beta, int max_band);
 void babe_cqt_plan_destroy(void* plan);
 const void* babe_cqt_plan_design(const void* plan);                  /* the plan's design (owned by the plan), for babe_cqt_design_get */
 long babe_cqt_workspace_bytes(const void* plan, int B);
