@@ -22,7 +22,8 @@
 //    diagonals of bucket k in ascending offset and writes the query tile's partial; a last pass adds the query tiles in order.
 //    The qk bias gradient is the row sum of dqk over t (double, fixed order).
 //
-// 3. norm2 / affine2: babe_gn_param_grad without the GELU, and the plain per-channel scale pass that rebuilds proj_in's input.
+// 3. norm2 / affine2: the plain per-channel scale pass that rebuilds proj_in's input (their parameter gradient,
+//    babe_gn_param_grad_nogelu, sits beside its GELU twin in wgrad.hip).
 #include "common.h"
 #include "../../include/babe_hip.h"
 #include <cmath>
@@ -287,39 +288,7 @@ inline bool pv_shape_ok(int B, int H, int F, int T, int nbk) {
 // static LDS of attn_demb_kernel<F/64> + its diagonals
 inline long demb_lds_bytes(int F, int T) { return 4L * (2L * F * 16 + 64 + 16 * 17 + diag_len(T)); }
 
-// ---------------------------------------------------------------- GroupNorm * FiLM without GELU, scale pass
-__device__ double block_sum_d(double v, double* sh) {
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
-
-// grid (C, B)
-__global__ __launch_bounds__(256) void gn_param_nogelu_kernel(const float* __restrict__ z, const float* __restrict__ da,
-                                                              const float* __restrict__ stats, const float* __restrict__ gamma,
-                                                              const float* __restrict__ film, long film_bs, float cs,
-                                                              float* __restrict__ dg, long dg_bs, float* __restrict__ dfilm,
-                                                              long dfilm_bs, int C, int G, long hw) {
-    __shared__ double sh[256];
-    const int c = blockIdx.x, b = blockIdx.y;
-    const long base = ((long)b * C + c) * hw;
-    double s = 0;
-    for (long i = threadIdx.x; i < hw; i += 256) s += (double)da[base + i] * (double)z[base + i];
-    s = block_sum_d(s, sh);
-    if (threadIdx.x == 0) {
-        const double ds = (double)cs * s;
-        const double r = stats[((long)b * G + c / (C / G)) * 3 + 2];
-        dg[(long)b * dg_bs + c] = (float)(ds * ((double)film[(long)b * film_bs + c] + 1.0) * r);
-        dfilm[(long)b * dfilm_bs + c] = (float)(ds * (double)gamma[c] * r);
-    }
-}
-
+// ---------------------------------------------------------------- scale pass
 // grid (ceil(hw/1024), C, B), 256 threads
 __global__ __launch_bounds__(256) void scale_channels_kernel(const float* __restrict__ x, const float* __restrict__ scale,
                                                              float* __restrict__ out, int C, long hw) {
@@ -398,17 +367,6 @@ extern "C" int babe_attn_param_vjp(const float* qk, const float* qk_bias, const 
         hipLaunchKernelGGL(rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
         BABE_LAUNCH_CHECK();
     }
-    return BABE_OK;
-}
-
-extern "C" int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stats, const float* gamma,
-                                         const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
-                                         long dfilm_bs, int B, int C, int G, long hw, void* stream) {
-    BABE_CHECK_ARG(z && da && stats && gamma && film_aff && dgamma_rows && dfilm && B > 0 && C > 0 && G > 0 && C % G == 0 && hw > 0,
-                   "gn_param_grad_nogelu: bad arguments");
-    hipLaunchKernelGGL(gn_param_nogelu_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, z, da, stats, gamma, film_aff, film_bs,
-                       cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, C, G, hw);
-    BABE_LAUNCH_CHECK();
     return BABE_OK;
 }
 

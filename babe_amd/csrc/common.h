@@ -90,3 +90,17 @@ __device__ __forceinline__ float wave_sumf(float v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+
+// Workgroup sum over NW waves: wave_sum, one LDS slot per wave (sh: NW doubles), one barrier, then the slots added in wave
+// order, ((w0 + w1) + w2) + ...: that order is part of every caller's result.  Every thread gets the sum.  A caller that
+// reduces twice through the same sh puts a barrier between the two.
+template <int NW>
+__device__ __forceinline__ double block_sum(double v, double* sh) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = sh[0];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) t += sh[w];
+    return t;
+}

@@ -74,10 +74,8 @@ __global__ __launch_bounds__(256) void clip_residual_kernel(const float* __restr
         }
         __syncthreads();
     }
-    acc = wave_sum(acc);
-    if (lane == 0) sh[wave] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    acc = block_sum<4>(acc, sh);
+    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = acc;
 }
 
 // out = clip(x, -c, c) (mask NULL) or out = x * mask (the adjoint; c unused).  One float4 per thread and pass; grid (bx, B).
@@ -182,10 +180,7 @@ __global__ __launch_bounds__(256) void stft_mag_vjp_ola_kernel(const float* __re
 __device__ __forceinline__ double block_sumsq(const float* __restrict__ v, int n, double* sh) {
     double acc = 0;
     for (int i = threadIdx.x; i < n; i += blockDim.x) acc += (double)v[i] * v[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const double t = sh[0] + sh[1] + sh[2] + sh[3];
+    const double t = block_sum<4>(acc, sh);
     __syncthreads();
     return t;
 }

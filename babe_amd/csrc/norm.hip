@@ -17,24 +17,66 @@ namespace {
 using babe_gelu::gelu_f;
 using babe_gelu::gelu_grad_f;
 
-__device__ __forceinline__ void block_reduce2(double& s0, double& s1, double* sh) {
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
+// Workgroup sums of NV values, valid in thread 0: wave_sum, one LDS slot per wave and value (sh: 4 * NV doubles), then thread 0
+// adds the slots of the blockDim.x / 64 waves in wave order, from zero.  (Not common.h's block_sum<4>: counting the waves at
+// run time is the form the two streaming kernels below were measured in, and unrolling changes their instruction mix.)
+template <int NV>
+__device__ __forceinline__ void block_reduce(double (&v)[NV], double* sh) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) v[k] = wave_sum(v[k]);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) {
-        sh[wave * 2] = s0;
-        sh[wave * 2 + 1] = s1;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) sh[wave * NV + k] = v[k];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        double a = 0, b = 0;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) v[k] = 0;
         for (int w = 0; w < (int)(blockDim.x >> 6); ++w) {
-            a += sh[w * 2];
-            b += sh[w * 2 + 1];
+#pragma unroll
+            for (int k = 0; k < NV; ++k) v[k] += sh[w * NV + k];
         }
-        s0 = a;
-        s1 = b;
     }
+}
+
+// The one GroupNorm finalize: (sum, sum of squares) of a group of n elements -> mean, unbiased std (variance clamped at 0) and
+// r = 1 / (std + eps).  gn_partial_kernel<true>, gn_finalize_kernel and scale_gelu_fin_kernel agree bit for bit through it.
+struct GnStat {
+    float mean, sd, r;
+};
+__device__ __forceinline__ GnStat gn_stat(double s0, double s1, long n, float eps) {
+    const double mean = s0 / (double)n;
+    double var = (s1 - (double)n * mean * mean) / (double)(n - 1);
+    if (var < 0) var = 0;
+    const float sd = (float)sqrt(var);
+    return {(float)mean, sd, 1.f / (sd + eps)};
+}
+__device__ __forceinline__ void gn_stat_store(float* __restrict__ stats, int bg, const GnStat st) {
+    stats[bg * 3 + 0] = st.mean;
+    stats[bg * 3 + 1] = st.sd;
+    stats[bg * 3 + 2] = st.r;
+}
+
+// the two sums of a 32-lane half-wave, to every lane of it
+__device__ __forceinline__ void half_wave_sum2(double& s0, double& s1) {
+#pragma unroll
+    for (int o = 16; o >= 1; o >>= 1) {
+        s0 += __shfl_xor(s0, o, 32);
+        s1 += __shfl_xor(s1, o, 32);
+    }
+}
+// The S partial pairs of a group, pairs row ... row + S - 1 of part, added by one half-wave: lane sub takes sub, sub + 32, ... in
+// that order, then the shuffles.  P: const double*, or const volatile double* for pairs that other workgroups of the same
+// launch wrote.
+template <typename P>
+__device__ __forceinline__ void gn_part_sum32(P part, long row, int S, int sub, double& s0, double& s1) {
+    s0 = 0, s1 = 0;
+    for (int q = sub; q < S; q += 32) {
+        s0 += part[(row + q) * 2];
+        s1 += part[(row + q) * 2 + 1];
+    }
+    half_wave_sum2(s0, s1);
 }
 
 // grid: (S, B*G).  FUSED: the workgroup that finishes a (b, g) group LAST also does gn_finalize's work for it (same reduction
@@ -84,10 +126,11 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
             s1 += v * v;
         }
     }
-    block_reduce2(s0, s1, sh);
+    double sum[2] = {s0, s1};
+    block_reduce(sum, sh);
     if (threadIdx.x == 0) {
-        part[(bg * S + s) * 2] = s0;
-        part[(bg * S + s) * 2 + 1] = s1;
+        part[(bg * S + s) * 2] = sum[0];
+        part[(bg * S + s) * 2 + 1] = sum[1];
     }
     if constexpr (FUSED) {
         if (threadIdx.x == 0) {
@@ -103,26 +146,12 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float* __restrict
         const int b = (int)(bg / G), g = (int)(bg % G);
         if (threadIdx.x < 32) {
             const volatile double* vp = part;                  // written by other workgroups of THIS launch: not through a stale L1 line
-            double t0 = 0, t1 = 0;
-            for (int q = threadIdx.x; q < S; q += 32) {
-                t0 += vp[(bg * S + q) * 2];
-                t1 += vp[(bg * S + q) * 2 + 1];
-            }
-#pragma unroll
-            for (int o = 16; o >= 1; o >>= 1) {
-                t0 += __shfl_xor(t0, o, 32);
-                t1 += __shfl_xor(t1, o, 32);
-            }
+            double t0, t1;
+            gn_part_sum32(vp, bg * S, S, threadIdx.x, t0, t1);
             if (threadIdx.x == 0) {
-                const double mean = t0 / (double)n;
-                double var = (t1 - (double)n * mean * mean) / (double)(n - 1);
-                if (var < 0) var = 0;
-                const float sd = (float)sqrt(var);
-                const float r = 1.f / (sd + eps);
-                stats[(b * G + g) * 3 + 0] = (float)mean;
-                stats[(b * G + g) * 3 + 1] = sd;
-                stats[(b * G + g) * 3 + 2] = r;
-                r_sh = r;
+                const GnStat st = gn_stat(t0, t1, n, eps);
+                gn_stat_store(stats, b * G + g, st);
+                r_sh = st.r;
             }
         }
         __syncthreads();
@@ -144,26 +173,12 @@ __global__ void gn_finalize_kernel(const double* __restrict__ part, const float*
     // S dependent-latency loads on 8 lanes made this tiny kernel take 8 us)
     const int sub = threadIdx.x & 31;
     for (int g = threadIdx.x >> 5; g < G; g += blockDim.x >> 5) {
-        double s0 = 0, s1 = 0;
-        for (int s = sub; s < S; s += 32) {
-            s0 += part[((long)(b * G + g) * S + s) * 2];
-            s1 += part[((long)(b * G + g) * S + s) * 2 + 1];
-        }
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) {
-            s0 += __shfl_xor(s0, o, 32);
-            s1 += __shfl_xor(s1, o, 32);
-        }
+        double s0, s1;
+        gn_part_sum32(part, (long)(b * G + g) * S, S, sub, s0, s1);
         if (sub != 0) continue;
-        const double mean = s0 / (double)n;
-        double var = (s1 - (double)n * mean * mean) / (double)(n - 1);
-        if (var < 0) var = 0;
-        const float sd = (float)sqrt(var);
-        const float r = 1.f / (sd + eps);
-        stats[(b * G + g) * 3 + 0] = (float)mean;
-        stats[(b * G + g) * 3 + 1] = sd;
-        stats[(b * G + g) * 3 + 2] = r;
-        rstd_sh[g] = r;
+        const GnStat st = gn_stat(s0, s1, n, eps);
+        gn_stat_store(stats, b * G + g, st);
+        rstd_sh[g] = st.r;
     }
     __syncthreads();
     const int cg = C / G;
@@ -224,26 +239,14 @@ __global__ __launch_bounds__(256) void scale_gelu_fin_kernel(const float* __rest
             t0 += red_sh[(threadIdx.x + 32 * j) * 2];
             t1 += red_sh[(threadIdx.x + 32 * j) * 2 + 1];
         }
-#pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) {
-            t0 += __shfl_xor(t0, o, 32);
-            t1 += __shfl_xor(t1, o, 32);
-        }
+        half_wave_sum2(t0, t1);
         if (threadIdx.x == 0) {
-            const double mean = t0 / (double)n;
-            double var = (t1 - (double)n * mean * mean) / (double)(n - 1);
-            if (var < 0) var = 0;
-            const float sd = (float)sqrt(var);
-            const float r = 1.f / (sd + eps);
-            const float scv = gamma[c] * (film[(long)b * film_bs + c] + 1.f) * r;
+            const GnStat st = gn_stat(t0, t1, n, eps);
+            const float scv = gamma[c] * (film[(long)b * film_bs + c] + 1.f) * st.r;
             sc_sh = scv;
             if (blockIdx.x == 0) {
                 scale[b * C + c] = scv;
-                if (c == g * cg) {
-                    stats[(b * G + g) * 3 + 0] = (float)mean;
-                    stats[(b * G + g) * 3 + 1] = sd;
-                    stats[(b * G + g) * 3 + 2] = r;
-                }
+                if (c == g * cg) gn_stat_store(stats, b * G + g, st);
             }
         }
     }
@@ -317,7 +320,7 @@ template <bool GELU>
 __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __restrict__ x, const float* __restrict__ dadu,
                                                              const float* __restrict__ scale,
                                                              double* __restrict__ part, int C, int G, long hw, int S) {
-    __shared__ double sh[8];
+    __shared__ double sh[4];
     const int s = blockIdx.x;
     const int bg = blockIdx.y;
     const int b = bg / G, g = bg % G;
@@ -328,7 +331,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
     long end = beg + chunk;
     if (end > n) end = n;
     const long base = ((long)b * C + (long)g * cg) * hw;
-    double s0 = 0, s1 = 0;
+    double s0 = 0;
     // hw is a multiple of 4 (checked on the host) so a float4 never straddles two channels.  Channel by channel: the
     // scale is a scalar of the inner loop and there is no 64-bit division per element (there was: i / hw).
     if (beg < end) {
@@ -362,8 +365,9 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const float* __rest
             s0 += (double)sc * sc_sum;
         }
     }
-    block_reduce2(s0, s1, sh);
-    if (threadIdx.x == 0) part[(long)bg * S + s] = s0;
+    double sum[1] = {s0};
+    block_reduce(sum, sh);
+    if (threadIdx.x == 0) part[(long)bg * S + s] = sum[0];
 }
 
 // grid: (blocks, C, B)
@@ -438,6 +442,12 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const float* __restri
     }
 }
 
+// workgroups along a plane of hw elements for the float4 grid-stride kernels: four float4 per thread, 1..64
+int plane_blocks(long hw) {
+    const int bx = cdiv(hw / 4, 256 * 4);
+    return bx < 1 ? 1 : bx > 64 ? 64 : bx;
+}
+
 }  // namespace
 
 extern "C" int babe_gn_partial(const float* x, double* part, int B, int G, long n, int S, void* stream) {
@@ -478,9 +488,7 @@ extern "C" int babe_scale_gelu(const float* x, const float* scale, float* a, int
     BABE_CHECK_ARG(x && scale && a && B > 0 && C > 0 && hw > 0, "scale_gelu: bad arguments");
     BABE_CHECK_ARG(hw % 4 == 0, "scale_gelu: plane size %ld not a multiple of 4", hw);
     BabeProfScope prof(BABE_SLOT_SCALE_GELU, 8.0 * B * C * (double)hw, 0, 0, stream);
-    int bx = cdiv(hw / 4, 256 * 4);
-    if (bx < 1) bx = 1;
-    if (bx > 64) bx = 64;
+    const int bx = plane_blocks(hw);
     hipLaunchKernelGGL(scale_gelu_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, scale, a, C, hw);
     BABE_LAUNCH_CHECK();
     return BABE_OK;
@@ -494,9 +502,7 @@ extern "C" int babe_scale_gelu_fin(const float* x, const double* part, const flo
     BABE_CHECK_ARG(x && part && gamma && film && stats && scale && a && B > 0 && C > 0 && hw > 0 && S > 0, "scale_gelu_fin: bad arguments");
     BABE_CHECK_ARG(hw % 4 == 0 && G <= 64 && C % G == 0, "scale_gelu_fin: hw=%ld C=%d G=%d unsupported", hw, C, G);
     BabeProfScope prof(BABE_SLOT_SCALE_GELU, 8.0 * B * C * (double)hw, 0, 0, stream);
-    int bx = cdiv(hw / 4, 256 * 4);
-    if (bx < 1) bx = 1;
-    if (bx > 64) bx = 64;
+    const int bx = plane_blocks(hw);
     const long n = (long)(C / G) * hw;
     hipLaunchKernelGGL(scale_gelu_fin_kernel, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, part, gamma, film, film_bs,
                        stats, scale, a, C, G, hw, n, S, eps);
@@ -521,27 +527,30 @@ extern "C" int babe_scale_gelu_units(const float* x, const float* scale, void* a
     return BABE_OK;
 }
 
-extern "C" int babe_gn_bwd_partial(const float* x, const float* da, const float* scale, double* part, int B, int C,
-                                   int G, long hw, int S, void* stream) {
+static int gn_bwd_partial_launch(bool gelu, const float* x, const float* da, const float* scale, double* part, int B, int C, int G,
+                                 long hw, int S, void* stream) {
     BABE_CHECK_ARG(x && da && scale && part, "gn_bwd_partial: null pointer");
     BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_partial: hw=%ld C=%d G=%d unsupported", hw, C, G);
     BabeProfScope prof(BABE_SLOT_GN_BWD_PARTIAL, 8.0 * B * C * (double)hw, 0, 0, stream);
-    hipLaunchKernelGGL(gn_bwd_partial_kernel<true>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
-                       part, C, G, hw, S);
+    if (gelu)
+        hipLaunchKernelGGL(gn_bwd_partial_kernel<true>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale, part, C, G,
+                           hw, S);
+    else
+        hipLaunchKernelGGL(gn_bwd_partial_kernel<false>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale, part, C, G,
+                           hw, S);
     BABE_LAUNCH_CHECK();
     return BABE_OK;
+}
+
+extern "C" int babe_gn_bwd_partial(const float* x, const float* da, const float* scale, double* part, int B, int C,
+                                   int G, long hw, int S, void* stream) {
+    return gn_bwd_partial_launch(true, x, da, scale, part, B, C, G, hw, S, stream);
 }
 
 /* babe_gn_bwd_partial of GroupNorm * FiLM without the GELU (forward a = x * scale; the time-attention branch's norm2) */
 extern "C" int babe_gn_bwd_partial_nogelu(const float* x, const float* da, const float* scale, double* part, int B, int C,
                                           int G, long hw, int S, void* stream) {
-    BABE_CHECK_ARG(x && da && scale && part, "gn_bwd_partial_nogelu: null pointer");
-    BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_partial_nogelu: hw=%ld C=%d G=%d unsupported", hw, C, G);
-    BabeProfScope prof(BABE_SLOT_GN_BWD_PARTIAL, 8.0 * B * C * (double)hw, 0, 0, stream);
-    hipLaunchKernelGGL(gn_bwd_partial_kernel<false>, dim3(S, B * G), dim3(256), 0, (hipStream_t)stream, x, da, scale,
-                       part, C, G, hw, S);
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return gn_bwd_partial_launch(false, x, da, scale, part, B, C, G, hw, S, stream);
 }
 
 static int gn_bwd_apply_launch(bool gelu, const float* acc, float ca, float cb, const float* x, const float* da, const float* gy, const float* scale,
@@ -550,9 +559,7 @@ static int gn_bwd_apply_launch(bool gelu, const float* acc, float ca, float cb, 
     BABE_CHECK_ARG(x && da && scale && stats && part && gx, "gn_bwd_apply: null pointer");
     BABE_CHECK_ARG(hw % 4 == 0 && C % G == 0, "gn_bwd_apply: hw=%ld C=%d G=%d unsupported", hw, C, G);
     BabeProfScope prof(BABE_SLOT_GN_BWD_APPLY, ((gy ? 16.0 : 12.0) + (acc ? 4.0 : 0.0)) * B * C * (double)hw, 0, 0, stream);
-    int bx = cdiv(hw / 4, 256 * 4);
-    if (bx < 1) bx = 1;
-    if (bx > 64) bx = 64;
+    const int bx = plane_blocks(hw);
     if (gelu)
         hipLaunchKernelGGL(gn_bwd_apply_kernel<true>, dim3(bx, C, B), dim3(256), 0, (hipStream_t)stream, x, da, gy, scale, stats,
                            part, gx, rbeta, C, G, hw, S, eps, acc, ca, cb);

@@ -27,10 +27,8 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
         const double v = p[i];
         acc += v * v;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    acc = block_sum<4>(acc, sh);
+    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = acc;
 }
 
 // Observation-noise regularisation (posterior_sampling.SNR_observations, testing/blind_bwe_sampler.py:80-86 and :542-548):
@@ -41,31 +39,18 @@ __global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restr
 __global__ __launch_bounds__(1024) void add_obs_noise_kernel(float* __restrict__ y, long y_bs, const float* __restrict__ noise,
                                                              long n_bs, float snr, long n) {
     __shared__ double sh[16];
-    __shared__ double res;
     float* p = y + (long)blockIdx.x * y_bs;
     const float* q = noise + (long)blockIdx.x * n_bs;
-    auto block_sum = [&](double v) {
-        v = wave_sum(v);
-        __syncthreads();                                   // (sh / res of the previous call are no longer read)
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double t = 0;
-            for (int w = 0; w < 16; ++w) t += sh[w];
-            res = t;
-        }
-        __syncthreads();
-        return res;
-    };
     double acc = 0;
     for (long i = threadIdx.x; i < n; i += 1024) acc += (double)p[i];
-    const double mean = block_sum(acc) / (double)n;
+    const double mean = block_sum<16>(acc, sh) / (double)n;
     acc = 0;
     for (long i = threadIdx.x; i < n; i += 1024) {
         const double d = (double)p[i] - mean;
         acc += d * d;
     }
-    const float var = (float)(block_sum(acc) / (double)(n - 1));
+    __syncthreads();                                       // (the slots of the first sum are no longer read)
+    const float var = (float)(block_sum<16>(acc, sh) / (double)(n - 1));
     const float sigma = sqrtf(var / snr);
     for (long i = threadIdx.x; i < n; i += 1024) p[i] = p[i] + sigma * q[i];
 }

@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ fr, 
                                                   const float* __restrict__ y, long y_bs, float* __restrict__ out,
                                                   long out_bs, double* __restrict__ part, int nblk, int L, int n,
                                                   int frames) {
-    __shared__ double sh[8];
+    __shared__ double sh[4];
     const int b = blockIdx.y;
     const int hop = n >> 1;
     const float* f = fr + (long)b * frames * n;
@@ -88,11 +88,8 @@ __global__ __launch_bounds__(256) void ola_kernel(const float* __restrict__ fr, 
         out[(long)b * out_bs + i] = v;
     }
     if (part) {
-        acc = wave_sum(acc);
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if (lane == 0) sh[wave] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+        acc = block_sum<4>(acc, sh);
+        if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = acc;
     }
 }
 
@@ -138,10 +135,8 @@ __global__ __launch_bounds__(256) void stft_dist_partial_kernel(const float* __r
         float mx;
         acc += (double)stft_dist_term(x2[i], r2[i], w[i % nbins], mode, mx);
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    acc = block_sum<4>(acc, sh);
+    if (threadIdx.x == 0) part[(long)b * nblk + blockIdx.x] = acc;
 }
 // G = dD/dX (real, imag); shared: one D over the whole batch (the reference's coupling), else one per batch item
 __global__ __launch_bounds__(256) void stft_dist_grad_kernel(const float* __restrict__ X, const float* __restrict__ R,

@@ -404,7 +404,8 @@ __global__ __launch_bounds__(256) void rows_sum_kernel(const float* __restrict__
     out[i] = beta == 0.f ? v : beta * out[i] + v;
 }
 
-// grid (C, B)
+// grid (C, B).  GELU = false: a = z * scale without the GELU (norm2 / affine2 of the attention branch); scale is not read.
+template <bool GELU>
 __global__ __launch_bounds__(256) void gn_param_kernel(const float* __restrict__ z, const float* __restrict__ da,
                                                        const float* __restrict__ scale, const float* __restrict__ stats,
                                                        const float* __restrict__ gamma, const float* __restrict__ film,
@@ -412,12 +413,16 @@ __global__ __launch_bounds__(256) void gn_param_kernel(const float* __restrict__
                                                        float* __restrict__ dfilm, long dfilm_bs, int C, int G, long hw) {
     __shared__ double sh[256];
     const int c = blockIdx.x, b = blockIdx.y;
-    const float sc = scale[(long)b * C + c];
     const long base = ((long)b * C + c) * hw;
     double s = 0;
-    for (long i = threadIdx.x; i < hw; i += 256) {
-        const float x = z[base + i];
-        s += (double)(da[base + i] * babe_gelu::gelu_grad_f(x * sc)) * (double)x;
+    if (GELU) {
+        const float sc = scale[(long)b * C + c];
+        for (long i = threadIdx.x; i < hw; i += 256) {
+            const float x = z[base + i];
+            s += (double)(da[base + i] * babe_gelu::gelu_grad_f(x * sc)) * (double)x;
+        }
+    } else {
+        for (long i = threadIdx.x; i < hw; i += 256) s += (double)da[base + i] * (double)z[base + i];
     }
     s = block_sum_d(s, sh);
     if (threadIdx.x == 0) {
@@ -570,15 +575,34 @@ extern "C" int babe_rows_sum(const float* rows, long rows_bs, int B, long n, flo
     return BABE_OK;
 }
 
+static int gn_param_launch(bool gelu, const float* z, const float* da, const float* scale, const float* stats, const float* gamma,
+                           const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
+                           long dfilm_bs, int B, int C, int G, long hw, void* stream) {
+    BABE_CHECK_ARG(z && da && (scale || !gelu) && stats && gamma && film_aff && dgamma_rows && dfilm && B > 0 && C > 0 && G > 0 &&
+                   C % G == 0 && hw > 0, "gn_param_grad: bad arguments");
+    if (gelu)
+        hipLaunchKernelGGL(gn_param_kernel<true>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, z, da, scale, stats, gamma, film_aff,
+                           film_bs, cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, C, G, hw);
+    else
+        hipLaunchKernelGGL(gn_param_kernel<false>, dim3(C, B), dim3(256), 0, (hipStream_t)stream, z, da, scale, stats, gamma, film_aff,
+                           film_bs, cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, C, G, hw);
+    BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
+
 extern "C" int babe_gn_param_grad(const float* z, const float* da, const float* scale, const float* stats, const float* gamma,
                                   const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
                                   long dfilm_bs, int B, int C, int G, long hw, void* stream) {
-    BABE_CHECK_ARG(z && da && scale && stats && gamma && film_aff && dgamma_rows && dfilm && B > 0 && C > 0 && G > 0 && C % G == 0 &&
-                   hw > 0, "gn_param_grad: bad arguments");
-    hipLaunchKernelGGL(gn_param_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, z, da, scale, stats, gamma, film_aff, film_bs,
-                       cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, C, G, hw);
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return gn_param_launch(true, z, da, scale, stats, gamma, film_aff, film_bs, cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, B, C, G, hw,
+                           stream);
+}
+
+/* babe_gn_param_grad for a = z * scale without the GELU (norm2 / affine2 of the attention branch) */
+extern "C" int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stats, const float* gamma,
+                                         const float* film_aff, long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm,
+                                         long dfilm_bs, int B, int C, int G, long hw, void* stream) {
+    return gn_param_launch(false, z, da, nullptr, stats, gamma, film_aff, film_bs, cs, dgamma_rows, dg_bs, dfilm, dfilm_bs, B, C, G, hw,
+                           stream);
 }
 
 extern "C" long babe_linear_bwd_workspace(int B, int K, int J) {

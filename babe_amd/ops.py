@@ -209,9 +209,28 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     return (part, S) if a.stat_mode else None
 
 
-def _splits(n, B, G):
-    s = max(1, min(64, n // 16384))
-    return int(s)
+def _splits(n):
+    """Split count of a GroupNorm group of n elements.  The same rule as Ctx::splits in csrc/unet_engine.hip, the only other
+    place it lives."""
+    return int(max(1, min(64, n // 16384)))
+
+
+def _gn_buffers(x, G, fused=None, vjp=False):
+    """(n, S, part, stats, scale) of a GroupNorm pass over x [B,C,F,T]: the group size, the split count, the float64 partial sums
+    (S pairs per group; S values for the VJP) and, for the forward, new stats [B,G,3] and scale [B,C].  fused=(part, S): the
+    partial sums a conv already formed."""
+    B, Cc, F, T = x.shape
+    n = (Cc // G) * F * T
+    if fused is not None:
+        part, S = fused
+    else:
+        S = _splits(n)
+        part = torch.empty(B * G * S * (1 if vjp else 2), device=x.device, dtype=torch.float64)
+    if vjp:
+        return n, S, part, None, None
+    stats = torch.empty(B, G, 3, device=x.device, dtype=torch.float32)
+    scale = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
+    return n, S, part, stats, scale
 
 
 _GN_TICKETS = {}
@@ -234,11 +253,7 @@ def gn_scale(x, gamma, film, G=8, eps=1e-7):
     workgroup of a group finalises it; bit-identical, measured slower on the whole job - see gn_fused in forms.py)."""
     assert x.is_contiguous()
     B, Cc, F, T = x.shape
-    n = (Cc // G) * F * T
-    S = _splits(n, B, G)
-    part = torch.empty(B * G * S * 2, device=x.device, dtype=torch.float64)
-    stats = torch.empty(B, G, 3, device=x.device, dtype=torch.float32)
-    scale = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
+    n, S, part, stats, scale = _gn_buffers(x, G)
     L = lib()
     assert film.stride(1) == 1
     if FORMS.gn_fused:
@@ -255,28 +270,16 @@ def gn_scale_gelu(x, gamma, film, out, G=8, eps=1e-7, fused=None):
     """gn_scale + scale_gelu with the finalize folded into the GELU kernel's prologue: out = gelu(x * scale); returns
     (stats [B,G,3], scale [B,C]) for the VJP.  Bit-identical to gn_scale followed by scale_gelu (BABE_GELU_FIN=0).
     fused=(part, S): the partial sums of x already formed by the conv that wrote it (conv2d(fwd_stat=)): no pass over x for them."""
-    if fused is not None:
-        assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and film.stride(1) == 1
-        B, Cc, F, T = x.shape
-        part, S = fused
-        stats = torch.empty(B, G, 3, device=x.device, dtype=torch.float32)
-        scale = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
-        check(lib().babe_scale_gelu_fin(ptr(x), ptr(part), ptr(gamma), ptr(film), film.stride(0), ptr(stats), ptr(scale), ptr(out),
-                                        B, Cc, G, F * T, S, eps, stream()), "scale_gelu_fin")
-        return stats, scale
-    if not FORMS.gelu_fin:
+    if fused is None and not FORMS.gelu_fin:
         stats, scale = gn_scale(x, gamma, film, G, eps)
         scale_gelu(x, scale, out)
         return stats, scale
     assert x.is_contiguous() and out.is_contiguous() and out.shape == x.shape and film.stride(1) == 1
     B, Cc, F, T = x.shape
-    n = (Cc // G) * F * T
-    S = _splits(n, B, G)
-    part = torch.empty(B * G * S * 2, device=x.device, dtype=torch.float64)
-    stats = torch.empty(B, G, 3, device=x.device, dtype=torch.float32)
-    scale = torch.empty(B, Cc, device=x.device, dtype=torch.float32)
+    n, S, part, stats, scale = _gn_buffers(x, G, fused)
     L = lib()
-    check(L.babe_gn_partial(ptr(x), ptr(part), B, G, n, S, stream()), "gn_partial")
+    if fused is None:
+        check(L.babe_gn_partial(ptr(x), ptr(part), B, G, n, S, stream()), "gn_partial")
     check(L.babe_scale_gelu_fin(ptr(x), ptr(part), ptr(gamma), ptr(film), film.stride(0), ptr(stats), ptr(scale), ptr(out),
                                 B, Cc, G, F * T, S, eps, stream()), "scale_gelu_fin")
     return stats, scale
@@ -328,28 +331,27 @@ def conv2d_units(au, pc, out, Cin, dil=1, res=None, oscale=None, alpha=1.0, rbet
     return out
 
 
-def gn_bwd(x, da, gy, scale, stats, gx, rbeta, G=8, eps=1e-7, merge=None, fused=None):
+def gn_bwd(x, da, gy, scale, stats, gx, rbeta, G=8, eps=1e-7, merge=None, fused=None, gelu=True):
     """gx = rbeta*gy + GN/FiLM/GELU input-VJP of da (gx may alias gy; da is only read).
     merge=(acc, ca, cb): gx = ca*acc + cb*(that result) in the same pass (a block's VJP tail, babe_gn_bwd_apply_merge).
-    fused=(part, S): the partial sums already formed by the conv that wrote da (conv2d(..., vjp_stat=)): no babe_gn_bwd_partial."""
+    fused=(part, S): the partial sums already formed by the conv that wrote da (conv2d(..., vjp_stat=)): no babe_gn_bwd_partial.
+    gelu=False: the VJP of a = x*scale, the babe_gn_bwd_*_nogelu entry points (gn_bwd_nogelu; neither merge nor fused)."""
     B, Cc, F, T = x.shape
     assert x.is_contiguous() and da.is_contiguous() and gx.is_contiguous() and (gy is None or gy.is_contiguous())
-    n = (Cc // G) * F * T
+    assert gelu or (merge is None and fused is None)
+    n, S, part, _, _ = _gn_buffers(x, G, fused, vjp=True)
     L = lib()
-    if fused is not None:
-        part, S = fused
-    else:
-        S = _splits(n, B, G)
-        part = torch.empty(B * G * S, device=x.device, dtype=torch.float64)
-        check(L.babe_gn_bwd_partial(ptr(x), ptr(da), ptr(scale), ptr(part), B, Cc, G, F * T, S, stream()), "gn_bwd_partial")
+    partial, apply = (L.babe_gn_bwd_partial, L.babe_gn_bwd_apply) if gelu else (L.babe_gn_bwd_partial_nogelu, L.babe_gn_bwd_apply_nogelu)
+    if fused is None:
+        check(partial(ptr(x), ptr(da), ptr(scale), ptr(part), B, Cc, G, F * T, S, stream()), "gn_bwd_partial")
     if merge is not None:
         acc, ca, cb = merge
         assert acc.is_contiguous() and acc.shape == x.shape
         check(L.babe_gn_bwd_apply_merge(ptr(x), ptr(da), ptr(gy), ptr(scale), ptr(stats), ptr(part), ptr(gx), rbeta, B, Cc, G,
                                         F * T, S, eps, stream(), ptr(acc), ca, cb), "gn_bwd_apply_merge")
         return gx
-    check(L.babe_gn_bwd_apply(ptr(x), ptr(da), ptr(gy), ptr(scale), ptr(stats), ptr(part), ptr(gx), rbeta, B, Cc, G,
-                              F * T, S, eps, stream()), "gn_bwd_apply")
+    check(apply(ptr(x), ptr(da), ptr(gy), ptr(scale), ptr(stats), ptr(part), ptr(gx), rbeta, B, Cc, G, F * T, S, eps, stream()),
+          "gn_bwd_apply")
     return gx
 
 
@@ -419,16 +421,7 @@ def rff(cnoise, freq):
 
 def gn_bwd_nogelu(x, da, gy, scale, stats, gx, rbeta, G=8, eps=1e-7):
     """gx = rbeta*gy + input-VJP of a = x*scale (BiasFreeGroupNorm * FiLM, no GELU: the attention branch's norm2) for da."""
-    B, Cc, F, T = x.shape
-    assert x.is_contiguous() and da.is_contiguous() and gx.is_contiguous() and (gy is None or gy.is_contiguous())
-    n = (Cc // G) * F * T
-    S = _splits(n, B, G)
-    part = torch.empty(B * G * S, device=x.device, dtype=torch.float64)
-    L = lib()
-    check(L.babe_gn_bwd_partial_nogelu(ptr(x), ptr(da), ptr(scale), ptr(part), B, Cc, G, F * T, S, stream()), "gn_bwd_partial_nogelu")
-    check(L.babe_gn_bwd_apply_nogelu(ptr(x), ptr(da), ptr(gy), ptr(scale), ptr(stats), ptr(part), ptr(gx), rbeta, B, Cc, G, F * T,
-                                     S, eps, stream()), "gn_bwd_apply_nogelu")
-    return gx
+    return gn_bwd(x, da, gy, scale, stats, gx, rbeta, G, eps, gelu=False)
 
 
 def attn_buckets(T, num_buckets=32, max_distance=64):
@@ -572,25 +565,23 @@ def rows_sum(rows, out, beta=0.0):
 
 def gn_param_grad(z, da, scale, stats, gamma, film_aff, dgamma_rows, dfilm, cs=1.0, G=8):
     """GroupNorm * FiLM parameter gradients of a = gelu(z * scale) given da (babe_gn_param_grad): dgamma_rows[b, c] (summed over b
-    later by rows_sum) and dfilm[b, c] (the gradient of the FiLM affine output); cs scales da."""
+    later by rows_sum) and dfilm[b, c] (the gradient of the FiLM affine output); cs scales da.
+    scale=None: a = z * scale without the GELU (babe_gn_param_grad_nogelu, which does not read scale)."""
     B, Cc, F, T = z.shape
     assert z.is_contiguous() and da.is_contiguous() and da.shape == z.shape
     assert film_aff.stride(1) == 1 and dgamma_rows.stride(1) == 1 and dfilm.stride(1) == 1
     assert dgamma_rows.shape == (B, Cc) and dfilm.shape == (B, Cc)
-    check(lib().babe_gn_param_grad(ptr(z), ptr(da), ptr(scale), ptr(stats), ptr(gamma), ptr(film_aff), film_aff.stride(0), cs,
-                                   ptr(dgamma_rows), dgamma_rows.stride(0), ptr(dfilm), dfilm.stride(0), B, Cc, G, F * T, stream()),
-          "gn_param_grad")
+    tail = (ptr(stats), ptr(gamma), ptr(film_aff), film_aff.stride(0), cs, ptr(dgamma_rows), dgamma_rows.stride(0), ptr(dfilm),
+            dfilm.stride(0), B, Cc, G, F * T, stream())
+    if scale is None:
+        check(lib().babe_gn_param_grad_nogelu(ptr(z), ptr(da), *tail), "gn_param_grad_nogelu")
+    else:
+        check(lib().babe_gn_param_grad(ptr(z), ptr(da), ptr(scale), *tail), "gn_param_grad")
 
 
 def gn_param_grad_nogelu(z, da, stats, gamma, film_aff, dgamma_rows, dfilm, cs=1.0, G=8):
     """gn_param_grad for a = z * scale without the GELU (babe_gn_param_grad_nogelu: norm2 / affine2 of the attention branch)."""
-    B, Cc, F, T = z.shape
-    assert z.is_contiguous() and da.is_contiguous() and da.shape == z.shape
-    assert film_aff.stride(1) == 1 and dgamma_rows.stride(1) == 1 and dfilm.stride(1) == 1
-    assert dgamma_rows.shape == (B, Cc) and dfilm.shape == (B, Cc)
-    check(lib().babe_gn_param_grad_nogelu(ptr(z), ptr(da), ptr(stats), ptr(gamma), ptr(film_aff), film_aff.stride(0), cs,
-                                          ptr(dgamma_rows), dgamma_rows.stride(0), ptr(dfilm), dfilm.stride(0), B, Cc, G, F * T,
-                                          stream()), "gn_param_grad_nogelu")
+    gn_param_grad(z, da, None, stats, gamma, film_aff, dgamma_rows, dfilm, cs, G)
 
 
 def scale_channels(x, scale, out):

@@ -286,10 +286,12 @@ def test_groupnorm_film_gelu_fwd_bwd(ops, B, C, Fq, T):
 def test_gn_stats_one_launch_equals_two_launches(ops, monkeypatch):
     """gn_partial_kernel<true> (the last workgroup of a group finalises it: one launch) against babe_gn_partial +
     babe_gn_finalize: bit-identical statistics and scales, over shapes with different split counts on the SAME ticket buffer
-    (every call must leave its tickets at zero), and from two streams at once."""
+    (every call must leave its tickets at zero), and from two streams at once.  Split counts 1, 2, 5, 7 and, where lanes of the
+    32-lane sum add two entries, 40 (a partly filled second round) and 64 (the workload's)."""
     from babe_amd.forms import FORMS
     g = torch.Generator().manual_seed(77)
-    shapes = [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64), (2, 64, 16, 256)]
+    shapes = [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64), (1, 64, 160, 512), (1, 64, 256, 512),
+              (2, 64, 16, 256)]
     for rep in range(2):
         for (B, C, F, T) in shapes:
             x = torch.randn(B, C, F, T, generator=g).cuda()
@@ -317,11 +319,12 @@ def test_gn_stats_one_launch_equals_two_launches(ops, monkeypatch):
     assert all(torch.equal(o[0], ref[0]) and torch.equal(o[1], ref[1]) for o in outs)
 
 def test_scale_gelu_with_folded_finalize_is_bit_identical(ops, monkeypatch):
-    """babe_scale_gelu_fin (gn_finalize's work in the GELU kernel's prologue) against gn_scale + scale_gelu."""
+    """babe_scale_gelu_fin (gn_finalize's work in the GELU kernel's prologue) against gn_scale + scale_gelu; the last two shapes
+    have 40 and 64 splits (lanes of the 32-lane sum add two entries)."""
     from babe_amd.forms import FORMS
     monkeypatch.setattr(FORMS, "gelu_fin", True)
     g = torch.Generator().manual_seed(78)
-    for (B, C, F, T) in [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64)]:
+    for (B, C, F, T) in [(2, 64, 16, 256), (1, 96, 24, 64), (2, 128, 40, 128), (1, 256, 56, 64), (1, 64, 160, 512), (1, 64, 256, 512)]:
         x = torch.randn(B, C, F, T, generator=g).cuda()
         gamma = (torch.rand(C, generator=g) + 0.5).cuda()
         film = torch.randn(B, C, generator=g).cuda()
@@ -919,7 +922,7 @@ def test_f45_epilogue_forms_the_groupnorm_vjp_partial_sums(ops, monkeypatch):
         part, S = fs
         got = part.view(B, 8, S).sum(-1)
         n = (Cc // 8) * Fq * T
-        Sp = ops._splits(n, B, 8)
+        Sp = ops._splits(n)
         ref = torch.empty(B * 8 * Sp, device="cuda", dtype=torch.float64)
         from babe_amd._lib import check, ptr, stream
         check(lib().babe_gn_bwd_partial(ptr(z), ptr(da0), ptr(scale), ptr(ref), B, Cc, 8, Fq * T, Sp, stream()), "gn_bwd_partial")
