@@ -151,6 +151,7 @@ SIGS = {
     "babe_prof_dispatch_counts": (_I, [_P, _I]),
     "babe_prof_timeline": (_L, [_P, _P, _P, _P, _P, _L]),
     "babe_prof_pending": (_L, []),
+    "babe_gn_splits": (_L, [_L]),
     "babe_gn_partial": (_I, [_P, _P, _I, _I, _L, _I, _P]),
     "babe_gn_stats": (_I, [_P, _P, _P, _P, _P, _L, _P, _P, _I, _I, _I, _L, _I, _F, _P]),
     "babe_gn_finalize": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _I, _L, _I, _F, _P]),

@@ -89,6 +89,21 @@ def check(rc, what=""):
         raise BabeHipError(f"{what} failed ({rc}): {lib().babe_last_error().decode()}")
 
 
+def workspace(cache, key, nbytes, device, what, keep_all=False):
+    """The caller-owned workspace of a library entry point, as a uint8 tensor kept in the dict `cache` under `key`: the latest key
+    only, or with keep_all one buffer per key.  nbytes: a callable returning what babe_<what>_workspace_bytes says, asked when
+    the key is new; a negative size raises with the library's message."""
+    ws = cache.get(key)
+    if ws is None:
+        n = nbytes()
+        if n < 0:
+            raise BabeHipError(f"{what}_workspace_bytes failed ({n}): {lib().babe_last_error().decode()}")
+        if not keep_all:
+            cache.clear()
+        ws = cache[key] = torch.empty(n, device=device, dtype=torch.uint8)
+    return ws
+
+
 def ptr(t):
     if t is None:
         return None

@@ -23,7 +23,7 @@ import torch
 
 from . import ops
 from ._cabi import CqtBands
-from ._lib import check, lib, ptr, stream
+from ._lib import check, lib, ptr, stream, workspace
 
 
 # ----------------------------------------------------------------------------- band design
@@ -350,11 +350,8 @@ class CQT_nsgt:
 
     def _plan_call(self, name, a, b, B):
         """a / b: a device tensor or a list of per-octave tensors (passed as an array of pointers), in the entry point's order."""
-        key = (B, torch.cuda.current_stream().cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None:
-            ws = torch.empty(lib().babe_cqt_workspace_bytes(self._plan, B) // 4 + 1, device=self.device)
-            self._ws[key] = ws
+        ws = workspace(self._ws, (B, torch.cuda.current_stream().cuda_stream), lambda: lib().babe_cqt_workspace_bytes(self._plan, B),
+                       self.device, "cqt", keep_all=True)
         conv = lambda v: (C.c_void_p * len(v))(*[ptr(t) for t in v]) if isinstance(v, (list, tuple)) else ptr(v)
         check(getattr(lib(), name)(self._plan, conv(a), conv(b), ptr(ws), B, stream()), name)
 

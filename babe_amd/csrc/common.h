@@ -20,6 +20,13 @@ void babe_set_error(const char* fmt, ...);
         }                                              \
     } while (0)
 
+// a host sequencer's step: return the first status that is not BABE_OK (its message is already set)
+#define BABE_TRY(call)                                 \
+    do {                                               \
+        const int rc__ = (call);                       \
+        if (rc__ != BABE_OK) return rc__;              \
+    } while (0)
+
 #define BABE_LAUNCH_CHECK()                                                       \
     do {                                                                          \
         hipError_t e__ = hipGetLastError();                                       \

@@ -13,6 +13,7 @@
 // power-of-two rasterisation) is stated in oracle/nsgt.py and DESIGN.md; the dependency is absent from the reference tree (parity
 // unpinned, as for the Python class).
 #include "common.h"
+#include "workspace.h"
 #include "../../include/babe_hip.h"
 #include <algorithm>
 #include <cmath>
@@ -431,9 +432,9 @@ extern "C" void* babe_cqt_plan_create_ex(double fs, int audio_len, int numocts, 
             const double a = 2.0 * M_PI * (double)((k1 * n2) % L) / (double)L;
             htw[2 * (k1 * N2 + n2)] = (float)std::cos(a), htw[2 * (k1 * N2 + n2) + 1] = (float)(-std::sin(a));
         }
-    // ---- one device allocation, 256-byte aligned pieces
+    // ---- one device allocation, each table 256-byte aligned
     struct Piece { const void* h; size_t bytes; void** dst; };
-    std::vector<Piece> pieces = {
+    std::vector<Piece> tables = {
         {hc.data(), hc.size() * 4, (void**)&p->c}, {hM.data(), hM.size() * 4, (void**)&p->M}, {hwoff.data(), hwoff.size() * 4, (void**)&p->woff},
         {hl2.data(), hl2.size() * 4, (void**)&p->log2T}, {hoct.data(), hoct.size() * 4, (void**)&p->oct}, {hbin.data(), hbin.size() * 4, (void**)&p->binoct},
         {d->wg_first.data(), d->wg_first.size() * 4, (void**)&p->wg_first}, {d->wg_count.data(), d->wg_count.size() * 4, (void**)&p->wg_count},
@@ -444,7 +445,7 @@ extern "C" void* babe_cqt_plan_create_ex(double fs, int audio_len, int numocts, 
         {hwba.data(), hwba.size() * 4, (void**)&p->win_bwd_adj}, {hhpf.data(), hhpf.size() * 4, (void**)&p->hpf_irfft},
         {hw1.data(), hw1.size() * 4, (void**)&p->w1}, {hw2.data(), hw2.size() * 4, (void**)&p->w2}, {htw.data(), htw.size() * 4, (void**)&p->tw}};
     size_t total = 0;
-    for (auto& pc : pieces) total += (pc.bytes + 255) / 256 * 256;
+    for (auto& pc : tables) total += (pc.bytes + 255) / 256 * 256;
     if (hipGetDevice(&p->device) != hipSuccess || hipMalloc((void**)&p->dev, total) != hipSuccess) {
         babe_set_error("cqt_plan_create: cannot allocate %zu bytes of device tables: %s", total, hipGetErrorString(hipGetLastError()));
         delete d;
@@ -453,7 +454,7 @@ extern "C" void* babe_cqt_plan_create_ex(double fs, int audio_len, int numocts, 
     }
     p->dev_bytes = total;
     size_t off = 0;
-    for (auto& pc : pieces) {
+    for (auto& pc : tables) {
         *pc.dst = pc.bytes ? (void*)(p->dev + off) : nullptr;
         if (pc.bytes && hipMemcpy(p->dev + off, pc.h, pc.bytes, hipMemcpyHostToDevice) != hipSuccess) {
             babe_set_error("cqt_plan_create: table upload failed: %s", hipGetErrorString(hipGetLastError()));
@@ -477,22 +478,21 @@ extern "C" void babe_cqt_plan_destroy(void* plan) {
 
 extern "C" const void* babe_cqt_plan_design(const void* plan) { return plan ? static_cast<const CqtPlan*>(plan)->d : nullptr; }
 
-/* Scratch of one transform call with B clips, in bytes: spectrum [B][2][KX] + four-step intermediate [B][2][L] + band spectra
- * [B][nwin][2] (bwd / fwd_adjoint only; allocated for all so that one buffer serves every call). */
-extern "C" long babe_cqt_workspace_bytes(const void* plan, int B) {
-    if (!plan || B < 1) return -1;
-    const CqtDesign* d = static_cast<const CqtPlan*>(plan)->d;
-    return (long)B * 4 * (2 * d->KX + 2 * d->L + 2 * d->nwin) + 1024;
-}
-
 namespace {
+// scratch of one transform call with B clips, whole floats: spectrum [B][2][KX], four-step intermediate [B][2][L], band spectra
+// [B][nwin][2] (bwd / fwd_adjoint only; carved for all so that one buffer serves every call)
 struct Work { float *spec, *four, *bs; };
-Work carve(const CqtDesign* d, float* ws, int B) {
+Work carve(Carver& c, const CqtDesign* d, int B) {
     Work w;
-    w.spec = ws;
-    w.four = w.spec + (size_t)B * 2 * d->KX;
-    w.bs = w.four + (size_t)B * 2 * d->L;
+    w.spec = c.take<float>((size_t)B * 2 * d->KX);
+    w.four = c.take<float>((size_t)B * 2 * d->L);
+    w.bs = c.take<float>((size_t)B * 2 * d->nwin);
     return w;
+}
+// the entry points take no size: the caller's buffer has babe_cqt_workspace_bytes(plan, B) bytes by contract
+Work carve(const CqtDesign* d, float* ws, int B) {
+    Carver c{reinterpret_cast<char*>(ws), (size_t)-1, 4};
+    return carve(c, d, B);
 }
 int rfft(const CqtPlan* p, const float* x, float* spec, float* four, int B, void* stream) {
     const CqtDesign* d = p->d;
@@ -508,8 +508,7 @@ int synth(const CqtPlan* p, float* const* coef, const float* win, float scale, c
     const CqtDesign* d = p->d;
     babe_cqt_bands b;
     fill_bands(p, &b, coef);
-    int rc = babe_cqt_band_synthesis(&b, w.bs, win, d->nwin, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(babe_cqt_band_synthesis(&b, w.bs, win, d->nwin, B, stream));
     return babe_cqt_gather(w.bs, d->nwin, p->rowptr, p->src, p->has_rec ? p->rec : nullptr, w.spec, (int)d->KX, (int)d->L, scale, nullptr, B, stream);
 }
 bool plan_args(const void* plan, const void* a, const void* b, const void* ws, int B, const char* who) {
@@ -521,14 +520,21 @@ bool plan_args(const void* plan, const void* a, const void* b, const void* ws, i
 }
 }  // namespace
 
+/* The carve's dry total and 1024 bytes. */
+extern "C" long babe_cqt_workspace_bytes(const void* plan, int B) {
+    if (!plan || B < 1) return -1;
+    Carver dry{nullptr, 0, 4};
+    carve(dry, static_cast<const CqtPlan*>(plan)->d, B);
+    return (long)dry.used + 1024;
+}
+
 /* CQT_nsgt.fwd: x [B][L] -> planar coefficients coef[j] = [B][2][binsoct][T_oct[j]] (index 0 = lowest octave).  ws: device scratch of
  * babe_cqt_workspace_bytes(plan, B) bytes. */
 extern "C" int babe_cqt_fwd(const void* plan, const float* x, float* const* coef, float* ws, int B, void* stream) {
     if (!plan_args(plan, x, coef, ws, B, "cqt_fwd")) return BABE_ERR_ARG;
     const CqtPlan* p = static_cast<const CqtPlan*>(plan);
     const Work w = carve(p->d, ws, B);
-    int rc = rfft(p, x, w.spec, w.four, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(rfft(p, x, w.spec, w.four, B, stream));
     babe_cqt_bands b;
     fill_bands(p, &b, coef);
     return babe_cqt_band_analysis(&b, w.spec, p->d->kdeg > 0 ? nullptr : p->win_fwd, B, stream);
@@ -538,8 +544,7 @@ extern "C" int babe_cqt_bwd(const void* plan, float* const* coef, float* x, floa
     if (!plan_args(plan, coef, x, ws, B, "cqt_bwd")) return BABE_ERR_ARG;
     const CqtPlan* p = static_cast<const CqtPlan*>(plan);
     const Work w = carve(p->d, ws, B);
-    int rc = synth(p, coef, p->win_bwd, (float)(2.0 / (double)p->d->L), w, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(synth(p, coef, p->win_bwd, (float)(2.0 / (double)p->d->L), w, B, stream));
     return rfft_T(p, w.spec, x, w.four, B, stream);
 }
 /* transpose of babe_cqt_fwd: gradients w.r.t. the coefficients -> gradient w.r.t. x */
@@ -547,8 +552,7 @@ extern "C" int babe_cqt_fwd_adjoint(const void* plan, float* const* gcoef, float
     if (!plan_args(plan, gcoef, gx, ws, B, "cqt_fwd_adjoint")) return BABE_ERR_ARG;
     const CqtPlan* p = static_cast<const CqtPlan*>(plan);
     const Work w = carve(p->d, ws, B);
-    int rc = synth(p, gcoef, p->d->kdeg > 0 ? nullptr : p->win_fwd, 1.0f, w, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(synth(p, gcoef, p->d->kdeg > 0 ? nullptr : p->win_fwd, 1.0f, w, B, stream));
     return rfft_T(p, w.spec, gx, w.four, B, stream);
 }
 /* transpose of babe_cqt_bwd: gradient w.r.t. x -> gradients w.r.t. the coefficients */
@@ -556,8 +560,7 @@ extern "C" int babe_cqt_bwd_adjoint(const void* plan, const float* gx, float* co
     if (!plan_args(plan, gx, gcoef, ws, B, "cqt_bwd_adjoint")) return BABE_ERR_ARG;
     const CqtPlan* p = static_cast<const CqtPlan*>(plan);
     const Work w = carve(p->d, ws, B);
-    int rc = rfft(p, gx, w.spec, w.four, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(rfft(p, gx, w.spec, w.four, B, stream));
     babe_cqt_bands b;
     fill_bands(p, &b, gcoef);
     return babe_cqt_band_analysis(&b, w.spec, p->win_bwd_adj, B, stream);
@@ -568,9 +571,7 @@ extern "C" int babe_cqt_hpf(const void* plan, const float* x, float* out, float*
     const CqtPlan* p = static_cast<const CqtPlan*>(plan);
     const CqtDesign* d = p->d;
     const Work w = carve(d, ws, B);
-    int rc = rfft(p, x, w.spec, w.four, B, stream);
-    if (rc != BABE_OK) return rc;
-    rc = babe_spec_scale(w.spec, nullptr, w.spec, p->hpf_irfft, (int)d->KX, (int)d->L, 1.0f, 0.0f, B, stream);
-    if (rc != BABE_OK) return rc;
+    BABE_TRY(rfft(p, x, w.spec, w.four, B, stream));
+    BABE_TRY(babe_spec_scale(w.spec, nullptr, w.spec, p->hpf_irfft, (int)d->KX, (int)d->L, 1.0f, 0.0f, B, stream));
     return rfft_T(p, w.spec, out, w.four, B, stream);
 }

@@ -450,6 +450,12 @@ int plane_blocks(long hw) {
 
 }  // namespace
 
+// the one statement of the rule; both sequencers (Ctx::splits in unet_engine.hip, babe_amd/ops.py _splits) call it
+extern "C" long babe_gn_splits(long n) {
+    const long s = n / 16384;
+    return s < 1 ? 1 : s > 64 ? 64 : s;
+}
+
 extern "C" int babe_gn_partial(const float* x, double* part, int B, int G, long n, int S, void* stream) {
     BABE_CHECK_ARG(x && part && B > 0 && G > 0 && n > 1 && S > 0, "gn_partial: bad arguments");
     BABE_CHECK_ARG(n % 4 == 0, "gn_partial: group size %ld not a multiple of 4", n);

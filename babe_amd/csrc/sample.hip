@@ -8,19 +8,22 @@
 // as the Python loop, so the two agree bit for bit (tests/test_gpu_sample_c.py).  Nothing allocates, nothing synchronises.
 #include <cmath>
 #include "common.h"
-#include "../../include/babe_hip.h"
+#include "eval_geom.h"
+#include "workspace.h"
 
 namespace {
 
-inline long round256(long bytes) { return (bytes + 255) / 256 * 256; }
-
-// the run's own buffers (everything but babe_score_eval's workspace): specY and seven [B][L] signals
-long own_bytes(const babe_eval_desc* e, int B) {
-    const int hop = e->nfft / 2, frames = 1 + e->L / hop, nbins = hop + 1;
-    return round256(4L * B * 2 * frames * nbins) + 7 * round256(4L * B * e->L);
+// the run's workspace, stated once (babe_sample_workspace_bytes runs it dry): babe_score_eval's block of ev_bytes, then the run's
+// own buffers, specY and seven [B][L] signals
+struct SampleWork {
+    void* ev;
+    float *specY, *buf[7];
+};
+void carve(Carver& c, const babe_eval_desc* e, const EvalGeom& g, int B, long ev_bytes, SampleWork& w) {
+    w.ev = c.take<char>((size_t)ev_bytes);
+    w.specY = c.take<float>((size_t)B * 2 * g.frames * g.nbins);
+    for (float*& b : w.buf) b = c.take<float>((size_t)B * e->L);
 }
-
-bool eval_dims_ok(const babe_eval_desc* e) { return e->nfft >= 256 && e->L >= e->nfft; }
 
 }  // namespace
 
@@ -31,7 +34,12 @@ extern "C" long babe_sample_workspace_bytes(const babe_sample_desc* d, int B) {
     }
     const long ev = babe_eval_workspace_bytes(&d->eval, B);
     if (ev < 0) return -1;
-    return round256(ev) + own_bytes(&d->eval, B);
+    EvalGeom g;
+    geom(&d->eval, g);                  // (it has a design: the evaluation was sized)
+    Carver dry{nullptr, 0, 256};
+    SampleWork w;
+    carve(dry, &d->eval, g, B, ev, w);
+    return (long)dry.used;
 }
 
 extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, float* x_out, const float* noise, long seed,
@@ -43,16 +51,20 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
     BABE_CHECK_ARG(B >= 1 && B <= 65535, "sample_bwe: B = %d", B);
     const babe_eval_desc* e = &d->eval;
     BABE_CHECK_ARG(eval_dims_ok(e), "sample_bwe: nfft = %d, L = %d", e->nfft, e->L);
-    BABE_CHECK_ARG(ws && ws_bytes >= own_bytes(e, B), "sample_bwe: workspace of %ld bytes, the run's own buffers alone need %ld",
-                   ws ? ws_bytes : 0L, own_bytes(e, B));
+    EvalGeom g;
+    geom(e, g);                         // (the STFT part, all this function uses, needs no plan: the plans are looked at below)
+    SampleWork w;
+    Carver own{nullptr, 0, 256};
+    carve(own, e, g, B, 0, w);
+    BABE_CHECK_ARG(ws && ws_bytes >= (long)own.used, "sample_bwe: workspace of %ld bytes, the run's own buffers alone need %ld",
+                   ws ? ws_bytes : 0L, (long)own.used);
     BABE_CHECK_ARG(y && params && x_out, "sample_bwe: NULL y, params or x_out");
-    BABE_CHECK_ARG(e->unet_plan && e->unet_state && e->cqt_plan && e->rff_freq && e->film_W && e->film_b && e->env_inv && e->tw4096,
-                   "sample_bwe: incomplete evaluation descriptor");
-    BABE_CHECK_ARG(e->K >= 1 && e->K <= 8 && e->rff_n > 0 && e->emb_dim[0] == 2 * e->rff_n, "sample_bwe: K = %d, rff_n = %d, emb_dim[0] = %d",
-                   e->K, e->rff_n, e->emb_dim[0]);
-    const long need = babe_sample_workspace_bytes(d, B);
-    BABE_CHECK_ARG(need >= 0, "sample_bwe: bad evaluation descriptor");
-    BABE_CHECK_ARG(ws_bytes >= need, "sample_bwe: workspace of %ld bytes, need %ld", ws_bytes, need);
+    BABE_TRY(eval_desc_check(e, "sample_bwe"));
+    const long ev_bytes = babe_eval_workspace_bytes(e, B);
+    BABE_CHECK_ARG(ev_bytes >= 0, "sample_bwe: bad evaluation descriptor");
+    Carver c{static_cast<char*>(ws), (size_t)ws_bytes, 256};
+    carve(c, e, g, B, ev_bytes, w);
+    BABE_CHECK_ARG(c.ok, "sample_bwe: workspace of %ld bytes, need %ld", ws_bytes, (long)c.used);
     BABE_CHECK_ARG(std::isfinite(d->t0), "sample_bwe: t0 is not finite");
     for (int i = 0; i < d->T; ++i) {
         const babe_sample_step& s = d->steps[i];
@@ -63,27 +75,11 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
     }
     if (!noise)
         BABE_CHECK_ARG(clip0 >= 0 && clip0 + B <= 0x100000000L && d->T + 1L < 0x100000000L, "sample_bwe: clip0 = %ld outside the counter word", clip0);
-    // ---- carve
     const long L = e->L, n = (long)B * L;
-    const int P = e->shared ? 1 : B, hop = e->nfft / 2, frames = 1 + e->L / hop, nbins = hop + 1;
-    const long ev_bytes = need - own_bytes(e, B);
-    char* p = static_cast<char*>(ws);
-    void* ev_ws = p;
-    p += ev_bytes;
-    float* specY = reinterpret_cast<float*>(p);
-    p += round256(4L * B * 2 * frames * nbins);
-    float* buf[7];
-    for (int k = 0; k < 7; ++k) {
-        buf[k] = reinterpret_cast<float*>(p);
-        p += round256(4L * n);
-    }
-    float *x = x_out, *x_hat = buf[0], *dd = buf[1], *x_den = buf[2], *x_prime = buf[3], *d2 = buf[4], *x_den2 = buf[5], *eps_ws = buf[6];
+    const int P = e->shared ? 1 : B, frames = g.frames;
+    float *x = x_out, *specY = w.specY, *x_hat = w.buf[0], *dd = w.buf[1], *x_den = w.buf[2], *x_prime = w.buf[3], *d2 = w.buf[4],
+          *x_den2 = w.buf[5], *eps_ws = w.buf[6];
     hipStream_t st = (hipStream_t)stream;
-#define EV(call)                          \
-    do {                                  \
-        const int rc__ = (call);          \
-        if (rc__ != BABE_OK) return rc__; \
-    } while (0)
 #define COPY(dst, src, bytes)                                                                          \
     do {                                                                                               \
         const hipError_t e__ = hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDeviceToDevice, st);     \
@@ -102,30 +98,29 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
         return babe_randn(eps_ws, L, B, L, seed, clip0, k, stream);
     };
     const float* eps = nullptr;
-    EV(babe_stft_fwd(y, L, (int)L, nullptr, specY, B, e->nfft, frames, e->tw4096, stream));
+    BABE_TRY(babe_stft_fwd(y, L, (int)L, nullptr, specY, B, e->nfft, frames, e->tw4096, stream));
     // ---- initial state (:311 / :314): t0 eps, or y + t0 eps with a warm start
-    EV(draw(0, &eps));
-    if (d->warm_start) EV(babe_lincomb3(x, 1.f, y, d->t0, eps, 0.f, nullptr, n, stream));
-    else EV(babe_lincomb3(x, d->t0, eps, 0.f, nullptr, 0.f, nullptr, n, stream));
+    BABE_TRY(draw(0, &eps));
+    if (d->warm_start) BABE_TRY(babe_lincomb3(x, 1.f, y, d->t0, eps, 0.f, nullptr, n, stream));
+    else BABE_TRY(babe_lincomb3(x, d->t0, eps, 0.f, nullptr, 0.f, nullptr, n, stream));
     for (int i = 0; i < d->T; ++i) {
         const babe_sample_step& s = d->steps[i];
-        EV(draw(i + 1L, &eps));
-        EV(babe_lincomb3(x_hat, 1.f, x, s.inject, eps, 0.f, nullptr, n, stream));
-        EV(babe_score_eval(e, x_hat, s.t_hat, s.c1[0], s.c1[1], s.c1[2], s.c1[3], y, specY, params, dd, x_den, nullptr, ev_ws, ev_bytes, B,
-                           stream));
+        BABE_TRY(draw(i + 1L, &eps));
+        BABE_TRY(babe_lincomb3(x_hat, 1.f, x, s.inject, eps, 0.f, nullptr, n, stream));
+        BABE_TRY(babe_score_eval(e, x_hat, s.t_hat, s.c1[0], s.c1[1], s.c1[2], s.c1[3], y, specY, params, dd, x_den, nullptr, w.ev, ev_bytes, B,
+                                 stream));
         if (rec_x_den) COPY(rec_x_den + (long)i * n, x_den, 4L * n);
         if (rec_params) COPY(rec_params + (long)i * P * 2 * e->K, params, 4L * P * 2 * e->K);
         if (!s.heun) {
-            EV(babe_lincomb3(x, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
+            BABE_TRY(babe_lincomb3(x, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
         } else {
-            EV(babe_lincomb3(x_prime, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
-            EV(babe_score_eval(e, x_prime, s.t_next, s.c2[0], s.c2[1], s.c2[2], s.c2[3], y, specY, params, d2, x_den2, nullptr, ev_ws, ev_bytes,
-                               B, stream));
-            EV(babe_lincomb3(x, 1.f, x_hat, 0.5f * s.h, dd, 0.5f * s.h, d2, n, stream));
+            BABE_TRY(babe_lincomb3(x_prime, 1.f, x_hat, s.h, dd, 0.f, nullptr, n, stream));
+            BABE_TRY(babe_score_eval(e, x_prime, s.t_next, s.c2[0], s.c2[1], s.c2[2], s.c2[3], y, specY, params, d2, x_den2, nullptr, w.ev, ev_bytes,
+                                     B, stream));
+            BABE_TRY(babe_lincomb3(x, 1.f, x_hat, 0.5f * s.h, dd, 0.5f * s.h, d2, n, stream));
         }
     }
 #undef COPY
-#undef EV
     return BABE_OK;
 }
 

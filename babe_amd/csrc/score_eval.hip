@@ -10,7 +10,8 @@
 // sequencer, which this call equals bit for bit on the default path: tests/test_gpu_eval_c.py).
 // Every intermediate lives in the caller's workspace (babe_eval_workspace_bytes); nothing is allocated, nothing synchronises.
 #include "common.h"
-#include "../../include/babe_hip.h"
+#include "eval_geom.h"
+#include "workspace.h"
 
 namespace {
 
@@ -19,57 +20,41 @@ __global__ void fill_kernel(float* out, float v, int n) {
     if (i < n) out[i] = v;
 }
 
-struct Carver {
-    char* p;
-    char* end;
-    bool ok = true;
-    template <typename T>
-    T* take(size_t n) {
-        const size_t bytes = (n * sizeof(T) + 255) / 256 * 256;
-        if (p + bytes > end) {
-            ok = false;
-            return nullptr;
-        }
-        T* r = reinterpret_cast<T*>(p);
-        p += bytes;
-        return r;
-    }
+// every buffer of one evaluation.  carve() is the workspace's layout, stated once: babe_eval_workspace_bytes runs it dry,
+// babe_score_eval on the caller's buffer.  A new buffer is one member and one take.
+struct EvalWork {
+    float* cqws;                        // the transforms' scratch (babe_cqt_workspace_bytes)
+    void* unws;                         // the network's workspace (babe_unet_workspace_bytes = unb)
+    long unb;
+    float *xin, *net, *xd, *r, *seed, *g_den, *g_net, *g_xin, *hp;      // [B][L] (g_x reuses xd)
+    float *coA[8], *coB[8];             // coefficients in / out, then their gradients
+    float *specX, *specS, *fr;          // spectra of x_den and of the seed, frames
+    float *cn, *h0, *h1, *h2, *h3, *film;
+    float* H;
+    double *stats, *part, *gpart;       // magnitude statistics, two sets of partial sums
+    int* nit;
 };
 
-struct EvalGeom {
-    int nocts, binsoct, T_oct[8];
-    long coef_floats;                 // per clip, all octaves
-    int hop, frames, nbins;
-    long ntot;
-};
-
-bool geom(const babe_eval_desc* e, EvalGeom& g) {
-    const void* d = babe_cqt_plan_design(e->cqt_plan);
-    if (!d) return false;
-    long nb = 0;
-    int Toct[8] = {0};
-    babe_cqt_design_get(d, "nb", &nb, 8);
-    const long bytes = babe_cqt_design_get(d, "T_oct", nullptr, 0);
-    if (bytes <= 0 || bytes > 32) return false;
-    babe_cqt_design_get(d, "T_oct", Toct, 32);
-    g.nocts = (int)(bytes / 4);
-    g.binsoct = (int)(nb / g.nocts);
-    g.coef_floats = 0;
-    for (int j = 0; j < g.nocts; ++j) {
-        g.T_oct[j] = Toct[j];
-        g.coef_floats += 2L * g.binsoct * Toct[j];
-    }
-    g.hop = e->nfft / 2;
-    g.frames = 1 + e->L / g.hop;
-    g.nbins = g.hop + 1;
-    g.ntot = e->nfft + (long)g.hop * (g.frames - 1);
+// false: a nested size query failed (its message stands)
+bool carve(Carver& c, const babe_eval_desc* e, const EvalGeom& g, int B, EvalWork& w) {
+    const long cq = babe_cqt_workspace_bytes(e->cqt_plan, B);
+    w.unb = babe_unet_workspace_bytes(e->unet_plan, B, g.T_oct);
+    if (cq < 0 || w.unb < 0) return false;
+    const size_t n = (size_t)B * e->L, spec = (size_t)B * 2 * g.frames * g.nbins;
+    const int P = e->shared ? 1 : B;
+    w.cqws = reinterpret_cast<float*>(c.take<char>((size_t)cq));
+    w.unws = c.take<char>((size_t)w.unb);
+    for (float** s : {&w.xin, &w.net, &w.xd, &w.r, &w.seed, &w.g_den, &w.g_net, &w.g_xin, &w.hp}) *s = c.take<float>(n);
+    for (int j = 0; j < g.nocts; ++j) w.coA[j] = c.take<float>((size_t)B * 2 * g.binsoct * g.T_oct[j]);
+    for (int j = 0; j < g.nocts; ++j) w.coB[j] = c.take<float>((size_t)B * 2 * g.binsoct * g.T_oct[j]);
+    w.specX = c.take<float>(spec), w.specS = c.take<float>(spec), w.fr = c.take<float>((size_t)B * g.frames * e->nfft);
+    w.cn = c.take<float>(B), w.h0 = c.take<float>((size_t)B * 2 * e->rff_n), w.h1 = c.take<float>((size_t)B * e->emb_dim[1]);
+    w.h2 = c.take<float>((size_t)B * e->emb_dim[2]), w.h3 = c.take<float>((size_t)B * e->emb_dim[3]);
+    w.film = c.take<float>((size_t)B * e->film_J);
+    w.H = c.take<float>((size_t)P * g.nbins);
+    w.stats = c.take<double>((size_t)P * 3 * g.nbins), w.part = c.take<double>((size_t)B * 64), w.gpart = c.take<double>((size_t)B * 64);
+    w.nit = c.take<int>(P);
     return true;
-}
-
-long unet_ws_bytes(const babe_eval_desc* e, const EvalGeom& g, int B) {
-    int Tlvl[8];
-    for (int j = 0; j < g.nocts; ++j) Tlvl[j] = g.T_oct[j];
-    return babe_unet_workspace_bytes(e->unet_plan, B, Tlvl);
 }
 
 }  // namespace
@@ -82,7 +67,7 @@ extern "C" int babe_fill(float* out, float v, int n, void* stream) {
 }
 
 extern "C" long babe_eval_workspace_bytes(const babe_eval_desc* e, int B) {
-    if (!e || !e->unet_plan || !e->cqt_plan || B < 1 || e->nfft < 256 || e->L < e->nfft) {
+    if (!e || !e->unet_plan || !e->cqt_plan || B < 1 || !eval_dims_ok(e)) {
         babe_set_error("eval_workspace_bytes: bad descriptor");
         return -1;
     }
@@ -91,18 +76,9 @@ extern "C" long babe_eval_workspace_bytes(const babe_eval_desc* e, int B) {
         babe_set_error("eval_workspace_bytes: the CQT plan has no design");
         return -1;
     }
-    const long cq = babe_cqt_workspace_bytes(e->cqt_plan, B), un = unet_ws_bytes(e, g, B);
-    if (cq < 0 || un < 0) return -1;
-    const long L = e->L, spec = 2L * g.frames * g.nbins, fr = (long)g.frames * e->nfft;
-    long fl = 0;                       // floats, every piece rounded up to 256 bytes by the carver: 64 floats of slack each
-    const int pieces = 40;
-    fl += 9L * B * L;                                              // xin net xd x_den r seed g_den g_net g_xin (g_x reuses xd)
-    fl += 2L * B * g.coef_floats;                                  // coefficients in / out (and their gradients: reused)
-    fl += 2L * B * spec + (long)B * fr;                            // specX, spec of the seed, frames
-    fl += (long)B * (1 + 2 * e->rff_n + e->emb_dim[1] + e->emb_dim[2] + e->emb_dim[3] + e->film_J);
-    fl += (long)B * g.nbins + 64;                                  // H
-    const long dbl = (long)B * 3 * g.nbins + 2L * B * 64;          // statistics, two sets of partial sums
-    return cq + un + 4 * fl + 8 * dbl + 4L * B + 256L * pieces + 4096;
+    Carver dry{nullptr, 0, 256};
+    EvalWork w;
+    return carve(dry, e, g, B, w) ? (long)dry.used : -1;
 }
 
 /* x [B][L]: the noisy state at noise level t; (cskip, cout, cin, cnoise): EDM preconditioning of t (diff_params/edm.py:46-60,
@@ -113,80 +89,54 @@ extern "C" long babe_eval_workspace_bytes(const babe_eval_desc* e, int B) {
 extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t, float cskip, float cout, float cin, float cnoise,
                                const float* y, const float* specY, float* params, float* d, float* x_den, int* n_iter, void* ws,
                                long ws_bytes, int B, void* stream) {
-    BABE_CHECK_ARG(e && x && y && specY && params && d && x_den && ws && B > 0, "score_eval: bad arguments");
-    BABE_CHECK_ARG(e->unet_plan && e->unet_state && e->cqt_plan && e->rff_freq && e->film_W && e->film_b && e->env_inv && e->tw4096,
-                   "score_eval: incomplete descriptor");
-    BABE_CHECK_ARG(e->K >= 1 && e->K <= 8 && e->rff_n > 0 && e->emb_dim[0] == 2 * e->rff_n, "score_eval: K = %d, rff_n = %d, emb_dim[0] = %d",
-                   e->K, e->rff_n, e->emb_dim[0]);
+    BABE_CHECK_ARG(e && x && y && specY && params && d && x_den && ws && ws_bytes >= 0 && B > 0, "score_eval: bad arguments");
+    BABE_TRY(eval_desc_check(e, "score_eval"));
+    BABE_CHECK_ARG(eval_dims_ok(e), "score_eval: nfft = %d, L = %d", e->nfft, e->L);
     EvalGeom g;
     BABE_CHECK_ARG(geom(e, g), "score_eval: the CQT plan has no design");
-    BABE_CHECK_ARG(ws_bytes >= babe_eval_workspace_bytes(e, B), "score_eval: workspace of %ld bytes, need %ld", ws_bytes,
-                   babe_eval_workspace_bytes(e, B));
+    Carver c{static_cast<char*>(ws), (size_t)ws_bytes, 256};
+    EvalWork w;
+    if (!carve(c, e, g, B, w)) return BABE_ERR_ARG;
+    BABE_CHECK_ARG(c.ok, "score_eval: workspace of %ld bytes, need %ld", ws_bytes, (long)c.used);
     const long L = e->L, n = (long)B * L;
     const int P = e->shared ? 1 : B;
-    Carver c{static_cast<char*>(ws), static_cast<char*>(ws) + ws_bytes};
-    float* cqws = reinterpret_cast<float*>(c.take<char>((size_t)babe_cqt_workspace_bytes(e->cqt_plan, B)));
-    const long unb = unet_ws_bytes(e, g, B);
-    void* unws = c.take<char>((size_t)unb);
-    float *xin = c.take<float>(n), *net = c.take<float>(n), *xd = c.take<float>(n), *r = c.take<float>(n), *seed = c.take<float>(n),
-          *g_den = c.take<float>(n), *g_net = c.take<float>(n), *g_xin = c.take<float>(n), *hp = c.take<float>(n);
-    float* coA[8];
-    float* coB[8];
-    for (int j = 0; j < g.nocts; ++j) coA[j] = c.take<float>((size_t)B * 2 * g.binsoct * g.T_oct[j]);
-    for (int j = 0; j < g.nocts; ++j) coB[j] = c.take<float>((size_t)B * 2 * g.binsoct * g.T_oct[j]);
-    const long spec = 2L * g.frames * g.nbins;
-    float *specX = c.take<float>((size_t)B * spec), *specS = c.take<float>((size_t)B * spec), *fr = c.take<float>((size_t)B * g.frames * e->nfft);
-    float *cn = c.take<float>(B), *h0 = c.take<float>((size_t)B * 2 * e->rff_n), *h1 = c.take<float>((size_t)B * e->emb_dim[1]),
-          *h2 = c.take<float>((size_t)B * e->emb_dim[2]), *h3 = c.take<float>((size_t)B * e->emb_dim[3]), *film = c.take<float>((size_t)B * e->film_J);
-    float* H = c.take<float>((size_t)P * g.nbins);
-    double *stats = c.take<double>((size_t)P * 3 * g.nbins), *part = c.take<double>((size_t)B * 64), *gpart = c.take<double>((size_t)B * 64);
-    int* nit = c.take<int>(P);
-    BABE_CHECK_ARG(c.ok, "score_eval: workspace carve failed (internal size formula)");
-    int Tlvl[8];
-    for (int j = 0; j < g.nocts; ++j) Tlvl[j] = g.T_oct[j];
-#define EV(call)                     \
-    do {                             \
-        const int rc__ = (call);     \
-        if (rc__ != BABE_OK) return rc__; \
-    } while (0)
     // ---- denoiser: cskip x + cout net(cin x, cnoise), then the DC / Nyquist high-pass
-    EV(babe_lincomb3(xin, cin, x, 0.f, nullptr, 0.f, nullptr, n, stream));
-    EV(babe_fill(cn, cnoise, B, stream));
-    EV(babe_rff(cn, e->rff_freq, h0, B, e->rff_n, stream));
-    EV(babe_linear(h0, e->emb_W[0], e->emb_b[0], h1, B, e->emb_dim[0], e->emb_dim[1], 1, stream));
-    EV(babe_linear(h1, e->emb_W[1], e->emb_b[1], h2, B, e->emb_dim[1], e->emb_dim[2], 1, stream));
-    EV(babe_linear(h2, e->emb_W[2], e->emb_b[2], h3, B, e->emb_dim[2], e->emb_dim[3], 1, stream));
-    EV(babe_linear(h3, e->film_W, e->film_b, film, B, e->emb_dim[3], e->film_J, 0, stream));
-    EV(babe_cqt_fwd(e->cqt_plan, xin, coA, cqws, B, stream));
-    EV(babe_unet_fwd(e->unet_plan, e->unet_state, coA, film, e->film_J, B, Tlvl, unws, unb, coB, stream));
-    EV(babe_cqt_bwd(e->cqt_plan, coB, net, cqws, B, stream));
-    EV(babe_lincomb3(xd, cskip, x, cout, net, 0.f, nullptr, n, stream));
-    if (e->hpf) EV(babe_cqt_hpf(e->cqt_plan, xd, x_den, cqws, B, stream));
-    else EV(babe_lincomb3(x_den, 1.f, xd, 0.f, nullptr, 0.f, nullptr, n, stream));
+    BABE_TRY(babe_lincomb3(w.xin, cin, x, 0.f, nullptr, 0.f, nullptr, n, stream));
+    BABE_TRY(babe_fill(w.cn, cnoise, B, stream));
+    BABE_TRY(babe_rff(w.cn, e->rff_freq, w.h0, B, e->rff_n, stream));
+    BABE_TRY(babe_linear(w.h0, e->emb_W[0], e->emb_b[0], w.h1, B, e->emb_dim[0], e->emb_dim[1], 1, stream));
+    BABE_TRY(babe_linear(w.h1, e->emb_W[1], e->emb_b[1], w.h2, B, e->emb_dim[1], e->emb_dim[2], 1, stream));
+    BABE_TRY(babe_linear(w.h2, e->emb_W[2], e->emb_b[2], w.h3, B, e->emb_dim[2], e->emb_dim[3], 1, stream));
+    BABE_TRY(babe_linear(w.h3, e->film_W, e->film_b, w.film, B, e->emb_dim[3], e->film_J, 0, stream));
+    BABE_TRY(babe_cqt_fwd(e->cqt_plan, w.xin, w.coA, w.cqws, B, stream));
+    BABE_TRY(babe_unet_fwd(e->unet_plan, e->unet_state, w.coA, w.film, e->film_J, B, g.T_oct, w.unws, w.unb, w.coB, stream));
+    BABE_TRY(babe_cqt_bwd(e->cqt_plan, w.coB, w.net, w.cqws, B, stream));
+    BABE_TRY(babe_lincomb3(w.xd, cskip, x, cout, w.net, 0.f, nullptr, n, stream));
+    if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.xd, x_den, w.cqws, B, stream));
+    else BABE_TRY(babe_lincomb3(x_den, 1.f, w.xd, 0.f, nullptr, 0.f, nullptr, n, stream));
     // ---- filter fit on STFT magnitudes, filter design
-    EV(babe_stft_fwd(x_den, L, (int)L, nullptr, specX, B, e->nfft, g.frames, e->tw4096, stream));
+    BABE_TRY(babe_stft_fwd(x_den, L, (int)L, nullptr, w.specX, B, e->nfft, g.frames, e->tw4096, stream));
     if (e->blind) {
-        EV(babe_stft_mag_stats(specX, specY, stats, B, g.nbins, g.frames, e->shared, stream));
-        EV(babe_filter_fit(stats, params, n_iter ? n_iter : nit, P, e->K, g.nbins, e->fs, e->nfft, &e->fit, stream));
+        BABE_TRY(babe_stft_mag_stats(w.specX, specY, w.stats, B, g.nbins, g.frames, e->shared, stream));
+        BABE_TRY(babe_filter_fit(w.stats, params, n_iter ? n_iter : w.nit, P, e->K, g.nbins, e->fs, e->nfft, &e->fit, stream));
     }
-    EV(babe_design_filter(params, H, P, e->K, g.nbins, e->fs, e->nfft, stream));
+    BABE_TRY(babe_design_filter(params, w.H, P, e->K, g.nbins, e->fs, e->nfft, stream));
     const long H_bs = P == B ? g.nbins : 0;            // per-clip filters, or one filter for the batch
     // ---- reconstruction guidance: residual y - A(x_den), its norm's gradient through iSTFT o H o STFT
-    EV(babe_spec_filter_istft(specX, H, H_bs, fr, B, e->nfft, g.frames, e->tw4096, stream));
-    EV(babe_ola(fr, e->env_inv, y, L, r, L, part, 64, B, (int)L, e->nfft, g.frames, stream));
-    EV(babe_residual_seed(r, L, part, 64, e->env_inv, seed, L, B, (int)L, stream));
-    EV(babe_stft_fwd(seed, L, (int)L, nullptr, specS, B, e->nfft, g.frames, e->tw4096, stream));
-    EV(babe_spec_filter_istft(specS, H, H_bs, fr, B, e->nfft, g.frames, e->tw4096, stream));
-    EV(babe_ola(fr, nullptr, nullptr, 0, e->hpf ? hp : g_den, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
-    if (e->hpf) EV(babe_cqt_hpf(e->cqt_plan, hp, g_den, cqws, B, stream));
+    BABE_TRY(babe_spec_filter_istft(w.specX, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+    BABE_TRY(babe_ola(w.fr, e->env_inv, y, L, w.r, L, w.part, 64, B, (int)L, e->nfft, g.frames, stream));
+    BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, w.seed, L, B, (int)L, stream));
+    BABE_TRY(babe_stft_fwd(w.seed, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+    BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+    BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, e->hpf ? w.hp : w.g_den, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+    if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.hp, w.g_den, w.cqws, B, stream));
     // ---- through the network: g_x = cskip g_den + cin net^T(cout g_den)
-    EV(babe_lincomb3(g_net, cout, g_den, 0.f, nullptr, 0.f, nullptr, n, stream));
-    EV(babe_cqt_bwd_adjoint(e->cqt_plan, g_net, coA, cqws, B, stream));
-    EV(babe_unet_vjp(e->unet_plan, e->unet_state, coA, coB, stream));
-    EV(babe_cqt_fwd_adjoint(e->cqt_plan, coB, g_xin, cqws, B, stream));
-    EV(babe_lincomb3(xd, cskip, g_den, cin, g_xin, 0.f, nullptr, n, stream));                 // g_x (xd is free again)
-    EV(babe_sumsq_partial(xd, L, gpart, 64, B, L, stream));
-    EV(babe_score_direction(x_den, x, xd, gpart, 64, d, t, e->xi, (float)e->audio_len_norm, e->shared, e->score_mode, B, L, stream));
-#undef EV
+    BABE_TRY(babe_lincomb3(w.g_net, cout, w.g_den, 0.f, nullptr, 0.f, nullptr, n, stream));
+    BABE_TRY(babe_cqt_bwd_adjoint(e->cqt_plan, w.g_net, w.coA, w.cqws, B, stream));
+    BABE_TRY(babe_unet_vjp(e->unet_plan, e->unet_state, w.coA, w.coB, stream));
+    BABE_TRY(babe_cqt_fwd_adjoint(e->cqt_plan, w.coB, w.g_xin, w.cqws, B, stream));
+    BABE_TRY(babe_lincomb3(w.xd, cskip, w.g_den, cin, w.g_xin, 0.f, nullptr, n, stream));                 // g_x (xd is free again)
+    BABE_TRY(babe_sumsq_partial(w.xd, L, w.gpart, 64, B, L, stream));
+    BABE_TRY(babe_score_direction(x_den, x, w.xd, w.gpart, 64, d, t, e->xi, (float)e->audio_len_norm, e->shared, e->score_mode, B, L, stream));
     return BABE_OK;
 }

@@ -213,8 +213,7 @@ struct Ctx {
         }
         ck(babe_resample(x.p, x.bs, x.cs, out.p, out.bs, out.cs, B(), x.C, x.F, T, mode, alpha, beta, st));
     }
-    // split count of a GroupNorm group of n elements: the same rule as babe_amd/ops.py _splits, the only other place it lives
-    static int splits(long n) { long s = n / 16384; return (int)(s < 1 ? 1 : (s > 64 ? 64 : s)); }
+    static int splits(long n) { return (int)babe_gn_splits(n); }      // split count of a GroupNorm group of n elements
     const float* film_at(int off) const { return S->film + off; }
 
     // ---- ResnetBlock (unet_engine.py block_fwd / block_vjp)

@@ -9,7 +9,7 @@ import ctypes as C
 import torch
 
 from .._cabi import CPackedConv, CPlanDesc
-from .._lib import check, lib, ptr, stream
+from .._lib import check, lib, ptr, stream, workspace
 
 
 def _pc(dst, pc):
@@ -78,8 +78,8 @@ class CUnet:
         self._owner = eng._plan                          # keeps the plan alive as long as this state
         self.n = eng.nocts
         self.state = lib().babe_unet_state_create()
-        self.ws = None
-        self.key = None
+        self._ws = {}
+        self.ws = None                                   # the workspace of the latest call
 
     def __del__(self):
         try:
@@ -95,18 +95,12 @@ class CUnet:
         Ts = [int(c.shape[-1]) for c in C_list]
         assert all(c.is_contiguous() and c.dtype == torch.float32 for c in C_list) and film.stride(1) == 1
         T_oct = (C.c_int * n)(*Ts)
-        key = (B, tuple(Ts))
-        if key != self.key:
-            nbytes = L.babe_unet_workspace_bytes(self.plan, B, T_oct)
-            if nbytes < 0:
-                raise RuntimeError("babe_unet_workspace_bytes: " + L.babe_last_error().decode())
-            self.ws = torch.empty(nbytes, device=C_list[0].device, dtype=torch.uint8)
-            self.key = key
+        ws = self.ws = workspace(self._ws, (B, tuple(Ts)), lambda: L.babe_unet_workspace_bytes(self.plan, B, T_oct), C_list[0].device, "unet")
         outs = [torch.empty_like(c) for c in C_list]
         cin = (C.c_void_p * n)(*[ptr(c) for c in C_list])
         cout = (C.c_void_p * n)(*[ptr(o) for o in outs])
         self._keep = (C_list, film)              # inputs are read again by nothing after the call, but keep them until the VJP
-        check(L.babe_unet_fwd(self.plan, self.state, cin, ptr(film), film.stride(0), B, T_oct, ptr(self.ws), self.ws.numel(), cout,
+        check(L.babe_unet_fwd(self.plan, self.state, cin, ptr(film), film.stride(0), B, T_oct, ptr(ws), ws.numel(), cout,
                               stream()), "unet_fwd")
         return outs
 

@@ -1,5 +1,6 @@
 """Python views of the babe_hip C-ABI ops (UNet building blocks).  Device tensors only."""
 import ctypes as C
+import functools
 import math
 
 import torch
@@ -209,10 +210,11 @@ def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=No
     return (part, S) if a.stat_mode else None
 
 
+@functools.lru_cache(maxsize=None)
 def _splits(n):
-    """Split count of a GroupNorm group of n elements.  The same rule as Ctx::splits in csrc/unet_engine.hip, the only other
-    place it lives."""
-    return int(max(1, min(64, n // 16384)))
+    """Split count of a GroupNorm group of n elements: the library's rule (babe_gn_splits), cached - this is on the per-launch
+    path and a network has a handful of group sizes."""
+    return int(lib().babe_gn_splits(int(n)))
 
 
 def _gn_buffers(x, G, fused=None, vjp=False):

@@ -7,7 +7,7 @@ import ctypes as C
 import torch
 
 from .._cabi import EvalDesc
-from .._lib import check, lib, ptr, stream
+from .._lib import check, lib, ptr, stream, workspace
 from ..cqt import MAX_BAND
 
 
@@ -57,19 +57,14 @@ class CEval:
         d.shared = int(smp.batch_semantics == "reference")
         d.hpf = int(bool(smp.args.tester.filter_out_cqt_DC_Nyq))
         d.xi, d.score_mode, d.audio_len_norm = float(smp.xi), int(smp.SCORE_MODE), float(smp.args.exp.audio_len)
-        self.desc, self.ws, self.key = d, None, None
+        self.desc, self._ws = d, {}
         self._keep = (eng, st, cq)
 
     def __call__(self, smp, x, t, y, specY, filter_params, blind):
         d = self.desc
         B, L = x.shape
         d.K, d.blind = int(filter_params.shape[-1]), int(bool(blind))
-        if self.key != B:
-            nbytes = lib().babe_eval_workspace_bytes(C.byref(d), B)
-            if nbytes < 0:
-                check(-1, "eval_workspace_bytes")
-            self.ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-            self.key = B
+        ws = workspace(self._ws, B, lambda: lib().babe_eval_workspace_bytes(C.byref(d), B), x.device, "eval")
         dp = smp.diff_params
         s = torch.as_tensor(t, dtype=torch.float32)
         cskip, cout, cin, cnoise = float(dp.cskip(s)), float(dp.cout(s)), float(dp.cin(s)), float(dp.cnoise(s))
@@ -77,7 +72,7 @@ class CEval:
         dd, x_den = torch.empty_like(x), torch.empty_like(x)
         nit = torch.empty(p.shape[0], dtype=torch.int32, device=x.device)
         check(lib().babe_score_eval(C.byref(d), ptr(x), float(t), cskip, cout, cin, cnoise, ptr(y), ptr(specY), ptr(p), ptr(dd),
-                                    ptr(x_den), ptr(nit), ptr(self.ws), self.ws.numel(), B, stream()), "score_eval")
+                                    ptr(x_den), ptr(nit), ptr(ws), ws.numel(), B, stream()), "score_eval")
         if blind:
             smp.last_n_iter = nit
         return dd, x_den, p

@@ -8,7 +8,7 @@ import ctypes as C
 import torch
 
 from .._cabi import SampleDesc, SampleStep
-from .._lib import check, lib, ptr, stream
+from .._lib import check, lib, ptr, stream, workspace
 from . import eval_c
 
 
@@ -50,7 +50,7 @@ class CSample:
 
     def __init__(self, smp, lane=None):
         self.ce = eval_c.CEval(smp, lane)
-        self.ws, self.key = None, None
+        self._ws = {}
         self.calls = 0                              # babe_sample_bwe calls made (tests/test_gpu_sample_c.py reads it)
 
     def __call__(self, smp, y, filter_params, blind, rows, t0, warm_start, noise=None, seed=0, clip0=0, rid=False):
@@ -62,12 +62,7 @@ class CSample:
         d.eval = self.ce.desc                       # (by value)
         d.eval.K, d.eval.blind = int(filter_params.shape[-1]), int(bool(blind))
         d.T, d.steps, d.t0, d.warm_start = T, rows, t0, int(bool(warm_start))
-        if self.key != (B, T):
-            nbytes = lib().babe_sample_workspace_bytes(C.byref(d), B)
-            if nbytes < 0:
-                check(-1, "sample_workspace_bytes")
-            self.ws = torch.empty(nbytes, device=y.device, dtype=torch.uint8)
-            self.key = (B, T)
+        ws = workspace(self._ws, (B, T), lambda: lib().babe_sample_workspace_bytes(C.byref(d), B), y.device, "sample")
         if noise is not None:
             assert noise.shape == (T + 1, B, L) and noise.is_contiguous() and noise.dtype == torch.float32 and noise.device == y.device
         p = filter_params.clone().contiguous()
@@ -76,5 +71,5 @@ class CSample:
         rec_p = torch.empty((T, *p.shape), device=y.device) if rid else None
         self.calls += 1
         check(lib().babe_sample_bwe(C.byref(d), ptr(y), ptr(p), ptr(x), ptr(noise), int(seed), int(clip0), ptr(rec_x), ptr(rec_p),
-                                    ptr(self.ws), self.ws.numel(), B, stream()), "sample_bwe")
+                                    ptr(ws), ws.numel(), B, stream()), "sample_bwe")
         return (x, p, rec_x, rec_p) if rid else (x, p)

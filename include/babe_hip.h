@@ -143,6 +143,8 @@ long babe_prof_timeline(double* t0_ms, double* t1_ms, int* slot, int* lane, doub
 long babe_prof_pending(void);
 
 /* ---- BiasFreeGroupNorm + FiLM + GELU: cqtdiff+.py:147-163, :472-482 ------------------------ */
+/* split count S of a GroupNorm group of n elements, as both sequencers launch it: max(1, min(64, n / 16384)) */
+long babe_gn_splits(long n);
 /* partial sums (double) of x and x^2 per (b,group,split): part[(b*G+g)*S+s] = {sum, sumsq} */
 int babe_gn_partial(const float* x, double* part, int B, int G, long n_per_group, int S, void* stream);
 /* babe_gn_partial + babe_gn_finalize in one launch (the workgroup that finishes a group last finalises it; bit-identical

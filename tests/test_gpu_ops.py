@@ -922,7 +922,7 @@ def test_f45_epilogue_forms_the_groupnorm_vjp_partial_sums(ops, monkeypatch):
         part, S = fs
         got = part.view(B, 8, S).sum(-1)
         n = (Cc // 8) * Fq * T
-        Sp = ops._splits(n)
+        Sp = lib().babe_gn_splits(n)
         ref = torch.empty(B * 8 * Sp, device="cuda", dtype=torch.float64)
         from babe_amd._lib import check, ptr, stream
         check(lib().babe_gn_bwd_partial(ptr(z), ptr(da0), ptr(scale), ptr(ref), B, Cc, 8, Fq * T, Sp, stream()), "gn_bwd_partial")

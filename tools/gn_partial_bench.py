@@ -1,10 +1,9 @@
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from babe_amd import ops
 from babe_amd._lib import lib, ptr, stream, check
 for (B, C, F, T) in [(1, 64, 64, 4096), (1, 128, 256, 512), (1, 256, 448, 64)]:
     x = torch.randn(B, C, F, T, device="cuda"); G = 8
-    n = (C // G) * F * T; S = ops._splits(n)
+    n = (C // G) * F * T; S = lib().babe_gn_splits(n)
     part = torch.empty(B * G * S * 2, device="cuda", dtype=torch.float64)
     f = lambda: check(lib().babe_gn_partial(ptr(x), ptr(part), B, G, n, S, stream()), "p")
     for _ in range(3): f()
