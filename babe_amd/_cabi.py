@@ -112,10 +112,28 @@ class DnConvArgs(C.Structure):
                 ("pad_mode", C.c_int), ("act", C.c_int), ("ksplit", C.c_int), ("ws", C.c_void_p)]
 
 
+class ModelEntry(C.Structure):
+    """babe_model_entry"""
+    _fields_ = [("name", C.c_char_p), ("ndim", C.c_int), ("shape", C.c_long * 4), ("data", C.c_void_p)]
+
+
+class ModelKV(C.Structure):
+    """babe_model_kv"""
+    _fields_ = [("key", C.c_char_p), ("str", C.c_char_p), ("num", C.c_double)]
+
+
+class ModelSummary(C.Structure):
+    """babe_model_summary"""
+    _fields_ = [("L", C.c_int), ("fs", C.c_float), ("nocts", C.c_int), ("bpo", C.c_int), ("Ns", C.c_int * 8),
+                ("params", C.c_long), ("device_bytes", C.c_long), ("cqt_device_bytes", C.c_long), ("device", C.c_int),
+                ("load_ms", C.c_double * 3)]
+
+
 # header struct name -> mirror (the layout test compiles a probe for each of them)
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv, "babe_unet_block": CBlock,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
-           "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc}
+           "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
+           "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
 _P, _L, _I, _F, _D, _S = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double, C.c_char_p
@@ -274,6 +292,14 @@ SIGS = {
     "babe_attn_param_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
     "babe_gn_param_grad_nogelu": (_I, [_P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P]),
     "babe_scale_channels": (_I, [_P, _P, _P, _I, _I, _L, _P]),
+    "babe_model_load": (_P, [_S, _P]),
+    "babe_model_create": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _P]),
+    "babe_model_destroy": (None, [_P]),
+    "babe_model_info": (_I, [_P, C.POINTER(ModelSummary)]),
+    "babe_model_setting": (_I, [_P, _S, C.POINTER(_D)]),
+    "babe_model_unet_plan": (_P, [_P]),
+    "babe_model_cqt_plan": (_P, [_P]),
+    "babe_model_eval_desc": (_I, [_P, _P, C.POINTER(EvalDesc)]),
 }
 
 

@@ -477,6 +477,8 @@ extern "C" void babe_cqt_plan_destroy(void* plan) {
 }
 
 extern "C" const void* babe_cqt_plan_design(const void* plan) { return plan ? static_cast<const CqtPlan*>(plan)->d : nullptr; }
+// bytes of the plan's device tables, for the owner of a plan inside this library (csrc/model.hip: babe_model_info)
+size_t babe_cqt_plan_table_bytes(const void* plan) { return plan ? static_cast<const CqtPlan*>(plan)->dev_bytes : 0; }
 
 namespace {
 // scratch of one transform call with B clips, whole floats: spectrum [B][2][KX], four-step intermediate [B][2][L], band spectra

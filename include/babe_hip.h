@@ -786,6 +786,45 @@ int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stat
  * its weight gradient. */
 int babe_scale_channels(const float* x, const float* scale, float* out, int B, int C, long hw, void* stream);
 
+
+/* ---- a whole network from one weights file (csrc/model.hip; the format: csrc/model_file.h, written by babe_amd/model_file.py,
+ * INTEGRATION.md section 2): what a host without Python calls instead of restating UnetEngine.__init__, ops.PackedConv, _FilmIndex,
+ * STFTOps and CEval.  The loader packs every image with this library's own pack kernels from the raw weights, as the Python
+ * engine does with its default forms, so babe_unet_fwd / _vjp, babe_score_eval and babe_sample_bwe on a loaded model are
+ * bit-identical to the same calls on Python-built descriptors (tests/test_gpu_model_c.py).
+ * Ownership: THE exception to "the library never allocates / never synchronises".  create / load allocate one arena on the
+ * CURRENT device (plus the CQT plan's tables), enqueue the upload and the pack kernels on `stream`, and wait on `stream` once
+ * before they release their host staging; destroy frees.  No other entry point here allocates or waits.  The device is recorded:
+ * babe_model_unet_plan / _cqt_plan / _eval_desc refuse while another device is current.  The handle outlives every plan pointer
+ * and descriptor taken from it: destroy it last.
+ * Refused with a message, before any device call, nothing allocated: a missing or empty file, a wrong magic, an unknown version, a
+ * truncated file, tensor data that overlaps or leaves the file, a duplicate / missing / unexpected name, a shape that does not fit
+ * the settings, attention flags, a precision other than f32, use_fencoding with bins per octave != 64, an audio length the
+ * mixed-radix FFT plan does not cover. */
+typedef struct { const char* name; int ndim; long shape[4]; const float* data; } babe_model_entry;   /* host fp32, state_dict name */
+typedef struct { const char* key; const char* str; double num; } babe_model_kv;                       /* str != NULL: a string setting */
+typedef struct {
+    int L; float fs; int nocts, bpo; int Ns[8];
+    long params;                 /* parameters and buffers of the network (the aux tables not counted) */
+    long device_bytes;           /* the arena, exactly as allocated */
+    long cqt_device_bytes;       /* the CQT plan's own tables (babe_cqt_plan_create_ex) */
+    int device;                  /* the device the model lives on */
+    double load_ms[3];           /* host wall time of create: read + parse + validate | staging + upload | pack + CQT plan + the wait */
+} babe_model_summary;
+void* babe_model_load(const char* path, void* stream);               /* NULL on failure: babe_last_error() */
+/* the same from tables in host memory: entries = every tensor the file would hold (the two aux.* tables included), settings = its
+ * settings block (dotted keys) */
+void* babe_model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream);
+void babe_model_destroy(void* model);
+int babe_model_info(const void* model, babe_model_summary* info);
+int babe_model_setting(const void* model, const char* key, double* value);   /* a numeric setting of the file; strings and unknown keys: error */
+const void* babe_model_unet_plan(const void* model);                 /* for babe_unet_workspace_bytes / babe_unet_fwd / babe_unet_vjp */
+const void* babe_model_cqt_plan(const void* model);                  /* babe_cqt_plan_create_ex(fs, L, octaves, bins, beta, 8192) */
+/* Fills EVERY field of desc: the plans, L, the embedding / FiLM pointers and dimensions, nfft, fs, env_inv, tw4096, and the sampler
+ * fields from the file's defaults (K and fit from tester.blind_bwe, blind = 1, shared = 0, hpf, xi, score_mode 0, audio_len_norm = L).
+ * unet_state: the caller's (babe_unet_state_create), one per concurrent stream.  The host overrides what it wants afterwards. */
+int babe_model_eval_desc(const void* model, void* unet_state, babe_eval_desc* desc);
+
 #ifdef __cplusplus
 }
 #endif
