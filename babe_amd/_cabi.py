@@ -86,7 +86,8 @@ class EvalDesc(C.Structure):
                 ("film_W", C.c_void_p), ("film_b", C.c_void_p), ("film_J", C.c_int),
                 ("nfft", C.c_int), ("fs", C.c_float), ("env_inv", C.c_void_p), ("tw4096", C.c_void_p), ("K", C.c_int),
                 ("fit", FitCfg), ("blind", C.c_int), ("shared", C.c_int), ("hpf", C.c_int),
-                ("xi", C.c_float), ("score_mode", C.c_int), ("audio_len_norm", C.c_float)]
+                ("xi", C.c_float), ("score_mode", C.c_int), ("audio_len_norm", C.c_float),
+                ("mask", C.c_void_p), ("mask_bs", C.c_long), ("dc_mask", C.c_void_p), ("dc_y", C.c_void_p)]
 
 
 class SampleStep(C.Structure):
@@ -98,6 +99,15 @@ class SampleStep(C.Structure):
 class SampleDesc(C.Structure):
     """babe_sample_desc"""
     _fields_ = [("eval", EvalDesc), ("T", C.c_int), ("steps", C.POINTER(SampleStep)), ("t0", C.c_float), ("warm_start", C.c_int)]
+
+
+class RecordingDesc(C.Structure):
+    """babe_recording_desc"""
+    _fields_ = [("eval", EvalDesc), ("T", C.c_int), ("t0", C.c_float), ("warm_start", C.c_int),
+                ("steps_blind", C.POINTER(SampleStep)), ("steps_known", C.POINTER(SampleStep)),
+                ("n_blind", C.c_int), ("blind_starts", C.c_long * 16), ("init_params", C.c_void_p),
+                ("target_std", C.c_float), ("overlap", C.c_long), ("discard_end", C.c_long),
+                ("inpaint_dc", C.c_int), ("dc_size", C.c_int), ("dc_window", C.c_void_p), ("std_dev", C.c_void_p)]
 
 
 class DnConvArgs(C.Structure):
@@ -133,6 +143,7 @@ class ModelSummary(C.Structure):
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv, "babe_unet_block": CBlock,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
            "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
+           "babe_recording_desc": RecordingDesc,
            "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
@@ -265,6 +276,13 @@ SIGS = {
     "babe_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I]),
     "babe_sample_bwe": (_I, [C.POINTER(SampleDesc), _P, _P, _P, _P, _L, _L, _P, _P, _P, _L, _I, _P]),
     "babe_edm_steps": (_I, [C.POINTER(SampleStep), _P, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
+    "babe_recording_plan": (_L, [_L, _L, _L, _L, _P, _P, _L]),
+    "babe_recording_workspace_bytes": (_L, [C.POINTER(RecordingDesc)]),
+    "babe_restore_recording": (_I, [C.POINTER(RecordingDesc), _P, _L, _P, _P, _P, _L, _L, _P, _L, _P]),
+    "babe_row_std": (_I, [_P, _L, _I, _L, _P, _P, _P]),
+    "babe_segment_cut": (_I, [_P, _L, _P, _L, _P]),
+    "babe_scale_dev": (_I, [_P, _P, _L, _F, _P, _I, _P]),
+    "babe_edge_masks": (_I, [_P, _P, _L, _L, _I, _P, _P]),
     "babe_dn_conv2d": (_I, [C.POINTER(DnConvArgs), _P, _P]),
     "babe_dn_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "babe_dn_packed_size": (_L, [_I, _I, _I, _I]),

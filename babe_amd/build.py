@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libbabe_hip.so")
-SOURCES = ["misc.hip", "conv.hip", "conv11p.hip", "conv_fewco.hip", "conv_bf16.hip", "conv_bf16p.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4p.hip", "conv_wino45.hip", "conv_wino85.hip", "norm.hip", "resample.hip", "resample_sinc.hip", "degrade.hip", "edm_tasks.hip", "cqt.hip", "cqt_plan.hip", "fft_mixed.hip", "unet_engine.hip", "score_eval.hip", "sample.hip", "model.hip", "randn.hip", "stft.hip", "sampler.hip", "denoiser.hip", "attention.hip", "attention_train.hip", "wgrad.hip", "fenc.hip", "loss.hip", "metrics.hip"]
+SOURCES = ["misc.hip", "conv.hip", "conv11p.hip", "conv_fewco.hip", "conv_bf16.hip", "conv_bf16p.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4p.hip", "conv_wino45.hip", "conv_wino85.hip", "norm.hip", "resample.hip", "resample_sinc.hip", "degrade.hip", "edm_tasks.hip", "cqt.hip", "cqt_plan.hip", "fft_mixed.hip", "unet_engine.hip", "score_eval.hip", "sample.hip", "recording.hip", "model.hip", "randn.hip", "stft.hip", "sampler.hip", "denoiser.hip", "attention.hip", "attention_train.hip", "wgrad.hip", "fenc.hip", "loss.hip", "metrics.hip"]
 
 
 # Every source is built WITHOUT packed-fp32 instructions: no SLP vectoriser (-fno-slp-vectorize) and the target feature
@@ -121,23 +121,25 @@ def _build_locked(force, verbose):
 EXAMPLE_SRC = os.path.join(os.path.dirname(HERE), "examples", "c_host", "babe_restore.c")
 
 
-def build_example(out=None, verbose=False):
-    """Compile examples/c_host/babe_restore.c (C99; no Python, no torch) against libbabe_hip.so and the HIP runtime with the
-    system's C compiler -> the program's path (default: next to its source).  Builds the library first if it is out of date.
-    The program finds libbabe_hip.so through an rpath to this directory."""
+def build_example(out=None, verbose=False, src=None):
+    """Compile examples/c_host/babe_restore.c - or `src`: another program of that directory, by file name or path - (C99; no
+    Python, no torch) against libbabe_hip.so and the HIP runtime with the system's C compiler -> the program's path (default: next
+    to its source).  Builds the library first if it is out of date.  The program finds libbabe_hip.so through an rpath to this
+    directory."""
     import shutil
     build(verbose=verbose)
-    out = out or os.path.splitext(EXAMPLE_SRC)[0]
+    src = EXAMPLE_SRC if src is None else (src if os.path.isabs(src) else os.path.join(os.path.dirname(EXAMPLE_SRC), src))
+    out = out or os.path.splitext(src)[0]
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
     cc = os.environ.get("CC") or shutil.which("cc") or shutil.which("gcc") or os.path.join(rocm, "llvm", "bin", "clang")
     cmd = [cc, "-std=c99", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", os.path.join(os.path.dirname(HERE), "include"),
-           "-I", os.path.join(rocm, "include"), EXAMPLE_SRC, "-o", out, "-L", HERE, "-lbabe_hip", "-L", os.path.join(rocm, "lib"),
-           "-lamdhip64", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"]
+           "-I", os.path.join(rocm, "include"), src, "-o", out, "-L", HERE, "-lbabe_hip", "-L", os.path.join(rocm, "lib"),
+           "-lamdhip64", "-lm", f"-Wl,-rpath,{HERE}", f"-Wl,-rpath,{os.path.join(rocm, 'lib')}"]
     if verbose:
         print(" ".join(cmd), flush=True)
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"building {EXAMPLE_SRC} failed:\n{r.stdout}")
+        raise RuntimeError(f"building {src} failed:\n{r.stdout}")
     return out
 
 
@@ -145,3 +147,4 @@ if __name__ == "__main__":
     build(force="--force" in sys.argv)
     if "--example" in sys.argv:
         print(build_example(verbose=True))
+        print(build_example(verbose=True, src="babe_restore_recording.c"))

@@ -1,6 +1,7 @@
-// What babe_score_eval (score_eval.hip) and babe_sample_bwe (sample.hip) both need of a babe_eval_desc before the first launch: the
-// STFT and CQT geometry, and the descriptor's completeness and range checks.
+// What babe_score_eval (score_eval.hip), babe_sample_bwe (sample.hip) and babe_restore_recording (recording.hip) need of a
+// babe_eval_desc and of a step table before the first launch: the STFT and CQT geometry, and the completeness and range checks.
 #pragma once
+#include <cmath>
 #include "common.h"
 #include "../../include/babe_hip.h"
 
@@ -30,9 +31,25 @@ inline bool geom(const babe_eval_desc* e, EvalGeom& g) {
 
 // who: the entry point's name, for the message
 inline int eval_desc_check(const babe_eval_desc* e, const char* who) {
+    BABE_CHECK_ARG(!(e->mask && e->blind), "%s: mask with blind = 1 (the AR observation model takes a known filter)", who);
+    BABE_CHECK_ARG(e->mask || (!e->dc_mask && !e->dc_y), "%s: dc_mask / dc_y without mask", who);
+    BABE_CHECK_ARG(!e->dc_mask == !e->dc_y, "%s: dc_mask and dc_y come together", who);
+    BABE_CHECK_ARG(!e->mask || e->mask_bs == 0 || e->mask_bs >= e->L, "%s: mask_bs = %ld (0, or at least L = %d)", who, e->mask_bs, e->L);
     BABE_CHECK_ARG(e->unet_plan && e->unet_state && e->cqt_plan && e->rff_freq && e->film_W && e->film_b && e->env_inv && e->tw4096,
                    "%s: incomplete evaluation descriptor", who);
     BABE_CHECK_ARG(e->K >= 1 && e->K <= 8 && e->rff_n > 0 && e->emb_dim[0] == 2 * e->rff_n, "%s: K = %d, rff_n = %d, emb_dim[0] = %d", who,
                    e->K, e->rff_n, e->emb_dim[0]);
+    return BABE_OK;
+}
+
+// the T rows of a run and its t0 (host memory)
+inline int sample_steps_check(const babe_sample_step* steps, int T, float t0, const char* who) {
+    BABE_CHECK_ARG(std::isfinite(t0), "%s: t0 is not finite", who);
+    for (int i = 0; i < T; ++i) {
+        const babe_sample_step& s = steps[i];
+        BABE_CHECK_ARG(s.t_hat > 0.f && std::isfinite(s.t_hat) && std::isfinite(s.inject) && std::isfinite(s.h) &&
+                           (s.heun == 0 || (s.heun == 1 && s.t_next > 0.f && std::isfinite(s.t_next))),
+                       "%s: step %d: t_hat = %g, inject = %g, t_next = %g, h = %g, heun = %d", who, i, s.t_hat, s.inject, s.t_next, s.h, s.heun);
+    }
     return BABE_OK;
 }

@@ -3,7 +3,8 @@
 // host: STFT of the observations, the initial state, and per step the noise injection (move_timestep :509-516), the score
 // evaluation (babe_score_eval, csrc/score_eval.hip) and the Euler or second-order Heun update (:687-761), with the filter
 // parameters handed from evaluation to evaluation on the device.
-// Scope: that of babe_score_eval.  Like it, the run contains no schedule formula: the caller passes one babe_sample_step per
+// Scope: that of babe_score_eval, the AR observation model of predict_bwe_AR included (desc.eval.mask / dc_mask: the loop is the
+// same, the descriptor goes through).  Like it, the run contains no schedule formula: the caller passes one babe_sample_step per
 // step (babe_edm_steps below fills the table for a host without the Python EDM class).  Same kernels, same order, same scalars
 // as the Python loop, so the two agree bit for bit (tests/test_gpu_sample_c.py).  Nothing allocates, nothing synchronises.
 #include <cmath>
@@ -65,14 +66,7 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
     Carver c{static_cast<char*>(ws), (size_t)ws_bytes, 256};
     carve(c, e, g, B, ev_bytes, w);
     BABE_CHECK_ARG(c.ok, "sample_bwe: workspace of %ld bytes, need %ld", ws_bytes, (long)c.used);
-    BABE_CHECK_ARG(std::isfinite(d->t0), "sample_bwe: t0 is not finite");
-    for (int i = 0; i < d->T; ++i) {
-        const babe_sample_step& s = d->steps[i];
-        BABE_CHECK_ARG(s.t_hat > 0.f && std::isfinite(s.t_hat) && std::isfinite(s.inject) && std::isfinite(s.h) &&
-                           (s.heun == 0 || (s.heun == 1 && s.t_next > 0.f && std::isfinite(s.t_next))),
-                       "sample_bwe: step %d: t_hat = %g, inject = %g, t_next = %g, h = %g, heun = %d", i, s.t_hat, s.inject, s.t_next, s.h,
-                       s.heun);
-    }
+    BABE_TRY(sample_steps_check(d->steps, d->T, d->t0, "sample_bwe"));
     if (!noise)
         BABE_CHECK_ARG(clip0 >= 0 && clip0 + B <= 0x100000000L && d->T + 1L < 0x100000000L, "sample_bwe: clip0 = %ld outside the counter word", clip0);
     const long L = e->L, n = (long)B * L;

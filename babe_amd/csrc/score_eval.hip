@@ -5,9 +5,11 @@
 //   filter fit (fit_params :533-595), design_filter / apply_filter (utils/blind_bwe_utils.py:82-119, 6-39), the reconstruction-
 //   guidance residual norm and its gradient through iSTFT o H o STFT and through the network (get_rec_grads :75-135), the score
 //   direction (:125-135, :701).
-// Scope: the default blind / known-fc_A configuration - L2 guidance norm, STFT-domain low-pass, no observation noise, no
-// data-consistency replacement, no AR mask, no FIR degradation (the options of the other tester YAMLs stay with the Python
-// sequencer, which this call equals bit for bit on the default path: tests/test_gpu_eval_c.py).
+// Scope: the default blind / known-fc_A configuration - L2 guidance norm, STFT-domain low-pass, no observation noise, no FIR
+// degradation - and, with desc.mask, the observation model of predict_bwe_AR over the known fc_A filter (:259-303): the mask mix
+// mask x + (1 - mask) A(x) and, with desc.dc_mask, the replacement step of inpaint_DC (:63-73).  The options of the other tester
+// YAMLs stay with the Python sequencer, which this call equals bit for bit on both paths: tests/test_gpu_eval_c.py,
+// tests/test_gpu_sample_ar_c.py.
 // Every intermediate lives in the caller's workspace (babe_eval_workspace_bytes); nothing is allocated, nothing synchronises.
 #include "common.h"
 #include "eval_geom.h"
@@ -89,7 +91,7 @@ extern "C" long babe_eval_workspace_bytes(const babe_eval_desc* e, int B) {
 extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t, float cskip, float cout, float cin, float cnoise,
                                const float* y, const float* specY, float* params, float* d, float* x_den, int* n_iter, void* ws,
                                long ws_bytes, int B, void* stream) {
-    BABE_CHECK_ARG(e && x && y && specY && params && d && x_den && ws && ws_bytes >= 0 && B > 0, "score_eval: bad arguments");
+    BABE_CHECK_ARG(e && x && y && (specY || !e->blind) && params && d && x_den && ws && ws_bytes >= 0 && B > 0, "score_eval: bad arguments");
     BABE_TRY(eval_desc_check(e, "score_eval"));
     BABE_CHECK_ARG(eval_dims_ok(e), "score_eval: nfft = %d, L = %d", e->nfft, e->L);
     EvalGeom g;
@@ -123,12 +125,32 @@ extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t,
     BABE_TRY(babe_design_filter(params, w.H, P, e->K, g.nbins, e->fs, e->nfft, stream));
     const long H_bs = P == B ? g.nbins : 0;            // per-clip filters, or one filter for the batch
     // ---- reconstruction guidance: residual y - A(x_den), its norm's gradient through iSTFT o H o STFT
+    float* const g_raw = e->hpf ? w.hp : w.g_den;       // the guidance gradient before the high-pass
     BABE_TRY(babe_spec_filter_istft(w.specX, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
-    BABE_TRY(babe_ola(w.fr, e->env_inv, y, L, w.r, L, w.part, 64, B, (int)L, e->nfft, g.frames, stream));
-    BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, w.seed, L, B, (int)L, stream));
-    BABE_TRY(babe_stft_fwd(w.seed, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
-    BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
-    BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, e->hpf ? w.hp : w.g_den, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+    if (!e->mask) {
+        BABE_TRY(babe_ola(w.fr, e->env_inv, y, L, w.r, L, w.part, 64, B, (int)L, e->nfft, g.frames, stream));
+        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, w.seed, L, B, (int)L, stream));
+        BABE_TRY(babe_stft_fwd(w.seed, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+        BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+        BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, g_raw, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+    } else {
+        // MaskMixDegradation over the STFT filter (babe_amd/degrade.py:191-213): r = y - (mask x_den + (1 - mask) A(x_den)); the
+        // observed part takes the seed as it is, the filtered part the seed with the overlap-add envelope through A^T.  The
+        // denoiser's buffers are free here and carry the intermediates: no buffer of its own.
+        float *ax = w.xin, *mix = w.net, *s_post = w.g_net, *seed_f = w.g_xin, *gA = w.xin, *seed_o = w.net;
+        BABE_TRY(babe_ola(w.fr, e->env_inv, nullptr, 0, ax, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+        BABE_TRY(babe_mask_blend(mix, e->mask, e->mask_bs, x_den, ax, B, L, stream));
+        BABE_TRY(babe_lincomb3(w.r, 1.f, y, -1.f, mix, 0.f, nullptr, n, stream));
+        BABE_TRY(babe_sumsq_partial(w.r, L, w.part, 64, B, L, stream));
+        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, nullptr, w.seed, L, B, (int)L, stream));
+        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, s_post, L, B, (int)L, stream));
+        BABE_TRY(babe_mask_blend(seed_f, e->mask, e->mask_bs, nullptr, s_post, B, L, stream));
+        BABE_TRY(babe_stft_fwd(seed_f, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+        BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+        BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, gA, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+        BABE_TRY(babe_mask_blend(seed_o, e->mask, e->mask_bs, w.seed, nullptr, B, L, stream));
+        BABE_TRY(babe_lincomb3(g_raw, 1.f, seed_o, 1.f, gA, 0.f, nullptr, n, stream));
+    }
     if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.hp, w.g_den, w.cqws, B, stream));
     // ---- through the network: g_x = cskip g_den + cin net^T(cout g_den)
     BABE_TRY(babe_lincomb3(w.g_net, cout, w.g_den, 0.f, nullptr, 0.f, nullptr, n, stream));
@@ -138,5 +160,20 @@ extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t,
     BABE_TRY(babe_lincomb3(w.xd, cskip, w.g_den, cin, w.g_xin, 0.f, nullptr, n, stream));                 // g_x (xd is free again)
     BABE_TRY(babe_sumsq_partial(w.xd, L, w.gpart, 64, B, L, stream));
     BABE_TRY(babe_score_direction(x_den, x, w.xd, w.gpart, 64, d, t, e->xi, (float)e->audio_len_norm, e->shared, e->score_mode, B, L, stream));
+    if (e->dc_mask) {
+        // replacement data-consistency step of inpaint_DC on the Tweedie estimate x0 = x - t d: x0 <- (1 - dc_mask) x0 + dc_y, and
+        // back to a direction (the scalars as the Python sequencer forms them: in double, rounded once)
+        float *x0 = w.xin, *kept = w.net, *x0r = w.r;
+        const float inv_t = (float)(1.0 / (double)t), neg_inv_t = (float)(-1.0 / (double)t);
+        BABE_TRY(babe_lincomb3(x0, 1.f, x, -t, d, 0.f, nullptr, n, stream));
+        BABE_TRY(babe_mask_blend(kept, e->dc_mask, e->mask_bs, nullptr, x0, B, L, stream));
+        if (e->mask_bs == L || B == 1) {
+            BABE_TRY(babe_lincomb3(x0r, 1.f, kept, 1.f, e->dc_y, 0.f, nullptr, n, stream));
+        } else {                                        // dc_y rows at stride mask_bs (0: one row for every clip)
+            for (int b = 0; b < B; ++b)
+                BABE_TRY(babe_lincomb3(x0r + b * L, 1.f, kept + b * L, 1.f, e->dc_y + b * e->mask_bs, 0.f, nullptr, L, stream));
+        }
+        BABE_TRY(babe_lincomb3(d, inv_t, x, neg_inv_t, x0r, 0.f, nullptr, n, stream));
+    }
     return BABE_OK;
 }

@@ -46,8 +46,8 @@ class BlindSampler:
 
     def __init__(self, model, diff_params, args, rid=False, batch_semantics="per_clip", noise_device="cpu",
                  max_segments_in_flight=32, loop="python", seed=None):
-        """loop: "python" (the default) - this class sequences the sampling loop; "library" - predict_blind_bwe and
-        predict_bwe(..., 'fc_A') run as ONE babe_sample_bwe call (csrc/sample.hip through testing/sample_c.py) where
+        """loop: "python" (the default) - this class sequences the sampling loop; "library" - predict_blind_bwe,
+        predict_bwe(..., 'fc_A') and predict_bwe_AR(..., 'fc_A') run as ONE babe_sample_bwe call (csrc/sample.hip through testing/sample_c.py) where
         sample_c.supported holds, and on the Python loop otherwise.  seed: None - the library run is fed torch's draws (_randn) as
         a [T+1][B][L] buffer; an integer - it draws from the library's counter-based generator (csrc/randn.hip), clip clip0 + b,
         draw 0 for the initial state and i + 1 for step i: a function of (weights, y, seed) alone, whatever the batching.
@@ -603,8 +603,10 @@ class BlindSampler:
         return new.unsqueeze(0).expand(B, -1).contiguous().to(mask.device)
 
     def predict_bwe_AR(self, ylpf, y_masked, filt, filt_type, rid=False, test_filter_fit=False, compute_sweep=False,
-                       mask=None):
-        """(:259-303) observations = mask*y_masked + (1-mask)*ylpf; degradation(x) = mask*x + (1-mask)*A(x)."""
+                       mask=None, clip0=0):
+        """(:259-303) observations = mask*y_masked + (1-mask)*ylpf; degradation(x) = mask*x + (1-mask)*A(x).
+        With loop="library" and 'fc_A' the run is ONE babe_sample_bwe call (the mask and the inpaint_DC pair go in its
+        descriptor); 'firwin' stays on the Python loop.  clip0: as for predict_bwe (seeded noise only)."""
         assert mask is not None
         if test_filter_fit or compute_sweep:
             raise NotImplementedError("test_filter_fit / compute_sweep (logging only)")
@@ -622,5 +624,5 @@ class BlindSampler:
             dc = (sm, mask_blend(sm, y_masked, None))
             self.data_consistency = True                      # the reference flips this permanently (:300)
         with self._guiding(MaskMixDegradation(mask, inner), dc):
-            res = self._sample(y, params, blind=False, rid=rid, snoise=self.diff_params.Snoise)
+            res = self._sample(y, params, blind=False, rid=rid, snoise=self.diff_params.Snoise, clip0=clip0)
         return res if rid else res[0]

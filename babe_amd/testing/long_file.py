@@ -8,6 +8,8 @@ overlap-added.  The reference restores the segments one at a time; they are inde
 batched (per-clip semantics) and can be sharded over GPUs.  Host-side plumbing only (slicing / cross-fade);
 the sampler does the work.
 """
+import itertools
+
 import torch
 
 
@@ -80,13 +82,17 @@ def restore_file(sampler, y, batch_size=8, blind=True, filt=None, filt_type="fc_
     return out, [((s, s + segL), f) for (s, _), f in zip(plan, filters)]
 
 
-def restore_file_AR(sampler, y, filt, filt_type="fc_A", overlap_s=0.25, discard_end=200):
+def restore_file_AR(sampler, y, filt, filt_type="fc_A", overlap_s=0.25, discard_end=200, clip0=None):
     """Autoregressive out-painting of a whole recording with a KNOWN (previously estimated) filter, as the second
     half of BlindTester.test_real_blind_bwe_complete does (/root/reference/testing/blind_bwe_tester.py:786-859):
     the first segment is restored with predict_bwe, every following segment starts `overlap` samples inside the
     previous result, which is passed as already-known signal (mask = 1 there) to predict_bwe_AR.  Sequential by
-    construction; y [L] device tensor -> restored [L]."""
+    construction; y [L] device tensor -> restored [L].
+    clip0: None - every call numbers its seeded noise from clip 0, as before; an integer - segment j of the walk draws as clip
+    clip0 + j (the numbering of babe_restore_recording, csrc/recording.hip)."""
     segL = sampler.args.exp.audio_len
+    seg_no = itertools.count()
+    ckw = lambda: {} if clip0 is None else {"clip0": int(clip0) + next(seg_no)}     # (one call per segment, in the walk's order)
     overlap = int(overlap_s * sampler.args.exp.sample_rate)
     L = y.shape[-1]
     dev = y.device
@@ -94,9 +100,9 @@ def restore_file_AR(sampler, y, filt, filt_type="fc_A", overlap_s=0.25, discard_
     if L <= segL:
         seg = torch.zeros(1, segL, device=dev)
         seg[0, :L] = y
-        return sampler.predict_bwe(seg, filt, filt_type)[0, :L]
+        return sampler.predict_bwe(seg, filt, filt_type, **ckw())[0, :L]
     ix = 0
-    pred = sampler.predict_bwe(y[ix:ix + segL].unsqueeze(0).contiguous(), filt, filt_type)
+    pred = sampler.predict_bwe(y[ix:ix + segL].unsqueeze(0).contiguous(), filt, filt_type, **ckw())
     prev = pred[..., : segL - discard_end]
     out[ix:ix + segL - discard_end] = prev[0]
     ix += segL - overlap - discard_end
@@ -105,7 +111,7 @@ def restore_file_AR(sampler, y, filt, filt_type="fc_A", overlap_s=0.25, discard_
     mask[..., overlap:] = 0
     while ix < L - segL - discard_end:
         y_masked[..., :overlap] = prev[..., segL - overlap - discard_end:]
-        pred = sampler.predict_bwe_AR(y[ix:ix + segL].unsqueeze(0).contiguous(), y_masked, filt, filt_type, mask=mask)
+        pred = sampler.predict_bwe_AR(y[ix:ix + segL].unsqueeze(0).contiguous(), y_masked, filt, filt_type, mask=mask, **ckw())
         prev = pred[..., : segL - discard_end]
         out[ix:ix + segL - discard_end] = prev[0]
         ix += segL - overlap - discard_end
@@ -120,7 +126,7 @@ def restore_file_AR(sampler, y, filt, filt_type="fc_A", overlap_s=0.25, discard_
     else:
         seg_zp = seg[:segL].unsqueeze(0).contiguous()
         n = segL
-    pred = sampler.predict_bwe_AR(seg_zp, y_masked, filt, filt_type, mask=mask)
+    pred = sampler.predict_bwe_AR(seg_zp, y_masked, filt, filt_type, mask=mask, **ckw())
     out[ix:ix + n] = pred[0, :n]
     return out
 
@@ -141,7 +147,7 @@ def rate_plan(fs, sample_rate, denoiser_rate=None):
 
 
 def restore_recording_complete(sampler, degraded, *, n_segments_blindstep=1, ix_start=0, std=0.1, overlap_s=0.25,
-                               typefilter="fc_A", denoiser=None, rng=None, fs=None, sample_rate_denoiser=None):
+                               typefilter="fc_A", denoiser=None, rng=None, fs=None, sample_rate_denoiser=None, clip0=None):
     """Whole-recording flow of BlindTester.test_real_blind_bwe_complete (/root/reference/testing/blind_bwe_tester.py:
     710-867; with the denoiser pre-pass: testing/denoise_and_bwe_tester.py:248-411, config #5):
 
@@ -159,6 +165,9 @@ def restore_recording_complete(sampler, degraded, *, n_segments_blindstep=1, ix_
     exactly where testing/denoise_and_bwe_tester.py:279-289 has them: with a denoiser, fs -> sample_rate_denoiser before it and
     sample_rate_denoiser -> exp.sample_rate after it - BOTH only `if fs != sample_rate_denoiser`, as the reference writes it (a
     file already at the denoiser's rate goes to the model unconverted there too); without one, fs -> exp.sample_rate.
+    A file shorter than one segment has one blind segment, the zero-padded file (the reference has no such case: its network
+    takes audio_len samples).  clip0: None - the seeded noise of every call is numbered from clip 0, as before; an integer - the
+    numbering of babe_restore_recording: blind row b draws as clip clip0 + b, segment j of the AR walk as clip0 + n + j.
     Returns (restored [L'] at exp.sample_rate, estimated_filter [2, K], blind-step prediction [n, segL])."""
     import numpy as np
     rng = rng or np.random
@@ -179,7 +188,10 @@ def restore_recording_complete(sampler, degraded, *, n_segments_blindstep=1, ix_
     d = std * d / s.unsqueeze(-1)
     L = d.shape[-1]
     ix_first = int(args.exp.sample_rate * ix_start)
-    if n_segments_blindstep == 1:
+    if L < segL:
+        y = torch.zeros(n_segments_blindstep, segL, device=d.device)
+        y[:, :L] = d[0]
+    elif n_segments_blindstep == 1:
         y = d[..., ix_first:ix_first + segL]
     else:
         y = d[..., ix_first:ix_first + segL].repeat(n_segments_blindstep, 1)
@@ -189,8 +201,80 @@ def restore_recording_complete(sampler, degraded, *, n_segments_blindstep=1, ix_
     keep = sampler.batch_semantics
     sampler.batch_semantics = "reference"
     try:
-        pred, estimated_filter = sampler.predict_blind_bwe(y.contiguous())
+        pred, estimated_filter = sampler.predict_blind_bwe(y.contiguous(), **({} if clip0 is None else {"clip0": int(clip0)}))
     finally:
         sampler.batch_semantics = keep
-    out = restore_file_AR(sampler, d[0], estimated_filter, typefilter, overlap_s=overlap_s)
+    out = restore_file_AR(sampler, d[0], estimated_filter, typefilter, overlap_s=overlap_s,
+                          clip0=None if clip0 is None else int(clip0) + y.shape[0])
     return out * (s / std), estimated_filter, pred
+
+
+def blind_starts_for(L, segL, sample_rate, n_segments_blindstep=1, ix_start=0, rng=None):
+    """The first samples of the blind step's segments, picked as restore_recording_complete picks them: the segment at ix_start
+    seconds if there is one, else that many draws of rng.randint(0, L - segL) (numpy's global generator by default); a file
+    shorter than a segment has the one at 0."""
+    import numpy as np
+    rng = rng or np.random
+    if L < segL:
+        return [0] * n_segments_blindstep
+    if n_segments_blindstep == 1:
+        return [int(sample_rate * ix_start)]
+    return [int(rng.randint(0, L - segL)) for _ in range(n_segments_blindstep)]
+
+
+def restore_recording_library(sampler, degraded, *, blind_starts, std=0.1, overlap_s=0.25, clip0=0, std_dev=None, discard_end=200):
+    """restore_recording_complete(..., clip0=clip0) without denoiser and rate conversion as ONE library call
+    (babe_restore_recording, csrc/recording.hip): degraded [L] or [1, L] on the GPU at exp.sample_rate; blind_starts: first
+    samples of the blind step's segments (blind_starts_for picks them the way the Python flow does).  The noise comes from the
+    library's generator under sampler.seed.  std_dev: a device tensor [1] holding the file's standard deviation (torch's, for
+    a bit-exact comparison with the Python flow), None: the call computes it.
+    Returns (restored [L], estimated_filter [2, K], blind-step prediction [n, segL]) like restore_recording_complete."""
+    import ctypes as C
+    from .._cabi import RecordingDesc
+    from .._lib import check, lib, ptr, stream
+    from . import eval_c, sample_c
+    smp, args = sampler, sampler.args
+    segL = int(args.exp.audio_len)
+    rec = degraded.reshape(-1).float().contiguous()
+    L = rec.numel()
+    if smp.seed is None:
+        raise ValueError("restore_recording_library draws from the library's generator: the sampler needs a seed")
+    if smp.data_consistency:
+        raise ValueError("restore_recording_library: posterior_sampling.data_consistency is set (by the configuration, or by an "
+                         "earlier predict_bwe_AR on this sampler): the classic replacement step stays with the Python flow")
+    if not eval_c.supported(smp, rec, True):
+        raise ValueError("restore_recording_library: this sampler's configuration stays with the Python flow "
+                         "(testing/eval_c.py::supported)")
+    with torch.cuda.device(rec.device):
+        smp.stft_ops(segL, rec.device)
+        cs = smp._csample
+        if cs is None or cs.ce._keep[1] is not smp._stft:
+            cs = smp._csample = sample_c.CSample(smp)
+        init = smp._init_params(1, rec.device)[0].contiguous()
+        T, dp = smp.nb_steps, smp.diff_params
+        rows_b, t0, _ = sample_c.steps_from(dp, T, smp.order, smp.start_sigma, 1.0)
+        rows_k, _, _ = sample_c.steps_from(dp, T, smp.order, smp.start_sigma, dp.Snoise)
+        size = 50                                                   # predict_bwe_AR smooths its mask over 50 samples
+        window = torch.hann_window(2 * size).to(rec.device)
+        d = RecordingDesc()
+        d.eval = cs.ce.desc
+        eval_c.CEval.observe(d.eval, smp)                           # (all off: the call sets the masks)
+        d.eval.K, d.eval.shared = int(init.shape[-1]), int(smp.batch_semantics == "reference")
+        d.T, d.t0, d.warm_start, d.steps_blind, d.steps_known = T, t0, int(smp.start_sigma is not None), rows_b, rows_k
+        d.n_blind = len(blind_starts)
+        for j, ix in enumerate(blind_starts[:16]):
+            d.blind_starts[j] = int(ix)
+        d.init_params, d.target_std = ptr(init), float(std)
+        d.overlap, d.discard_end = int(overlap_s * args.exp.sample_rate), int(discard_end)
+        d.inpaint_dc, d.dc_size, d.dc_window = int(bool(args.tester.complete_recording.inpaint_DC)), size, ptr(window)
+        d.std_dev = ptr(std_dev)
+        need = lib().babe_recording_workspace_bytes(C.byref(d))
+        if need < 0:
+            check(int(need), "recording_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=rec.device)
+        out = torch.empty(L, device=rec.device)
+        filt = torch.empty(2, d.eval.K, device=rec.device)
+        pred = torch.empty(d.n_blind, segL, device=rec.device)
+        check(lib().babe_restore_recording(C.byref(d), ptr(rec), L, ptr(out), ptr(filt), ptr(pred), int(smp.seed), int(clip0), ptr(ws),
+                                           need, stream(rec)), "restore_recording")
+    return out, filt, pred

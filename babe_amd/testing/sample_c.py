@@ -1,8 +1,8 @@
 """BlindSampler(loop="library"): a whole sampling run as ONE call into the library (csrc/sample.hip, babe_sample_bwe) - the path a
 non-Python host takes: the evaluation descriptor of testing/eval_c.py, one babe_sample_step row per step made from the EDM object,
-and the noise either as a [T+1][B][L] buffer or from the library's counter-based generator (csrc/randn.hip).  Default
-configuration only, like the library evaluation; everything else stays with the Python loop.  Bit-identical to it:
-tests/test_gpu_sample_c.py."""
+and the noise either as a [T+1][B][L] buffer or from the library's counter-based generator (csrc/randn.hip).  The
+configurations of the library evaluation (predict_bwe_AR(..., 'fc_A') among them); everything else stays with the Python loop.
+Bit-identical to it: tests/test_gpu_sample_c.py, tests/test_gpu_sample_ar_c.py."""
 import ctypes as C
 
 import torch
@@ -61,6 +61,7 @@ class CSample:
         d = SampleDesc()
         d.eval = self.ce.desc                       # (by value)
         d.eval.K, d.eval.blind = int(filter_params.shape[-1]), int(bool(blind))
+        eval_c.CEval.observe(d.eval, smp)
         d.T, d.steps, d.t0, d.warm_start = T, rows, t0, int(bool(warm_start))
         ws = workspace(self._ws, (B, T), lambda: lib().babe_sample_workspace_bytes(C.byref(d), B), y.device, "sample")
         if noise is not None:

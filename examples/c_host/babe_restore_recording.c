@@ -1,0 +1,155 @@
+/* babe_restore_recording: blind bandwidth extension of a whole recording from C - no Python, no torch in the process.
+ *
+ *     babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s]
+ *
+ * model.babe: written by `python -m babe_amd.export`.  in.f32: the recording, float32 samples of any length at the model's rate.
+ * out.f32: the restored recording, as many samples.  The low-pass filter of the recording is estimated blind on
+ * --blind-segments segments (default 1: the one that starts --ix-start seconds into the file, default 0; more: evenly spread
+ * over the file), then the file is restored segment by segment, every segment out-painted from the end of the previous one.
+ * The estimated filter is printed: K cut-off frequencies in Hz, then K slopes in dB.  --T: sampling steps (default: the file's
+ * tester.T); --seed: the noise is the library's counter-based generator under this seed (default 0), so the output is a
+ * function of (model, input, seed, T, blind segments).  Links against libbabe_hip.so and the HIP runtime
+ * (babe_amd/build.py::build_example).  Exit status: 0, or 1 with the failing step and babe_last_error() on stderr. */
+#include <hip/hip_runtime_api.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "babe_hip.h"
+
+#define FAIL(...) do { fprintf(stderr, "babe_restore_recording: " __VA_ARGS__); fprintf(stderr, "\n"); goto done; } while (0)
+#define LIB(call, what) do { if ((call) != 0) FAIL("%s: %s", what, babe_last_error()); } while (0)
+#define HIP(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) FAIL("%s: %s", what, hipGetErrorString(e_)); } while (0)
+
+#define DC_SIZE 50          /* predict_bwe_AR smooths the edge of its mask over 50 samples */
+#define DISCARD_END 200     /* samples at the end of a restored segment that are not kept */
+
+static double setting(const void* model, const char* key, double fallback) {
+    double v;
+    return babe_model_setting(model, key, &v) == 0 ? v : fallback;
+}
+
+int main(int argc, char** argv) {
+    int status = 1, T = 0, n_blind = 1;
+    long seed = 0, Lrec = 0;
+    double ix_start = 0.0;
+    void *model = NULL, *state = NULL, *ws = NULL;
+    float *rec = NULL, *out = NULL, *filter = NULL, *init = NULL, *window = NULL, *host = NULL;
+    babe_sample_step* steps = NULL;
+    FILE* fh = NULL;
+    if (argc < 4) {
+        fprintf(stderr, "usage: babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s]\n");
+        return 2;
+    }
+    for (int i = 4; i < argc; ++i) {
+        if (i + 1 >= argc) FAIL("option %s needs a value", argv[i]);
+        if (!strcmp(argv[i], "--seed")) seed = atol(argv[++i]);
+        else if (!strcmp(argv[i], "--T")) T = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--blind-segments")) n_blind = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--ix-start")) ix_start = atof(argv[++i]);
+        else FAIL("unknown option %s", argv[i]);
+    }
+    if (n_blind < 1 || n_blind > 16) FAIL("--blind-segments must be 1..16");
+
+    /* the recording */
+    fh = fopen(argv[2], "rb");
+    if (!fh) FAIL("cannot open %s", argv[2]);
+    if (fseek(fh, 0, SEEK_END) != 0 || (Lrec = ftell(fh) / (long)sizeof(float)) < 2) FAIL("%s: fewer than 2 float32 samples", argv[2]);
+    rewind(fh);
+    host = (float*)malloc((size_t)Lrec * sizeof(float));
+    if (!host) FAIL("out of memory");
+    if (fread(host, sizeof(float), (size_t)Lrec, fh) != (size_t)Lrec) FAIL("cannot read %s", argv[2]);
+    fclose(fh), fh = NULL;
+
+    /* [core] the listing of INTEGRATION.md, "A whole recording from one call" */
+    /* 1. the network and one evaluation's bookkeeping, as in babe_restore.c */
+    model = babe_model_load(argv[1], NULL);
+    if (!model) FAIL("babe_model_load: %s", babe_last_error());
+    state = babe_unet_state_create();
+    if (!state) FAIL("babe_unet_state_create failed");
+    babe_recording_desc d;
+    memset(&d, 0, sizeof d);
+    LIB(babe_model_eval_desc(model, state, &d.eval), "babe_model_eval_desc");
+    const int K = d.eval.K;
+    const long segL = d.eval.L;
+
+    /* 2. two step tables over one schedule: the blind loop injects with Snoise = 1, the known-filter loops with the tester's */
+    if (T == 0) T = (int)setting(model, "tester.T", 35);
+    if (T < 2) FAIL("--T must be at least 2");
+    steps = (babe_sample_step*)calloc((size_t)2 * T, sizeof *steps);
+    if (!steps) FAIL("out of memory");
+    const double start_sigma = setting(model, "tester.posterior_sampling.start_sigma", -1.0);
+    const double snoise[2] = {1.0, setting(model, "tester.diff_params.Snoise", 1.0)};
+    for (int k = 0; k < 2; ++k)
+        LIB(babe_edm_steps(steps + k * T, &d.t0, T, (int)setting(model, "tester.order", 2), setting(model, "tester.diff_params.sigma_min", 1e-4),
+                           setting(model, "tester.diff_params.sigma_max", 1.0), setting(model, "tester.diff_params.ro", 8.0),
+                           setting(model, "tester.diff_params.sigma_data", 0.063), setting(model, "tester.diff_params.Schurn", 10.0),
+                           setting(model, "tester.diff_params.Stmin", 0.0), setting(model, "tester.diff_params.Stmax", 50.0), snoise[k],
+                           start_sigma),
+            "babe_edm_steps");
+    d.T = T, d.steps_blind = steps, d.steps_known = steps + T, d.warm_start = start_sigma > 0;
+
+    /* 3. the policy is the host's: where the blind segments start, how loud the model hears the file, how far segments overlap */
+    d.n_blind = Lrec > segL ? n_blind : 1;
+    for (int j = 0; j < d.n_blind; ++j)
+        d.blind_starts[j] = Lrec <= segL ? 0 : d.n_blind == 1 ? (long)(ix_start * d.eval.fs) : (long)((double)j * (Lrec - segL) / (d.n_blind - 1));
+    d.target_std = (float)setting(model, "tester.complete_recording.std", 0.1);
+    d.overlap = (long)(0.25 * d.eval.fs), d.discard_end = DISCARD_END;
+    d.inpaint_dc = (int)setting(model, "tester.complete_recording.inpaint_DC", 1), d.dc_size = DC_SIZE;
+    d.std_dev = NULL;                             /* the call measures the file */
+
+    /* 4. tables come from the caller: the initial filter and the periodic Hann window the mask's edge is smoothed with */
+    float host_init[2 * 8], host_window[2 * DC_SIZE];
+    for (int k = 0; k < K; ++k) {
+        char key[64];
+        snprintf(key, sizeof key, "tester.blind_bwe.initial_conditions.fc.%d", k);
+        host_init[k] = (float)setting(model, key, 0);
+        snprintf(key, sizeof key, "tester.blind_bwe.initial_conditions.A.%d", k);
+        host_init[K + k] = (float)setting(model, key, 0);
+    }
+    for (int k = 0; k < 2 * DC_SIZE; ++k) host_window[k] = (float)(0.5 - 0.5 * cos(2.0 * 3.14159265358979323846 * k / (2 * DC_SIZE)));
+    HIP(hipMalloc((void**)&init, sizeof host_init), "hipMalloc(init)");
+    HIP(hipMalloc((void**)&window, sizeof host_window), "hipMalloc(window)");
+    HIP(hipMemcpy(init, host_init, sizeof host_init, hipMemcpyHostToDevice), "hipMemcpy(init)");
+    HIP(hipMemcpy(window, host_window, sizeof host_window, hipMemcpyHostToDevice), "hipMemcpy(window)");
+    d.init_params = init, d.dc_window = window;
+
+    /* 5. the workspace does not depend on the file's length; 6. the file and the result are the caller's buffers */
+    const long ws_bytes = babe_recording_workspace_bytes(&d);
+    if (ws_bytes < 0) FAIL("babe_recording_workspace_bytes: %s", babe_last_error());
+    HIP(hipMalloc(&ws, (size_t)ws_bytes), "hipMalloc(workspace)");
+    HIP(hipMalloc((void**)&rec, (size_t)Lrec * sizeof(float)), "hipMalloc(rec)");
+    HIP(hipMalloc((void**)&out, (size_t)Lrec * sizeof(float)), "hipMalloc(out)");
+    HIP(hipMalloc((void**)&filter, (size_t)2 * K * sizeof(float)), "hipMalloc(filter)");
+    HIP(hipMemcpy(rec, host, (size_t)Lrec * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(rec)");
+
+    /* 7. the whole recording: blind estimate, then the autoregressive walk, enqueued by one call */
+    LIB(babe_restore_recording(&d, rec, Lrec, out, filter, NULL, seed, 0, ws, ws_bytes, NULL), "babe_restore_recording");
+    HIP(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    HIP(hipMemcpy(host, out, (size_t)Lrec * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(out)");
+    HIP(hipMemcpy(host_init, filter, (size_t)2 * K * sizeof(float), hipMemcpyDeviceToHost), "hipMemcpy(filter)");
+    /* [/core] */
+
+    printf("fc_Hz");
+    for (int k = 0; k < K; ++k) printf(" %.9g", host_init[k]);
+    printf("\nA_dB");
+    for (int k = 0; k < K; ++k) printf(" %.9g", host_init[K + k]);
+    printf("\n");
+    fh = fopen(argv[3], "wb");
+    if (!fh || fwrite(host, sizeof(float), (size_t)Lrec, fh) != (size_t)Lrec) FAIL("cannot write %s", argv[3]);
+    fclose(fh), fh = NULL;
+    status = 0;
+done:
+    if (fh) fclose(fh);
+    free(host), free(steps);
+    if (ws) (void)hipFree(ws);
+    if (rec) (void)hipFree(rec);
+    if (out) (void)hipFree(out);
+    if (filter) (void)hipFree(filter);
+    if (init) (void)hipFree(init);
+    if (window) (void)hipFree(window);
+    if (state) babe_unet_state_destroy(state);
+    if (model) babe_model_destroy(model);          /* last: the descriptor points into its arena */
+    return status;
+}

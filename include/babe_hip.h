@@ -557,8 +557,11 @@ int babe_score_direction(const float* xden, const float* xhat, const float* g, c
  * Python (testing/blind_bwe_sampler.py:75-170, 503-595, 687-761; diff_params/edm.py:144-159), as one call for a non-Python host:
  * preconditioned denoiser (CQT.fwd -> UNet -> CQT.bwd) -> apply_hpf_DC -> STFT -> [filter fit] -> filter design -> residual
  * y - A(x_den) and the gradient of its norm through iSTFT o H o STFT, the high-pass and the network -> score direction.
- * Default configuration only (L2 guidance norm, STFT-domain low-pass, no observation noise / data-consistency / AR mask / FIR);
- * bit-identical to the Python sequencer on it (tests/test_gpu_eval_c.py).  No allocation, no synchronisation. */
+ * Default configuration (L2 guidance norm, STFT-domain low-pass, no observation noise / FIR) and, with desc.mask, the AR
+ * observation model over the known filter: residual y - (mask x_den + (1 - mask) A(x_den)), gradient mask s + A^T((1 - mask)
+ * s_post), and with desc.dc_mask the replacement step on x0 = x - t d after the score direction.  Bit-identical to the Python
+ * sequencer on both (tests/test_gpu_eval_c.py, tests/test_gpu_sample_ar_c.py).  specY may be NULL when blind = 0.  No allocation,
+ * no synchronisation. */
 typedef struct {
     const void* unet_plan; void* unet_state;      /* babe_unet_plan_create / babe_unet_state_create (one state per stream) */
     const void* cqt_plan;                         /* babe_cqt_plan_create for (fs, L) */
@@ -577,6 +580,12 @@ typedef struct {
     int shared;                                   /* 1: the reference's batch coupling (one filter, whole-batch norms); 0: per clip */
     int hpf;                                      /* tester.filter_out_cqt_DC_Nyq */
     float xi; int score_mode; float audio_len_norm;   /* babe_score_direction's xi, mode and audio_len */
+    /* the observation model of predict_bwe_AR (blind_bwe_sampler.py:259-303), all NULL / 0 = off (babe_model_eval_desc sets that):
+     * mask [L], or [B][L] at row stride mask_bs (0: one mask for every clip) - 1 where y is the known signal itself, 0 where it
+     * is the filtered one; needs blind = 0.  dc_mask / dc_y (together, and only with mask; rows at the same stride): the
+     * smoothed mask and dc_mask * y_masked of the replacement step x0 <- (1 - dc_mask) x0 + dc_y of inpaint_DC (:63-73). */
+    const float* mask; long mask_bs;
+    const float* dc_mask; const float* dc_y;
 } babe_eval_desc;
 long babe_eval_workspace_bytes(const babe_eval_desc* desc, int B);
 int babe_score_eval(const babe_eval_desc* desc, const float* x, float t, float cskip, float cout, float cin, float cnoise,
@@ -604,8 +613,8 @@ int babe_rand_bits(int* out, long out_bs, int B, long n, long seed, long clip0, 
  * _heun_second sequence from Python (testing/blind_bwe_sampler.py:619-769, :509-516), as one call for a non-Python host:
  * specY = babe_stft_fwd(y) -> initial state -> per step: noise injection babe_lincomb3(1, x, inject, eps), babe_score_eval at
  * t_hat, then the Euler update x_hat + h d or the Heun pair (x' = x_hat + h d, babe_score_eval at t_next, x_hat + h/2 d + h/2 d').
- * Scope: exactly babe_score_eval's (blind or known fc_A filter, L2 guidance, no observation noise / data consistency / AR mask /
- * FIR or IIR degradation, fp32 network without attention).  Like babe_score_eval the run contains no schedule formula: the
+ * Scope: exactly babe_score_eval's (blind or known fc_A filter, L2 guidance, the AR mask and its replacement step through
+ * eval.mask / eval.dc_mask, no observation noise, no FIR or IIR degradation, fp32 network without attention).  Like babe_score_eval the run contains no schedule formula: the
  * caller passes one row per step (babe_edm_steps fills them for a host without the Python EDM class).  Same kernels, order and
  * scalars as the Python loop: bit-identical to it (tests/test_gpu_sample_c.py).  No allocation, no synchronisation; a failing
  * inner call returns its code; every argument is checked on the host before the first launch.  Two runs on two streams, each
@@ -638,6 +647,54 @@ int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, fl
  * The Python class evaluates the same formulas in float32, so its rows differ in the last bits ((ro + 4) 2^-23 relative). */
 int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double sigma_min, double sigma_max, double ro,
                    double sigma_data, double Schurn, double Stmin, double Stmax, double Snoise, double start_sigma);
+
+/* ---- one WHOLE RECORDING from plan handles (csrc/recording.hip): what long_file.restore_recording_complete (without denoiser and
+ * rate conversion) and restore_file_AR sequence from Python (BlindTester.test_real_blind_bwe_complete, testing/
+ * blind_bwe_tester.py:710-867), as one call for a non-Python host: normalise the file to target_std, estimate the low-pass filter
+ * blind on n_blind segments in one coupled batch (babe_sample_bwe with blind = 1, shared = 1), restore the first segment with that
+ * filter, out-paint every following segment from the last `overlap` samples of the previous result (babe_sample_bwe with
+ * eval.mask / eval.dc_mask), undo the normalisation.  Bit-identical to the Python flow on the same noise numbering
+ * (tests/test_gpu_recording_c.py).  Tables and schedules come from the caller, the library holds no random policy: the host
+ * picks the blind segments. */
+/* the walk of restore_file_AR, host only: segment j starts at j (segL - overlap - discard_end); the last one is the first whose
+ * start is not below Lrec - segL - discard_end and has Lrec - start samples (truncated to segL where that is more; always more
+ * than overlap); a file of at most segL samples is one segment.  Fills starts / n_valid (each may be NULL) up to max_segments
+ * entries and returns the number of segments, -1 unless 1 <= overlap < segL - discard_end and Lrec >= 1. */
+long babe_recording_plan(long Lrec, long segL, long overlap, long discard_end, long* starts, long* n_valid, long max_segments);
+typedef struct {
+    babe_eval_desc eval;                  /* as for babe_score_eval (segL = eval.L); blind and the mask fields are set by the call;
+                                             eval.shared is that of the known-filter runs, the blind batch is always coupled */
+    int T; float t0; int warm_start;      /* as in babe_sample_desc, for both tables */
+    const babe_sample_step* steps_blind;  /* host, T rows: the blind loop injects with Snoise = 1 ...                        */
+    const babe_sample_step* steps_known;  /* ... the known-filter loops with the tester's Snoise                              */
+    int n_blind; long blind_starts[16];   /* 1..16 segments of the blind step, first samples in [0, max(Lrec - segL, 0)]    */
+    const float* init_params;             /* device [2][K]: initial conditions of the filter fit                             */
+    float target_std;                     /* complete_recording.std                                                          */
+    long overlap, discard_end;            /* samples: known head of an AR segment; tail of a prediction that is not kept     */
+    int inpaint_dc, dc_size;              /* complete_recording.inpaint_DC: the replacement step with a mask smoothed over   */
+    const float* dc_window;               /* dc_size samples; device [2 dc_size]: the periodic Hann window of that length    */
+    const float* std_dev;                 /* device [1]: the file's standard deviation, or NULL: computed by the call        */
+} babe_recording_desc;
+long babe_recording_workspace_bytes(const babe_recording_desc* d);         /* (does not depend on the file's length) */
+/* rec [Lrec] the degraded file at the model's rate; out [Lrec] the restored file (zero past the last written sample: only a
+ * last segment longer than segL leaves such a tail); filter_out [2][K] the estimated filter and blind_pred [n_blind][segL] the
+ * blind step's restorations, in normalised units (each may be NULL).  Noise comes from babe_randn under `seed`: blind row b
+ * draws as clip clip0 + b, segment j of the walk as clip clip0 + n_blind + j.  Normalisation: (target_std x) / s on the way in,
+ * x (s (1 / target_std)) on the way out, s and the products read from device memory by the kernels.  Every argument is checked
+ * on the host before the first device call; no allocation, no synchronisation, no host copy: all of it is enqueued on stream. */
+int babe_restore_recording(const babe_recording_desc* d, const float* rec, long Lrec, float* out, float* filter_out,
+                           float* blind_pred, long seed, long clip0, void* ws, long ws_bytes, void* stream);
+/* the driver's own kernels as entries (tests pin them one by one):
+ * out[b] = unbiased standard deviation of x[b][0..n) (row stride x_bs), n >= 2: double sums of x - x[b][0] and its square over 64
+ * slices in a fixed order (part: [B][128] doubles of the caller), one rounding of the square root to float */
+int babe_row_std(const float* x, long x_bs, int B, long n, float* out, double* part, void* stream);
+/* dst[i] = i < n ? src[i] : 0 for i in [0, len), n <= len: a segment with a zero tail, or (n = len) a kept piece into the file */
+int babe_segment_cut(const float* src, long n, float* dst, long len, void* stream);
+/* by a scalar in device memory: mode 0: out = (a x) / s[0];  mode 1: out = x (s[0] a).  out may be x. */
+int babe_scale_dev(float* out, const float* x, long n, float a, const float* s_dev, int mode, void* stream);
+/* the masks of an edge at sample e, size <= e <= L: mask[i] = i < e; smooth[i] = 1 before e - size, window[size + i - (e - size)]
+ * on [e - size, e), 0 from e on - BlindSampler.prepare_smooth_mask of that mask (:232-257).  smooth may be NULL. */
+int babe_edge_masks(float* mask, float* smooth, long L, long e, int size, const float* window, void* stream);
 
 /* ---- Denoiser pre-pass: networks/denoiser.py:232-321 (MultiStage_denoise, inference only) and
  * testing/denoise_and_bwe_tester.py:146-165 (STFT 1024/256 -> network -> inverse STFT).  csrc/denoiser.hip --------- */
