@@ -223,6 +223,7 @@ SIGS = {
     "babe_unet_form_get": (_I, [_I]),
     "babe_unet_form_set": (_I, [_I, _I]),
     "babe_axpby4d": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),
+    "babe_fill4d": (_I, [_P, _L, _L, _I, _I, _I, _I, _F, _P]),
     "babe_axpby2_4d": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),
     "babe_linear": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "babe_rff": (_I, [_P, _P, _P, _I, _I, _P]),
