@@ -42,6 +42,14 @@ class CPackedConv(C.Structure):
                 ("w_raw", C.c_void_p), ("fwd_wino85", C.c_void_p), ("bwd_wino85", C.c_void_p)]
 
 
+class PackedConvLayout(C.Structure):
+    """babe_packed_conv_layout: babe_packed_conv_plan's answer; bytes in the order of IMAGE_SLOTS"""
+    _fields_ = [("nt", C.c_int), ("splits", C.c_int), ("raw", C.c_int), ("bytes", C.c_long * 10)]
+
+
+IMAGE_SLOTS = ("fwd", "bwd", "fwd_wino", "bwd_wino", "fwd_wino4", "bwd_wino4", "fwd_wino45", "bwd_wino45", "fwd_wino85", "bwd_wino85")
+
+
 class CBlock(C.Structure):
     """babe_unet_block"""
     _fields_ = [("N", C.c_int), ("nd", C.c_int), ("k53", C.c_int),
@@ -140,7 +148,8 @@ class ModelSummary(C.Structure):
 
 
 # header struct name -> mirror (the layout test compiles a probe for each of them)
-STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv, "babe_unet_block": CBlock,
+STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv,
+           "babe_packed_conv_layout": PackedConvLayout, "babe_unet_block": CBlock,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
            "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
            "babe_recording_desc": RecordingDesc,
@@ -212,6 +221,8 @@ SIGS = {
     "babe_conv2d_wino85_preferred": (_I, [C.POINTER(ConvArgs)]),
     "babe_conv2d_wino85": (_I, [C.POINTER(ConvArgs), _P, _P]),
     "babe_conv2d_wino85_set_waves": (_I, [_I]),
+    "babe_packed_conv_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(PackedConvLayout)]),
+    "babe_packed_conv_pack": (_I, [C.POINTER(CPackedConv), _P, _P]),
     "babe_conv2d_auto": (_I, [C.POINTER(ConvArgs), C.POINTER(CPackedConv), _I, _P]),
     "babe_unet_plan_create": (_P, [C.POINTER(CPlanDesc)]),
     "babe_unet_plan_destroy": (None, [_P]),

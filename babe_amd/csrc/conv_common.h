@@ -1,8 +1,9 @@
-// Pieces shared by the nine conv translation units (conv*.hip).
+// Pieces shared by the conv translation units (conv*.hip).
 //   device: the fused epilogue and sel_scale (conv.hip, conv_bf16.hip; conv11p.hip for the weights' layout), the A-operand fragment
 //           read, and conv_w_tap, the one statement of how a packed image reads the reference weight (every pack_* kernel);
 //   host:   what the launchers, the *_supported rules and the packed_size / pack_weights entry points have in common: padding,
-//           the (co, ci) of the executed op, view alignment, the 32-bit offset limits and the time x frequency split of a tile.
+//           the (co, ci) of the executed op and the weight shapes each kernel family takes, view alignment, the 32-bit offset
+//           limits and the time x frequency split of a tile.
 #pragma once
 #include "common.h"
 #include "../../include/babe_hip.h"
@@ -148,6 +149,18 @@ struct ConvIO {
 inline ConvIO conv_exec_io(int Cout, int Cin, int transpose_flip) {
     return transpose_flip ? ConvIO{Cin, Cout} : ConvIO{Cout, Cin};
 }
+
+// Which weight shapes a kernel family takes, on the (ci, co) of the EXECUTED op: the channel clauses of that family's *_supported
+// rule and, through babe_packed_conv_plan (conv_auto.hip), the reason a direction has the family's image.  Stated here only.
+//   nested F(2,5) x F(4,3): no padded input channels and an even number of 8-channel slabs (the channel part of a load address is
+//   a scalar offset the buffer range check does not cover; the slab loop is unrolled by two), more than one 32-channel tile out
+inline bool conv_wino45_shape(int ci, int co, int KH, int KW) { return KH == 5 && KW == 3 && ci >= 16 && ci % 16 == 0 && co > 32; }
+//   nested F(4,5) x F(4,3): the same input rule, output channels a whole number of 128-, 96- or 64-channel tiles
+inline bool conv_wino85_shape(int ci, int co, int KH, int KW) {
+    return KH == 5 && KW == 3 && ci >= 16 && ci % 16 == 0 && (co % 128 == 0 || co % 96 == 0 || co % 64 == 0);
+}
+//   few-output-channel vector kernel, which reads the RAW weights: 3 taps along time, at most 4 output channels
+inline bool conv_fewco_shape(int co, int KW) { return KW == 3 && co >= 1 && co <= 4; }
 
 // a [B][C][F][T] float view whose rows may be read / written as `bytes`-wide vectors (16: float4, 8: float2)
 inline bool view_aligned(const void* p, long bs, long cs, int bytes = 16) {

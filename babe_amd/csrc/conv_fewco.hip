@@ -7,11 +7,8 @@
 // walks the input channels and frequency taps, and reads the weights (co x ci x KH x 3, reference layout, flipped and
 // transposed on the fly when computing the input-VJP) from an LDS copy by broadcast.  HBM-side it reads the input once
 // (the KH row re-reads hit L2).  out = alpha * conv + rbeta * res like every conv entry point.
-#include "common.h"
-#include "../../include/babe_hip.h"
+#include "conv_common.h"
 #include "prof.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -148,7 +145,7 @@ extern "C" int babe_conv2d_fewco_supported(const babe_conv_args* ap) {
     if (!ap) return 0;
     const babe_conv_args& a = *ap;
     auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    if (a.Cout < 1 || a.Cout > 4 || a.KW != 3 || a.KH < 1 || a.KH > 7 || a.T % 4 || a.in2 || a.in_scale) return 0;
+    if (!conv_fewco_shape(a.Cout, a.KW) || a.KH < 1 || a.KH > 7 || a.T % 4 || a.in2 || a.in_scale) return 0;
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
     if (!al16(a.in) || a.in_bs % 4 || a.in_cs % 4 || !al16(a.out) || a.out_bs % 4 || a.out_cs % 4) return 0;
     if (a.res && (!al16(a.res) || a.res_bs % 4 || a.res_cs % 4)) return 0;

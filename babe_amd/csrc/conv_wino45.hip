@@ -997,11 +997,9 @@ extern "C" int babe_conv2d_wino45_supported(const babe_conv_args* ap) {
     static const char* ov = getenv("BABE_CONV_WINO45");
     if (ov && ov[0] == '0') return 0;
     const babe_conv_args& a = *ap;
-    if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;   // (tiles are 64 time steps wide)
+    if (a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;     // (tiles are 64 time steps wide)
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
-    if (a.Cin < 16 || a.Cin % 16 != 0 || a.Cout < 33) return 0;   // (the channel part of a load address is a scalar offset,
-    // which the buffer range check does not cover: no padded input channels; an even number of 8-channel slabs per pass: the
-    // slab loop is unrolled by two; few-channel convs run on conv_fewco / direct)
+    if (!conv_wino45_shape(a.Cin, a.Cout, a.KH, a.KW)) return 0;     // (few-channel convs run on conv_fewco / direct)
     if (!view_aligned(a.in, a.in_bs, a.in_cs)) return 0;
     if (a.in2) return 0;                                     // one source only (csrc/conv_wino45.hip, descriptors)
     if (!view_aligned(a.out, a.out_bs, a.out_cs)) return 0;

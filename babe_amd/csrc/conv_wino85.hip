@@ -854,9 +854,9 @@ extern "C" int babe_conv_pack_weights_wino85(const float* w, float* dst, int Cou
 extern "C" int babe_conv2d_wino85_supported(const babe_conv_args* ap) {
     if (!ap) return 0;
     const babe_conv_args& a = *ap;
-    if (a.KH != 5 || a.KW != 3 || a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;
+    if (a.T % 4 != 0 || a.T < 64 || a.dil < 1) return 0;
     if (a.fbias) return 0;                                   // the frequency bias is the (1,1) fp32 kernels' (babe_conv2d_nt)
-    if (a.Cin < 16 || a.Cin % 16 != 0 || (a.Cout % 128 != 0 && a.Cout % 96 != 0 && a.Cout % 64 != 0)) return 0;
+    if (!conv_wino85_shape(a.Cin, a.Cout, a.KH, a.KW)) return 0;
     if (!view_aligned(a.in, a.in_bs, a.in_cs) || a.in2) return 0;
     if (!view_aligned(a.out, a.out_bs, a.out_cs)) return 0;
     if (a.res && !view_aligned(a.res, a.res_bs, a.res_cs)) return 0;

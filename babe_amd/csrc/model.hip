@@ -2,10 +2,7 @@
 // a host without Python calls instead of restating UnetEngine.__init__, _Block, _FilmIndex, ops.PackedConv, STFTOps and CEval.
 // The loader does what the Python engine does, with the same pack kernels on the same raw weights, so every image, table and
 // descriptor field is bit-identical to the Python-built one (tests/test_gpu_model_c.py):
-//   images       ops.PackedConv with the default forms of forms.py: nt = 2 for a (1,1) conv whose 32-channel tile counts are both
-//                even; w_raw (the raw weights themselves) for KW == 3 with <= 4 channels on one side; wino / wino4 for KW == 3;
-//                wino45 for (5,3) where the executed op has input channels % 16 == 0 and more than 32 output channels; wino85 for
-//                (5,3), input channels % 16 == 0 and output channels a multiple of 128, 96 or 64 - per direction
+//   images       babe_packed_conv_plan (csrc/conv_auto.hip) with the default forms, as ops.PackedConv asks it
 //   block order  UnetEngine.blocks(): init, main, mid_blk, mid_out, up_out, up_blk
 //   FiLM         _FilmIndex: blocks in CONSTRUCTION order (init i, main i per octave; mid_blk, mid_out; up_out i, up_blk i), per
 //                dilation layer the affine rows, then the gate rows
@@ -64,39 +61,23 @@ struct Builder {
     float* staged(float* d) const { return reinterpret_cast<float*>(staging + (reinterpret_cast<char*>(d) - c.base)); }
     const Tensor& T(const std::string& name) const { return *f.find(name); }       // (check_tensors found every name)
 
-    // ops.PackedConv(w) with the default forms: every image of one conv, packed from the device copy of its raw weights
+    // every image of one conv, as babe_packed_conv_plan lays them out (default forms; nt 2 where the (1,1) rule allows it), carved
+    // direction by direction and packed from the device copy of the raw weights
     int conv(babe_packed_conv& pc, const float* w, int Cout, int Cin, int KH, int KW) {
+        babe_packed_conv_layout lay;
+        BABE_TRY(babe_packed_conv_plan(Cout, Cin, KH, KW, 0, 0, 2, BABE_CONV_FORMS_ALL, &lay));
         memset(&pc, 0, sizeof pc);
-        pc.Cout = Cout, pc.Cin = Cin, pc.KH = KH, pc.KW = KW;
-        if (KH * KW == 1 && ((Cout + 31) / 32) % 2 == 0 && ((Cin + 31) / 32) % 2 == 0) pc.nt = 2;
-        if (KW == 3 && std::min(Cout, Cin) <= 4) pc.w_raw = w;
-        const bool k53 = KH == 5 && KW == 3;
-        for (int tf = 0; tf < 2; ++tf) {
-            const int ci = tf ? Cout : Cin, co = tf ? Cin : Cout;        // channels of the op this direction's image executes
-            float* img = c.take<float>((size_t)babe_conv_packed_size(Cout, Cin, KH, KW, tf));
-            (tf ? pc.bwd : pc.fwd) = img;
-            if (!dry()) BABE_TRY(babe_conv_pack_weights_nt(w, img, Cout, Cin, KH, KW, tf, pc.nt, stream));
-            if (KW == 3) {
-                float* w2 = c.take<float>((size_t)babe_conv_packed_size_wino(Cout, Cin, KH, tf));
-                float* w4 = c.take<float>((size_t)babe_conv_packed_size_wino4(Cout, Cin, KH, tf));
-                (tf ? pc.bwd_wino : pc.fwd_wino) = w2, (tf ? pc.bwd_wino4 : pc.fwd_wino4) = w4;
-                if (!dry()) {
-                    BABE_TRY(babe_conv_pack_weights_wino(w, w2, Cout, Cin, KH, KW, tf, stream));
-                    BABE_TRY(babe_conv_pack_weights_wino4(w, w4, Cout, Cin, KH, KW, tf, stream));
-                }
+        pc.Cout = Cout, pc.Cin = Cin, pc.KH = KH, pc.KW = KW, pc.nt = lay.nt;
+        if (lay.raw) pc.w_raw = w;
+        const float** family[8] = {&pc.fwd_wino, &pc.bwd_wino, &pc.fwd_wino4, &pc.bwd_wino4, &pc.fwd_wino45, &pc.bwd_wino45, &pc.fwd_wino85, &pc.bwd_wino85};
+        for (int tf = 0; tf < 2; ++tf)
+            for (int i = tf; i < 10; i += 2) {
+                if (!lay.bytes[i]) continue;
+                float* img = c.take<float>((size_t)lay.bytes[i] / sizeof(float));
+                if (i < 2) (tf ? pc.bwd : pc.fwd) = img;
+                else *family[i - 2] = img;
             }
-            if (k53 && ci % 16 == 0 && co > 32) {
-                float* img45 = c.take<float>((size_t)babe_conv_packed_size_wino45(Cout, Cin, tf));
-                (tf ? pc.bwd_wino45 : pc.fwd_wino45) = img45;
-                if (!dry()) BABE_TRY(babe_conv_pack_weights_wino45(w, img45, Cout, Cin, KH, KW, tf, stream));
-            }
-            if (k53 && ci % 16 == 0 && (co % 128 == 0 || co % 96 == 0 || co % 64 == 0)) {
-                float* img85 = c.take<float>((size_t)babe_conv_packed_size_wino85(Cout, Cin, tf));
-                (tf ? pc.bwd_wino85 : pc.fwd_wino85) = img85;
-                if (!dry()) BABE_TRY(babe_conv_pack_weights_wino85(w, img85, Cout, Cin, KH, KW, tf, stream));
-            }
-        }
-        return BABE_OK;
+        return dry() ? BABE_OK : babe_packed_conv_pack(&pc, w, stream);
     }
     int conv(babe_packed_conv& pc, const std::string& name) {
         const Tensor& t = T(name);

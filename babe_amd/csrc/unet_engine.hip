@@ -17,42 +17,6 @@
 #include <cstdlib>
 #include <cstring>
 
-/* out = alpha*conv(in[,in2]; W)*oscale + rbeta*res with the kernel chosen by the library - the one place that choice is made
- * (babe_amd/ops.py::conv2d calls this too): bf16 images, few-output-channel vector kernel, nested Winograd F(4,5)xF(4,3) /
- * F(2,5)xF(4,3) where their tiles are full, F(4,3), F(2,3), direct / pipelined (1,1); an image left NULL takes its kernel out.
- * The caller fills every field of *a except w_packed, Cin, Cout, KH, KW (taken from pc and transpose).  A requested fused
- * reduction (a->stat_mode) is formed only by the F(4,5) kernels: on return a->stat_mode is 0 if it was NOT produced.
- * A frequency bias (a->fbias) is never dropped: every *_supported rule below refuses it, so such a call ends in babe_conv2d_nt,
- * which adds it ((1,1) kernels) or returns an error; so does babe_conv2d_bf16. */
-extern "C" int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, int transpose, void* stream) {
-    BABE_CHECK_ARG(a && pc, "conv2d_auto: null arguments");
-    a->Cin = transpose ? pc->Cout : pc->Cin;
-    a->Cout = transpose ? pc->Cin : pc->Cout;
-    a->KH = pc->KH;
-    a->KW = pc->KW;
-    const void* wq = transpose ? pc->bwd : pc->fwd;
-    BABE_CHECK_ARG(wq, "conv2d_auto: weights not packed for this direction");
-    if (!a->in2) a->cin_split = a->Cin;
-    if (pc->splits) {
-        a->w_packed = nullptr;
-        a->stat_mode = 0;
-        return babe_conv2d_bf16(a, wq, pc->splits, stream);
-    }
-    a->w_packed = (const float*)wq;
-    const float* w45 = transpose ? pc->bwd_wino45 : pc->fwd_wino45;
-    if (pc->w_raw && a->Cout <= 4 && babe_conv2d_fewco_supported(a)) {
-        a->stat_mode = 0;
-        return babe_conv2d_fewco(a, pc->w_raw, transpose, stream);
-    }
-    const float* w85 = transpose ? pc->bwd_wino85 : pc->fwd_wino85;
-    if (w85 && !a->in2 && babe_conv2d_wino85_preferred(a)) return babe_conv2d_wino85(a, w85, stream);
-    a->stat_mode = 0;                  // only the F(4,5) kernels form the fused reduction: tell the caller it was not produced
-    if (w45 && babe_conv2d_wino45_preferred(a)) return babe_conv2d_wino45(a, w45, stream);
-    if (pc->fwd_wino4 && babe_conv2d_wino4_supported(a)) return babe_conv2d_wino4(a, transpose ? pc->bwd_wino4 : pc->fwd_wino4, stream);
-    if (pc->fwd_wino && babe_conv2d_wino_supported(a)) return babe_conv2d_wino(a, transpose ? pc->bwd_wino : pc->fwd_wino, stream);
-    return babe_conv2d_nt(a, pc->nt, stream);
-}
-
 /* The two forms BOTH sequencers of the UNet layer path act on (this file's and babe_amd/networks/unet_engine.py's), one value
  * per process: the environment is read here, once, and nowhere else; babe_unet_form_set changes a form at run time and
  * babe_amd/forms.py (FORMS.fuse_gn_fwd / FORMS.fuse_gn) is a view of these values.

@@ -6,7 +6,7 @@ import math
 import torch
 
 from . import _lib
-from ._cabi import ConvArgs, CPackedConv, WgradArgs
+from ._cabi import IMAGE_SLOTS, ConvArgs, CPackedConv, PackedConvLayout, WgradArgs
 from .forms import FORMS
 from ._lib import check, lib, ptr, stream
 
@@ -40,28 +40,8 @@ def _fill_out(a, pc, out, Cin, dil, res, oscale, alpha, rbeta):
 PRECISIONS = {"f32": 0, "bf16": 1, "bf16x3": 2}
 
 
-def _io(pc, tf):
-    """(input, output) channels of the op a direction's image EXECUTES: tf 0 the conv, 1 its input-VJP (the transposed conv)."""
-    return (pc.Cout, pc.Cin) if tf else (pc.Cin, pc.Cout)
-
-
-# The Winograd image families of an fp32 PackedConv: construction allocates them, repack() fills them.  (suffix of the fwd_ / bwd_
-# attribute, size function, pack function, may direction tf be packed?).  Images exist only for the direction(s) their kernel can
-# take (the *_supported rules of include/babe_hip.h, on the executed op's channels):
-#   wino / wino4   F(2,3) / F(4,3) along time: every 3-tap kernel
-#   wino45         nested F(2,5) x F(4,3), 36 floats per weight pair: input channels % 16 == 0, more than 32 output channels
-#   wino85         nested F(4,5) x F(4,3): input channels % 16 == 0, output channels a multiple of a tile width (128, 96 or 64)
-_FAMILIES = (
-    ("wino", lambda L, pc, tf: L.babe_conv_packed_size_wino(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino,
-     lambda pc, tf: pc.KW == 3 and FORMS.winograd),
-    ("wino4", lambda L, pc, tf: L.babe_conv_packed_size_wino4(pc.Cout, pc.Cin, pc.KH, tf), lambda L: L.babe_conv_pack_weights_wino4,
-     lambda pc, tf: pc.KW == 3 and FORMS.winograd4),
-    ("wino45", lambda L, pc, tf: L.babe_conv_packed_size_wino45(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino45,
-     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and FORMS.winograd45 and _io(pc, tf)[0] % 16 == 0 and _io(pc, tf)[1] > 32),
-    ("wino85", lambda L, pc, tf: L.babe_conv_packed_size_wino85(pc.Cout, pc.Cin, tf), lambda L: L.babe_conv_pack_weights_wino85,
-     lambda pc, tf: pc.KH == 5 and pc.KW == 3 and FORMS.winograd85 and _io(pc, tf)[0] % 16 == 0
-     and any(_io(pc, tf)[1] % tile == 0 for tile in (128, 96, 64))),
-)
+# bit i of babe_packed_conv_plan's form mask (BABE_CONV_FORM_* of include/babe_hip.h): the attribute of FORMS that switches it
+_FORM_BITS = ("winograd", "winograd4", "winograd45", "winograd85", "fewco")
 
 
 _DESC_FIELDS = frozenset(k for k, _ in CPackedConv._fields_)
@@ -72,36 +52,28 @@ class PackedConv:
     precision: 'f32' (exact fp32 MFMA), 'bf16' or 'bf16x3' (bf16 MFMA, see csrc/conv_bf16.hip).
     `desc` is the C descriptor (babe_packed_conv) babe_conv2d_auto picks the kernel from: every shape and image attribute is
     written through to it, so assigning None to an image after construction takes its kernel out of the dispatch.
-    The forms that decide which images exist (forms.py: the Winograd families of _FAMILIES, fewco for w_raw, conv11_nt for nt,
+    Which images exist, how large each is, nt and whether the raw weights are kept is the library's rule (babe_packed_conv_plan,
+    include/babe_hip.h).  The forms it is asked with (forms.py: the Winograd families and fewco as its mask, conv11_nt for nt,
     bf16_hbm_f32 for splits_for) are read when the object is CONSTRUCTED: selecting another form later does not repack it."""
 
     def __init__(self, w, precision="f32", nt=0):
         """nt: row tiles (x32 output channels) per workgroup of the direct kernel, 0 = default (include/babe_hip.h)."""
-        self.desc = CPackedConv()
-        self.precision = precision
-        self.nt = nt
-        c11 = FORMS.conv11_nt
-        if nt == 0 and c11 and w.shape[2] * w.shape[3] == 1 and ((w.shape[0] + 31) // 32) % c11 == 0 \
-                and ((w.shape[1] + 31) // 32) % c11 == 0:
-            self.nt = c11
-        self.splits = self.splits_for(w.shape, precision)
         assert w.is_cuda and w.dtype == torch.float32 and w.dim() == 4
         w = w.contiguous()
+        self.desc = CPackedConv()
+        self.precision = precision
         self.Cout, self.Cin, self.KH, self.KW = w.shape
-        L = lib()
-        shp = (self.Cout, self.Cin, self.KH, self.KW)
-        if self.splits:
-            for tf, d in ((0, "fwd"), (1, "bwd")):
-                setattr(self, d, torch.empty(L.babe_conv_packed_size_bf16(*shp, tf, self.splits), device=w.device, dtype=torch.int16))
-        else:
-            # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip):
-            # the caller's tensor itself
-            self.w_raw = w if (FORMS.fewco and self.KW == 3 and min(self.Cout, self.Cin) <= 4) else None
-            for tf, d in ((0, "fwd"), (1, "bwd")):
-                setattr(self, d, torch.empty(L.babe_conv_packed_size(*shp, tf), device=w.device, dtype=torch.float32))
-            for name, size, _, eligible in _FAMILIES:
-                for tf, d in ((0, "fwd_"), (1, "bwd_")):
-                    setattr(self, d + name, torch.empty(size(L, self, tf), device=w.device) if eligible(self, tf) else None)
+        lay = PackedConvLayout()
+        forms = sum(1 << i for i, name in enumerate(_FORM_BITS) if getattr(FORMS, name))
+        check(lib().babe_packed_conv_plan(*w.shape, self.splits_for(w.shape, precision), nt, FORMS.conv11_nt, forms, C.byref(lay)),
+              "packed_conv_plan")
+        self.nt, self.splits = lay.nt, lay.splits
+        dtype, size = (torch.int16, 2) if lay.splits else (torch.float32, 4)
+        for name, nbytes in zip(IMAGE_SLOTS, lay.bytes):
+            setattr(self, name, torch.empty(nbytes // size, device=w.device, dtype=dtype) if nbytes else None)
+        # raw weights for the few-output-channel kernel (the input-VJP of a 2..4-input-channel conv, csrc/conv_fewco.hip): the
+        # caller's tensor itself
+        self.w_raw = w if lay.raw else None
         self.repack(w)
 
     @staticmethod
@@ -128,21 +100,9 @@ class PackedConv:
         step.  Construction packs through this function too, so the images are exactly those a freshly built PackedConv holds."""
         assert w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (self.Cout, self.Cin, self.KH, self.KW)
         w = w.contiguous()
-        L = lib()
-        shp = (self.Cout, self.Cin, self.KH, self.KW)
-        if self.splits:
-            for tf, dst in ((0, self.fwd), (1, self.bwd)):
-                check(L.babe_conv_pack_weights_bf16(ptr(w), ptr(dst), *shp, tf, self.splits, stream()), "pack_bf16")
-            return
         if self.w_raw is not None and self.w_raw.data_ptr() != w.data_ptr():
             self.w_raw.copy_(w)
-        for tf, dst in ((0, self.fwd), (1, self.bwd)):
-            check(L.babe_conv_pack_weights_nt(ptr(w), ptr(dst), *shp, tf, self.nt, stream()), "pack")
-        for name, _, pack, _ in _FAMILIES:
-            for tf, d in ((0, "fwd_"), (1, "bwd_")):
-                dst = getattr(self, d + name)
-                if dst is not None:
-                    check(pack(L)(ptr(w), ptr(dst), *shp, tf, stream()), "pack_" + name)
+        check(lib().babe_packed_conv_pack(C.byref(self.desc), ptr(w), stream()), "packed_conv_pack")
 
 
 def conv2d(x, pc, out, *, dil=1, transpose=False, x2=None, res=None, in_scale=None, oscale=None, alpha=1.0, rbeta=0.0,

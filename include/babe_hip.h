@@ -268,13 +268,32 @@ int babe_conv2d_wino85_set_waves(int waves);
 /* ---- the whole UNet body from one call: networks/cqtdiff+.py:746-839 (forward), ResnetBlock :452-493, and its input-VJP
  * (the autograd pass of testing/blind_bwe_sampler.py:120).  csrc/unet_engine.hip sequences the op-level functions of this header
  * exactly as babe_amd/networks/unet_engine.py does (bit-identical results); fp32 convs.  All device memory is the caller's. */
-typedef struct {                       /* every image babe_amd/ops.py::PackedConv builds for one Conv2d; NULL = not packed */
+typedef struct {                       /* the images of one Conv2d, as babe_packed_conv_plan lays them out; NULL = not packed */
     int Cout, Cin, KH, KW, nt, splits; /* Cout == 0: the layer does not exist; splits: 0 fp32, 1 bf16, 2 bf16x3 */
     const void *fwd, *bwd;             /* babe_conv_pack_weights_nt (fp32) or babe_conv_pack_weights_bf16 images, transpose_flip 0 / 1 */
     const float *fwd_wino, *bwd_wino, *fwd_wino4, *bwd_wino4, *fwd_wino45, *bwd_wino45;
     const float* w_raw;                /* reference layout, for babe_conv2d_fewco (<= 4 channels on one side) */
     const float *fwd_wino85, *bwd_wino85;  /* babe_conv_pack_weights_wino85 images, or NULL */
 } babe_packed_conv;
+/* Which images one Conv2d with weights [Cout][Cin][KH][KW] gets and how large each is - the one statement of that rule; both the
+ * model loader and babe_amd/ops.py::PackedConv build their descriptors from it.  Pure host arithmetic like the packed_size
+ * functions: no GPU, no environment variable.
+ *   splits  0: fp32 images; 1 / 2: only fwd / bwd exist, babe_conv_pack_weights_bf16 images (2-byte elements)
+ *   nt      the caller's row-tile count for the direct kernel; 0: nt11 (0 = none) for a (1,1) conv whose 32-channel tile counts
+ *           are multiples of it in both directions, the library default otherwise.  The layout's nt goes into the descriptor.
+ *   forms   mask of the kernel families that may get an image (a direction gets a family's image where that family's kernel
+ *           takes the executed op's channels and kernel size), BABE_CONV_FORMS_ALL by default
+ *   raw     set the descriptor's w_raw to the raw weights themselves (they stay the caller's memory): <= 4 channels on one side
+ * bytes[i], in the order fwd, bwd, fwd_wino, bwd_wino, fwd_wino4, bwd_wino4, fwd_wino45, bwd_wino45, fwd_wino85, bwd_wino85: the
+ * size of that image, 0 = the image is absent and its pointer stays NULL. */
+enum { BABE_CONV_FORM_F23 = 1, BABE_CONV_FORM_F43 = 2, BABE_CONV_FORM_F25 = 4, BABE_CONV_FORM_F45 = 8, BABE_CONV_FORM_FEWCO = 16,
+       BABE_CONV_FORMS_ALL = 31 };
+typedef struct { int nt, splits, raw; long bytes[10]; } babe_packed_conv_layout;
+int babe_packed_conv_plan(int Cout, int Cin, int KH, int KW, int splits, int nt, int nt11, int forms,
+                          babe_packed_conv_layout* out);
+/* Fills every non-NULL image of *pc (shape, nt, splits set) from raw weights w of that shape: the per-family pack_weights calls,
+ * enqueued on stream.  Allocates nothing, waits for nothing, leaves w_raw alone. */
+int babe_packed_conv_pack(const babe_packed_conv* pc, const float* w, void* stream);
 /* conv with the kernel chosen by the library; a->w_packed, Cin, Cout, KH, KW are filled in from pc / transpose */
 int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, int transpose, void* stream);
 typedef struct {                       /* one ResnetBlock */

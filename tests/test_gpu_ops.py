@@ -232,6 +232,83 @@ def test_conv2d_few_output_channels_vjp_of_pyramid_projection(ops, B, N, Fq, T, 
     assert rel(out, 0.7 * gref + acc.double()) < 2e-6
 
 
+@pytest.fixture(scope="module")
+def recorded_layouts():
+    """{case: (nt, raw, [bytes of the ten slots])} of tests/golden/packed_conv_layout.json, the table of
+    tests/test_packed_conv_layout_cpu.py: which images a conv is to have comes from there, not from a rule restated here."""
+    import importlib.util
+    import json
+    import os
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_packed_conv_layout_golden", os.path.join(golden, "make_packed_conv_layout_golden.py"))
+    grid = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(grid)
+    with open(os.path.join(golden, "packed_conv_layout.json")) as fh:
+        return dict(zip(grid.cases(), grid.expand(json.load(fh))))
+
+
+@pytest.mark.parametrize("shape,precision", [
+    ((64, 64, 5, 3), "f32"),            # every family, both directions
+    ((128, 96, 5, 3), "f32"),           # 96- and 128-channel F(4,5) tiles
+    ((33, 16, 5, 3), "f32"),            # forward: F(2,5) image, no F(4,5) image; transposed: neither
+    ((64, 2, 5, 3), "f32"),             # raw image, few channels
+    ((2, 64, 1, 1), "f32"),             # the folded-column shape
+    ((96, 192, 1, 1), "f32"),           # odd tile count: no nt override
+    ((128, 64, 1, 1), "f32"),           # nt = 2
+    ((64, 64, 5, 3), "bf16"),
+    ((64, 64, 5, 3), "bf16x3"),
+])
+def test_packed_conv_images_are_the_per_family_packs(ops, recorded_layouts, shape, precision):
+    """Every image of a PackedConv equals, bit for bit, what the family's own babe_conv_pack_weights_* writes into a fresh buffer of
+    its babe_conv_packed_size_* size; the images the recorded table does not list are absent, in the object and in its descriptor."""
+    from babe_amd._cabi import IMAGE_SLOTS
+    from babe_amd._lib import check, lib, ptr, stream
+    from babe_amd.forms import FORMS
+    L = lib()
+    splits = ops.PRECISIONS[precision]
+    forms = sum(1 << i for i, name in enumerate(ops._FORM_BITS) if getattr(FORMS, name))
+    nt, raw, nbytes = recorded_layouts[shape + (splits, 0, FORMS.conv11_nt, forms)]
+    w = torch.randn(shape, generator=torch.Generator().manual_seed(sum(shape))).cuda()
+    pc = ops.PackedConv(w, precision)
+    assert (pc.splits, pc.desc.splits, pc.nt, pc.desc.nt) == (splits, splits, nt, nt)
+    assert (pc.desc.Cout, pc.desc.Cin, pc.desc.KH, pc.desc.KW) == shape
+    if raw:
+        assert pc.w_raw.data_ptr() == w.data_ptr() == pc.desc.w_raw
+    else:
+        assert pc.w_raw is None and not pc.desc.w_raw
+    co, ci, kh, kw = shape
+    families = ((L.babe_conv_packed_size, (co, ci, kh, kw), lambda d, tf: L.babe_conv_pack_weights_nt(ptr(w), ptr(d), *shape, tf, nt, stream())),
+                (L.babe_conv_packed_size_wino, (co, ci, kh), lambda d, tf: L.babe_conv_pack_weights_wino(ptr(w), ptr(d), *shape, tf, stream())),
+                (L.babe_conv_packed_size_wino4, (co, ci, kh), lambda d, tf: L.babe_conv_pack_weights_wino4(ptr(w), ptr(d), *shape, tf, stream())),
+                (L.babe_conv_packed_size_wino45, (co, ci), lambda d, tf: L.babe_conv_pack_weights_wino45(ptr(w), ptr(d), *shape, tf, stream())),
+                (L.babe_conv_packed_size_wino85, (co, ci), lambda d, tf: L.babe_conv_pack_weights_wino85(ptr(w), ptr(d), *shape, tf, stream())))
+    have = set()
+    for i, name in enumerate(IMAGE_SLOTS):
+        img, tf = getattr(pc, name), i & 1
+        if not nbytes[i]:
+            assert img is None and not getattr(pc.desc, name), name
+            continue
+        have.add(name)
+        if splits:
+            want = torch.full((L.babe_conv_packed_size_bf16(*shape, tf, splits),), -1, dtype=torch.int16, device="cuda")
+            check(L.babe_conv_pack_weights_bf16(ptr(w), ptr(want), *shape, tf, splits, stream()), name)
+        else:
+            size, args, pack = families[i // 2]
+            want = torch.full((size(*args, tf),), 1.5e30, device="cuda")
+            check(pack(want, tf), name)
+        assert img.dtype == want.dtype and img.numel() == want.numel() and img.numel() * img.element_size() == nbytes[i], name
+        assert getattr(pc.desc, name) == img.data_ptr(), name
+        assert torch.equal(img, want), name
+    if forms == 31 and not splits:                      # the cases are what their comments say (default forms)
+        if shape in ((64, 64, 5, 3), (128, 96, 5, 3)):
+            assert have == set(IMAGE_SLOTS)
+        if shape == (33, 16, 5, 3):
+            assert have == set(IMAGE_SLOTS[:6]) | {"fwd_wino45"}
+        if shape in ((64, 2, 5, 3), (2, 64, 1, 1)):
+            assert raw == (kw == 3)
+        assert shape[2:] != (1, 1) or nt == (2 if shape == (128, 64, 1, 1) else 0)
+
+
 def test_conv2d_winograd_dispatch_rules(ops):
     """Problems the Winograd kernel does not take (T % 4, misaligned views, 1x1) run on the direct kernel."""
     import ctypes as C
