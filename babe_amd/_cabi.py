@@ -147,13 +147,31 @@ class ModelSummary(C.Structure):
                 ("load_ms", C.c_double * 3)]
 
 
+class DenoiserSummary(C.Structure):
+    """babe_denoiser_summary"""
+    _fields_ = [("depth", C.c_int), ("num_tfc", C.c_int), ("num_stages", C.c_int), ("use_SAM", C.c_int), ("use_fencoding", C.c_int),
+                ("f_dim", C.c_int), ("sample_rate", C.c_int), ("win", C.c_int), ("hop", C.c_int), ("segment", C.c_long),
+                ("params", C.c_long), ("device_bytes", C.c_long), ("device", C.c_int), ("load_ms", C.c_double * 3)]
+
+
+class SincTable(C.Structure):
+    """babe_sinc_table"""
+    _fields_ = [("kernel", C.c_void_p), ("krange", C.c_void_p), ("width", C.c_int), ("orig", C.c_int), ("new_", C.c_int)]
+
+
+class FileDesc(C.Structure):
+    """babe_file_desc"""
+    _fields_ = [("rec", RecordingDesc), ("denoiser", C.c_void_p), ("conv", SincTable * 2), ("lengths", C.c_long * 3)]
+
+
 # header struct name -> mirror (the layout test compiles a probe for each of them)
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv,
            "babe_packed_conv_layout": PackedConvLayout, "babe_unet_block": CBlock,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
            "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
            "babe_recording_desc": RecordingDesc,
-           "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary}
+           "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary,
+           "babe_denoiser_summary": DenoiserSummary, "babe_sinc_table": SincTable, "babe_file_desc": FileDesc}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
 _P, _L, _I, _F, _D, _S = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double, C.c_char_p
@@ -330,6 +348,24 @@ SIGS = {
     "babe_model_unet_plan": (_P, [_P]),
     "babe_model_cqt_plan": (_P, [_P]),
     "babe_model_eval_desc": (_I, [_P, _P, C.POINTER(EvalDesc)]),
+    "babe_resample_sinc_table_size": (_L, [_L, _L, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
+    "babe_resample_sinc_table": (_I, [_L, _L, _P, _P]),
+    "babe_resampled_length": (_L, [_L, _L, _L]),
+    "babe_denoiser_load": (_P, [_S, _P]),
+    "babe_denoiser_create": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _P]),
+    "babe_denoiser_destroy": (None, [_P]),
+    "babe_denoiser_info": (_I, [_P, C.POINTER(DenoiserSummary)]),
+    "babe_dn_ksplit": (_I, [C.POINTER(DnConvArgs)]),
+    "babe_denoiser_workspace_bytes": (_L, [_P, _I, _I, _I]),
+    "babe_denoiser_fwd": (_I, [_P, _P, _P, _P, _P, _L, _I, _I, _I, _P]),
+    "babe_denoise_signal_plan": (_L, [_L, _L, _L, _P, _L]),
+    "babe_denoise_signal_workspace_bytes": (_L, [_P, _I, _L]),
+    "babe_denoise_signal": (_I, [_P, _P, _L, _P, _L, _I, _L, _P, _L, _P]),
+    "babe_dn_segment_pad": (_I, [_P, _L, _L, _P, _L, _L, _I, _P]),
+    "babe_dn_fade_add": (_I, [_P, _L, _P, _L, _I, _L, _L, _P, _I, _I, _I, _P]),
+    "babe_restore_file_plan": (_I, [_L, _L, _L, _L, _P]),
+    "babe_restore_file_workspace_bytes": (_L, [C.POINTER(FileDesc)]),
+    "babe_restore_file": (_I, [C.POINTER(FileDesc), _P, _L, _P, _P, _P, _P, _L, _L, _P, _L, _P]),
 }
 
 

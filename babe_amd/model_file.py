@@ -15,7 +15,9 @@ and all of `tester` (config.default_args), with two values resolved the way the 
 "nyquist" is sample_rate // 2, and `tester.diff_params` holds the training values when `same_as_training` is set.
 Tensors carry the reference's state_dict keys, plus `aux.env_inv` and `aux.tw4096`: the two tables of stft.STFTOps, whose bits
 this host defines (torch's float32 Hamming window, numpy's cos / sin), so that a descriptor built by the library is bit-identical
-to one built here.  csrc/model_file.h is the reader the library uses; `read` below is the Python one."""
+to one built here.  csrc/model_file.h is the reader the library uses; `read` below is the Python one.
+The denoiser pre-pass has a file of its own in the same container (`export_denoiser`, babe_denoiser_load): the string setting
+`kind` = "denoiser" tells the two apart, and each loader refuses the other's file."""
 import struct
 
 import numpy as np
@@ -136,6 +138,36 @@ def export(net, args, path):
     tensors = {k: v.detach().to("cpu", torch.float32) for k, v in sd.items()}
     tensors.update(aux_tensors(args))
     return write(path, settings_of(args), tensors)
+
+
+DENOISER_LEAVES = ("depth", "num_tfc", "num_stages", "use_SAM", "use_fencoding", "f_dim", "sample_rate_denoiser", "segment_size",
+                   "stft_win_size", "stft_hop_size")
+
+
+def denoiser_aux_tensors():
+    """{'aux.tw4096', 'aux.fade'}: the twiddle table of testing.denoise.DenoiserPrepass and the 2048-point Hamming window its
+    apply_denoiser cross-fades with, as that class builds them."""
+    q = np.arange(2048)
+    tw = torch.tensor(np.stack([np.cos(2 * np.pi * q / 4096), -np.sin(2 * np.pi * q / 4096)], -1), dtype=torch.float32)
+    return {"aux.tw4096": tw.contiguous(), "aux.fade": torch.hamming_window(window_length=2048)}
+
+
+def export_denoiser(sd_or_net, dargs, path):
+    """Write the denoiser's weights file (csrc/dn_engine.hip: babe_denoiser_load): the same container with the string setting
+    kind = "denoiser", the leaves of `dargs` - the configuration's tester.denoiser node: DENOISER_LEAVES, and any other leaf it
+    has (the use_* options the library refuses when set) - under tester.denoiser.*, the reference state_dict and the two tables
+    of denoiser_aux_tensors."""
+    sd = sd_or_net.state_dict() if hasattr(sd_or_net, "state_dict") else sd_or_net
+    get = (lambda k: dargs[k]) if isinstance(dargs, dict) else (lambda k: getattr(dargs, k))
+    missing = [k for k in DENOISER_LEAVES if (k not in dargs if isinstance(dargs, dict) else not hasattr(dargs, k))]
+    if missing:
+        raise ValueError(f"export_denoiser: tester.denoiser lacks {missing}")
+    keys = list(dargs.keys()) if hasattr(dargs, "keys") else list(DENOISER_LEAVES)
+    settings = {"kind": "denoiser"}
+    flatten({k: get(k) for k in keys}, "tester.denoiser.", settings)
+    tensors = {k: v.detach().to("cpu", torch.float32) for k, v in sd.items()}
+    tensors.update(denoiser_aux_tensors())
+    return write(path, settings, tensors)
 
 
 def read(path, aux=False):

@@ -224,19 +224,48 @@ def blind_starts_for(L, segL, sample_rate, n_segments_blindstep=1, ix_start=0, r
 
 def restore_recording_library(sampler, degraded, *, blind_starts, std=0.1, overlap_s=0.25, clip0=0, std_dev=None, discard_end=200):
     """restore_recording_complete(..., clip0=clip0) without denoiser and rate conversion as ONE library call
-    (babe_restore_recording, csrc/recording.hip): degraded [L] or [1, L] on the GPU at exp.sample_rate; blind_starts: first
-    samples of the blind step's segments (blind_starts_for picks them the way the Python flow does).  The noise comes from the
+    (babe_restore_recording, csrc/recording.hip; with them: restore_file_library): degraded [L] or [1, L] on the GPU at
+    exp.sample_rate; blind_starts: first samples of the blind step's segments (blind_starts_for picks them the way the Python flow does).  The noise comes from the
     library's generator under sampler.seed.  std_dev: a device tensor [1] holding the file's standard deviation (torch's, for
     a bit-exact comparison with the Python flow), None: the call computes it.
     Returns (restored [L], estimated_filter [2, K], blind-step prediction [n, segL]) like restore_recording_complete."""
+    rec = degraded.reshape(-1).float().contiguous()
+    return _library_call(sampler, rec, None, blind_starts, std, overlap_s, clip0, std_dev, discard_end)[:3]
+
+
+def restore_file_library(sampler, degraded, fs, *, blind_starts, denoiser=None, std=0.1, overlap_s=0.25, clip0=0, discard_end=200,
+                         python_tables=False):
+    """restore_recording_complete(..., fs=fs, denoiser=..., clip0=clip0) as ONE library call (babe_restore_file,
+    csrc/dn_engine.hip): degraded [L] or [1, L] on the GPU at `fs`; denoiser: a testing.denoiser_c.LibraryDenoiser or None;
+    blind_starts: callable(L') or list - first samples of the blind step's segments in the CONVERTED file of L' samples
+    (babe_restore_file_plan gives L').  The tables come from the library's own builder, or from babe_amd/resample.py with
+    python_tables=True.  The file's standard deviation is computed by the call.
+    Returns (restored [L'], estimated_filter [2, K], blind-step prediction [n, segL], the signal handed to the model [L'])."""
     import ctypes as C
-    from .._cabi import RecordingDesc
+    from .._lib import check, lib
+    from .denoiser_c import sinc_table
+    rec = degraded.reshape(-1).float().contiguous()
+    fs_dn = int(denoiser._get("sample_rate_denoiser")) if denoiser is not None else 0
+    fs_model = int(sampler.args.exp.sample_rate)
+    lengths = (C.c_long * 3)()
+    mask = lib().babe_restore_file_plan(rec.numel(), int(fs), fs_dn, fs_model, lengths)
+    if mask < 0:
+        check(int(mask), "restore_file_plan")
+    rates = [(int(fs), fs_dn if denoiser is not None else fs_model), (fs_dn, fs_model)]
+    tables = [sinc_table(a, b, rec.device, python_tables) if mask >> k & 1 else None for k, (a, b) in enumerate(rates)]
+    starts = blind_starts(int(lengths[2])) if callable(blind_starts) else blind_starts
+    return _library_call(sampler, rec, (denoiser, tables, lengths), starts, std, overlap_s, clip0, None, discard_end)
+
+
+def _library_call(sampler, rec, file_part, blind_starts, std, overlap_s, clip0, std_dev, discard_end):
+    """babe_restore_recording on rec (file_part None), or babe_restore_file with file_part = (denoiser, tables, lengths)."""
+    import ctypes as C
+    from .._cabi import FileDesc, RecordingDesc
     from .._lib import check, lib, ptr, stream
     from . import eval_c, sample_c
     smp, args = sampler, sampler.args
     segL = int(args.exp.audio_len)
-    rec = degraded.reshape(-1).float().contiguous()
-    L = rec.numel()
+    L = rec.numel() if file_part is None else int(file_part[2][2])
     if smp.seed is None:
         raise ValueError("restore_recording_library draws from the library's generator: the sampler needs a seed")
     if smp.data_consistency:
@@ -268,13 +297,30 @@ def restore_recording_library(sampler, degraded, *, blind_starts, std=0.1, overl
         d.overlap, d.discard_end = int(overlap_s * args.exp.sample_rate), int(discard_end)
         d.inpaint_dc, d.dc_size, d.dc_window = int(bool(args.tester.complete_recording.inpaint_DC)), size, ptr(window)
         d.std_dev = ptr(std_dev)
-        need = lib().babe_recording_workspace_bytes(C.byref(d))
-        if need < 0:
-            check(int(need), "recording_workspace_bytes")
-        ws = torch.empty(need, dtype=torch.uint8, device=rec.device)
         out = torch.empty(L, device=rec.device)
         filt = torch.empty(2, d.eval.K, device=rec.device)
         pred = torch.empty(d.n_blind, segL, device=rec.device)
-        check(lib().babe_restore_recording(C.byref(d), ptr(rec), L, ptr(out), ptr(filt), ptr(pred), int(smp.seed), int(clip0), ptr(ws),
-                                           need, stream(rec)), "restore_recording")
-    return out, filt, pred
+        if file_part is None:
+            need = lib().babe_recording_workspace_bytes(C.byref(d))
+            if need < 0:
+                check(int(need), "recording_workspace_bytes")
+            ws = torch.empty(need, dtype=torch.uint8, device=rec.device)
+            check(lib().babe_restore_recording(C.byref(d), ptr(rec), L, ptr(out), ptr(filt), ptr(pred), int(smp.seed), int(clip0), ptr(ws),
+                                               need, stream(rec)), "restore_recording")
+            return out, filt, pred, rec
+        denoiser, tables, lengths = file_part
+        fd = FileDesc()
+        fd.rec, fd.denoiser = d, (denoiser.handle if denoiser is not None else None)
+        for k, tb in enumerate(tables):
+            if tb is not None:
+                fd.conv[k] = tb[0]
+        for k in range(3):
+            fd.lengths[k] = lengths[k]
+        need = lib().babe_restore_file_workspace_bytes(C.byref(fd))
+        if need < 0:
+            check(int(need), "restore_file_workspace_bytes")
+        ws = torch.empty(need, dtype=torch.uint8, device=rec.device)
+        pre = torch.empty(L, device=rec.device)
+        check(lib().babe_restore_file(C.byref(fd), ptr(rec), rec.numel(), ptr(out), ptr(filt), ptr(pred), ptr(pre), int(smp.seed),
+                                      int(clip0), ptr(ws), need, stream(rec)), "restore_file")
+    return out, filt, pred, pre

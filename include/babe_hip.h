@@ -668,7 +668,7 @@ int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double 
                    double sigma_data, double Schurn, double Stmin, double Stmax, double Snoise, double start_sigma);
 
 /* ---- one WHOLE RECORDING from plan handles (csrc/recording.hip): what long_file.restore_recording_complete (without denoiser and
- * rate conversion) and restore_file_AR sequence from Python (BlindTester.test_real_blind_bwe_complete, testing/
+ * rate conversion: babe_restore_file below puts them in front) and restore_file_AR sequence from Python (BlindTester.test_real_blind_bwe_complete, testing/
  * blind_bwe_tester.py:710-867), as one call for a non-Python host: normalise the file to target_std, estimate the low-pass filter
  * blind on n_blind segments in one coupled batch (babe_sample_bwe with blind = 1, shared = 1), restore the first segment with that
  * filter, out-paint every following segment from the last `overlap` samples of the previous result (babe_sample_bwe with
@@ -900,6 +900,95 @@ const void* babe_model_cqt_plan(const void* model);                  /* babe_cqt
  * fields from the file's defaults (K and fit from tester.blind_bwe, blind = 1, shared = 0, hpf, xi, score_mode 0, audio_len_norm = L).
  * unet_state: the caller's (babe_unet_state_create), one per concurrent stream.  The host overrides what it wants afterwards. */
 int babe_model_eval_desc(const void* model, void* unet_state, babe_eval_desc* desc);
+
+
+/* ---- a recording FILE: rate conversion and the denoiser pre-pass in front of babe_restore_recording (csrc/dn_engine.hip, host
+ * parts in csrc/dn_host.h) - the flow of BlindTester.test_real_blind_bwe_complete with a denoiser (testing/
+ * denoise_and_bwe_tester.py:248-411): file rate -> denoiser rate, apply_denoiser over the whole file, denoiser rate -> model rate,
+ * then normalise / blind estimate / AR pass.  What long_file.restore_recording_complete(fs=..., denoiser=...) sequences from Python,
+ * for a host without it; every piece is bit-identical to its Python counterpart (tests/test_gpu_dn_library.py). */
+/* The table of babe_resample_sinc, host only (no GPU): babe_amd/resample.py::sinc_resample_kernel / _table for the two rates (any
+ * common factor is divided out here), lowpass_filter_width 6, rolloff 0.99.  The builder follows the published float32 operation
+ * sequence, one rounding per operation, no contraction - evaluating the formulas in double and rounding once gives another table
+ * (up to 2.1e-5 of the largest tap for 441:320).  width, orig, new_ and krange (the support |t| < 6) are exactly Python's; a tap
+ * differs from Python's only through the sine / cosine implementation.  _size returns the number of floats of kernel
+ * (new_ (2 width + orig); krange has 2 new_ ints), -1 for rates outside 1..2^20. */
+long babe_resample_sinc_table_size(long orig_freq, long new_freq, int* width, int* orig, int* new_);
+int babe_resample_sinc_table(long orig_freq, long new_freq, float* kernel, int* krange);
+/* ceil(new L / orig) as the published code computes it (the quotient passes through float32): resample.py::resampled_length */
+long babe_resampled_length(long L, long orig_freq, long new_freq);
+
+/* The denoiser from one weights file: the container of babe_model_load (csrc/model_file.h) with the string setting kind =
+ * "denoiser", the leaves of the configuration's tester.denoiser node (depth, num_tfc, num_stages, use_SAM, use_fencoding, f_dim,
+ * sample_rate_denoiser, segment_size, stft_win_size, stft_hop_size) under tester.denoiser.*, the reference state_dict
+ * (freq_encoding.fembeddings included) and two tables whose bits the Python host defines: aux.tw4096 [2048][2] and aux.fade
+ * [2048], the Hamming window of apply_denoiser's cross-fade.  babe_amd/model_file.py::export_denoiser writes it.
+ * Ownership is babe_model_load's: create / load allocate ONE arena on the current device, upload, pack every convolution with
+ * babe_dn_pack_weights (mode 0; the four parity images of a transposed one) on `stream`, and wait on `stream` once; destroy frees;
+ * nothing else here allocates or waits.  Refused with a message before any device call: a file that is no denoiser file (a UNet
+ * file), a missing / duplicate / unexpected / wrong-shape tensor, use_csff / use_cam / use_fam / use_tdf / use_alttdfs set, a depth
+ * outside 1..6, a number of stages outside {1, 2}, use_fencoding with f_dim != stft_win_size / 2 + 1. */
+typedef struct {
+    int depth, num_tfc, num_stages, use_SAM, use_fencoding, f_dim;
+    int sample_rate, win, hop;
+    long segment;                /* samples: int(sample_rate_denoiser * segment_size) */
+    long params;                 /* parameters and buffers of the network (the aux tables not counted) */
+    long device_bytes;           /* the arena, exactly as allocated */
+    int device;
+    double load_ms[3];           /* as babe_model_summary */
+} babe_denoiser_summary;
+void* babe_denoiser_load(const char* path, void* stream);           /* NULL on failure: babe_last_error() */
+void* babe_denoiser_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream);
+void babe_denoiser_destroy(void* denoiser);
+int babe_denoiser_info(const void* denoiser, babe_denoiser_summary* info);
+/* The split-K rule of the denoiser's convolutions, host only: the number of input-channel splits networks/denoiser.py::_split_k
+ * gives a launch of these shapes (1: none).  Reads B, Cin, Cout, OH, OW, KH, KW. */
+int babe_dn_ksplit(const babe_dnconv_args* a);
+/* MultiStage_denoise.forward from the handle: X [B][2][T][F] dense -> pred2, pred1 [B][2][T][F] dense (one stage: pred1 alone,
+ * pred2 is not looked at; two stages: pred1 may be NULL).  The launch sequence of networks/denoiser.py::DenoiserEngine.forward -
+ * same kernels, order and arguments, so the same bits.  Buffers are carved from ws (babe_denoiser_workspace_bytes, -1 on bad
+ * arguments); no allocation, no synchronisation.  F must be f_dim when the network has frequency encodings. */
+long babe_denoiser_workspace_bytes(const void* denoiser, int B, int T, int F);
+int babe_denoiser_fwd(const void* denoiser, const float* X, float* pred2, float* pred1, void* ws, long ws_bytes, int B, int T, int F,
+                      void* stream);
+/* The walk of DenoiserPrepass.apply_denoiser, host only: full segments while start + segment < n, hopping by segment - overlap,
+ * then one zero-padded remainder.  Fills starts up to max entries and returns the number of segments; -1 where the reference fails
+ * (after a first full segment the remainder is longer than segment - overlap) and unless n >= 1, overlap >= 1, segment >= 2 overlap. */
+long babe_denoise_signal_plan(long n, long segment, long overlap, long* starts, long max);
+/* DenoiserPrepass.apply_denoiser: x [B][n] (row stride x_bs) -> out [B][n], at the denoiser's rate.  Per segment of the walk:
+ * babe_dn_segment_pad (cut, zero tail of one STFT window) -> babe_dn_stft -> babe_denoiser_fwd -> babe_dn_istft ->
+ * babe_dn_fade_add.  Everything is checked before the first launch; no allocation, no synchronisation. */
+long babe_denoise_signal_workspace_bytes(const void* denoiser, int B, long n);
+int babe_denoise_signal(const void* denoiser, const float* x, long x_bs, float* out, long out_bs, int B, long n, void* ws,
+                        long ws_bytes, void* stream);
+/* its two element-wise kernels as entries (tests pin them one by one):
+ * dst[b][i] = i < n ? x[b][i] : 0 for i in [0, len), n <= len */
+int babe_dn_segment_pad(const float* x, long x_bs, long n, float* dst, long dst_bs, long len, int B, void* stream);
+/* out[b][i] = out[b][i] + y[b][i] w(i) for i in [0, n), n <= seg: w = fade[i] on [0, size) with fade_in, fade[size + i - (seg - size)]
+ * on [seg - size, seg) with fade_out, 1 elsewhere (fade: device [2 size], seg >= 2 size).  One rounded product, one rounded sum,
+ * in the order of `y[:, :size] *= wl; y[:, -size:] *= wr; out += y`. */
+int babe_dn_fade_add(const float* y, long y_bs, float* out, long out_bs, int B, long n, long seg, const float* fade, int size,
+                     int fade_in, int fade_out, void* stream);
+
+/* long_file.rate_plan, host only.  fs_denoiser 0: no denoiser.  lengths = {Lfile, samples the denoiser sees, samples handed to
+ * the model}.  Returns bit 0: conv[0] runs (file rate -> denoiser rate; without a denoiser file rate -> model rate), bit 1:
+ * conv[1] runs (denoiser rate -> model rate); -1 on bad arguments.  With a denoiser both hang on fs_file != fs_denoiser, as in the
+ * reference: a file already at the denoiser's rate reaches the model unconverted. */
+int babe_restore_file_plan(long Lfile, long fs_file, long fs_denoiser, long fs_model, long* lengths);
+typedef struct { const float* kernel; const int* krange; int width, orig, new_; } babe_sinc_table;   /* device tables, the caller's */
+typedef struct {
+    babe_recording_desc rec;     /* as for babe_restore_recording; blind_starts refer to lengths[2]                         */
+    const void* denoiser;        /* babe_denoiser_load handle, or NULL: no pre-pass                                          */
+    babe_sinc_table conv[2];     /* the conversion before / after the denoiser; kernel NULL: that conversion does not run    */
+    long lengths[3];             /* babe_restore_file_plan's                                                                 */
+} babe_file_desc;
+long babe_restore_file_workspace_bytes(const babe_file_desc* d);
+/* rec [Lfile] at the file's rate -> conv[0] -> babe_denoise_signal -> conv[1] -> exactly babe_restore_recording on the result:
+ * out [lengths[2]], filter_out, blind_pred as there; pre_out [lengths[2]] (may be NULL) receives the signal handed to that last
+ * step.  rec.std_dev NULL: the converted file's standard deviation is computed by the call (babe_row_std).  Every argument is
+ * checked on the host before the first device call; no allocation, no synchronisation. */
+int babe_restore_file(const babe_file_desc* d, const float* rec, long Lfile, float* out, float* filter_out, float* blind_pred,
+                      float* pre_out, long seed, long clip0, void* ws, long ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
