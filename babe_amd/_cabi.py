@@ -164,6 +164,16 @@ class FileDesc(C.Structure):
     _fields_ = [("rec", RecordingDesc), ("denoiser", C.c_void_p), ("conv", SincTable * 2), ("lengths", C.c_long * 3)]
 
 
+class OptTensor(C.Structure):
+    """babe_opt_tensor"""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("ema", C.c_void_p), ("n", C.c_long)]
+
+
+class OptChunk(C.Structure):
+    """babe_opt_chunk"""
+    _fields_ = [("off", C.c_long), ("t", C.c_int), ("n", C.c_int)]
+
+
 # header struct name -> mirror (the layout test compiles a probe for each of them)
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv,
            "babe_packed_conv_layout": PackedConvLayout, "babe_unet_block": CBlock,
@@ -171,7 +181,8 @@ STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packe
            "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
            "babe_recording_desc": RecordingDesc,
            "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary,
-           "babe_denoiser_summary": DenoiserSummary, "babe_sinc_table": SincTable, "babe_file_desc": FileDesc}
+           "babe_denoiser_summary": DenoiserSummary, "babe_sinc_table": SincTable, "babe_file_desc": FileDesc,
+           "babe_opt_tensor": OptTensor, "babe_opt_chunk": OptChunk}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
 _P, _L, _I, _F, _D, _S = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double, C.c_char_p
@@ -366,6 +377,9 @@ SIGS = {
     "babe_restore_file_plan": (_I, [_L, _L, _L, _L, _P]),
     "babe_restore_file_workspace_bytes": (_L, [C.POINTER(FileDesc)]),
     "babe_restore_file": (_I, [C.POINTER(FileDesc), _P, _L, _P, _P, _P, _P, _L, _L, _P, _L, _P]),
+    "babe_opt_chunks": (_L, [_P, _L, _L, _P, _L]),
+    "babe_grad_sqnorm": (_I, [_P, _P, _L, _P, _P, _P]),
+    "babe_adam_ema_step": (_I, [_P, _P, _L, _P, _D, _D, _D, _D, _D, _D, _D, _D, _P]),
 }
 
 

@@ -1,7 +1,7 @@
 """Command line: train the CQTDiff+ prior from audio files on the MI355X path.
 
     python -m babe_amd.train --config FILE [key.sub=value ...] [--precision f32|bf16] [--wgrad f32|bf16] [--its N]
-                               [--dump-params PREFIX]
+                               [--dump-params PREFIX] [--fused-tail]
 
 Follows the reference's train.py / utils/setup.py: load the configuration, build the dataset named by dset.callable
 (`datasets.X` there is `babe_amd.datasets.X` here) behind a DataLoader (batch_size = exp.batch, num_workers = exp.num_workers;
@@ -10,6 +10,8 @@ training.Trainer.training_loop.  FILE is one YAML with the sections exp, network
 what it leaves out comes from config.default_train_args().  key.sub=value overrides are read as YAML scalars or flow lists.
 --its N: stop when the iteration counter reaches N (a resumed run counts from its checkpoint) and write a last checkpoint;
 without it the loop runs until interrupted.  A checkpoint loads with `python -m babe_amd.restore --ckpt`.
+--fused-tail: gradient clipping, Adam and the EMA as the HIP kernels of optim.FusedAdamEMA instead of clip_grad_norm_,
+torch.optim.Adam and update_ema; checkpoints are the same and resume under either.
 
 Several GPUs: start it under torch.distributed.run (RANK, WORLD_SIZE, LOCAL_RANK); rank r trains on cuda:LOCAL_RANK with its
 dataset seeded exp.seed + r, gradients are averaged over RCCL (BABE_DIST_BACKEND=gloo for tests that share one GPU), rank 0
@@ -65,6 +67,8 @@ def main(argv=None):
     ap.add_argument("--dump-params", default=None, metavar="PREFIX",
                     help="when the loop ends, every rank writes its network's state_dict to PREFIX.rank<r>.pt (to check that "
                          "the ranks hold the same weights)")
+    ap.add_argument("--fused-tail", action="store_true",
+                    help="gradient norm, clipping, Adam and the EMA in one HIP pass (optim.FusedAdamEMA)")
     ap.add_argument("overrides", nargs="*", help="key.sub=value")
     a = ap.parse_args(argv)
     args = load_config(a.config, a.overrides)
@@ -101,7 +105,11 @@ def main(argv=None):
     opt = args.exp.optimizer
     if opt.type != "adam":
         raise NotImplementedError(f"exp.optimizer.type={opt.type!r} (the reference implements 'adam' only)")
-    optimizer = torch.optim.Adam(net.parameters(), lr=args.exp.lr, betas=(opt.beta1, opt.beta2), eps=opt.eps)
+    if a.fused_tail:
+        from .optim import FusedAdamEMA
+        optimizer = FusedAdamEMA(net.parameters(), lr=args.exp.lr, betas=(opt.beta1, opt.beta2), eps=opt.eps)
+    else:
+        optimizer = torch.optim.Adam(net.parameters(), lr=args.exp.lr, betas=(opt.beta1, opt.beta2), eps=opt.eps)
     trainer = Trainer(args, loader, net, optimizer, EDM(args), device=device, group=group)
     if rank == 0:
         print(f"total_params: {trainer.total_params / 1e6:.3f} M, model_dir: {trainer.model_dir}, world: {world}" +

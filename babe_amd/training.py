@@ -13,11 +13,13 @@ import torch
 
 
 def train_step(net, optimizer, diff_params, get_batch, it, *, lr, lr_rampup_it=0, num_accumulation_rounds=1,
-               use_grad_clip=True, max_grad_norm=1.0, group=None):
+               use_grad_clip=True, max_grad_norm=1.0, group=None, ema_s=None):
     """One optimizer step: zero_grad, `num_accumulation_rounds` x (loss_fn on get_batch(), loss.mean().backward()), the linear
     learning-rate ramp-up while it <= lr_rampup_it, clip_grad_norm_, step.  Returns (loss of the last round, error, sigma).
     group: a torch.distributed process group; the gradients are averaged over its ranks (allreduce_grads) after the accumulation
-    rounds, so the ramp, the clipping and the step see the same gradient on every rank.  None: nothing is added."""
+    rounds, so the ramp, the clipping and the step see the same gradient on every rank.  None: nothing is added.
+    An optimizer with the fused tail (optim.FusedAdamEMA) clips inside its step() and averages its attached EMA tensors there
+    with the decay ema_s (None: no EMA); .grad then keeps the unclipped gradient."""
     optimizer.zero_grad()
     for _ in range(num_accumulation_rounds):
         audio = get_batch()
@@ -29,17 +31,26 @@ def train_step(net, optimizer, diff_params, get_batch, it, *, lr, lr_rampup_it=0
     if it <= lr_rampup_it:
         for g in optimizer.param_groups:
             g["lr"] = lr * min(it / max(lr_rampup_it, 1e-8), 1)
+    if getattr(optimizer, "fused_tail", False):
+        optimizer.step(max_grad_norm=max_grad_norm if use_grad_clip else None, ema_s=ema_s)
+        return loss.detach(), error.detach(), sigma
     if use_grad_clip:
         torch.nn.utils.clip_grad_norm_(net.parameters(), max_grad_norm)
     optimizer.step()
     return loss.detach(), error.detach(), sigma
 
 
+def ema_decay(it, batch, ema_rampup=10000, ema_rate=0.9999):
+    """The EMA's decay at iteration `it`: t / ema_rampup clipped to [0, ema_rate] while t = it * batch is below ema_rampup,
+    ema_rate from there on (reference :426-439)."""
+    t = it * batch
+    return np.clip(t / ema_rampup, 0.0, ema_rate) if t < ema_rampup else ema_rate
+
+
 def update_ema(ema, net, it, batch, ema_rampup=10000, ema_rate=0.9999):
     """Exponential moving average of net's parameters into ema's (in place; the ema network repacks on its next forward)."""
-    t = it * batch
+    s = ema_decay(it, batch, ema_rampup, ema_rate)
     with torch.no_grad():
-        s = np.clip(t / ema_rampup, 0.0, ema_rate) if t < ema_rampup else ema_rate
         for dst, src in zip(ema.parameters(), net.parameters()):
             dst.copy_(dst * s + src * (1 - s))
 
@@ -140,6 +151,10 @@ class Trainer:
         self.ema = type(network)(network.args, device, precision=network.precision)
         self.ema.load_state_dict(network.state_dict())
         self.ema.eval().requires_grad_(False)
+        # an optimizer with the fused tail (optim.FusedAdamEMA) averages the EMA in its step(): rank 0 attaches the pairs
+        self.fused_tail = bool(getattr(optimizer, "fused_tail", False))
+        if self.fused_tail and self.rank == 0:
+            optimizer.attach_ema(zip(network.parameters(), self.ema.parameters()))
         self.it = 0
         self.latest_checkpoint = None
         self._saved_it = None                  # `it` of the last checkpoint written or loaded (the same on every rank)
@@ -180,11 +195,17 @@ class Trainer:
     # ---------------------------------------------------------------- the step functions, with exp.* values
     def train_step(self):
         ex = self.args.exp
+        ema_s = None
+        if self.fused_tail and self.rank == 0:
+            ema_s = ema_decay(self.it, ex.batch, ema_rampup=ex.ema_rampup, ema_rate=ex.ema_rate)
         return train_step(self.network, self.optimizer, self._tap, self.get_batch, self.it, lr=ex.lr,
                           lr_rampup_it=ex.lr_rampup_it, num_accumulation_rounds=ex.num_accumulation_rounds,
-                          use_grad_clip=ex.use_grad_clip, max_grad_norm=ex.max_grad_norm, group=self.group)
+                          use_grad_clip=ex.use_grad_clip, max_grad_norm=ex.max_grad_norm, group=self.group, ema_s=ema_s)
 
     def update_ema(self):
+        """Nothing with the fused tail: train_step has averaged already."""
+        if self.fused_tail:
+            return
         ex = self.args.exp
         update_ema(self.ema, self.network, self.it, ex.batch, ema_rampup=ex.ema_rampup, ema_rate=ex.ema_rate)
 

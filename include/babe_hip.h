@@ -990,6 +990,34 @@ long babe_restore_file_workspace_bytes(const babe_file_desc* d);
 int babe_restore_file(const babe_file_desc* d, const float* rec, long Lfile, float* out, float* filter_out, float* blind_pred,
                       float* pre_out, long seed, long clip0, void* ws, long ws_bytes, void* stream);
 
+/* ---- Training: the fused optimizer tail (csrc/optim.hip).  Gradient norm, clipping, Adam and the EMA of the weights over a TABLE
+ * of tensors in device memory - a network has hundreds of them, too many for kernel arguments.  Entry: fp32 arrays of n
+ * elements, 4-byte aligned (16-byte accesses are used where every pointer of the entry allows them).  g NULL: an EMA-only
+ * entry - p is read, ema = ema ema_s + p ema_1ms, nothing else is touched (a parameter without a gradient this step, a frozen
+ * parameter).  ema NULL: no EMA for that entry.  Both NULL: the entry is skipped. */
+typedef struct { float* p; const float* g; float* m; float* v; float* ema; long n; } babe_opt_tensor;
+/* One workgroup's share: elements [off, off + n) of tensor t of the table. */
+typedef struct { long off; int t; int n; } babe_opt_chunk;
+/* Host only: cuts nt tensors of n[i] elements into chunks of at most `chunk` elements (a positive multiple of 4), tensor by
+ * tensor in table order, every element in exactly one chunk and no chunk across two tensors.  Writes out[0 .. count) and returns
+ * the count; out NULL: counts only.  -1: nt <= 0, an n[i] <= 0, a bad chunk size, or more than cap chunks. */
+long babe_opt_chunks(const long* n, long nt, long chunk, babe_opt_chunk* out, long cap);
+/* partials[c] = sum of g^2 over chunk c in double (0 for an entry without g), then norm_out[0] = sqrt(sum of the partials), a
+ * double in device memory: two launches, the second one workgroup.  Fixed summation order, no atomics: the same bits every run. */
+int babe_grad_sqnorm(const babe_opt_tensor* table, const babe_opt_chunk* chunks, long nchunks, double* partials, double* norm_out,
+                     void* stream);
+/* Per element of every chunk, with coef = norm ? min(1, max_norm / (norm[0] + 1e-6)) : 1 read from device memory:
+ *   g' = coef g;  m += (1 - beta1) (g' - m);  v = beta2 v + (1 - beta2) g' g';  p -= lr_over_bc1 (m / (sqrt(v) / bc2_sqrt + eps));
+ *   ema = ema ema_s + p ema_1ms  (the new p)
+ * i.e. clip_grad_norm_ + torch.optim.Adam (no amsgrad / weight decay / maximize) + the trainer's EMA; g itself is NOT rewritten.
+ * g', m and v in fp32 with the roundings of torch's kernels (its bits from equal inputs); the update of p and the EMA in double
+ * from the stored moments, rounded once.
+ * lr_over_bc1 = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step), formed by the caller in double.  One launch.
+ * BABE_ERR_ARG before any launch: NULL table or chunks, nchunks <= 0, a beta outside [0, 1), eps <= 0, a negative lr_over_bc1. */
+int babe_adam_ema_step(const babe_opt_tensor* table, const babe_opt_chunk* chunks, long nchunks, const double* norm, double max_norm,
+                       double lr_over_bc1, double bc2_sqrt, double beta1, double beta2, double eps, double ema_s, double ema_1ms,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,12 @@ the parts add up.  Compare with `step_ms` of tools/train_bench.py run next to it
 JSON document (profiles/train_loop.json).
 
     python tools/train_loop_bench.py [--B 4] [--L 368368] [--its 20] [--warmup 3] [--wgrad {f32,bf16}] [--precision {f32,bf16}]
-                                     [--num-workers 0]
+                                     [--num-workers 0] [--fused-tail | --torch-fused]
+
+--fused-tail: optim.FusedAdamEMA (norm, clipping, Adam and the EMA in the library's kernels; update_ema_ms is then 0 and the
+tail's time is part of train_step_ms).  --torch-fused: torch.optim.Adam(fused=True) with clip_grad_norm_ and update_ema as they are.
+Compare train_step_ms + update_ema_ms between runs; tail_kernel_ms (--fused-tail) is the HIP-event time of the tail's launches
+alone, with the fraction of the 6.29 TB/s copy rate its 40 bytes per parameter come to.
 
 The data are four one-minute 16-bit stereo wavs written to a temporary directory and read through AudioFolderDataset.
 """
@@ -32,6 +37,8 @@ def main():
     ap.add_argument("--wgrad", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--precision", choices=["f32", "bf16"], default="f32")
     ap.add_argument("--num-workers", type=int, default=0)
+    ap.add_argument("--fused-tail", action="store_true")
+    ap.add_argument("--torch-fused", action="store_true")
     a = ap.parse_args()
     from scipy.io import wavfile
     from babe_amd.config import default_train_args
@@ -56,7 +63,11 @@ def main():
         net = Unet_CQT_oct_with_attention(args, "cuda", precision=a.precision)
         net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0))
         net.set_trainable(True, wgrad=a.wgrad)
-        opt = torch.optim.Adam(net.parameters(), lr=args.exp.lr)
+        if a.fused_tail:
+            from babe_amd.optim import FusedAdamEMA
+            opt = FusedAdamEMA(net.parameters(), lr=args.exp.lr)
+        else:
+            opt = torch.optim.Adam(net.parameters(), lr=args.exp.lr, **({"fused": True} if a.torch_fused else {}))
         tr = Trainer(args, loader, net, opt, EDM(args), device="cuda")
         tr.sync_timers = True
         tr.training_loop(total_its=a.warmup)
@@ -69,7 +80,7 @@ def main():
         wall = time.perf_counter() - t0
         n = tr.timers["its"]
         res = {"B": a.B, "L": a.L, "precision": a.precision, "wgrad": a.wgrad, "num_workers": a.num_workers, "iterations": n,
-               "iteration_ms": round(1e3 * wall / n, 2)}
+               "tail": "fused" if a.fused_tail else "torch-fused-adam" if a.torch_fused else "torch", "iteration_ms": round(1e3 * wall / n, 2)}
         for k in ("get_batch", "train_step", "update_ema", "log"):
             res[k + "_ms"] = round(1e3 * tr.timers[k] / n, 2)
         # one log line WITH the band energies (every logging.freq_cqt_logging-th iteration; none falls into the timed ones)
@@ -79,6 +90,24 @@ def main():
         t0 = time.perf_counter()
         net.CQTransform.band_energy(x).mean(0).cpu()
         res["band_energy_ms"] = round(1e3 * (time.perf_counter() - t0), 2)
+        if a.fused_tail:
+            # the tail's launches alone (the table's 29 KB copy included), between HIP events: the gradients of the last iteration
+            # are still there; a matrix product in front keeps the GPU busy until step() has queued everything
+            ex = args.exp
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            big = torch.randn(8192, 8192, device="cuda")
+            ms = []
+            for _ in range(5):
+                big @ big
+                ev[0].record()
+                opt.step(max_grad_norm=ex.max_grad_norm, ema_s=ex.ema_rate)
+                ev[1].record()
+                torch.cuda.synchronize()
+                ms.append(ev[0].elapsed_time(ev[1]))
+            nparam = sum(p.numel() for p in net.parameters())
+            res["tail_kernel_ms"] = round(min(ms), 4)
+            res["tail_bytes"] = 40 * nparam
+            res["tail_fraction_of_6.29TBps"] = round(40 * nparam / (min(ms) * 1e-3) / 6.29e12, 3)
         print(json.dumps(res, indent=1))
     finally:
         shutil.rmtree(root, ignore_errors=True)
