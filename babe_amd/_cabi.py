@@ -251,6 +251,8 @@ SIGS = {
     "babe_conv2d_wino85": (_I, [C.POINTER(ConvArgs), _P, _P]),
     "babe_conv2d_wino85_set_waves": (_I, [_I]),
     "babe_packed_conv_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(PackedConvLayout)]),
+    "babe_conv_splits_for": (_I, [_I, _I, _I, _I, _I, _I]),
+    "babe_conv2d_bf16_units_shape": (_I, [C.POINTER(CPackedConv), _I]),
     "babe_packed_conv_pack": (_I, [C.POINTER(CPackedConv), _P, _P]),
     "babe_conv2d_auto": (_I, [C.POINTER(ConvArgs), C.POINTER(CPackedConv), _I, _P]),
     "babe_unet_plan_create": (_P, [C.POINTER(CPlanDesc)]),
@@ -353,6 +355,9 @@ SIGS = {
     "babe_scale_channels": (_I, [_P, _P, _P, _I, _I, _L, _P]),
     "babe_model_load": (_P, [_S, _P]),
     "babe_model_create": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _P]),
+    "babe_model_load_ex": (_P, [_S, _I, _P]),
+    "babe_model_create_ex": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _I, _P]),
+    "babe_model_precision": (_I, [_P]),
     "babe_model_destroy": (None, [_P]),
     "babe_model_info": (_I, [_P, C.POINTER(ModelSummary)]),
     "babe_model_setting": (_I, [_P, _S, C.POINTER(_D)]),

@@ -1,7 +1,9 @@
 // One Conv2d's packed images from end to end: which exist and how large each is (babe_packed_conv_plan), filling them
 // (babe_packed_conv_pack) and picking a kernel from them (babe_conv2d_auto).  Both builders of a babe_packed_conv - csrc/model.hip
 // and babe_amd/ops.py::PackedConv - ask the first and call the second, so they cannot disagree; the channel clauses are the
-// conv_*_shape predicates of conv_common.h, which the kernels' *_supported rules call too.  Host code only.
+// conv_*_shape predicates of conv_common.h, which the kernels' *_supported rules call too.  Two more rules both builders and both
+// UNet sequencers share live here: which convs a precision turns into bf16 products (babe_conv_splits_for) and which layers may
+// take bf16 units (babe_conv2d_bf16_units_shape).  Host code only.
 #include "conv_common.h"
 
 /* Pure host arithmetic: no HIP call, no environment variable.  Slot i of bytes[] is direction i & 1 (0 the conv, 1 its input-VJP)
@@ -31,6 +33,29 @@ extern "C" int babe_packed_conv_plan(int Cout, int Cin, int KH, int KW, int spli
     // one raw image serves whichever direction executes with <= 4 output channels
     out->raw = !splits && (forms & BABE_CONV_FORM_FEWCO) && (conv_fewco_shape(Cout, KW) || conv_fewco_shape(Cin, KW));
     return BABE_OK;
+}
+
+/* Which convs a requested precision turns into bf16 products - the one statement of that rule (ops.PackedConv.splits_for and the
+ * model loader both ask it).  Shapes that gain nothing from bf16 MFMA stay on the fp32 kernels under hbm_f32 (exact AND at least
+ * as fast): <= 4 channels on one side (few-channel kernels), (1,1) kernels with fewer than 32 channels on one side (HBM-bound:
+ * all-DMA kernel), and every (1,1) kernel of bf16x3.  Wide (1,1) kernels are MFMA-bound in fp32 and take the pipelined bf16
+ * kernel under bf16.  Bad arguments: -1 with the message set. */
+extern "C" int babe_conv_splits_for(int Cout, int Cin, int KH, int KW, int precision, int hbm_f32) {
+    if (Cout < 1 || Cin < 1 || KH < 1 || KW < 1 || precision < BABE_PRECISION_F32 || precision > BABE_PRECISION_BF16X3) {
+        babe_set_error("conv_splits_for: bad arguments (weights [%d][%d][%d][%d], precision %d)", Cout, Cin, KH, KW, precision);
+        return -1;
+    }
+    const int splits = precision, narrow = Cout < Cin ? Cout : Cin;
+    const bool k11 = KH * KW == 1;
+    if (splits && hbm_f32 && (narrow <= 4 || (k11 && (splits == 2 || narrow < 32)))) return 0;
+    return splits;
+}
+
+/* The static half of "this (5,3) forward conv takes its input as bf16 units" (csrc/conv_bf16p.hip, UNITS variant): what the
+ * weights and the time length decide.  Alignment, the 2 GiB descriptor limits and BABE_CONV_BF16U are the call's own verdict,
+ * babe_conv2d_bf16_units_supported. */
+extern "C" int babe_conv2d_bf16_units_shape(const babe_packed_conv* pc, int T) {
+    return pc && pc->splits == 1 && pc->KH == 5 && pc->KW == 3 && T > 0 && T % 4 == 0 && pc->Cin % 8 == 0 && pc->Cout > 32;
 }
 
 /* Per direction: direct, then F(2,3), F(4,3), F(2,5)xF(4,3), F(4,5)xF(4,3); a NULL image is skipped.  Enqueues the pack kernels

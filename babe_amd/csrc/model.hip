@@ -2,7 +2,8 @@
 // a host without Python calls instead of restating UnetEngine.__init__, _Block, _FilmIndex, ops.PackedConv, STFTOps and CEval.
 // The loader does what the Python engine does, with the same pack kernels on the same raw weights, so every image, table and
 // descriptor field is bit-identical to the Python-built one (tests/test_gpu_model_c.py):
-//   images       babe_packed_conv_plan (csrc/conv_auto.hip) with the default forms, as ops.PackedConv asks it
+//   images       babe_packed_conv_plan (csrc/conv_auto.hip) with the default forms, as ops.PackedConv asks it; each conv's splits
+//                from babe_conv_splits_for under the precision the HOST asked for at load time (the file holds the fp32 masters)
 //   block order  UnetEngine.blocks(): init, main, mid_blk, mid_out, up_out, up_blk
 //   FiLM         _FilmIndex: blocks in CONSTRUCTION order (init i, main i per octave; mid_blk, mid_out; up_out i, up_blk i), per
 //                dilation layer the affine rows, then the gate rows
@@ -28,7 +29,7 @@ using namespace babe_model;
 struct Model {
     NetCfg cfg;
     std::map<std::string, Setting> settings;
-    int device = -1;
+    int device = -1, precision = 0;
     char* arena = nullptr;
     size_t arena_bytes = 0, upload_bytes = 0;
     long params = 0;
@@ -62,20 +63,24 @@ struct Builder {
     const Tensor& T(const std::string& name) const { return *f.find(name); }       // (check_tensors found every name)
 
     // every image of one conv, as babe_packed_conv_plan lays them out (default forms; nt 2 where the (1,1) rule allows it), carved
-    // direction by direction and packed from the device copy of the raw weights
+    // direction by direction and packed from the device copy of the raw weights.  splits: the library's rule for the model's
+    // precision with bf16_hbm_f32 on, as the Python engine has it by default; bf16 images are 2-byte elements, carved by their byte
+    // count on the same 256-byte granules
     int conv(babe_packed_conv& pc, const float* w, int Cout, int Cin, int KH, int KW) {
         babe_packed_conv_layout lay;
-        BABE_TRY(babe_packed_conv_plan(Cout, Cin, KH, KW, 0, 0, 2, BABE_CONV_FORMS_ALL, &lay));
+        const int splits = babe_conv_splits_for(Cout, Cin, KH, KW, m.precision, 1);
+        if (splits < 0) return BABE_ERR_ARG;
+        BABE_TRY(babe_packed_conv_plan(Cout, Cin, KH, KW, splits, 0, 2, BABE_CONV_FORMS_ALL, &lay));
         memset(&pc, 0, sizeof pc);
-        pc.Cout = Cout, pc.Cin = Cin, pc.KH = KH, pc.KW = KW, pc.nt = lay.nt;
+        pc.Cout = Cout, pc.Cin = Cin, pc.KH = KH, pc.KW = KW, pc.nt = lay.nt, pc.splits = lay.splits;
         if (lay.raw) pc.w_raw = w;
         const float** family[8] = {&pc.fwd_wino, &pc.bwd_wino, &pc.fwd_wino4, &pc.bwd_wino4, &pc.fwd_wino45, &pc.bwd_wino45, &pc.fwd_wino85, &pc.bwd_wino85};
         for (int tf = 0; tf < 2; ++tf)
             for (int i = tf; i < 10; i += 2) {
                 if (!lay.bytes[i]) continue;
-                float* img = c.take<float>((size_t)lay.bytes[i] / sizeof(float));
+                char* img = c.take<char>((size_t)lay.bytes[i]);
                 if (i < 2) (tf ? pc.bwd : pc.fwd) = img;
-                else *family[i - 2] = img;
+                else *family[i - 2] = reinterpret_cast<float*>(img);
             }
         return dry() ? BABE_OK : babe_packed_conv_pack(&pc, w, stream);
     }
@@ -205,9 +210,10 @@ void destroy(Model* m) {
 
 // f (validated here) -> a model on the current device, or nullptr with the message set.  t0: when the caller began (load: before
 // it read the file).
-void* create(File& f, void* stream, double t0) {
+void* create(File& f, int precision, void* stream, double t0) {
     std::unique_ptr<Model> guard(new Model);
     Model& m = *guard;
+    m.precision = precision;
     std::string err;
     if (!validate(f, m.cfg, err)) return babe_set_error("model: %s", err.c_str()), nullptr;
     const NetCfg& cfg = m.cfg;
@@ -275,8 +281,16 @@ const Model* use(const void* model, const char* who) {
 }
 }  // namespace
 
-extern "C" void* babe_model_load(const char* path, void* stream) {
+// (asked first: a host's own mistake, whatever the file holds)
+static bool precision_ok(int precision, const char* who) {
+    if (precision >= BABE_PRECISION_F32 && precision <= BABE_PRECISION_BF16X3) return true;
+    babe_set_error("%s: precision %d is none of BABE_PRECISION_F32 (0), _BF16 (1), _BF16X3 (2)", who, precision);
+    return false;
+}
+
+extern "C" void* babe_model_load_ex(const char* path, int precision, void* stream) {
     const double t0 = now_ms();
+    if (!precision_ok(precision, "model_load")) return nullptr;
     if (!path) return babe_set_error("model_load: null path"), nullptr;
     FILE* fh = fopen(path, "rb");
     if (!fh) return babe_set_error("model_load: cannot open %s: %s", path, strerror(errno)), nullptr;
@@ -294,11 +308,14 @@ extern "C" void* babe_model_load(const char* path, void* stream) {
     File f;
     std::string err;
     if (!parse(buf.data(), buf.size(), f, err)) return babe_set_error("model_load: %s: %s", path, err.c_str()), nullptr;
-    return create(f, stream, t0);
+    return create(f, precision, stream, t0);
 }
+extern "C" void* babe_model_load(const char* path, void* stream) { return babe_model_load_ex(path, BABE_PRECISION_F32, stream); }
 
-extern "C" void* babe_model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream) {
+extern "C" void* babe_model_create_ex(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision,
+                                      void* stream) {
     const double t0 = now_ms();
+    if (!precision_ok(precision, "model_create")) return nullptr;
     if (!entries || !settings || n < 1 || nsettings < 1) return babe_set_error("model_create: null or empty tables"), nullptr;
     File f;
     std::string err;
@@ -314,7 +331,16 @@ extern "C" void* babe_model_create(const babe_model_entry* entries, int n, const
         if (!add_tensor(f, entries[i].name, entries[i].ndim, entries[i].shape, entries[i].data, err))
             return babe_set_error("model_create: %s", err.c_str()), nullptr;
     }
-    return create(f, stream, t0);
+    return create(f, precision, stream, t0);
+}
+extern "C" void* babe_model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream) {
+    return babe_model_create_ex(entries, n, settings, nsettings, BABE_PRECISION_F32, stream);
+}
+
+extern "C" int babe_model_precision(const void* model) {
+    const Model* m = static_cast<const Model*>(model);
+    if (!m) return babe_set_error("model_precision: null model"), -1;
+    return m->precision;
 }
 
 extern "C" void babe_model_destroy(void* model) { destroy(static_cast<Model*>(model)); }

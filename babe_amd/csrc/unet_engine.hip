@@ -3,7 +3,9 @@
 // as the Python engine (babe_amd/networks/unet_engine.py; /root/reference/networks/cqtdiff+.py:746-839 forward, ResnetBlock :452-493;
 // the VJP replaces torch.autograd through the network, testing/blind_bwe_sampler.py:120) - the two are bit-identical
 // (tests/test_gpu_unet_c.py) - so a non-Python host gets the whole network through the C-ABI, and the Python host sheds its
-// per-evaluation enqueue time.  fp32 arithmetic only (precision 'bf16' / 'bf16x3' stay on the Python engine).
+// per-evaluation enqueue time.  The images decide the arithmetic: fp32, or bf16 / bf16x3 images (babe_packed_conv::splits) that
+// babe_conv2d_auto runs over the same fp32 activations; under bf16 the wide (5,3) layers take their input as bf16 units, as the
+// Python engine's block_fwd does (tests/test_gpu_bf16_library.py).
 //
 // Memory: the caller owns everything.  Activations, saved tensors and scratch are carved from ONE workspace by a bump allocator
 // (256-byte granules) that is reset by babe_unet_fwd; what the VJP needs (one tensor per dilation layer + per-layer statistics)
@@ -65,6 +67,8 @@ struct babe_unet_state_s {
     bool dry = false;
     float* scr_a = nullptr;
     size_t scr_a_n = 0;
+    void* units = nullptr;         // the bf16 units of the layer being run (babe_scale_gelu_units), grown like scr_a
+    size_t units_n = 0;            // in floats
     Saved saved[6][8][8];          // [kind][index][layer]: kinds 0 init, 1 main, 2 up_out, 3 up_blk, 4 mid_blk, 5 mid_out
     View hs[8];
     const float* film = nullptr;
@@ -115,6 +119,12 @@ struct Ctx {
     float* scratch_a(size_t n) {
         if (n > S->scr_a_n) { S->scr_a = alloc(n); S->scr_a_n = n; }
         return S->scr_a;
+    }
+    // B * nu 16-byte units (nu = babe_units_size) = B * nu * 8 int16
+    void* scratch_units(size_t nu) {
+        const size_t n = (size_t)B() * nu * 4;
+        if (n > S->units_n) { S->units = alloc(n); S->units_n = n; }
+        return S->units;
     }
     void ck(int e) { if (e && !err) err = e; }
 
@@ -193,6 +203,12 @@ struct Ctx {
             z = buf(N, Fq, T);
             axpby(x, z);
         }
+        // bf16 images: the GELU output goes to the wide (5,3) convs as bf16 units (half the bytes, both conv operands by LDS-DMA).
+        // The buffer is carved wherever the static rule holds, whatever the per-layer verdict will be, so that
+        // babe_unet_workspace_bytes does not depend on it; an fp32 plan never carves it.
+        const bool units = blk.nd > 0 && babe_conv2d_bf16_units_shape(&blk.H[0], T) && z.dense();
+        const long nu = units ? babe_units_size(N, Fq, T) : 0;
+        void* au = units ? scratch_units((size_t)nu) : nullptr;
         double* zpart = nullptr;                 // GroupNorm sums of z formed by the conv that wrote it (zS slots per group; 0: none)
         int zS = 0;
         for (int d = 0; d < blk.nd; ++d) {
@@ -210,7 +226,23 @@ struct Ctx {
             double* part = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * Sp * 2 * 2));
             float* stats = alloc((size_t)B() * G_GROUPS * 3);
             float* scale = alloc((size_t)B() * N);
-            if (!dry() && !err) {
+            const int dil = blk.k53 ? (1 << d) : 1, cg = N / G_GROUPS;
+            // the library's own verdict on the units call (ops.units_args: in_bs = units per item, in_cs = per 8-channel group, no
+            // second source, no in_scale), asked BEFORE writing units
+            babe_conv_args ua{};
+            bool take_units = false;
+            if (units && !dry() && !err) {
+                ua = conv_args(z, znew, dil, nullptr, &z, nullptr, gate, RS2, RS2);
+                ua.in = static_cast<const float*>(au); ua.in_bs = nu; ua.in_cs = nu / (N / 8);
+                ua.Cin = ua.Cout = ua.cin_split = N; ua.KH = blk.H[d].KH; ua.KW = blk.H[d].KW;
+                take_units = babe_conv2d_bf16_units_supported(&ua) != 0;
+            }
+            if (take_units) {
+                ck(babe_gn_partial(z.p, part, B(), G_GROUPS, n, Sp, st));
+                ck(babe_gn_finalize(part, blk.gamma[d], film_at(blk.film_aff[d]), S->film_bs, stats, scale, B(), N, G_GROUPS, n, Sp, GN_EPS, st));
+                ck(babe_scale_gelu_units(z.p, scale, au, B(), N, Fq, T, st));
+                ck(babe_conv2d_bf16_units(&ua, blk.H[d].fwd, st));
+            } else if (!dry() && !err) {
                 if (!zS) ck(babe_gn_partial(z.p, part, B(), G_GROUPS, n, Sp, st));
                 ck(babe_scale_gelu_fin(z.p, zS ? zpart : part, blk.gamma[d], film_at(blk.film_aff[d]), S->film_bs, stats, scale, a, B(), N,
                                        G_GROUPS, (long)Fq * T, zS ? zS : Sp, GN_EPS, st));
@@ -218,7 +250,6 @@ struct Ctx {
             View av = z; av.p = a; av.cs = (long)Fq * T; av.bs = (long)N * Fq * T;
             // the next layer's GroupNorm reads znew: its sums come out of this conv's epilogue when the F(4,5) kernel runs it
             // (unet_engine.py: ops.conv2d(..., fwd_stat=))
-            const int dil = blk.k53 ? (1 << d) : 1, cg = N / G_GROUPS;
             double* npart = nullptr;
             int nS = 0;
             // (carved whatever the form is, so that babe_unet_workspace_bytes does not depend on it: a form may change between
@@ -227,8 +258,8 @@ struct Ctx {
                 nS = stat_slots(cg, Fq, T, dil);
                 npart = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * nS * 2 * 2));
             }
-            const bool made = conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, form(BABE_FORM_FUSE_GN_FWD) ? npart : nullptr);
-            zS = made ? nS : 0;
+            const bool made = !take_units && conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, form(BABE_FORM_FUSE_GN_FWD) ? npart : nullptr);
+            zS = made ? nS : 0;                                                      // (a units layer drops the carried sums)
             zpart = npart;
             saved[d] = Saved{z, stats, scale, gate};
             z = znew;
@@ -551,7 +582,7 @@ extern "C" int babe_unet_fwd(const void* plan, void* state, const float* const* 
     auto* S = static_cast<babe_unet_state_s*>(state);
     if (int e = unet_set_shape(S, P, B, T_oct)) return e;
     S->ws = static_cast<float*>(workspace); S->cap = (size_t)workspace_bytes; S->off = 0; S->high = 0; S->dry = false;
-    S->scr_a = nullptr; S->scr_a_n = 0; S->film = film; S->film_bs = film_bs; S->have_fwd = false;
+    S->scr_a = nullptr; S->scr_a_n = 0; S->units = nullptr; S->units_n = 0; S->film = film; S->film_bs = film_bs; S->have_fwd = false;
     Ctx c{P, S, (hipStream_t)stream};
     c.forward(C_in, const_cast<float**>(outs));
     if (c.err) return c.err;

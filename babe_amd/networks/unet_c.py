@@ -3,7 +3,8 @@
 `CPlan` describes a `UnetEngine`'s packed weights to the library once (a plan handle, owned by the engine); a `CUnet` is one
 library-side state and workspace over it, whose `fwd` / `vjp` are ONE C call per direction instead of ~1100 op-level calls from
 Python.  Results are bit-identical to the Python-sequenced engine
-(tests/test_gpu_unet_c.py).  fp32 convs only.  Workspace and outputs are torch allocations (the library never allocates)."""
+(tests/test_gpu_unet_c.py; tests/test_gpu_bf16_library.py for a 'bf16' / 'bf16x3' engine, whose images the library sequences as
+they are).  Workspace and outputs are torch allocations (the library never allocates)."""
 import ctypes as C
 
 import torch
@@ -39,7 +40,6 @@ class CPlan:
 
     def get(self, eng):
         if self.handle is None:
-            assert eng.precision == "f32", "the library-side engine sequences the fp32 network"
             if eng.has_attention:
                 raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
                                           "(such networks run on the Python sequencer)")

@@ -78,15 +78,13 @@ class PackedConv:
 
     @staticmethod
     def splits_for(shape, precision):
-        """bf16 products per multiply a conv of this weight shape runs with under `precision`; 0 = the fp32 kernels."""
-        splits = PRECISIONS[precision]
-        # Shapes that gain nothing from bf16 MFMA run on the fp32 kernels whatever the requested precision (exact AND at
-        # least as fast): convs with <= 4 channels on one side (few-channel kernels), (1,1) kernels with fewer than 32
-        # channels on one side (HBM-bound: all-DMA kernel), and every (1,1) kernel of the bf16x3 mode.  Wide (1,1) kernels are
-        # MFMA-bound in fp32 (up to 85 flop/B) and take the pipelined bf16 kernel under 'bf16'.
-        k11 = shape[2] * shape[3] == 1
-        if splits and FORMS.bf16_hbm_f32 and (min(shape[0], shape[1]) <= 4 or (k11 and (splits == 2 or min(shape[0], shape[1]) < 32))):
-            return 0
+        """bf16 products per multiply a conv of this weight shape runs with under `precision`; 0 = the fp32 kernels.  The
+        library's rule (babe_conv_splits_for, csrc/conv_auto.hip: which shapes stay fp32 whatever the precision), asked with this
+        process's bf16_hbm_f32 form."""
+        splits = lib().babe_conv_splits_for(int(shape[0]), int(shape[1]), int(shape[2]), int(shape[3]), PRECISIONS[precision],
+                                            int(bool(FORMS.bf16_hbm_f32)))
+        if splits < 0:
+            raise _lib.BabeHipError("conv_splits_for: " + lib().babe_last_error().decode())
         return splits
 
     def __setattr__(self, k, v):
@@ -256,7 +254,8 @@ def scale_gelu(x, scale, out):
 
 def units_ok(pc, Cin, Cout, T):
     """True if the forward of this (5,3) conv can take its input as bf16 units (csrc/conv_bf16p.hip, UNITS variant)."""
-    return FORMS.units and pc.splits == 1 and pc.KH == 5 and pc.KW == 3 and T % 4 == 0 and Cin % 8 == 0 and Cout > 32
+    assert (Cin, Cout) == (pc.Cin, pc.Cout)
+    return bool(FORMS.units and lib().babe_conv2d_bf16_units_shape(C.byref(pc.desc), int(T)))
 
 
 def scale_gelu_units(x, scale, au):

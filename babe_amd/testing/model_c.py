@@ -8,13 +8,15 @@ from .._lib import BabeHipError, check, lib, stream
 
 
 class LibraryModel:
-    """babe_model_load(path) on the current device and stream; `close()` (or garbage collection) destroys it.  Plans and
+    """babe_model_load_ex(path, precision) on the current device and stream; `close()` (or garbage collection) destroys it.
+    precision: 'f32' | 'bf16' | 'bf16x3' (ops.PRECISIONS) - the host's choice, the file holds the fp32 masters.  Plans and
     descriptors taken from it point into its arena: keep the object alive while they are in use."""
 
-    def __init__(self, path):
-        self.handle = lib().babe_model_load(str(path).encode(), stream())
+    def __init__(self, path, precision="f32"):
+        from ..ops import PRECISIONS
+        self.handle = lib().babe_model_load_ex(str(path).encode(), PRECISIONS[precision], stream())
         if not self.handle:
-            raise BabeHipError("babe_model_load: " + lib().babe_last_error().decode())
+            raise BabeHipError("babe_model_load_ex: " + lib().babe_last_error().decode())
 
     def close(self):
         if getattr(self, "handle", None):
@@ -32,6 +34,11 @@ class LibraryModel:
         s = ModelSummary()
         check(lib().babe_model_info(self.handle, C.byref(s)), "model_info")
         return s
+
+    @property
+    def precision(self):
+        """babe_model_precision: 0 f32, 1 bf16, 2 bf16x3."""
+        return lib().babe_model_precision(self.handle)
 
     def setting(self, key):
         v = C.c_double()

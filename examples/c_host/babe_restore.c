@@ -1,12 +1,13 @@
 /* babe_restore: blind bandwidth extension of one clip batch from C - no Python, no torch in the process.
  *
- *     babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32]
+ *     babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32] [--precision f32|bf16|bf16x3]
  *
  * model.babe: written by `python -m babe_amd.export`.  in.f32: B * L float32 samples at the model's rate (L and the rate are the
  * model's: babe_model_info), B clips one after the other.  out.f32: the B * L restored samples.  --params: the estimated filter
  * of each clip, B * 2 * K float32 (K cut-off frequencies in Hz, then K slopes in dB).  --T: sampling steps (default: the file's
  * tester.T); --seed: the noise is the library's counter-based generator under this seed (default 0), so the output is a function
- * of (model, input, seed, T).  Links against libbabe_hip.so and the HIP runtime (babe_amd/build.py::build_example).
+ * of (model, input, seed, T, precision).  --precision: the conv arithmetic the loader packs the file's fp32 weights for (default
+ * f32; bf16 is the fast one).  Links against libbabe_hip.so and the HIP runtime (babe_amd/build.py::build_example).
  * Exit status: 0, or 1 with the failing step and babe_last_error() on stderr. */
 #include <hip/hip_runtime_api.h>
 #include <stdio.h>
@@ -19,13 +20,17 @@
 #define LIB(call, what) do { if ((call) != 0) FAIL("%s: %s", what, babe_last_error()); } while (0)
 #define HIP(call, what) do { hipError_t e_ = (call); if (e_ != hipSuccess) FAIL("%s: %s", what, hipGetErrorString(e_)); } while (0)
 
+static int precision_of(const char* s) {
+    return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
+}
+
 static double setting(const void* model, const char* key, double fallback) {
     double v;
     return babe_model_setting(model, key, &v) == 0 ? v : fallback;
 }
 
 int main(int argc, char** argv) {
-    int status = 1, B = 1, T = 0;
+    int status = 1, B = 1, T = 0, precision = BABE_PRECISION_F32;
     long seed = 0;
     const char* params_path = NULL;
     void *model = NULL, *state = NULL, *ws = NULL;
@@ -33,7 +38,8 @@ int main(int argc, char** argv) {
     babe_sample_step* steps = NULL;
     FILE* fh = NULL;
     if (argc < 4) {
-        fprintf(stderr, "usage: babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32]\n");
+        fprintf(stderr, "usage: babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32] "
+                        "[--precision f32|bf16|bf16x3]\n");
         return 2;
     }
     for (int i = 4; i < argc; ++i) {
@@ -42,14 +48,17 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--T")) T = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--batch")) B = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--params")) params_path = argv[++i];
+        else if (!strcmp(argv[i], "--precision")) {
+            if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
         else FAIL("unknown option %s", argv[i]);
     }
     if (B < 1) FAIL("--batch must be at least 1");
 
     /* [core] the listing of INTEGRATION.md section 2 */
     /* 1. the network: weights, packed images, CQT plan, STFT tables - one handle, one device arena */
-    model = babe_model_load(argv[1], NULL);
-    if (!model) FAIL("babe_model_load: %s", babe_last_error());
+    model = babe_model_load_ex(argv[1], precision, NULL);
+    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
     babe_model_summary info;
     LIB(babe_model_info(model, &info), "babe_model_info");
     const long L = info.L;

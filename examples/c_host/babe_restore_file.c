@@ -2,7 +2,7 @@
  * Python, no torch in the process.
  *
  *     babe_restore_file model.babe in.f32 RATE out.f32 [--denoiser denoiser.babe] [--seed N] [--T n] [--blind-segments N]
- *                       [--ix-start s]
+ *                       [--ix-start s] [--precision f32|bf16|bf16x3]
  *
  * model.babe: written by `python -m babe_amd.export`; denoiser.babe: by `python -m babe_amd.export_denoiser`.  in.f32: the
  * recording, float32 samples of any length at RATE Hz.  out.f32: the restored recording at the MODEL's rate.  The file is
@@ -29,13 +29,17 @@
 #define DC_SIZE 50          /* predict_bwe_AR smooths the edge of its mask over 50 samples */
 #define DISCARD_END 200     /* samples at the end of a restored segment that are not kept */
 
+static int precision_of(const char* s) {
+    return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
+}
+
 static double setting(const void* model, const char* key, double fallback) {
     double v;
     return babe_model_setting(model, key, &v) == 0 ? v : fallback;
 }
 
 int main(int argc, char** argv) {
-    int status = 1, T = 0, n_blind = 1;
+    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32;
     long seed = 0, Lfile = 0, Lrec = 0, fs_file = 0;
     double ix_start = 0.0;
     const char* denoiser_path = NULL;
@@ -47,7 +51,7 @@ int main(int argc, char** argv) {
     FILE* fh = NULL;
     if (argc < 5) {
         fprintf(stderr, "usage: babe_restore_file model.babe in.f32 RATE out.f32 [--denoiser denoiser.babe] [--seed N] [--T n] "
-                        "[--blind-segments N] [--ix-start s]\n");
+                        "[--blind-segments N] [--ix-start s] [--precision f32|bf16|bf16x3]\n");
         return 2;
     }
     fs_file = atol(argv[3]);
@@ -59,6 +63,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--T")) T = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--blind-segments")) n_blind = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--ix-start")) ix_start = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--precision")) {
+            if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
         else FAIL("unknown option %s", argv[i]);
     }
     if (n_blind < 1 || n_blind > 16) FAIL("--blind-segments must be 1..16");
@@ -75,8 +82,8 @@ int main(int argc, char** argv) {
 
     /* [core] the listing of INTEGRATION.md, "A recording file at any rate, with the denoiser" */
     /* 1. the network, the denoiser and one evaluation's bookkeeping */
-    model = babe_model_load(argv[1], NULL);
-    if (!model) FAIL("babe_model_load: %s", babe_last_error());
+    model = babe_model_load_ex(argv[1], precision, NULL);
+    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
     if (denoiser_path && !(denoiser = babe_denoiser_load(denoiser_path, NULL))) FAIL("babe_denoiser_load: %s", babe_last_error());
     state = babe_unet_state_create();
     if (!state) FAIL("babe_unet_state_create failed");

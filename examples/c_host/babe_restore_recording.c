@@ -1,6 +1,7 @@
 /* babe_restore_recording: blind bandwidth extension of a whole recording from C - no Python, no torch in the process.
  *
  *     babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s]
+ *                            [--precision f32|bf16|bf16x3]
  *
  * model.babe: written by `python -m babe_amd.export`.  in.f32: the recording, float32 samples of any length at the model's rate.
  * out.f32: the restored recording, as many samples.  The low-pass filter of the recording is estimated blind on
@@ -25,13 +26,17 @@
 #define DC_SIZE 50          /* predict_bwe_AR smooths the edge of its mask over 50 samples */
 #define DISCARD_END 200     /* samples at the end of a restored segment that are not kept */
 
+static int precision_of(const char* s) {
+    return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
+}
+
 static double setting(const void* model, const char* key, double fallback) {
     double v;
     return babe_model_setting(model, key, &v) == 0 ? v : fallback;
 }
 
 int main(int argc, char** argv) {
-    int status = 1, T = 0, n_blind = 1;
+    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32;
     long seed = 0, Lrec = 0;
     double ix_start = 0.0;
     void *model = NULL, *state = NULL, *ws = NULL;
@@ -39,7 +44,8 @@ int main(int argc, char** argv) {
     babe_sample_step* steps = NULL;
     FILE* fh = NULL;
     if (argc < 4) {
-        fprintf(stderr, "usage: babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s]\n");
+        fprintf(stderr, "usage: babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s] "
+                        "[--precision f32|bf16|bf16x3]\n");
         return 2;
     }
     for (int i = 4; i < argc; ++i) {
@@ -48,6 +54,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--T")) T = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--blind-segments")) n_blind = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--ix-start")) ix_start = atof(argv[++i]);
+        else if (!strcmp(argv[i], "--precision")) {
+            if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
         else FAIL("unknown option %s", argv[i]);
     }
     if (n_blind < 1 || n_blind > 16) FAIL("--blind-segments must be 1..16");
@@ -64,8 +73,8 @@ int main(int argc, char** argv) {
 
     /* [core] the listing of INTEGRATION.md, "A whole recording from one call" */
     /* 1. the network and one evaluation's bookkeeping, as in babe_restore.c */
-    model = babe_model_load(argv[1], NULL);
-    if (!model) FAIL("babe_model_load: %s", babe_last_error());
+    model = babe_model_load_ex(argv[1], precision, NULL);
+    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
     state = babe_unet_state_create();
     if (!state) FAIL("babe_unet_state_create failed");
     babe_recording_desc d;

@@ -83,7 +83,10 @@ long babe_conv_packed_size_bf16(int Cout, int Cin, int KH, int KW, int transpose
  * babe_units_size = units per batch item.  babe_conv2d_bf16_units takes such a tensor as a->in (a->in_bs / a->in_cs = units
  * per batch item / per 8-channel group = F*4*(T/4+1); no second source, no in_scale) and moves BOTH operands by LDS-DMA;
  * result identical to babe_conv2d_bf16 (splits = 1) on the fp32 tensor.  Needs KH x KW = 5 x 3, T % 4 == 0, Cin % 8 == 0,
- * Cout > 32, 16-byte aligned out / res rows (babe_conv2d_bf16_units_supported). */
+ * Cout > 32, 16-byte aligned out / res rows (babe_conv2d_bf16_units_supported: the verdict on one call, BABE_CONV_BF16U included;
+ * what the weights and the time length alone decide is babe_conv2d_bf16_units_shape, declared with babe_packed_conv below).  Both
+ * UNet sequencers - babe_amd/networks/unet_engine.py and csrc/unet_engine.hip - ask the static rule per block and the verdict per
+ * layer, and launch babe_gn_partial, babe_gn_finalize, babe_scale_gelu_units, babe_conv2d_bf16_units in that order. */
 long babe_units_size(int C, int F, int T);
 int babe_scale_gelu_units(const float* x, const float* scale, void* units, int B, int C, int F, int T, void* stream);
 int babe_conv2d_bf16_units_supported(const babe_conv_args* a);
@@ -267,7 +270,8 @@ int babe_conv2d_wino85_set_waves(int waves);
 
 /* ---- the whole UNet body from one call: networks/cqtdiff+.py:746-839 (forward), ResnetBlock :452-493, and its input-VJP
  * (the autograd pass of testing/blind_bwe_sampler.py:120).  csrc/unet_engine.hip sequences the op-level functions of this header
- * exactly as babe_amd/networks/unet_engine.py does (bit-identical results); fp32 convs.  All device memory is the caller's. */
+ * exactly as babe_amd/networks/unet_engine.py does (bit-identical results), whatever the images' precision: fp32 images, bf16 /
+ * bf16x3 images over fp32 activations, and under bf16 the units path of the wide (5,3) layers.  All device memory is the caller's. */
 typedef struct {                       /* the images of one Conv2d, as babe_packed_conv_plan lays them out; NULL = not packed */
     int Cout, Cin, KH, KW, nt, splits; /* Cout == 0: the layer does not exist; splits: 0 fp32, 1 bf16, 2 bf16x3 */
     const void *fwd, *bwd;             /* babe_conv_pack_weights_nt (fp32) or babe_conv_pack_weights_bf16 images, transpose_flip 0 / 1 */
@@ -291,6 +295,16 @@ enum { BABE_CONV_FORM_F23 = 1, BABE_CONV_FORM_F43 = 2, BABE_CONV_FORM_F25 = 4, B
 typedef struct { int nt, splits, raw; long bytes[10]; } babe_packed_conv_layout;
 int babe_packed_conv_plan(int Cout, int Cin, int KH, int KW, int splits, int nt, int nt11, int forms,
                           babe_packed_conv_layout* out);
+/* The `splits` a conv with weights [Cout][Cin][KH][KW] runs with under a requested precision - the one statement of that rule
+ * (ops.PackedConv.splits_for and the model loader ask it).  Host arithmetic.  With hbm_f32 != 0 (the default form
+ * BABE_BF16_HBM_F32) the shapes bf16 MFMA gains nothing on stay fp32, whatever the precision: <= 4 channels on one side, a (1,1)
+ * kernel with fewer than 32 channels on one side, every (1,1) kernel under bf16x3.  -1: bad arguments (babe_last_error). */
+enum { BABE_PRECISION_F32 = 0, BABE_PRECISION_BF16 = 1, BABE_PRECISION_BF16X3 = 2 };
+int babe_conv_splits_for(int Cout, int Cin, int KH, int KW, int precision, int hbm_f32);
+/* The static half of the units rule (see babe_units_size above): may the forward of this conv at time length T take its input as
+ * bf16 units?  splits == 1, 5 x 3, T % 4 == 0, Cin % 8 == 0, Cout > 32.  Host arithmetic; both UNet sequencers ask it per block
+ * and then, per layer, the call's own verdict babe_conv2d_bf16_units_supported (alignment, 2 GiB limits, BABE_CONV_BF16U). */
+int babe_conv2d_bf16_units_shape(const babe_packed_conv* pc, int T);
 /* Fills every non-NULL image of *pc (shape, nt, splits set) from raw weights w of that shape: the per-family pack_weights calls,
  * enqueued on stream.  Allocates nothing, waits for nothing, leaves w_raw alone. */
 int babe_packed_conv_pack(const babe_packed_conv* pc, const float* w, void* stream);
@@ -867,7 +881,12 @@ int babe_scale_channels(const float* x, const float* scale, float* out, int B, i
  * INTEGRATION.md section 2): what a host without Python calls instead of restating UnetEngine.__init__, ops.PackedConv, _FilmIndex,
  * STFTOps and CEval.  The loader packs every image with this library's own pack kernels from the raw weights, as the Python
  * engine does with its default forms, so babe_unet_fwd / _vjp, babe_score_eval and babe_sample_bwe on a loaded model are
- * bit-identical to the same calls on Python-built descriptors (tests/test_gpu_model_c.py).
+ * bit-identical to the same calls on Python-built descriptors (tests/test_gpu_model_c.py, tests/test_gpu_bf16_library.py).
+ * Precision is the HOST's choice at load time (the _ex forms; BABE_PRECISION_*), as --precision is for python -m babe_amd.restore:
+ * the file always holds the fp32 master weights and says network.precision = f32.  Each conv's images follow
+ * babe_conv_splits_for(shape, precision, 1): bf16 / bf16x3 images where bf16 MFMA gains, fp32 images for the 2-channel convs, the
+ * narrow (1,1) convs and the folded frequency-encoding convs (so a use_fencoding file loads at any precision).  babe_model_load /
+ * babe_model_create are the _ex forms at BABE_PRECISION_F32.
  * Ownership: THE exception to "the library never allocates / never synchronises".  create / load allocate one arena on the
  * CURRENT device (plus the CQT plan's tables), enqueue the upload and the pack kernels on `stream`, and wait on `stream` once
  * before they release their host staging; destroy frees.  No other entry point here allocates or waits.  The device is recorded:
@@ -875,8 +894,8 @@ int babe_scale_channels(const float* x, const float* scale, float* out, int B, i
  * and descriptor taken from it: destroy it last.
  * Refused with a message, before any device call, nothing allocated: a missing or empty file, a wrong magic, an unknown version, a
  * truncated file, tensor data that overlaps or leaves the file, a duplicate / missing / unexpected name, a shape that does not fit
- * the settings, attention flags, a precision other than f32, use_fencoding with bins per octave != 64, an audio length the
- * mixed-radix FFT plan does not cover. */
+ * the settings, attention flags, a file whose network.precision is not f32, a requested precision outside 0..2, use_fencoding with
+ * bins per octave != 64, an audio length the mixed-radix FFT plan does not cover. */
 typedef struct { const char* name; int ndim; long shape[4]; const float* data; } babe_model_entry;   /* host fp32, state_dict name */
 typedef struct { const char* key; const char* str; double num; } babe_model_kv;                       /* str != NULL: a string setting */
 typedef struct {
@@ -891,6 +910,11 @@ void* babe_model_load(const char* path, void* stream);               /* NULL on 
 /* the same from tables in host memory: entries = every tensor the file would hold (the two aux.* tables included), settings = its
  * settings block (dotted keys) */
 void* babe_model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream);
+/* the same with the conv arithmetic chosen: precision = BABE_PRECISION_F32 / _BF16 / _BF16X3 */
+void* babe_model_load_ex(const char* path, int precision, void* stream);
+void* babe_model_create_ex(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision,
+                           void* stream);
+int babe_model_precision(const void* model);                         /* what it was loaded with; -1: null model */
 void babe_model_destroy(void* model);
 int babe_model_info(const void* model, babe_model_summary* info);
 int babe_model_setting(const void* model, const char* key, double* value);   /* a numeric setting of the file; strings and unknown keys: error */

@@ -1,11 +1,12 @@
 """Load time of a network from a model file, library against Python, on one GPU:
 
-    python tools/model_load_bench.py [--out profiles/model_load.json] [--sample-rate 44100 --audio-len 368368] [key.sub=value ...]
+    python tools/model_load_bench.py [--out profiles/model_load.json] [--precision f32|bf16|bf16x3]
+                                     [--sample-rate 44100 --audio-len 368368] [key.sub=value ...]
 
 Exports the configured network (random weights: the timings do not depend on the values) to a temporary model file, then records
-  library   babe_model_load: wall time, its own split (read + parse + validate | staging + upload | pack + CQT plan + the wait),
+  library   babe_model_load_ex at --precision: wall time, its own split (read + parse + validate | staging + upload | pack + CQT plan + the wait),
             device bytes held (arena, CQT tables)
-  python    constructing Unet_CQT_oct_with_attention + load_state_dict(model_file.read) + the first c_plan(), synchronised:
+  python    constructing Unet_CQT_oct_with_attention (same precision) + load_state_dict(model_file.read) + the first c_plan(), synchronised:
             wall time, device bytes torch holds afterwards
 in one process, the library first (its file read warms the page cache for the Python side; the read time is listed on its own),
 and writes one JSON document."""
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--out", default=os.path.join("profiles", "model_load.json"))
     ap.add_argument("--sample-rate", type=int, default=44100)
     ap.add_argument("--audio-len", type=int, default=368368)
+    ap.add_argument("--precision", default="f32", choices=("f32", "bf16", "bf16x3"))
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     import torch
@@ -33,7 +35,7 @@ def main():
     from babe_amd.testing.model_c import LibraryModel
     args = apply_overrides(default_args(sample_rate=a.sample_rate, audio_len=a.audio_len), a.overrides)
     nw = args.network
-    res = dict(config=dict(sample_rate=a.sample_rate, audio_len=a.audio_len, Ns=list(nw.Ns), num_dils=list(nw.num_dils)),
+    res = dict(config=dict(sample_rate=a.sample_rate, audio_len=a.audio_len, precision=a.precision, Ns=list(nw.Ns), num_dils=list(nw.num_dils)),
                device=torch.cuda.get_device_name())
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "model.babe")
@@ -44,7 +46,7 @@ def main():
         torch.zeros(1, device="cuda")
         torch.cuda.synchronize()
         t = time.perf_counter()
-        m = LibraryModel(path)
+        m = LibraryModel(path, a.precision)
         wall = time.perf_counter() - t
         info = m.info
         res["library"] = dict(wall_s=wall, read_s=info.load_ms[0] / 1e3, upload_s=info.load_ms[1] / 1e3, pack_s=info.load_ms[2] / 1e3,
@@ -53,7 +55,7 @@ def main():
         torch.cuda.synchronize()
         base = torch.cuda.memory_allocated()
         t = time.perf_counter()
-        net = Unet_CQT_oct_with_attention(args, "cuda")
+        net = Unet_CQT_oct_with_attention(args, "cuda", precision=a.precision)
         t1 = time.perf_counter()
         net.load_state_dict(model_file.read(path)[1])
         t2 = time.perf_counter()
