@@ -95,7 +95,15 @@ class EvalDesc(C.Structure):
                 ("nfft", C.c_int), ("fs", C.c_float), ("env_inv", C.c_void_p), ("tw4096", C.c_void_p), ("K", C.c_int),
                 ("fit", FitCfg), ("blind", C.c_int), ("shared", C.c_int), ("hpf", C.c_int),
                 ("xi", C.c_float), ("score_mode", C.c_int), ("audio_len_norm", C.c_float),
-                ("mask", C.c_void_p), ("mask_bs", C.c_long), ("dc_mask", C.c_void_p), ("dc_y", C.c_void_p)]
+                ("mask", C.c_void_p), ("mask_bs", C.c_long), ("dc_mask", C.c_void_p), ("dc_y", C.c_void_p),
+                # the known observation model (all zero: the STFT filter) and the classic replacement step
+                ("obs_kind", C.c_int), ("taps", C.c_void_p), ("ntaps", C.c_int),
+                ("b", C.c_void_p), ("a", C.c_void_p), ("order", C.c_int), ("clamp", C.c_int),
+                ("obs_mask", C.c_void_p), ("obs_mask_bs", C.c_long), ("clip_value", C.c_float), ("dc_classic", C.c_int)]
+
+
+# babe_eval_desc.obs_kind
+OBS_STFT, OBS_FIR, OBS_IIR, OBS_MASK, OBS_CLIP = range(5)
 
 
 class SampleStep(C.Structure):
@@ -106,7 +114,8 @@ class SampleStep(C.Structure):
 
 class SampleDesc(C.Structure):
     """babe_sample_desc"""
-    _fields_ = [("eval", EvalDesc), ("T", C.c_int), ("steps", C.POINTER(SampleStep)), ("t0", C.c_float), ("warm_start", C.c_int)]
+    _fields_ = [("eval", EvalDesc), ("T", C.c_int), ("steps", C.POINTER(SampleStep)), ("t0", C.c_float), ("warm_start", C.c_int),
+                ("skip_zero_inject", C.c_int)]
 
 
 class RecordingDesc(C.Structure):
@@ -319,6 +328,8 @@ SIGS = {
     "babe_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I]),
     "babe_sample_bwe": (_I, [C.POINTER(SampleDesc), _P, _P, _P, _P, _L, _L, _P, _P, _P, _L, _I, _P]),
     "babe_edm_steps": (_I, [C.POINTER(SampleStep), _P, _I, _I, _D, _D, _D, _D, _D, _D, _D, _D, _D]),
+    "babe_firwin_kaiser": (_I, [_I, _D, _D, _D, _I, _P]),
+    "babe_iir_check": (_I, [_P, _P, _I]),
     "babe_recording_plan": (_L, [_L, _L, _L, _L, _P, _P, _L]),
     "babe_recording_workspace_bytes": (_L, [C.POINTER(RecordingDesc)]),
     "babe_restore_recording": (_I, [C.POINTER(RecordingDesc), _P, _L, _P, _P, _P, _L, _L, _P, _L, _P]),

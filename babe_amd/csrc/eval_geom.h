@@ -29,8 +29,38 @@ inline bool geom(const babe_eval_desc* e, EvalGeom& g) {
     return true;
 }
 
-// who: the entry point's name, for the message
-inline int eval_desc_check(const babe_eval_desc* e, const char* who) {
+// the evaluation reads params / specY only through the STFT filter
+inline bool eval_reads_params(const babe_eval_desc* e, bool has_y) { return has_y && e->obs_kind == BABE_OBS_STFT; }
+
+// the known observation model (obs_kind and its parameters, dc_classic, y == NULL), host only
+inline int eval_obs_check(const babe_eval_desc* e, bool has_y, const char* who) {
+    const int k = e->obs_kind;
+    BABE_CHECK_ARG(k >= BABE_OBS_STFT && k <= BABE_OBS_CLIP, "%s: bad descriptor: obs_kind = %d is no BABE_OBS_* value", who, k);
+    BABE_CHECK_ARG(k != BABE_OBS_FIR || (e->taps && e->ntaps >= 1), "%s: bad descriptor: BABE_OBS_FIR with NULL taps or ntaps = %d", who,
+                   e->ntaps);
+    BABE_CHECK_ARG(k != BABE_OBS_IIR || (e->order >= 1 && e->order <= 16), "%s: bad descriptor: BABE_OBS_IIR with order = %d outside 1..16",
+                   who, e->order);
+    BABE_CHECK_ARG(k != BABE_OBS_IIR || (e->b && e->a), "%s: bad descriptor: BABE_OBS_IIR with NULL b or a", who);
+    BABE_CHECK_ARG(k != BABE_OBS_MASK || e->obs_mask, "%s: bad descriptor: BABE_OBS_MASK with NULL obs_mask", who);
+    BABE_CHECK_ARG(k != BABE_OBS_MASK || e->obs_mask_bs == 0 || e->obs_mask_bs >= e->L,
+                   "%s: bad descriptor: obs_mask_bs = %ld (0, or at least L = %d)", who, e->obs_mask_bs, e->L);
+    BABE_CHECK_ARG(k != BABE_OBS_CLIP || e->clip_value >= 0.f, "%s: bad descriptor: BABE_OBS_CLIP with clip_value = %g (must be >= 0)", who,
+                   e->clip_value);
+    BABE_CHECK_ARG(!(e->dc_classic && k == BABE_OBS_CLIP), "%s: bad descriptor: dc_classic with BABE_OBS_CLIP (the replacement step "
+                   "holds for linear A only)", who);
+    BABE_CHECK_ARG(!(e->dc_classic && e->dc_mask), "%s: bad descriptor: dc_classic with dc_mask (one replacement step)", who);
+    BABE_CHECK_ARG(!(e->blind && k != BABE_OBS_STFT), "%s: bad descriptor: blind = 1 with obs_kind = %d (only the STFT filter is fitted)",
+                   who, k);
+    BABE_CHECK_ARG(!e->mask || k == BABE_OBS_STFT || k == BABE_OBS_FIR, "%s: bad descriptor: mask with obs_kind = %d (the AR mix goes "
+                   "over the STFT filter or a FIR)", who, k);
+    BABE_CHECK_ARG(has_y || (k == BABE_OBS_STFT && !e->mask && !e->dc_classic),
+                   "%s: bad descriptor: y == NULL (unconditional) with obs_kind = %d, mask or dc_classic", who, k);
+    return BABE_OK;
+}
+
+// who: the entry point's name, for the message; has_y: the call has observations (false: unconditional)
+inline int eval_desc_check(const babe_eval_desc* e, const char* who, bool has_y = true) {
+    BABE_TRY(eval_obs_check(e, has_y, who));
     BABE_CHECK_ARG(!(e->mask && e->blind), "%s: mask with blind = 1 (the AR observation model takes a known filter)", who);
     BABE_CHECK_ARG(e->mask || (!e->dc_mask && !e->dc_y), "%s: dc_mask / dc_y without mask", who);
     BABE_CHECK_ARG(!e->dc_mask == !e->dc_y, "%s: dc_mask and dc_y come together", who);

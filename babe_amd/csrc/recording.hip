@@ -4,6 +4,8 @@
 //   normalise the file to target_std -> blind filter estimate on n_blind segments in one coupled batch (babe_sample_bwe, blind = 1,
 //   shared = 1) -> first segment with that filter -> every following segment out-painted from the tail of the previous result
 //   (the observation model of predict_bwe_AR: babe_sample_bwe with eval.mask / eval.dc_mask) -> undo the normalisation.
+// Scope: the STFT filter the flow estimates itself (eval.obs_kind = BABE_OBS_STFT, no classic replacement step); the known
+// degradations babe_score_eval sequences besides are refused here, before the first device call.
 // The file is never copied: every segment is cut from it and normalised on the way (element-wise, so the same bits as normalising
 // the file first), and the restored pieces are written straight into `out`, which is scaled back in place at the end.  The scale
 // factors stay on the device.  The quirks of the Python flow are kept: a last segment longer than segL is truncated, and the last
@@ -192,12 +194,16 @@ int desc_check(const babe_recording_desc* d, const char* who) {
     BABE_CHECK_ARG(d->overlap < d->eval.L - d->discard_end, "%s: overlap = %ld must be below L - discard_end = %ld", who, d->overlap,
                    d->eval.L - d->discard_end);
     BABE_CHECK_ARG(!d->eval.mask && !d->eval.dc_mask && !d->eval.dc_y, "%s: eval.mask / dc_mask / dc_y are the call's to set", who);
+    BABE_CHECK_ARG(d->eval.obs_kind == BABE_OBS_STFT && !d->eval.dc_classic, "%s: eval.obs_kind = %d, dc_classic = %d: a recording is "
+                   "restored against the STFT filter it estimates (BABE_OBS_STFT, no classic replacement step)", who, d->eval.obs_kind,
+                   d->eval.dc_classic);
     return BABE_OK;
 }
 
 // the two runs' descriptors and the larger of their workspace sizes (-1: a size query failed, its message stands)
 long run_descs(const babe_recording_desc* d, babe_sample_desc& blind, babe_sample_desc& known) {
     blind.eval = d->eval, blind.T = d->T, blind.steps = d->steps_blind, blind.t0 = d->t0, blind.warm_start = d->warm_start;
+    blind.skip_zero_inject = 0;
     blind.eval.blind = 1, blind.eval.shared = 1;
     known = blind;
     known.steps = d->steps_known;

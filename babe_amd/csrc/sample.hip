@@ -3,10 +3,13 @@
 // host: STFT of the observations, the initial state, and per step the noise injection (move_timestep :509-516), the score
 // evaluation (babe_score_eval, csrc/score_eval.hip) and the Euler or second-order Heun update (:687-761), with the filter
 // parameters handed from evaluation to evaluation on the device.
-// Scope: that of babe_score_eval, the AR observation model of predict_bwe_AR included (desc.eval.mask / dc_mask: the loop is the
-// same, the descriptor goes through).  Like it, the run contains no schedule formula: the caller passes one babe_sample_step per
-// step (babe_edm_steps below fills the table for a host without the Python EDM class).  Same kernels, same order, same scalars
-// as the Python loop, so the two agree bit for bit (tests/test_gpu_sample_c.py).  Nothing allocates, nothing synchronises.
+// Scope: that of babe_score_eval - the AR observation model of predict_bwe_AR (desc.eval.mask / dc_mask) and the known
+// degradations of desc.eval.obs_kind included: the loop is the same, the descriptor goes through - and, with
+// desc.skip_zero_inject and y == NULL, the loop of testing/edm_sampler.Sampler.predict_conditional: no injection on a step with
+// gamma == 0, unconditional sampling.  Like babe_score_eval, the run contains no schedule formula: the caller passes one
+// babe_sample_step per step (babe_edm_steps below fills the table for a host without the Python EDM class).  Same kernels, same
+// order, same scalars as the Python loops, so they agree bit for bit (tests/test_gpu_sample_c.py, tests/test_gpu_obs_library.py).
+// Nothing allocates, nothing synchronises.  Below the run: the host helpers babe_firwin_kaiser and babe_iir_check.
 #include <cmath>
 #include "common.h"
 #include "eval_geom.h"
@@ -59,8 +62,11 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
     carve(own, e, g, B, 0, w);
     BABE_CHECK_ARG(ws && ws_bytes >= (long)own.used, "sample_bwe: workspace of %ld bytes, the run's own buffers alone need %ld",
                    ws ? ws_bytes : 0L, (long)own.used);
-    BABE_CHECK_ARG(y && params && x_out, "sample_bwe: NULL y, params or x_out");
-    BABE_TRY(eval_desc_check(e, "sample_bwe"));
+    BABE_CHECK_ARG(y || !d->warm_start, "sample_bwe: warm_start without y");
+    BABE_TRY(eval_desc_check(e, "sample_bwe", y != nullptr));
+    const bool reads_params = eval_reads_params(e, y != nullptr);
+    BABE_CHECK_ARG(x_out && (params || !reads_params), "sample_bwe: NULL params or x_out");
+    BABE_CHECK_ARG(params || !rec_params, "sample_bwe: rec_params without params");
     const long ev_bytes = babe_eval_workspace_bytes(e, B);
     BABE_CHECK_ARG(ev_bytes >= 0, "sample_bwe: bad evaluation descriptor");
     Carver c{static_cast<char*>(ws), (size_t)ws_bytes, 256};
@@ -92,15 +98,19 @@ extern "C" int babe_sample_bwe(const babe_sample_desc* d, const float* y, float*
         return babe_randn(eps_ws, L, B, L, seed, clip0, k, stream);
     };
     const float* eps = nullptr;
-    BABE_TRY(babe_stft_fwd(y, L, (int)L, nullptr, specY, B, e->nfft, frames, e->tw4096, stream));
+    if (reads_params) BABE_TRY(babe_stft_fwd(y, L, (int)L, nullptr, specY, B, e->nfft, frames, e->tw4096, stream));
     // ---- initial state (:311 / :314): t0 eps, or y + t0 eps with a warm start
     BABE_TRY(draw(0, &eps));
     if (d->warm_start) BABE_TRY(babe_lincomb3(x, 1.f, y, d->t0, eps, 0.f, nullptr, n, stream));
     else BABE_TRY(babe_lincomb3(x, d->t0, eps, 0.f, nullptr, 0.f, nullptr, n, stream));
     for (int i = 0; i < d->T; ++i) {
         const babe_sample_step& s = d->steps[i];
-        BABE_TRY(draw(i + 1L, &eps));
-        BABE_TRY(babe_lincomb3(x_hat, 1.f, x, s.inject, eps, 0.f, nullptr, n, stream));
+        if (d->skip_zero_inject && s.inject == 0.f) {
+            COPY(x_hat, x, 4L * n);                    // the state as it is: draw i + 1 is left unused
+        } else {
+            BABE_TRY(draw(i + 1L, &eps));
+            BABE_TRY(babe_lincomb3(x_hat, 1.f, x, s.inject, eps, 0.f, nullptr, n, stream));
+        }
         BABE_TRY(babe_score_eval(e, x_hat, s.t_hat, s.c1[0], s.c1[1], s.c1[2], s.c1[3], y, specY, params, dd, x_den, nullptr, w.ev, ev_bytes, B,
                                  stream));
         if (rec_x_den) COPY(rec_x_den + (long)i * n, x_den, 4L * n);
@@ -152,6 +162,95 @@ extern "C" int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int ord
         s.heun = (tn != 0.0 && order == 2) ? 1 : 0;
         precond(t_hat, s.c1);
         if (s.heun) precond(tn, s.c2);
+    }
+    return BABE_OK;
+}
+
+// ---- host helpers for hosts without scipy (no GPU call) --------------------------------------------------------------------
+namespace {
+
+// sum of v[0..n) with the rounding errors carried along (Neumaier): correct to the last bit or two whatever the order
+double compensated_sum(const double* v, int n) {
+    double s = 0.0, c = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const double t = s + v[i];
+        c += std::fabs(s) >= std::fabs(v[i]) ? (s - t) + v[i] : (v[i] - t) + s;
+        s = t;
+    }
+    return s + c;
+}
+
+// modified Bessel function I0 by its power series sum ((x/2)^2)^k / (k!)^2: positive terms only, so no cancellation
+double bessel_i0(double x) {
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 1000 && term > 1e-18 * sum; ++k) {
+        term *= q / ((double)k * (double)k);
+        sum += term;
+    }
+    return sum;
+}
+
+// numpy.sinc: sin(pi x) / (pi x), with x = 0 replaced by 1e-20
+double np_sinc(double x) {
+    const double y = M_PI * (x == 0.0 ? 1.0e-20 : x);
+    return std::sin(y) / y;
+}
+
+}  // namespace
+
+extern "C" int babe_firwin_kaiser(int numtaps, double cutoff, double width, double fs, int highpass, double* taps_out) {
+    BABE_CHECK_ARG(taps_out && numtaps >= 1, "firwin_kaiser: bad arguments (numtaps = %d)", numtaps);
+    BABE_CHECK_ARG(fs > 0 && width > 0 && std::isfinite(fs) && std::isfinite(width), "firwin_kaiser: fs = %g, width = %g", fs, width);
+    const double nyq = 0.5 * fs, c = cutoff / nyq;
+    BABE_CHECK_ARG(c > 0 && c < 1, "firwin_kaiser: cutoff = %g outside (0, fs / 2 = %g)", cutoff, nyq);
+    BABE_CHECK_ARG(!highpass || (numtaps & 1), "firwin_kaiser: a high-pass with an even number of taps (%d) cannot pass the Nyquist "
+                   "frequency", numtaps);
+    // kaiser_atten and kaiser_beta
+    const double atten = 2.285 * (numtaps - 1) * M_PI * (width / nyq) + 7.95;
+    const double beta = atten > 50 ? 0.1102 * (atten - 8.7) : atten > 21 ? 0.5842 * std::pow(atten - 21, 0.4) + 0.07886 * (atten - 21) : 0.0;
+    const double left = highpass ? c : 0.0, right = highpass ? 1.0 : c;
+    const double alpha = 0.5 * (numtaps - 1), i0b = bessel_i0(beta);
+    for (int n = 0; n < numtaps; ++n) {
+        const double m = n - alpha;
+        double h = 0.0;
+        h += right * np_sinc(right * m);
+        h -= left * np_sinc(left * m);
+        double win = 1.0;                              // (one tap: the window is 1)
+        if (numtaps > 1) {
+            const double u = (n - alpha) / alpha;
+            win = bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
+        }
+        taps_out[n] = h * win;
+    }
+    // unit gain at the centre of the pass band: frequency 0, or 1 (Nyquist) for the high-pass
+    const double scale_frequency = highpass ? 1.0 : 0.0;
+    double* hc = new double[numtaps];
+    for (int n = 0; n < numtaps; ++n) hc[n] = taps_out[n] * std::cos(M_PI * (n - alpha) * scale_frequency);
+    const double s = compensated_sum(hc, numtaps);
+    delete[] hc;
+    for (int n = 0; n < numtaps; ++n) taps_out[n] /= s;
+    return BABE_OK;
+}
+
+extern "C" int babe_iir_check(const float* b, const float* a, int order) {
+    BABE_CHECK_ARG(b && a, "iir_check: NULL b or a");
+    BABE_CHECK_ARG(order >= 1 && order <= 16, "iir_check: order %d outside 1..16", order);
+    BABE_CHECK_ARG(a[0] == 1.0f, "iir_check: a[0] = %g (the coefficients are divided by a[0] first)", (double)a[0]);
+    // step-down (Schur-Cohn / Jury): z^N + a1 z^(N-1) + ... + aN has all roots inside the unit circle iff every reflection
+    // coefficient k_m = a_m[m] of the recursion a_(m-1)[i] = (a_m[i] - k_m a_m[m - i]) / (1 - k_m^2) is below 1 in modulus
+    double p[17], q[17];
+    for (int i = 0; i <= order; ++i) {
+        BABE_CHECK_ARG(std::isfinite(a[i]) && std::isfinite(b[i]), "iir_check: coefficient %d is not finite", i);
+        p[i] = (double)a[i];
+    }
+    for (int m = order; m >= 1; --m) {
+        const double k = p[m];
+        BABE_CHECK_ARG(std::fabs(k) < 1.0, "iir_check: unstable at float32 coefficients (reflection coefficient %d is %g: a pole on or "
+                       "outside the unit circle)", m, k);
+        const double den = 1.0 - k * k;
+        for (int i = 0; i < m; ++i) q[i] = (p[i] - k * p[m - i]) / den;
+        for (int i = 0; i < m; ++i) p[i] = q[i];
     }
     return BABE_OK;
 }

@@ -5,11 +5,15 @@
 //   filter fit (fit_params :533-595), design_filter / apply_filter (utils/blind_bwe_utils.py:82-119, 6-39), the reconstruction-
 //   guidance residual norm and its gradient through iSTFT o H o STFT and through the network (get_rec_grads :75-135), the score
 //   direction (:125-135, :701).
-// Scope: the default blind / known-fc_A configuration - L2 guidance norm, STFT-domain low-pass, no observation noise, no FIR
-// degradation - and, with desc.mask, the observation model of predict_bwe_AR over the known fc_A filter (:259-303): the mask mix
-// mask x + (1 - mask) A(x) and, with desc.dc_mask, the replacement step of inpaint_DC (:63-73).  The options of the other tester
-// YAMLs stay with the Python sequencer, which this call equals bit for bit on both paths: tests/test_gpu_eval_c.py,
-// tests/test_gpu_sample_ar_c.py.
+// Scope: the L2 guidance norm without observation noise, on one of the observation models of babe_amd/degrade.py (desc.obs_kind):
+// the STFT-domain low-pass of filter_params (blind or known fc_A), a FIR ('firwin' / 'firwin_hpf'), an IIR filter ('cheby1' /
+// 'biquad'), a mask (inpainting, compressed sensing) or a clip (declipping) - residual, block sums, seed and transpose launch for
+// launch as those objects sequence them; with desc.mask the mask mix mask x + (1 - mask) A(x) of predict_bwe_AR (:259-303) over
+// the STFT filter or the FIR and, with desc.dc_mask, the replacement step of inpaint_DC (:63-73); with desc.dc_classic the
+// replacement step x0 <- y + x0 - A(x0) of posterior_sampling.data_consistency and the no-guidance branch of
+// edm_sampler.Sampler.evaluate; y == NULL is unconditional sampling.  'resample' / 'decimate', phase retrieval, the other
+// distances, observation noise and attention networks stay with the Python sequencer, which this call equals bit for bit:
+// tests/test_gpu_eval_c.py, tests/test_gpu_sample_ar_c.py, tests/test_gpu_obs_library.py.
 // Every intermediate lives in the caller's workspace (babe_eval_workspace_bytes); nothing is allocated, nothing synchronises.
 #include "common.h"
 #include "eval_geom.h"
@@ -35,6 +39,10 @@ struct EvalWork {
     float* H;
     double *stats, *part, *gpart;       // magnitude statistics, two sets of partial sums
     int* nit;
+    void* iirws;                        // BABE_OBS_IIR: babe_iir_filter's workspace (iirb bytes)
+    long iirb;
+    unsigned char* m8;                  // [B][L] the clamp mask of the IIR forward / the |x| <= c mask of the fused clip residual
+    float* a0;                          // [B][L] A(x0) of the classic replacement step
 };
 
 // false: a nested size query failed (its message stands)
@@ -56,6 +64,17 @@ bool carve(Carver& c, const babe_eval_desc* e, const EvalGeom& g, int B, EvalWor
     w.H = c.take<float>((size_t)P * g.nbins);
     w.stats = c.take<double>((size_t)P * 3 * g.nbins), w.part = c.take<double>((size_t)B * 64), w.gpart = c.take<double>((size_t)B * 64);
     w.nit = c.take<int>(P);
+    w.iirb = 0;
+    if (e->obs_kind == BABE_OBS_IIR) {
+        w.iirb = babe_iir_workspace(B, e->L, e->order);
+        if (w.iirb < 0) {
+            babe_set_error("eval workspace: babe_iir_workspace(%d, %d, %d) failed", B, e->L, e->order);
+            return false;
+        }
+    }
+    w.iirws = c.take<char>((size_t)w.iirb);
+    w.m8 = c.take<unsigned char>((e->obs_kind == BABE_OBS_CLIP || (e->obs_kind == BABE_OBS_IIR && e->clamp)) ? n : 0);
+    w.a0 = c.take<float>(e->dc_classic ? n : 0);
     return true;
 }
 
@@ -84,15 +103,17 @@ extern "C" long babe_eval_workspace_bytes(const babe_eval_desc* e, int B) {
 }
 
 /* x [B][L]: the noisy state at noise level t; (cskip, cout, cin, cnoise): EDM preconditioning of t (diff_params/edm.py:46-60,
- * computed by the host, so that this call contains no formula of its own); y [B][L]: the observations; specY = babe_stft_fwd(y);
+ * computed by the host, so that this call contains no formula of its own); y [B][L]: the observations (NULL: unconditional);
+ * specY = babe_stft_fwd(y) (read by the blind fit only); params may be NULL where desc.obs_kind is not the STFT filter;
  * params [P][2][K], P = B (per-clip semantics) or 1 (desc.shared: the reference's batch coupling): filter parameters, updated IN
  * PLACE when desc.blind; d [B][L] receives -t * score, x_den [B][L] the denoised estimate (after the DC / Nyquist high-pass);
  * n_iter [P] (may be NULL) the fit's iteration counts. */
 extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t, float cskip, float cout, float cin, float cnoise,
                                const float* y, const float* specY, float* params, float* d, float* x_den, int* n_iter, void* ws,
                                long ws_bytes, int B, void* stream) {
-    BABE_CHECK_ARG(e && x && y && (specY || !e->blind) && params && d && x_den && ws && ws_bytes >= 0 && B > 0, "score_eval: bad arguments");
-    BABE_TRY(eval_desc_check(e, "score_eval"));
+    BABE_CHECK_ARG(e && x && d && x_den && ws && ws_bytes >= 0 && B > 0, "score_eval: bad arguments");
+    BABE_TRY(eval_desc_check(e, "score_eval", y != nullptr));
+    BABE_CHECK_ARG((specY || !e->blind) && (params || !eval_reads_params(e, y != nullptr)), "score_eval: bad arguments (NULL specY or params)");
     BABE_CHECK_ARG(eval_dims_ok(e), "score_eval: nfft = %d, L = %d", e->nfft, e->L);
     EvalGeom g;
     BABE_CHECK_ARG(geom(e, g), "score_eval: the CQT plan has no design");
@@ -113,43 +134,106 @@ extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t,
     BABE_TRY(babe_cqt_fwd(e->cqt_plan, w.xin, w.coA, w.cqws, B, stream));
     BABE_TRY(babe_unet_fwd(e->unet_plan, e->unet_state, w.coA, w.film, e->film_J, B, g.T_oct, w.unws, w.unb, w.coB, stream));
     BABE_TRY(babe_cqt_bwd(e->cqt_plan, w.coB, w.net, w.cqws, B, stream));
-    BABE_TRY(babe_lincomb3(w.xd, cskip, x, cout, w.net, 0.f, nullptr, n, stream));
-    if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.xd, x_den, w.cqws, B, stream));
-    else BABE_TRY(babe_lincomb3(x_den, 1.f, w.xd, 0.f, nullptr, 0.f, nullptr, n, stream));
-    // ---- filter fit on STFT magnitudes, filter design
-    BABE_TRY(babe_stft_fwd(x_den, L, (int)L, nullptr, w.specX, B, e->nfft, g.frames, e->tw4096, stream));
-    if (e->blind) {
-        BABE_TRY(babe_stft_mag_stats(w.specX, specY, w.stats, B, g.nbins, g.frames, e->shared, stream));
-        BABE_TRY(babe_filter_fit(w.stats, params, n_iter ? n_iter : w.nit, P, e->K, g.nbins, e->fs, e->nfft, &e->fit, stream));
+    // xi = 0 in the EDM sampler (edm_sampler.Sampler.evaluate): no guidance, the replacement step on the plain estimate, which
+    // gets no high-pass and is the combination itself
+    const bool unguided = y && e->dc_classic && e->xi == 0.f && e->score_mode == 1;
+    BABE_TRY(babe_lincomb3(unguided ? x_den : w.xd, cskip, x, cout, w.net, 0.f, nullptr, n, stream));
+    if (!unguided) {
+        if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.xd, x_den, w.cqws, B, stream));
+        else BABE_TRY(babe_lincomb3(x_den, 1.f, w.xd, 0.f, nullptr, 0.f, nullptr, n, stream));
     }
-    BABE_TRY(babe_design_filter(params, w.H, P, e->K, g.nbins, e->fs, e->nfft, stream));
+    // (the scalars of a step back to a direction as the Python sequencer forms them: in double, rounded once)
+    const float inv_t = (float)(1.0 / (double)t), neg_inv_t = (float)(-1.0 / (double)t);
+    const int kind = e->obs_kind;
     const long H_bs = P == B ? g.nbins : 0;            // per-clip filters, or one filter for the batch
-    // ---- reconstruction guidance: residual y - A(x_den), its norm's gradient through iSTFT o H o STFT
-    float* const g_raw = e->hpf ? w.hp : w.g_den;       // the guidance gradient before the high-pass
-    BABE_TRY(babe_spec_filter_istft(w.specX, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
-    if (!e->mask) {
-        BABE_TRY(babe_ola(w.fr, e->env_inv, y, L, w.r, L, w.part, 64, B, (int)L, e->nfft, g.frames, stream));
-        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, w.seed, L, B, (int)L, stream));
-        BABE_TRY(babe_stft_fwd(w.seed, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+    // A(src) -> dst for the kinds with a plain forward (Degradation.fwd_dc: under the AR mix the inner filter alone).  The STFT
+    // filter is designed again, as a fresh STFTFilterDegradation does; src and dst are distinct.
+    auto forward = [&](const float* src, float* dst) -> int {
+        if (kind == BABE_OBS_FIR) return babe_fir_same(src, L, e->taps, e->ntaps, dst, L, B, (int)L, 0, stream);
+        if (kind == BABE_OBS_IIR)
+            return babe_iir_filter(src, L, dst, L, B, L, e->b, e->a, e->order, e->clamp, 0, e->clamp ? w.m8 : nullptr, e->clamp ? L : 0,
+                                   w.iirws, w.iirb, stream);
+        if (kind == BABE_OBS_MASK) return babe_mask_blend(dst, e->obs_mask, e->obs_mask_bs, src, nullptr, B, L, stream);
+        BABE_TRY(babe_design_filter(params, w.H, P, e->K, g.nbins, e->fs, e->nfft, stream));
+        BABE_TRY(babe_stft_fwd(src, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
         BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
-        BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, g_raw, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
-    } else {
-        // MaskMixDegradation over the STFT filter (babe_amd/degrade.py:191-213): r = y - (mask x_den + (1 - mask) A(x_den)); the
-        // observed part takes the seed as it is, the filtered part the seed with the overlap-add envelope through A^T.  The
-        // denoiser's buffers are free here and carry the intermediates: no buffer of its own.
-        float *ax = w.xin, *mix = w.net, *s_post = w.g_net, *seed_f = w.g_xin, *gA = w.xin, *seed_o = w.net;
-        BABE_TRY(babe_ola(w.fr, e->env_inv, nullptr, 0, ax, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+        return babe_ola(w.fr, e->env_inv, nullptr, 0, dst, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream);
+    };
+    // A^T(src) -> dst of the same kinds and of the clip; the masks are those the forward of this call left in w.m8
+    auto adjoint = [&](const float* src, float* dst) -> int {
+        if (kind == BABE_OBS_FIR) return babe_fir_same(src, L, e->taps, e->ntaps, dst, L, B, (int)L, 1, stream);
+        if (kind == BABE_OBS_IIR)
+            return babe_iir_filter(src, L, dst, L, B, L, e->b, e->a, e->order, e->clamp, 1, e->clamp ? w.m8 : nullptr, e->clamp ? L : 0,
+                                   w.iirws, w.iirb, stream);
+        if (kind == BABE_OBS_MASK) return babe_mask_blend(dst, e->obs_mask, e->obs_mask_bs, src, nullptr, B, L, stream);
+        return babe_clip_adj(src, L, w.m8, L, dst, L, B, L, stream);
+    };
+    if (!y)                                            // unconditional (get_score :160-170): d = (x - x_den) / t
+        return babe_lincomb3(d, inv_t, x, neg_inv_t, x_den, 0.f, nullptr, n, stream);
+    if (unguided) {                                    // x0 = x_den + y - A(x_den), d = (x - x0) / t
+        BABE_TRY(forward(x_den, w.a0));
+        BABE_TRY(babe_lincomb3(w.r, 1.f, x_den, 1.f, y, -1.f, w.a0, n, stream));
+        return babe_lincomb3(d, inv_t, x, neg_inv_t, w.r, 0.f, nullptr, n, stream);
+    }
+    float* const g_raw = e->hpf ? w.hp : w.g_den;       // the guidance gradient before the high-pass
+    if (kind != BABE_OBS_STFT && !e->mask) {
+        // ---- Degradation.guidance (babe_amd/degrade.py:122-131): r = y - A(x_den) and its block sums, the seed -r / ||r||, A^T
+        if (kind == BABE_OBS_CLIP) {                   // (ClipDegradation.residual: one fused pass, which leaves the mask)
+            BABE_TRY(babe_clip_residual(x_den, L, y, L, e->clip_value, w.r, L, w.m8, L, w.part, 64, B, L, stream));
+        } else {
+            BABE_TRY(forward(x_den, w.xin));
+            BABE_TRY(babe_lincomb3(w.r, 1.f, y, -1.f, w.xin, 0.f, nullptr, n, stream));
+            BABE_TRY(babe_sumsq_partial(w.r, L, w.part, 64, B, L, stream));
+        }
+        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, nullptr, w.seed, L, B, (int)L, stream));
+        BABE_TRY(adjoint(w.seed, g_raw));
+    } else if (kind == BABE_OBS_FIR) {
+        // ---- MaskMixDegradation over a FIR (babe_amd/degrade.py:191-208): the inner filter has no envelope, so the observed and
+        // the filtered part take the same seed
+        float *ax = w.xin, *mix = w.net, *seed_f = w.g_xin, *gA = w.xin, *seed_o = w.net;
+        BABE_TRY(forward(x_den, ax));
         BABE_TRY(babe_mask_blend(mix, e->mask, e->mask_bs, x_den, ax, B, L, stream));
         BABE_TRY(babe_lincomb3(w.r, 1.f, y, -1.f, mix, 0.f, nullptr, n, stream));
         BABE_TRY(babe_sumsq_partial(w.r, L, w.part, 64, B, L, stream));
         BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, nullptr, w.seed, L, B, (int)L, stream));
-        BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, s_post, L, B, (int)L, stream));
-        BABE_TRY(babe_mask_blend(seed_f, e->mask, e->mask_bs, nullptr, s_post, B, L, stream));
-        BABE_TRY(babe_stft_fwd(seed_f, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
-        BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
-        BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, gA, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+        BABE_TRY(babe_mask_blend(seed_f, e->mask, e->mask_bs, nullptr, w.seed, B, L, stream));
+        BABE_TRY(adjoint(seed_f, gA));
         BABE_TRY(babe_mask_blend(seed_o, e->mask, e->mask_bs, w.seed, nullptr, B, L, stream));
         BABE_TRY(babe_lincomb3(g_raw, 1.f, seed_o, 1.f, gA, 0.f, nullptr, n, stream));
+    } else {
+        // ---- filter fit on STFT magnitudes, filter design
+        BABE_TRY(babe_stft_fwd(x_den, L, (int)L, nullptr, w.specX, B, e->nfft, g.frames, e->tw4096, stream));
+        if (e->blind) {
+            BABE_TRY(babe_stft_mag_stats(w.specX, specY, w.stats, B, g.nbins, g.frames, e->shared, stream));
+            BABE_TRY(babe_filter_fit(w.stats, params, n_iter ? n_iter : w.nit, P, e->K, g.nbins, e->fs, e->nfft, &e->fit, stream));
+        }
+        BABE_TRY(babe_design_filter(params, w.H, P, e->K, g.nbins, e->fs, e->nfft, stream));
+        // ---- reconstruction guidance: residual y - A(x_den), its norm's gradient through iSTFT o H o STFT
+        BABE_TRY(babe_spec_filter_istft(w.specX, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+        if (!e->mask) {
+            BABE_TRY(babe_ola(w.fr, e->env_inv, y, L, w.r, L, w.part, 64, B, (int)L, e->nfft, g.frames, stream));
+            BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, w.seed, L, B, (int)L, stream));
+            BABE_TRY(babe_stft_fwd(w.seed, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+            BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+            BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, g_raw, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+        } else {
+            // MaskMixDegradation over the STFT filter (babe_amd/degrade.py:191-213): r = y - (mask x_den + (1 - mask) A(x_den)); the
+            // observed part takes the seed as it is, the filtered part the seed with the overlap-add envelope through A^T.  The
+            // denoiser's buffers are free here and carry the intermediates: no buffer of its own.
+            float *ax = w.xin, *mix = w.net, *s_post = w.g_net, *seed_f = w.g_xin, *gA = w.xin, *seed_o = w.net;
+            BABE_TRY(babe_ola(w.fr, e->env_inv, nullptr, 0, ax, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+            BABE_TRY(babe_mask_blend(mix, e->mask, e->mask_bs, x_den, ax, B, L, stream));
+            BABE_TRY(babe_lincomb3(w.r, 1.f, y, -1.f, mix, 0.f, nullptr, n, stream));
+            BABE_TRY(babe_sumsq_partial(w.r, L, w.part, 64, B, L, stream));
+            BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, nullptr, w.seed, L, B, (int)L, stream));
+            BABE_TRY(babe_residual_seed(w.r, L, w.part, 64, e->env_inv, s_post, L, B, (int)L, stream));
+            BABE_TRY(babe_mask_blend(seed_f, e->mask, e->mask_bs, nullptr, s_post, B, L, stream));
+            BABE_TRY(babe_stft_fwd(seed_f, L, (int)L, nullptr, w.specS, B, e->nfft, g.frames, e->tw4096, stream));
+            BABE_TRY(babe_spec_filter_istft(w.specS, w.H, H_bs, w.fr, B, e->nfft, g.frames, e->tw4096, stream));
+            BABE_TRY(babe_ola(w.fr, nullptr, nullptr, 0, gA, L, nullptr, 64, B, (int)L, e->nfft, g.frames, stream));
+            BABE_TRY(babe_mask_blend(seed_o, e->mask, e->mask_bs, w.seed, nullptr, B, L, stream));
+            BABE_TRY(babe_lincomb3(g_raw, 1.f, seed_o, 1.f, gA, 0.f, nullptr, n, stream));
+        }
     }
     if (e->hpf) BABE_TRY(babe_cqt_hpf(e->cqt_plan, w.hp, w.g_den, w.cqws, B, stream));
     // ---- through the network: g_x = cskip g_den + cin net^T(cout g_den)
@@ -162,9 +246,8 @@ extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t,
     BABE_TRY(babe_score_direction(x_den, x, w.xd, w.gpart, 64, d, t, e->xi, (float)e->audio_len_norm, e->shared, e->score_mode, B, L, stream));
     if (e->dc_mask) {
         // replacement data-consistency step of inpaint_DC on the Tweedie estimate x0 = x - t d: x0 <- (1 - dc_mask) x0 + dc_y, and
-        // back to a direction (the scalars as the Python sequencer forms them: in double, rounded once)
+        // back to a direction
         float *x0 = w.xin, *kept = w.net, *x0r = w.r;
-        const float inv_t = (float)(1.0 / (double)t), neg_inv_t = (float)(-1.0 / (double)t);
         BABE_TRY(babe_lincomb3(x0, 1.f, x, -t, d, 0.f, nullptr, n, stream));
         BABE_TRY(babe_mask_blend(kept, e->dc_mask, e->mask_bs, nullptr, x0, B, L, stream));
         if (e->mask_bs == L || B == 1) {
@@ -173,6 +256,14 @@ extern "C" int babe_score_eval(const babe_eval_desc* e, const float* x, float t,
             for (int b = 0; b < B; ++b)
                 BABE_TRY(babe_lincomb3(x0r + b * L, 1.f, kept + b * L, 1.f, e->dc_y + b * e->mask_bs, 0.f, nullptr, L, stream));
         }
+        BABE_TRY(babe_lincomb3(d, inv_t, x, neg_inv_t, x0r, 0.f, nullptr, n, stream));
+    } else if (e->dc_classic) {
+        // the classic replacement step (posterior_sampling.data_consistency; :63-73, :178-188) on the same estimate:
+        // x0 <- y + x0 - A(x0), and back to a direction
+        float *x0 = w.xin, *x0r = w.r;
+        BABE_TRY(babe_lincomb3(x0, 1.f, x, -t, d, 0.f, nullptr, n, stream));
+        BABE_TRY(forward(x0, w.a0));
+        BABE_TRY(babe_lincomb3(x0r, 1.f, x0, 1.f, y, -1.f, w.a0, n, stream));
         BABE_TRY(babe_lincomb3(d, inv_t, x, neg_inv_t, x0r, 0.f, nullptr, n, stream));
     }
     return BABE_OK;

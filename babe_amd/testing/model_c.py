@@ -1,6 +1,8 @@
 """ctypes view of a library-built network (csrc/model.hip: babe_model_load and friends) - what a host without Python holds instead
-of a UnetEngine, a CQT_nsgt, an STFTOps and a CEval.  Used by tests/test_gpu_model_c.py and tools/model_load_bench.py only: the
-samplers keep building their descriptors from the Python engine."""
+of a UnetEngine, a CQT_nsgt, an STFTOps and a CEval -, and of the descriptor's observation model (observe: a degrade.py object
+onto babe_eval_desc.obs_kind and its parameters) and the host helpers babe_firwin_kaiser / babe_iir_check.  Used by the tests
+(tests/test_gpu_model_c.py, tests/test_gpu_obs_library.py) and tools/model_load_bench.py only: the samplers keep building their
+descriptors from the Python engine."""
 import ctypes as C
 
 from .._cabi import EvalDesc, ModelSummary
@@ -98,23 +100,100 @@ def edm_steps(model, T, snoise=1.0):
     return rows, t0.value, start > 0
 
 
-def sample(model, state, y, params, rows, t0, warm_start, seed, clip0=0, blind=True, desc=None):
-    """babe_sample_bwe on the model's descriptor: y [B,L], params [P,2,K] (left alone), the noise from the library's generator
-    under (seed, clip0) -> (x, params, the babe_sample_desc used)."""
+def observe(desc, degradation, dc_classic=False):
+    """The known observation model `degradation` (babe_amd/degrade.py: FIRDegradation, IIRDegradation, MaskDegradation,
+    ClipDegradation, or MaskMixDegradation over a FIR or over None = the STFT filter; None = the STFT filter alone) into the
+    babe_eval_desc `desc`, with blind = 0 for every known one; dc_classic: the replacement step x0 <- y + x0 - A(x0).  The tensors
+    whose addresses the descriptor now holds stay alive with it (desc._keep; a copy by value, as into a babe_sample_desc, does not
+    carry them: keep `desc` itself while the copy is in use).  Returns desc."""
+    from .._cabi import OBS_CLIP, OBS_FIR, OBS_IIR, OBS_MASK, OBS_STFT
+    from .._lib import ptr
+    from ..degrade import ClipDegradation, FIRDegradation, IIRDegradation, MaskDegradation, MaskMixDegradation
+    d, keep = desc, []
+    d.obs_kind, d.taps, d.ntaps, d.b, d.a, d.order, d.clamp = OBS_STFT, None, 0, None, None, 0, 0
+    d.obs_mask, d.obs_mask_bs, d.clip_value, d.dc_classic = None, 0, 0.0, int(bool(dc_classic))
+    d.mask, d.mask_bs = None, 0
+
+    def rows(m):              # ([L] or [B,L] float32 rows, their stride: 0 = one row for every clip)
+        m = m.float().contiguous()
+        keep.append(m)
+        return ptr(m), (0 if m.dim() == 1 or m.shape[0] == 1 else m.stride(0))
+
+    deg = degradation
+    if isinstance(deg, MaskMixDegradation):
+        d.mask, d.mask_bs = rows(deg.mask)
+        deg = deg.inner
+        if deg is not None and not isinstance(deg, FIRDegradation):
+            raise NotImplementedError("the AR mix runs over the STFT filter or a FIR")
+    if deg is None:
+        pass
+    elif isinstance(deg, FIRDegradation):
+        keep.append(deg.taps)
+        d.obs_kind, d.taps, d.ntaps = OBS_FIR, ptr(deg.taps), deg.taps.numel()
+    elif isinstance(deg, IIRDegradation):
+        keep.extend([deg.b, deg.a])
+        d.obs_kind, d.b, d.a, d.order, d.clamp = OBS_IIR, ptr(deg.b), ptr(deg.a), deg.a.numel() - 1, int(deg.clamp)
+    elif isinstance(deg, MaskDegradation):
+        d.obs_kind = OBS_MASK
+        d.obs_mask, d.obs_mask_bs = rows(deg.mask)
+    elif isinstance(deg, ClipDegradation):
+        d.obs_kind, d.clip_value = OBS_CLIP, deg.c
+    else:
+        raise NotImplementedError(f"{type(deg).__name__}: the observation is not of the state's shape, or has no library-side "
+                                  f"sequencing")
+    if degradation is not None:
+        d.blind = 0
+    desc._keep = keep
+    return desc
+
+
+def firwin_kaiser(numtaps, cutoff, width, fs, highpass=False):
+    """babe_firwin_kaiser -> the taps as a float64 numpy array (scipy.signal.firwin(..., width=width, window='kaiser', fs=fs))."""
+    import numpy as np
+    taps = np.empty(int(numtaps), dtype=np.float64)
+    check(lib().babe_firwin_kaiser(int(numtaps), float(cutoff), float(width), float(fs), int(bool(highpass)), taps.ctypes.data),
+          "firwin_kaiser")
+    return taps
+
+
+def iir_check(b, a):
+    """babe_iir_check on float32 coefficients already divided by a[0] -> (ok, message).  One `order` describes both arrays in the
+    C call, so arrays of different lengths - which degrade.prepare_iir refuses - have no call to make: refused here."""
+    import numpy as np
+    b, a = np.ascontiguousarray(b, dtype=np.float32).reshape(-1), np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if b.size != a.size:
+        return False, f"len(b) = {b.size} != len(a) = {a.size}"
+    rc = lib().babe_iir_check(b.ctypes.data, a.ctypes.data, a.size - 1)
+    return rc == 0, ("" if rc == 0 else lib().babe_last_error().decode())
+
+
+def sample(model, state, y, params, rows, t0, warm_start, seed, clip0=0, blind=True, desc=None, noise=None, skip_zero_inject=False,
+           shape=None):
+    """babe_sample_bwe on the model's descriptor: y [B,L] (None: unconditional sampling of `shape` = (B, L)), params [P,2,K] (left
+    alone; None where the descriptor's observation model is not the STFT filter), the noise from the library's generator under
+    (seed, clip0) or, with noise [T+1,B,L], from that buffer; skip_zero_inject: a step with inject == 0 evaluates the state as it
+    is -> (x, params, the babe_sample_desc used)."""
     import torch
     from .._cabi import SampleDesc
     from .._lib import ptr
-    B, T = y.shape[0], len(rows)
+    T = len(rows)
+    B, L = y.shape if y is not None else shape
     d = SampleDesc()
     d.eval = desc if desc is not None else model.eval_desc(state)
-    d.eval.K, d.eval.blind = int(params.shape[-1]), int(bool(blind))
-    d.T, d.steps, d.t0, d.warm_start = T, rows, t0, int(bool(warm_start))
+    if params is not None:
+        d.eval.K = int(params.shape[-1])
+    d.eval.blind = int(bool(blind))
+    d.T, d.steps, d.t0, d.warm_start, d.skip_zero_inject = T, rows, t0, int(bool(warm_start)), int(bool(skip_zero_inject))
     n = lib().babe_sample_workspace_bytes(C.byref(d), B)
     if n < 0:
         raise BabeHipError("sample_workspace_bytes: " + lib().babe_last_error().decode())
-    ws = torch.empty(n, device=y.device, dtype=torch.uint8)
-    p, x = params.clone().contiguous(), torch.empty_like(y)
-    check(lib().babe_sample_bwe(C.byref(d), ptr(y), ptr(p), ptr(x), None, int(seed), int(clip0), None, None, ptr(ws), n, B, stream()),
-          "sample_bwe")
-    torch.cuda.synchronize(y.device)                     # ws is released on return
+    dev = y.device if y is not None else torch.device("cuda", torch.cuda.current_device())
+    ws = torch.empty(n, device=dev, dtype=torch.uint8)
+    p = params.clone().contiguous() if params is not None else None
+    x = torch.empty((B, L), device=dev, dtype=torch.float32)
+    if noise is not None:
+        assert noise.shape == (T + 1, B, L) and noise.is_contiguous() and noise.dtype == torch.float32 and noise.device == dev
+    check(lib().babe_sample_bwe(C.byref(d), ptr(y), ptr(p), ptr(x), ptr(noise), int(seed), int(clip0), None, None, ptr(ws), n, B,
+                                stream()), "sample_bwe")
+    torch.cuda.synchronize(dev)                          # ws is released on return
     return x, p, d

@@ -594,7 +594,14 @@ int babe_score_direction(const float* xden, const float* xhat, const float* g, c
  * observation model over the known filter: residual y - (mask x_den + (1 - mask) A(x_den)), gradient mask s + A^T((1 - mask)
  * s_post), and with desc.dc_mask the replacement step on x0 = x - t d after the score direction.  Bit-identical to the Python
  * sequencer on both (tests/test_gpu_eval_c.py, tests/test_gpu_sample_ar_c.py).  specY may be NULL when blind = 0.  No allocation,
- * no synchronisation. */
+ * no synchronisation.
+ * Known degradations (desc.obs_kind, below): FIR, IIR ('cheby1' / 'biquad'), mask (inpainting, compressed sensing) and clip
+ * (declipping) take the place of the STFT filter - residual, block sums, seed and transpose as the degrade.py objects sequence
+ * them -, the classic replacement step (desc.dc_classic) and the EDM sampler's no-guidance branch follow the score direction,
+ * and y == NULL is unconditional sampling: d = (x - x_den) / t (STFT kind without mask only).  Bit-identical to the Python
+ * sequencers BlindSampler.evaluate and edm_sampler.Sampler.evaluate (tests/test_gpu_obs_library.py).  Still with the Python
+ * sequencer: 'resample' / 'decimate' and phase retrieval (the observation is not of the state's shape), the smooth-L1, cosine
+ * and STFT-domain distances, observation noise, attention networks. */
 typedef struct {
     const void* unet_plan; void* unet_state;      /* babe_unet_plan_create / babe_unet_state_create (one state per stream) */
     const void* cqt_plan;                         /* babe_cqt_plan_create for (fs, L) */
@@ -619,7 +626,26 @@ typedef struct {
      * smoothed mask and dc_mask * y_masked of the replacement step x0 <- (1 - dc_mask) x0 + dc_y of inpaint_DC (:63-73). */
     const float* mask; long mask_bs;
     const float* dc_mask; const float* dc_y;
+    /* the KNOWN observation model y = A(x) (babe_amd/degrade.py; all zero = BABE_OBS_STFT, the filter of `params`).  Every other
+     * kind needs blind = 0 and reads neither params nor specY (both may be NULL); `mask` above combines with STFT and FIR only
+     * (MaskMixDegradation over that filter: the observed part takes the plain seed).
+     *   FIR:  taps [ntaps] (device): F.conv1d(padding="same"), babe_fir_same and its transpose.
+     *   IIR:  b, a [order + 1] (device, float32, already divided by a[0]; babe_iir_check decides what degrade.prepare_iir decides),
+     *         order 1..16; clamp = 1: lfilter's clamp to [-1, 1] ('biquad'), whose mask the transpose of the same call reads.
+     *   MASK: A(x) = obs_mask x; obs_mask [L], or [B][L] at row stride obs_mask_bs (0: one row for every clip); self-adjoint.
+     *   CLIP: A(x) = clip(x, -clip_value, clip_value), clip_value >= 0; the transpose multiplies by |x| <= clip_value.
+     * dc_classic = 1 (STFT, FIR, IIR, MASK; not with dc_mask): after the score direction, the replacement step x0 <- y + x0 - A(x0)
+     * on x0 = x - t d, then back to a direction (posterior_sampling.data_consistency; under `mask` A is the inner filter without
+     * the mix, as in the Python sequencer).  With xi == 0 and score_mode == 1 it is the EDM sampler's no-guidance branch
+     * (edm_sampler.Sampler.evaluate): the step on the denoised estimate itself, which then gets no high-pass. */
+    int obs_kind;                                 /* BABE_OBS_* */
+    const float* taps; int ntaps;
+    const float* b; const float* a; int order; int clamp;
+    const float* obs_mask; long obs_mask_bs;
+    float clip_value;
+    int dc_classic;
 } babe_eval_desc;
+enum { BABE_OBS_STFT = 0, BABE_OBS_FIR = 1, BABE_OBS_IIR = 2, BABE_OBS_MASK = 3, BABE_OBS_CLIP = 4 };
 long babe_eval_workspace_bytes(const babe_eval_desc* desc, int B);
 int babe_score_eval(const babe_eval_desc* desc, const float* x, float t, float cskip, float cout, float cin, float cnoise,
                     const float* y, const float* specY, float* params, float* d, float* x_den, int* n_iter, void* ws,
@@ -647,7 +673,8 @@ int babe_rand_bits(int* out, long out_bs, int B, long n, long seed, long clip0, 
  * specY = babe_stft_fwd(y) -> initial state -> per step: noise injection babe_lincomb3(1, x, inject, eps), babe_score_eval at
  * t_hat, then the Euler update x_hat + h d or the Heun pair (x' = x_hat + h d, babe_score_eval at t_next, x_hat + h/2 d + h/2 d').
  * Scope: exactly babe_score_eval's (blind or known fc_A filter, L2 guidance, the AR mask and its replacement step through
- * eval.mask / eval.dc_mask, no observation noise, no FIR or IIR degradation, fp32 network without attention).  Like babe_score_eval the run contains no schedule formula: the
+ * eval.mask / eval.dc_mask, the known degradations of eval.obs_kind, y == NULL for unconditional sampling; no observation noise,
+ * no network with attention).  Like babe_score_eval the run contains no schedule formula: the
  * caller passes one row per step (babe_edm_steps fills them for a host without the Python EDM class).  Same kernels, order and
  * scalars as the Python loop: bit-identical to it (tests/test_gpu_sample_c.py).  No allocation, no synchronisation; a failing
  * inner call returns its code; every argument is checked on the host before the first launch.  Two runs on two streams, each
@@ -663,6 +690,9 @@ typedef struct {
     babe_eval_desc eval;      /* as for babe_score_eval; K and blind are read from here                        */
     int T; const babe_sample_step* steps;   /* host memory, T rows                                             */
     float t0; int warm_start; /* x_0 = (warm_start ? y : 0) + t0 * eps_init                                    */
+    int skip_zero_inject;     /* 1: a step whose inject == 0 evaluates the state as it is, no draw and no injection launch (the EDM
+                                 sampler's rule for gamma == 0, edm_sampler.py:187-198).  Row i + 1 of `noise` and draw i + 1 of
+                                 the generator still belong to step i: a skipped step shifts nothing                             */
 } babe_sample_desc;
 long babe_sample_workspace_bytes(const babe_sample_desc* d, int B);
 /* y [B][L] observations; params [P][2][K] (P = B, or 1 with eval.shared): in the initial filter parameters, out the final ones
@@ -670,7 +700,9 @@ long babe_sample_workspace_bytes(const babe_sample_desc* d, int B);
  * during the run).  noise [T+1][B][L]: draw 0 is the initial state, draw i + 1 step i; NULL: the draws come from
  * babe_randn(seed, clip0, draw) into one workspace buffer, so that the run is a function of (weights, y, seed) alone.
  * rec_x_den [T][B][L] / rec_params [T][P][2][K] (each may be NULL): the FIRST evaluation's denoised estimate of every step and the
- * parameters after it - what predict_blind_bwe(rid=True) keeps -, copied device to device on the stream. */
+ * parameters after it - what predict_blind_bwe(rid=True) keeps -, copied device to device on the stream.
+ * y == NULL (needs warm_start = 0, the STFT kind and no mask): unconditional sampling.  params may be NULL where no evaluation
+ * reads it: a kind other than BABE_OBS_STFT, or y == NULL (rec_params must then be NULL too). */
 int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, float* x_out, const float* noise, long seed, long clip0,
                     float* rec_x_den, float* rec_params, void* ws, long ws_bytes, int B, void* stream);
 /* host helper for hosts without the Python EDM class: fills steps[T] and *t0 from the tester's diff_params in double arithmetic
@@ -680,6 +712,19 @@ int babe_sample_bwe(const babe_sample_desc* d, const float* y, float* params, fl
  * The Python class evaluates the same formulas in float32, so its rows differ in the last bits ((ro + 4) 2^-23 relative). */
 int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double sigma_min, double sigma_max, double ro,
                    double sigma_data, double Schurn, double Stmin, double Stmax, double Snoise, double start_sigma);
+/* host helpers for hosts without scipy (no GPU call; csrc/sample.hip).
+ * babe_firwin_kaiser: scipy.signal.firwin(numtaps, cutoff, width=width, window="kaiser", fs=fs[, pass_zero="highpass"]) in double -
+ * what the reference's get_FIR_lowpass / get_FIR_high_pass compute with the config's "beta" as the width
+ * (utils/bandwidth_extension.py): attenuation a = 2.285 (numtaps - 1) pi width / (fs / 2) + 7.95, Kaiser beta from a
+ * (0.1102 (a - 8.7) above 50 dB, 0.5842 (a - 21)^0.4 + 0.07886 (a - 21) above 21 dB, else 0), h[n] = w[n] (r sinc(r m) - l sinc(l m))
+ * over the band [l, r] = [0, c] or [c, 1], c = cutoff / (fs / 2), m = n - (numtaps - 1) / 2, scaled to unit gain at the band's
+ * centre frequency (0, or 1 for the high-pass).  taps_out [numtaps] doubles (host).  Refused: numtaps < 1, cutoff outside
+ * (0, fs / 2), width <= 0, an even numtaps for the high-pass. */
+int babe_firwin_kaiser(int numtaps, double cutoff, double width, double fs, int highpass, double* taps_out);
+/* babe_iir_check: 0 where degrade.prepare_iir accepts (b, a) [order + 1] (host, float32, after the division by a[0]): order in
+ * 1..16, a[0] == 1, and every root of a inside the unit circle - the step-down (Schur-Cohn) recursion in double on the float32
+ * coefficients: all reflection coefficients below 1 in modulus.  Anything else returns BABE_ERR_ARG with the reason. */
+int babe_iir_check(const float* b, const float* a, int order);
 
 /* ---- one WHOLE RECORDING from plan handles (csrc/recording.hip): what long_file.restore_recording_complete (without denoiser and
  * rate conversion: babe_restore_file below puts them in front) and restore_file_AR sequence from Python (BlindTester.test_real_blind_bwe_complete, testing/
@@ -696,6 +741,7 @@ int babe_edm_steps(babe_sample_step* steps, float* t0, int T, int order, double 
 long babe_recording_plan(long Lrec, long segL, long overlap, long discard_end, long* starts, long* n_valid, long max_segments);
 typedef struct {
     babe_eval_desc eval;                  /* as for babe_score_eval (segL = eval.L); blind and the mask fields are set by the call;
+                                             obs_kind must be BABE_OBS_STFT and dc_classic 0: the flow estimates its filter;
                                              eval.shared is that of the known-filter runs, the blind batch is always coupled */
     int T; float t0; int warm_start;      /* as in babe_sample_desc, for both tables */
     const babe_sample_step* steps_blind;  /* host, T rows: the blind loop injects with Snoise = 1 ...                        */
