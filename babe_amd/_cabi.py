@@ -58,6 +58,17 @@ class CBlock(C.Structure):
                 ("fb_proj_in", C.c_void_p), ("fb_res_conv", C.c_void_p)]
 
 
+class PwArgs(C.Structure):
+    """babe_pw_args: the operands of one fused (1,1) ResnetBlock pass (csrc/pw_block.hip)."""
+    _fields_ = [("B", C.c_int), ("F", C.c_int), ("T", C.c_int), ("S", C.c_int), ("plan_splits", C.c_int),
+                ("z", C.c_void_p), ("z_bs", C.c_long), ("z_cs", C.c_long),
+                ("x", C.c_void_p), ("x_bs", C.c_long), ("x_cs", C.c_long),
+                ("out", C.c_void_p), ("out_bs", C.c_long), ("out_cs", C.c_long),
+                ("add", C.c_void_p), ("add_bs", C.c_long), ("add_cs", C.c_long),
+                ("part", C.c_void_p), ("film", C.c_void_p), ("film_bs", C.c_long), ("gate", C.c_void_p),
+                ("stats", C.c_void_p), ("scale", C.c_void_p)]
+
+
 class CPlanDesc(C.Structure):
     """babe_unet_plan_desc"""
     _fields_ = [("nocts", C.c_int), ("bpo", C.c_int), ("Ns", C.c_int * 8),
@@ -185,7 +196,7 @@ class OptChunk(C.Structure):
 
 # header struct name -> mirror (the layout test compiles a probe for each of them)
 STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packed_conv": CPackedConv,
-           "babe_packed_conv_layout": PackedConvLayout, "babe_unet_block": CBlock,
+           "babe_packed_conv_layout": PackedConvLayout, "babe_unet_block": CBlock, "babe_pw_args": PwArgs,
            "babe_unet_plan_desc": CPlanDesc, "babe_cqt_bands": CqtBands, "babe_fit_cfg": FitCfg, "babe_eval_desc": EvalDesc,
            "babe_dnconv_args": DnConvArgs, "babe_sample_step": SampleStep, "babe_sample_desc": SampleDesc,
            "babe_recording_desc": RecordingDesc,
@@ -273,6 +284,9 @@ SIGS = {
     "babe_unet_vjp": (_I, [_P, _P, C.POINTER(_P), C.POINTER(_P), _P]),
     "babe_unet_form_get": (_I, [_I]),
     "babe_unet_form_set": (_I, [_I, _I]),
+    "babe_pw_block_enable": (_I, [_I]),
+    "babe_pw_block_supported": (_I, [C.POINTER(CBlock), C.POINTER(PwArgs), _I]),
+    "babe_pw_block_fwd": (_I, [C.POINTER(CBlock), C.POINTER(PwArgs), _P]),
     "babe_axpby4d": (_I, [_P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),
     "babe_fill4d": (_I, [_P, _L, _L, _I, _I, _I, _I, _F, _P]),
     "babe_axpby2_4d": (_I, [_P, _L, _L, _P, _L, _L, _P, _L, _L, _I, _I, _I, _I, _F, _F, _P]),

@@ -191,8 +191,12 @@ struct Ctx {
     const float* film_at(int off) const { return S->film + off; }
 
     // ---- ResnetBlock (unet_engine.py block_fwd / block_vjp)
-    View block_fwd(const babe_unet_block& blk, Saved* saved, const View& x, const View& out, const View* x2) {
+    // fold (an output head): the caller's next step is fold = RS2 * out + RS2 * fold; a block that runs as the fused pass
+    // (babe_pw_block_supported) does that itself, writes fold instead of out and sets *folded
+    View block_fwd(const babe_unet_block& blk, Saved* saved, const View& x, const View& out, const View* x2,
+                   const View* fold = nullptr, bool* folded = nullptr) {
         const int N = blk.N, Fq = x.F, T = x.T;
+        bool pw = false;                         // the block ran as one fused pass (csrc/pw_block.hip)
         View z;
         if (blk.proj_in.Cout) {
             z = buf(N, Fq, T);
@@ -237,7 +241,26 @@ struct Ctx {
                 ua.Cin = ua.Cout = ua.cin_split = N; ua.KH = blk.H[d].KH; ua.KW = blk.H[d].KW;
                 take_units = babe_conv2d_bf16_units_supported(&ua) != 0;
             }
-            if (take_units) {
+            // a k = (1,1) block the library's rule takes: GroupNorm sums, then ONE pass for the rest of the block.  Everything is
+            // carved as for the layer-by-layer form, so that babe_unet_workspace_bytes does not depend on the switch
+            babe_pw_args pa;
+            memset(&pa, 0, sizeof pa);
+            if (blk.nd == 1 && !blk.k53 && !dry() && !err) {
+                pa.B = B(); pa.F = Fq; pa.T = T; pa.S = Sp;
+                pa.plan_splits = P->main_blk[0].H[0].splits;                     // the (5,3) layers carry the network's precision
+                pa.z = z.p; pa.z_bs = z.bs; pa.z_cs = z.cs;
+                if (blk.proj_in.Cout) { pa.x = x.p; pa.x_bs = x.bs; pa.x_cs = x.cs; }
+                const View& o = fold ? *fold : out;
+                pa.out = o.p; pa.out_bs = o.bs; pa.out_cs = o.cs;
+                if (fold) { pa.add = fold->p; pa.add_bs = fold->bs; pa.add_cs = fold->cs; }
+                pa.part = part; pa.film = S->film; pa.film_bs = S->film_bs; pa.gate = gate; pa.stats = stats; pa.scale = scale;
+                pw = !x2 && babe_pw_block_supported(&blk, &pa, 0) != 0;
+            }
+            if (pw) {
+                ck(babe_gn_partial(z.p, part, B(), G_GROUPS, n, Sp, st));
+                ck(babe_pw_block_fwd(&blk, &pa, st));
+                if (fold && folded) *folded = true;
+            } else if (take_units) {
                 ck(babe_gn_partial(z.p, part, B(), G_GROUPS, n, Sp, st));
                 ck(babe_gn_finalize(part, blk.gamma[d], film_at(blk.film_aff[d]), S->film_bs, stats, scale, B(), N, G_GROUPS, n, Sp, GN_EPS, st));
                 ck(babe_scale_gelu_units(z.p, scale, au, B(), N, Fq, T, st));
@@ -258,7 +281,7 @@ struct Ctx {
                 nS = stat_slots(cg, Fq, T, dil);
                 npart = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * nS * 2 * 2));
             }
-            const bool made = !take_units && conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, form(BABE_FORM_FUSE_GN_FWD) ? npart : nullptr);
+            const bool made = !pw && !take_units && conv(av, blk.H[d], znew, dil, false, nullptr, &z, nullptr, gate, RS2, RS2, cg, form(BABE_FORM_FUSE_GN_FWD) ? npart : nullptr);
             zS = made ? nS : 0;                                                      // (a units layer drops the carried sums)
             zpart = npart;
             saved[d] = Saved{z, stats, scale, gate};
@@ -266,9 +289,10 @@ struct Ctx {
         }
         if (blk.proj_out.Cout) {
             View zo = buf(blk.proj_out.Cout, Fq, T);
-            conv(z, blk.proj_out, zo, 1, false, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f);
+            if (!pw) conv(z, blk.proj_out, zo, 1, false, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f);
             z = zo;
         }
+        if (pw) return out;
         if (blk.res_conv.Cout) conv(x, blk.res_conv, out, 1, false, x2, &z, nullptr, nullptr, RS2, RS2, 0, nullptr, blk.fb_res_conv);
         else axpby2(z, x, out, RS2, RS2);
         return out;
@@ -407,8 +431,9 @@ struct Ctx {
             View R = buf(Nout, Fj, Ts[j]);
             block_fwd(P->up_blk[i], S->saved[3][i], X, R, &S->hs[j]);
             View O = buf(2, Fj, Ts[j]);
-            block_fwd(P->up_out[i], S->saved[2][i], R, O, nullptr);
-            axpby(O, Xout, RS2, RS2);
+            bool folded = false;                                     // the fused head adds itself into Xout
+            block_fwd(P->up_out[i], S->saved[2][i], R, O, nullptr, &Xout, &folded);
+            if (!folded) axpby(O, Xout, RS2, RS2);
             View o; o.p = outs[i]; o.C = 2; o.F = bpo; o.T = Ts[j]; o.cs = (long)bpo * Ts[j]; o.bs = 2 * o.cs;
             axpby(sub_f(Xout, 0, bpo), o);
             if (j > 0) {

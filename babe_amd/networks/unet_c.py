@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from .._cabi import CPackedConv, CPlanDesc
+from .._cabi import CBlock, CPackedConv, CPlanDesc
 from .._lib import check, lib, ptr, stream, workspace
 
 
@@ -19,7 +19,8 @@ def _pc(dst, pc):
         C.memmove(C.addressof(dst), C.addressof(pc.desc), C.sizeof(CPackedConv))
 
 
-def _blk(dst, b):
+def fill_block(dst, b):
+    """_Block -> babe_unet_block: copies of its convs' descriptors, pointers to its gammas (the images repack in place)."""
     dst.N, dst.nd, dst.k53 = b.N, b.nd, int(b.k53)
     _pc(dst.proj_in, b.proj_in)
     _pc(dst.res_conv, b.res_conv)
@@ -30,6 +31,13 @@ def _blk(dst, b):
         dst.film_aff[d], dst.film_gate[d] = b.film_off[d]
     if b.fenc is not None:                                # folded frequency encodings: the tables are rewritten in place by refresh
         dst.fb_proj_in, dst.fb_res_conv = ptr(b.fb_proj_in), ptr(b.fb_res_conv)
+
+
+def c_block(b):
+    """A _Block as a babe_unet_block of its own: what the fused (1,1) block passes take from the Python sequencer."""
+    dst = CBlock()
+    fill_block(dst, b)
+    return dst
 
 
 class CPlan:
@@ -48,13 +56,13 @@ class CPlan:
             for i, v in enumerate(eng.Ns):
                 d.Ns[i] = v
             for i in range(eng.nocts):
-                _blk(d.init_blk[i], eng.init_blk[i])
-                _blk(d.main_blk[i], eng.main_blk[i])
-                _blk(d.up_out[i], eng.up_out[i])
-                _blk(d.up_blk[i], eng.up_blk[i])
+                fill_block(d.init_blk[i], eng.init_blk[i])
+                fill_block(d.main_blk[i], eng.main_blk[i])
+                fill_block(d.up_out[i], eng.up_out[i])
+                fill_block(d.up_blk[i], eng.up_blk[i])
                 _pc(d.pyr_conv[i], eng.pyr_conv[i])
-            _blk(d.mid_blk, eng.mid_blk)
-            _blk(d.mid_out, eng.mid_out)
+            fill_block(d.mid_blk, eng.mid_blk)
+            fill_block(d.mid_out, eng.mid_out)
             self.handle = lib().babe_unet_plan_create(C.byref(d))
             if not self.handle:
                 raise RuntimeError("babe_unet_plan_create: " + lib().babe_last_error().decode())

@@ -21,7 +21,7 @@ import torch
 
 from .. import ops
 from ..forms import FORMS
-from .unet_c import CPlan, CUnet
+from .unet_c import CPlan, CUnet, c_block
 
 RS2 = 1.0 / math.sqrt(2.0)
 
@@ -93,6 +93,13 @@ class _Block:
             self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias"), prefix + f"affine.{d}"),
                                   film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"), prefix + f"gate.{d}")))
         self.attn = _Attn(g, attn[0], self.N, film_index, attn[1], prefix) if attn else None
+        self._cblk = None
+
+    def c_block(self):
+        """The library's descriptor of this block (babe_unet_block), made on first use: the fused (1,1) block passes take it."""
+        if self._cblk is None:
+            self._cblk = c_block(self)
+        return self._cblk
 
     def dil(self, d):
         return 2 ** d if self.k53 else 1
@@ -338,8 +345,10 @@ class UnetEngine:
         return film[:, off:off + N]
 
     # ------------------------------------------------------------------ ResnetBlock
-    def block_fwd(self, blk, x, film, out, x2=None):
-        """out <- ResnetBlock(cat(x,x2)); out may be a strided frequency sub-view."""
+    def block_fwd(self, blk, x, film, out, x2=None, fold=None):
+        """out <- ResnetBlock(cat(x,x2)); out may be a strided frequency sub-view.
+        fold (an output head): the caller's next step is fold <- RS2*out + RS2*fold.  A block that runs as the fused pass
+        (ops.pw_block_fwd) does that itself: it writes fold instead of out and returns fold."""
         B, _, Fq, T = x.shape
         N = blk.N
         st = self._state
@@ -352,6 +361,14 @@ class UnetEngine:
             z = x if x.is_contiguous() else ops.axpby(x, self.buf(B, N, Fq, T))
         if blk.attn is not None:
             z = self.attn_fwd(blk, z, film)
+        if blk.nd == 1 and not blk.k53 and x2 is None and blk.attn is None:
+            # a k = (1,1) block: GroupNorm sums, then ONE pass for the rest of the block where the library's rule takes it
+            gate = self._film(film, blk.film_off[0][1], N).contiguous()
+            ss = ops.pw_block_fwd(blk.c_block(), z, film, gate, out if fold is None else fold,
+                                  x=x if blk.proj_in is not None else None, add=fold, train=st.train, precision=self.precision)
+            if ss is not None:
+                st.saved[blk.idx] = [(z, ss[0], ss[1], gate)]
+                return out if fold is None else fold
         saved = []
         # precision='bf16': the GELU output goes to the conv as bf16 units (half the bytes, both conv operands by LDS-DMA)
         units = blk.nd > 0 and ops.units_ok(blk.H[0], N, N, T) and z.is_contiguous()
@@ -673,8 +690,9 @@ class UnetEngine:
             Fj = bpo * (j + 1)
             Nout = Ns[max(j - 1, 0)]
             R = self.block_fwd(self.up_blk[i], X, film, self.buf(B, Nout, Fj, Ts[j]), x2=hs[j])
-            O = self.block_fwd(self.up_out[i], R, film, self.buf(B, 2, Fj, Ts[j]))
-            ops.axpby(O, Xout, alpha=RS2, beta=RS2)               # Xout <- (Xout + O)/sqrt2
+            O = self.block_fwd(self.up_out[i], R, film, self.buf(B, 2, Fj, Ts[j]), fold=Xout)
+            if O is not Xout:                                     # (the fused head has added itself into Xout)
+                ops.axpby(O, Xout, alpha=RS2, beta=RS2)           # Xout <- (Xout + O)/sqrt2
             outs[i] = ops.axpby(Xout[:, :, :bpo, :], self.buf(B, 2, bpo, Ts[j]))
             if j > 0:
                 X = ops.resample(R[:, :, bpo:, :], self.buf(B, Nout, Fj - bpo, Ts[j - 1]), 1)

@@ -6,7 +6,7 @@ import math
 import torch
 
 from . import _lib
-from ._cabi import IMAGE_SLOTS, ConvArgs, CPackedConv, PackedConvLayout, WgradArgs
+from ._cabi import IMAGE_SLOTS, ConvArgs, CPackedConv, PackedConvLayout, PwArgs, WgradArgs
 from .forms import FORMS
 from ._lib import check, lib, ptr, stream
 
@@ -242,6 +242,40 @@ def gn_scale_gelu(x, gamma, film, out, G=8, eps=1e-7, fused=None):
         check(L.babe_gn_partial(ptr(x), ptr(part), B, G, n, S, stream()), "gn_partial")
     check(L.babe_scale_gelu_fin(ptr(x), ptr(part), ptr(gamma), ptr(film), film.stride(0), ptr(stats), ptr(scale), ptr(out),
                                 B, Cc, G, F * T, S, eps, stream()), "scale_gelu_fin")
+    return stats, scale
+
+
+def pw_block_enable(on):
+    """Sets the library's switch of the fused (1,1) ResnetBlock passes (BABE_PW_BLOCK); returns the previous value."""
+    return bool(lib().babe_pw_block_enable(int(bool(on))))
+
+
+def pw_block_fwd(cblk, z, film, gate, out, x=None, add=None, train=False, precision="f32", G=8):
+    """A k = (1,1) ResnetBlock forward as one fused pass (csrc/pw_block.hip) if the library's rule takes it
+    (babe_pw_block_supported: the one statement of that rule): babe_gn_partial over z, then the pass.  Returns (stats, scale) as
+    gn_scale_gelu does, or None - nothing launched - when the block has to run layer by layer.
+    cblk: the block's babe_unet_block; z [B,N,F,T] the GroupNorm input; film [B,J] the FiLM rows; gate [B,N] contiguous;
+    out: the head's 2-channel or the init block's N-channel output view; x: the init block's 2-channel input;
+    add: the head's running sum, out = RS2*(block) + RS2*add (may be out); precision: the network's (fp32 networks only)."""
+    if not z.is_contiguous():
+        return None
+    B, N, F, T = z.shape
+    n, S, part, stats, scale = _gn_buffers(z, G)
+    a = PwArgs()
+    a.B, a.F, a.T, a.S, a.plan_splits = B, F, T, S, PRECISIONS[precision]
+    a.z, a.z_bs, a.z_cs = _view(z)
+    if x is not None:
+        a.x, a.x_bs, a.x_cs = _view(x)
+    a.out, a.out_bs, a.out_cs = _view(out)
+    if add is not None:
+        a.add, a.add_bs, a.add_cs = _view(add)
+    assert film.stride(1) == 1 and gate.is_contiguous() and gate.shape == (B, N)
+    a.part, a.film, a.film_bs, a.gate, a.stats, a.scale = ptr(part), ptr(film), film.stride(0), ptr(gate), ptr(stats), ptr(scale)
+    L = lib()
+    if not L.babe_pw_block_supported(C.byref(cblk), C.byref(a), int(bool(train))):
+        return None
+    check(L.babe_gn_partial(ptr(z), ptr(part), B, G, n, S, stream()), "gn_partial")
+    check(L.babe_pw_block_fwd(C.byref(cblk), C.byref(a), stream()), "pw_block_fwd")
     return stats, scale
 
 

@@ -342,6 +342,43 @@ enum { BABE_FORM_FUSE_GN_FWD = 0, BABE_FORM_FUSE_GN = 1 };
 int babe_unet_form_get(int which);
 int babe_unet_form_set(int which, int on);
 
+/* ---- the k = (1,1) ResnetBlocks (the init blocks 2 -> N and the output heads N -> 2, up_out / mid_out) forward as one fused pass
+ * over the block's N-channel tensor (csrc/pw_block.hip): GroupNorm finalize, scale, GELU, the N x N layer on fp32 MFMA, gate,
+ * residual and the block's 2-channel side convs in registers - z is read once where the layer-by-layer path moves 8 - 9 planes.
+ * Views are (pointer, batch stride, channel stride) of [B][C][F][T] tensors with contiguous rows, as everywhere in this header.
+ *   z     the GroupNorm input, N channels, dense: the head's block input; the init block's proj_in output (the caller runs
+ *         that conv itself: z is what the VJP keeps)
+ *   x     init: the block's 2-channel input; head: NULL
+ *   out   head: 2 channels, out = RS2 res_conv(z) + RS2 proj_out(y); init: N channels, out = RS2 res_conv(x) + RS2 y, with
+ *         y = RS2 gate H gelu(scale z) + RS2 z
+ *   add   head, optional: out = RS2 (the block) + RS2 add, the decoder's running sum; may be `out` itself
+ *   part, S      babe_gn_partial's sums of z (G = 8 groups, n = N / 8 * F * T, S splits)
+ *   film, film_bs   the FiLM rows [B][J]; the block's own offsets (film_aff[0]) are applied here
+ *   gate  [B][N] contiguous, film_gate[0]'s vector
+ *   plan_splits  the precision of the network the block belongs to, as babe_packed_conv::splits of its (5,3) layers: 0 fp32.  In a
+ *         bf16 / bf16x3 network the (1,1) blocks may hold fp32 images, but such a network keeps one GELU launch per layer
+ *   stats [B][8][3], scale [B][N]: written bit for bit as babe_scale_gelu_fin writes them (the VJP reads them)
+ * _supported is the ONE statement of which blocks take the pass, asked by both UNet sequencers: returns 0 (run the block layer by
+ * layer), 1 (head) or 2 (init).  an fp32 network (plan_splits == 0) and fp32 images, one (1,1) layer, N % 32 == 0, 64 <= N <= 256, T % 4 == 0, 16-byte aligned views,
+ * z dense, no frequency bias, no parameter gradients wanted (train == 0), and the process's switch on.
+ * _enable sets that switch and returns its previous value; it starts from BABE_PW_BLOCK (0: off), read only by the library.
+ * babe_unet_workspace_bytes does not depend on it. */
+typedef struct {
+    int B, F, T, S;
+    int plan_splits;
+    const float* z; long z_bs, z_cs;
+    const float* x; long x_bs, x_cs;
+    float* out; long out_bs, out_cs;
+    const float* add; long add_bs, add_cs;
+    const double* part;
+    const float* film; long film_bs;
+    const float* gate;
+    float *stats, *scale;
+} babe_pw_args;
+int babe_pw_block_enable(int on);
+int babe_pw_block_supported(const babe_unet_block* blk, const babe_pw_args* a, int train);
+int babe_pw_block_fwd(const babe_unet_block* blk, const babe_pw_args* a, void* stream);
+
 /* ---- strided copy / axpby: out = alpha*in + beta*out on [B][C][F][T] views (torch.cat / slicing /
  * (a+b)/sqrt2 residual merges, cqtdiff+.py:769-774,794,814-822) */
 int babe_axpby4d(const float* in, long in_bs, long in_cs, float* out, long out_bs, long out_cs,
