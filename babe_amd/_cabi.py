@@ -362,6 +362,8 @@ SIGS = {
     "babe_attn_buckets": (_I, [_P, _I, _I, _I]),
     "babe_attn_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
     "babe_attn_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "babe_attn_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
+    "babe_attn_vjp_bf16": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "babe_conv_wgrad_workspace": (_L, [C.POINTER(WgradArgs)]),
     "babe_conv_wgrad_rows": (_I, [C.POINTER(WgradArgs), _P, _P, _F, _P, _P, _L, _F, _P, _L, _P]),
     "babe_conv_wgrad_bf16_workspace": (_L, [C.POINTER(WgradArgs)]),

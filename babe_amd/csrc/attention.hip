@@ -21,15 +21,13 @@
 // The scores are formed TRANSPOSED where the probabilities feed the next product as its B operand (forward, dQ: S^T, rows =
 // keys) and untransposed where they feed it as B over queries (dK/dV: S, rows = queries): the accumulator's four rows per lane
 // are then exactly the k-slots of four consecutive MFMA steps, so P never leaves its registers.
-#include "common.h"
+#include "attention_common.h"
 #include "../../include/babe_hip.h"
 #include <cmath>
 
 namespace {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-constexpr int FMAX = 448;          // largest head dimension (7 octaves x 64 bins)
 
 __device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -137,17 +135,6 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ 
             for (int r = 0; r < 4; ++r) o[(long)(t * 16 + 4 * lg + r) * T + n] = acc[t][r] * il;
         if (lg == 0) lse[((long)b * H + h) * T + n] = mrow + logf(l);
     }
-}
-
-// D[b][h][n] = sum_f dO[f][n] O[f][n]; grid (ceil(T/256), H, B), 256 threads
-__global__ __launch_bounds__(256) void attn_rowdot_kernel(const float* __restrict__ dout, const float* __restrict__ out,
-                                                          float* __restrict__ D, int H, int F, int T) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= T) return;
-    const long base = ((long)blockIdx.z * H + blockIdx.y) * F * T + n;
-    float s = 0.f;
-    for (int f = 0; f < F; ++f) s += dout[base + (long)f * T] * out[base + (long)f * T];
-    D[((long)blockIdx.z * H + blockIdx.y) * T + n] = s;
 }
 
 // ---------------------------------------------------------------- VJP, query side: dQ
@@ -313,13 +300,6 @@ __global__ __launch_bounds__(64) void attn_vjp_kv_kernel(const float* __restrict
         default: hipLaunchKernelGGL(KER<7>, __VA_ARGS__); break;                                         \
     }
 
-int check_shape(const char* who, int B, int H, int F, int T, int nbk) {
-    BABE_CHECK_ARG(B > 0 && H > 0 && T > 0, "%s: bad shape B=%d H=%d T=%d", who, B, H, T);
-    BABE_CHECK_ARG(F % 64 == 0 && F >= 64 && F <= FMAX, "%s: F=%d unsupported (need a multiple of 64, at most %d)", who, F, FMAX);
-    BABE_CHECK_ARG(nbk >= 0 && nbk <= 64, "%s: %d buckets unsupported (at most 64)", who, nbk);
-    return BABE_OK;
-}
-
 }  // namespace
 
 extern "C" int babe_attn_buckets(int* out, int T, int num_buckets, int max_distance) {
@@ -349,7 +329,7 @@ extern "C" int babe_attn_fwd(const float* qk, const float* qk_bias, const float*
                              int num_buckets, float* out, float* lse, int B, int H, int F, int T, float scale, void* stream) {
     BABE_CHECK_ARG(qk && a && out && lse, "attn_fwd: null pointer");
     BABE_CHECK_ARG(!bucket == !emb, "attn_fwd: bucket table and embedding go together");
-    if (int e = check_shape("attn_fwd", B, H, F, T, bucket ? num_buckets : 0)) return e;
+    if (int e = attn_check_shape("attn_fwd", B, H, F, T, bucket ? num_buckets : 0)) return e;
     const dim3 grid(cdiv(T, 16), H, B);
     ATTN_DISPATCH(F / 64, attn_fwd_kernel, grid, dim3(64), 0, (hipStream_t)stream, qk, qk_bias, a, bucket, emb,
                   bucket ? num_buckets : 0, out, lse, H, T, scale);
@@ -362,7 +342,7 @@ extern "C" int babe_attn_vjp(const float* qk, const float* qk_bias, const float*
                              float* dv, int B, int H, int F, int T, float scale, void* stream) {
     BABE_CHECK_ARG(qk && a && out && lse && dout && D && dqk && dv, "attn_vjp: null pointer");
     BABE_CHECK_ARG(!bucket == !emb, "attn_vjp: bucket table and embedding go together");
-    if (int e = check_shape("attn_vjp", B, H, F, T, bucket ? num_buckets : 0)) return e;
+    if (int e = attn_check_shape("attn_vjp", B, H, F, T, bucket ? num_buckets : 0)) return e;
     const int nbk = bucket ? num_buckets : 0;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(attn_rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);

@@ -8,8 +8,10 @@ reference's checkpoints load with ``load_state_dict(state['ema'])``; ``net(x[B,L
 sampler code - which calls ``torch.autograd.grad`` through the model - runs on it unchanged.
 There is no CPU path: device must be a GPU and libbabe_hip.so must be present.
 
-Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run in fp32 on the Python sequencer
-(csrc/attention.hip; precision 'bf16' / 'bf16x3' refuse them); their parameter gradients are opt-in
+Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run on the Python sequencer, in fp32
+(csrc/attention.hip) unless ``attention_precision`` opts in: 'f32' keeps the fp32 core inside a network of any precision, 'bf16'
+runs it on bf16 MFMA (csrc/attention_bf16.hip); without the option precision 'bf16' / 'bf16x3' refuse them.  Their parameter
+gradients (fp32 core only) are opt-in
 (``set_trainable(True, attention=True)``, csrc/attention_train.hip).
 
 Frequency encodings (``use_fencoding``, AddFreqEncodingRFF) are never materialised as channels: the 64 encoding channels are
@@ -38,6 +40,16 @@ def attention_options(attention_dict):
 
 
 N_FREQ_ENCODING = 32                     # RFF frequencies per octave (networks/cqtdiff+.py:627): 64 sin / cos encoding channels
+
+
+ATTENTION_PRECISIONS = (None, "f32", "bf16")
+
+
+def check_attention_precision(v):
+    """The attention core's arithmetic: None (fp32; a bf16 / bf16x3 network refuses attention layers), 'f32' or 'bf16'."""
+    if v not in ATTENTION_PRECISIONS:
+        raise ValueError(f"attention_precision must be None, 'f32' or 'bf16', got {v!r}")
+    return v
 
 
 def freq_embedding(rff_freq, f_dim):
@@ -188,21 +200,27 @@ class _UnetFn(torch.autograd.Function):
 
 
 class Unet_CQT_oct_with_attention(nn.Module):
-    def __init__(self, args, device, precision=None):
+    def __init__(self, args, device, precision=None, attention_precision=None):
         super().__init__()
         self.args = args
         nw = args.network
         # conv arithmetic: 'f32' (default, the parity path), 'bf16x3', 'bf16' (csrc/conv_bf16.hip); can also be
         # given as args.network.precision
         self.precision = precision or nw.get("precision", "f32")
+        # the attention core's arithmetic, whatever the network's: None (fp32, and a network of another precision refuses attention
+        # layers), 'f32' (csrc/attention.hip) or 'bf16' (csrc/attention_bf16.hip); also args.network.attention_precision.  Does
+        # nothing on a network without attention layers
+        self.attention_precision = check_attention_precision(
+            attention_precision if attention_precision is not None else nw.get("attention_precision", None))
         self.use_fencoding = bool(nw.get("use_fencoding", False))
         self.attention_layers = [int(bool(v)) for v in (nw.get("attention_layers", None) or [0] * 8)]
         self.attention_dict = nw.get("attention_dict", None) if any(self.attention_layers) else None
         if any(self.attention_layers):
             if len(self.attention_layers) != 8:
                 raise ValueError(f"attention_layers needs one flag per octave plus the bottleneck (8), got {self.attention_layers}")
-            if self.precision != "f32":
-                raise NotImplementedError(f"attention layers run in fp32 only (precision={self.precision!r})")
+            if self.precision != "f32" and self.attention_precision is None:
+                raise NotImplementedError(f"attention layers run in fp32 only (precision={self.precision!r}) unless "
+                                          "attention_precision ('f32' | 'bf16') opts in")
         if not nw.get("use_norm", True):
             raise NotImplementedError("use_norm=False")
         self.Ns, self.num_dils = list(nw.Ns), list(nw.num_dils)
@@ -251,7 +269,8 @@ class Unet_CQT_oct_with_attention(nn.Module):
         if self._engine is None:
             sd = self._engine_sd()
             self._engine = UnetEngine(sd, self.Ns, self.num_dils, self.num_octs, self.bins_per_oct, self.precision,
-                                      attention_layers=self.attention_layers, attention_dict=self.attention_dict)
+                                      attention_layers=self.attention_layers, attention_dict=self.attention_dict,
+                                      attention_precision=self.attention_precision)
             self._engine.wgrad = self._wgrad or "f32"
             self._versions = self._param_versions()
         return self._engine
@@ -280,6 +299,7 @@ class Unet_CQT_oct_with_attention(nn.Module):
         grad.  The opt-in is about memory: a qk weight is a [16 F, 8 F] matrix per attention block (25.7 M floats at F = 448), and
         the attention_layers [0,0,0,0,1,1,1,1] layout carries about 141 M of them - weights, gradients and the two Adam moments
         come to about 2 GB on top of the attention-free network.  On a network without attention layers the flag does nothing.
+        A network whose attention core runs in bf16 (attention_precision='bf16') refuses the opt-in: training stays fp32-only.
         wgrad: arithmetic of the UNet body's conv weight gradients (H.*, res_conv, proj_in / proj_out, the pyramid convs): None,
         'f32' or 'bf16'.  'bf16' is mixed-precision training: both operands rounded once to bf16, fp32 accumulation, fp32 master
         weights and gradients (babe_conv_wgrad_bf16_rows).  The signal columns of a folded frequency-encoding conv, the
@@ -289,6 +309,9 @@ class Unet_CQT_oct_with_attention(nn.Module):
         on the kernel named here, from the fp32 activations the forward saved."""
         if wgrad not in (None, "f32", "bf16"):
             raise ValueError(f"set_trainable: wgrad must be None, 'f32' or 'bf16', got {wgrad!r}")
+        if flag and attention and self.bf16_attention:
+            raise NotImplementedError("set_trainable(True, attention=True): the attention branch's parameter gradients need the "
+                                      "fp32 attention core; this network was built with attention_precision='bf16'")
         self._train_attention = bool(flag) and bool(attention)
         self._wgrad = wgrad if flag else None
         eng = getattr(self, "_engine", None)
@@ -381,14 +404,25 @@ class Unet_CQT_oct_with_attention(nn.Module):
     # BABE_BF16_LANES=1 opts in to two clip lanes (measured +13 %, profiles/r04_bench_bf16_two_lanes.json) for a host that knows
     # what else it launches - and even then a live torch.distributed process group or device-side noise falls back to one
     # stream (BlindSampler asks lanes_ok_for()).  The fp32 network has no bf16 MFMA anywhere and always runs two lanes.
+    # The same holds for a network of any conv precision whose attention core runs on bf16 MFMA (attention_precision='bf16').
+    @property
+    def bf16_attention(self):
+        """True if this network launches the bf16 attention core (csrc/attention_bf16.hip)."""
+        return self.has_attention and self.attention_precision == "bf16"
+
+    @property
+    def runs_bf16_mfma(self):
+        """True if any kernel of this network executes bf16 MFMA with single-split operands: the lane rule's condition."""
+        return self.precision == "bf16" or self.bf16_attention
+
     @property
     def concurrent_lanes_ok(self):
-        return self.precision != "bf16" or os.environ.get("BABE_BF16_LANES", "0") == "1"
+        return not self.runs_bf16_mfma or os.environ.get("BABE_BF16_LANES", "0") == "1"
 
     def lanes_ok_for(self, noise_device="cpu"):
         """concurrent_lanes_ok narrowed by what the CALLER will launch beside the lanes: with precision='bf16' two lanes also
         need host-side noise (torch.randn on the device is an ATen kernel inside the lane loop) and no live process group."""
-        if self.precision != "bf16":
+        if not self.runs_bf16_mfma:
             return True
         if not self.concurrent_lanes_ok:
             return False

@@ -30,11 +30,14 @@ class _Attn:
     """The time-attention branch of a ResnetBlock (reference ResnetBlock.forward with attention_dict, TimeAttentionBlock):
         a1  = proj_in(z * scale2)                        scale2 = norm2.gamma * (affine2(emb) + 1) / (std_g(z) + eps)  (no GELU)
         qk  = Conv1d(a1.view(B, H*F, T))                 a (1,1) conv on the [B, H*F, 1, T] view
-        o   = attention(qk, V = a1)                      csrc/attention.hip
+        o   = attention(qk, V = a1)                      csrc/attention.hip, or csrc/attention_bf16.hip (attention_precision)
         z'  = (gate2(emb) * proj_out(o) + z) / sqrt2
-    z is the block's proj_in output, z' feeds the dilated conv stack.  Weights only, shared by every engine handle."""
+    z is the block's proj_in output, z' feeds the dilated conv stack.  Weights only, shared by every engine handle.
+    The three convs are packed at the network's precision, each under the rule of every other conv (babe_conv_splits_for): the
+    wide qk conv runs on the bf16 kernels under 'bf16'; proj_in and proj_out have 8 channels on one side and stay on the fp32
+    (1,1) kernels at any precision, as does qk under 'bf16x3'."""
 
-    def __init__(self, g, Fdim, N, film_index, opts, prefix=""):
+    def __init__(self, g, Fdim, N, film_index, opts, prefix="", precision="f32"):
         self.H, self.bias_qkv, self.rel_pos, self.nbk, self.maxd = opts
         self.F = Fdim
         self.p = prefix
@@ -42,11 +45,11 @@ class _Attn:
         self.gamma = g("norm2.gamma").reshape(-1).contiguous()
         self.film_off = (film_index.add(g("affine2.weight"), g("affine2.bias"), prefix + "affine2"),
                          film_index.add(g("gate2.weight"), g("gate2.bias"), prefix + "gate2"))
-        self.proj_in = ops.PackedConv(g("attn_block.proj_in.weight"))
-        self.proj_out = ops.PackedConv(g("attn_block.proj_out.weight"))
+        self.proj_in = ops.PackedConv(g("attn_block.proj_in.weight"), precision)
+        self.proj_out = ops.PackedConv(g("attn_block.proj_out.weight"), precision)
         self.proj_out_w = g("attn_block.proj_out.weight").contiguous()             # raw weights (the gate2 gradient)
         w = g("attn_block.qk.weight")
-        self.qk = ops.PackedConv(w.reshape(w.shape[0], w.shape[1], 1, 1))
+        self.qk = ops.PackedConv(w.reshape(w.shape[0], w.shape[1], 1, 1), precision)
         self.qk_bias = g("attn_block.qk.bias").contiguous() if self.bias_qkv else None
         self.emb = g("attn_block.rel_pos.relative_attention_bias.weight").contiguous() if self.rel_pos else None
 
@@ -92,7 +95,7 @@ class _Block:
         for d in range(num_dils):
             self.film_off.append((film_index.add(g(f"affine.{d}.weight"), g(f"affine.{d}.bias"), prefix + f"affine.{d}"),
                                   film_index.add(g(f"gate.{d}.weight"), g(f"gate.{d}.bias"), prefix + f"gate.{d}")))
-        self.attn = _Attn(g, attn[0], self.N, film_index, attn[1], prefix) if attn else None
+        self.attn = _Attn(g, attn[0], self.N, film_index, attn[1], prefix, precision) if attn else None
         self._cblk = None
 
     def c_block(self):
@@ -194,15 +197,22 @@ class ParamGrads:
 
 
 class UnetEngine:
-    def __init__(self, sd, Ns, num_dils, num_octs=7, bins_per_oct=64, precision="f32", attention_layers=None, attention_dict=None):
+    def __init__(self, sd, Ns, num_dils, num_octs=7, bins_per_oct=64, precision="f32", attention_layers=None, attention_dict=None,
+                 attention_precision=None):
         """sd: dict of DEVICE fp32 tensors with the reference's state_dict key names.
         precision: conv arithmetic, 'f32' (exact fp32 MFMA, the parity path), 'bf16x3' or 'bf16'.
-        attention_layers / attention_dict: the reference's time-attention flags (one per octave + the bottleneck); fp32 only."""
-        from .cqtdiff_plus import attention_options
+        attention_layers / attention_dict: the reference's time-attention flags (one per octave + the bottleneck).
+        attention_precision: arithmetic of the attention core.  None: fp32, and a network of another precision refuses attention
+        layers; 'f32' / 'bf16': the core on babe_attn_fwd / _vjp or on babe_attn_fwd_bf16 / _vjp_bf16, in a network of any
+        precision.  Does nothing without attention layers."""
+        from .cqtdiff_plus import attention_options, check_attention_precision
+        check_attention_precision(attention_precision)
         att = [int(bool(v)) for v in (attention_layers or [0] * (num_octs + 1))]
         self.has_attention = any(att)
-        if self.has_attention and precision != "f32":
-            raise NotImplementedError(f"attention layers run in fp32 only (precision={precision!r})")
+        if self.has_attention and precision != "f32" and attention_precision is None:
+            raise NotImplementedError(f"attention layers run in fp32 only (precision={precision!r}) unless attention_precision "
+                                      "('f32' | 'bf16') opts in")
+        self.attn_core = (attention_precision or "f32") if self.has_attention else None      # what attn_fwd / attn_vjp launch
         opts = attention_options(attention_dict)
         A = lambda flag, Fd: (Fd, opts) if flag else None
         self.precision = precision
@@ -417,7 +427,7 @@ class UnetEngine:
         qk = ops.conv2d(a1.view(B, H * Fq, 1, T), at.qk, self.buf(B, 2 * H * Fq, 1, T))
         o = self.buf(B, H, Fq, T)
         lse = self.buf(B, H, T)
-        ops.attn_fwd(qk, a1, o, lse, at.scale, qk_bias=at.qk_bias, bucket=self._bucket(at, T), emb=at.emb)
+        ops.attn_fwd(qk, a1, o, lse, at.scale, qk_bias=at.qk_bias, bucket=self._bucket(at, T), emb=at.emb, precision=self.attn_core)
         gate = self._film(film, at.film_off[1], N).contiguous()
         zn = ops.conv2d(o, at.proj_out, self.buf(B, N, Fq, T), res=z, oscale=gate, alpha=RS2, rbeta=RS2)
         self._state.attn[blk.idx] = (z, stats, scale, gate, a1, qk, o, lse)
@@ -442,7 +452,7 @@ class UnetEngine:
         dqk = self.buf(B, 2 * H * Fq, 1, T) if pg is None else pg.qk[p][0].view(B, 2 * H * Fq, 1, T)
         dv = self.buf(B, H, Fq, T)
         bucket = self._bucket(at, T)
-        ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb)
+        ops.attn_vjp(qk, a1, o, lse, do, dqk, dv, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb, precision=self.attn_core)
         if pg is not None:
             ops.axpby(a1.view(B, H * Fq, 1, T), pg.qk[p][1].view(B, H * Fq, 1, T))
             if at.rel_pos or at.bias_qkv:

@@ -427,9 +427,10 @@ def attn_buckets(T, num_buckets=32, max_distance=64):
     return out
 
 
-def attn_fwd(qk, a, out, lse, scale, qk_bias=None, bucket=None, emb=None):
+def attn_fwd(qk, a, out, lse, scale, qk_bias=None, bucket=None, emb=None, precision="f32"):
     """Time attention forward.  qk [B,2HF,T], a/out [B,H,F,T], lse [B,H,T], all dense; bucket int32 [2T-1] and emb [nb,H]
-    (device) or both None."""
+    (device) or both None.  precision: 'f32' (babe_attn_fwd, exact fp32 MFMA) or 'bf16' (babe_attn_fwd_bf16: operands rounded
+    once to bf16, fp32 accumulation and softmax; csrc/attention_bf16.hip)."""
     B, H, F, T = a.shape
     for t in (qk, a, out, lse):
         assert t.is_contiguous() and t.dtype == torch.float32
@@ -438,21 +439,31 @@ def attn_fwd(qk, a, out, lse, scale, qk_bias=None, bucket=None, emb=None):
     if bucket is not None:
         assert bucket.dtype == torch.int32 and bucket.numel() == 2 * T - 1 and emb.is_contiguous() and emb.shape[1] == H
         nb = emb.shape[0]
-    check(lib().babe_attn_fwd(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), B, H, F, T, scale,
-                              stream()), "attn_fwd")
+    args = (ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), B, H, F, T, scale, stream())
+    if precision == "bf16":
+        check(lib().babe_attn_fwd_bf16(*args), "attn_fwd_bf16")
+    else:
+        assert precision == "f32", precision
+        check(lib().babe_attn_fwd(*args), "attn_fwd")
     return out, lse
 
 
-def attn_vjp(qk, a, out, lse, dout, dqk, dv, scale, qk_bias=None, bucket=None, emb=None):
-    """Input-VJP of attn_fwd for the gradient dout: writes dqk [B,2HF,T] and dv [B,H,F,T] (deterministic, no atomics)."""
+def attn_vjp(qk, a, out, lse, dout, dqk, dv, scale, qk_bias=None, bucket=None, emb=None, precision="f32"):
+    """Input-VJP of attn_fwd for the gradient dout: writes dqk [B,2HF,T] and dv [B,H,F,T] (deterministic, no atomics).
+    precision as for attn_fwd; out and lse are those the forward of the same precision wrote."""
     B, H, F, T = a.shape
     for t in (qk, a, out, lse, dout, dqk, dv):
         assert t.is_contiguous() and t.dtype == torch.float32
     assert dout.shape == a.shape and dv.shape == a.shape and dqk.numel() == qk.numel()
     nb = 0 if bucket is None else emb.shape[0]
     D = torch.empty(B, H, T, device=a.device, dtype=torch.float32)
-    check(lib().babe_attn_vjp(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(D),
-                              ptr(dqk), ptr(dv), B, H, F, T, scale, stream()), "attn_vjp")
+    args = (ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(D), ptr(dqk), ptr(dv), B, H,
+            F, T, scale, stream())
+    if precision == "bf16":
+        check(lib().babe_attn_vjp_bf16(*args), "attn_vjp_bf16")
+    else:
+        assert precision == "f32", precision
+        check(lib().babe_attn_vjp(*args), "attn_vjp")
     return dqk, dv
 
 

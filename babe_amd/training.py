@@ -148,7 +148,8 @@ class Trainer:
         self.dataset = getattr(dset, "dataset", None)
         self.dset = iter(dset)
         self.total_params = sum(p.numel() for p in network.parameters() if p.requires_grad)
-        self.ema = type(network)(network.args, device, precision=network.precision)
+        self.ema = type(network)(network.args, device, precision=network.precision,
+                                 attention_precision=getattr(network, "attention_precision", None))
         self.ema.load_state_dict(network.state_dict())
         self.ema.eval().requires_grad_(False)
         # an optimizer with the fused tail (optim.FusedAdamEMA) averages the EMA in its step(): rank 0 attaches the pairs

@@ -864,6 +864,16 @@ int babe_attn_fwd(const float* qk, const float* qk_bias, const float* a, const i
 int babe_attn_vjp(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
                   const float* out, const float* lse, const float* dout, float* D, float* dqk, float* dv, int B, int H, int F,
                   int T, float scale, void* stream);
+/* The same two passes on the bf16 MFMA pipe (csrc/attention_bf16.hip): same tensors (fp32 in HBM), same contract and refusals.
+ * Q + bias, K + bias, V and dO are rounded once to bf16 (to nearest even) on their way into LDS, P and dS in registers as the
+ * operand of the second product; accumulators, the relative bias, the online maximum and sum, lse and D stay fp32.  Four waves
+ * per 32-row tile, the other side staged through LDS; every output element is written once (deterministic).  All pointers
+ * 4-byte aligned.  babe_attn_vjp_bf16 takes the lse babe_attn_fwd_bf16 wrote. */
+int babe_attn_fwd_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
+                       float* out, float* lse, int B, int H, int F, int T, float scale, void* stream);
+int babe_attn_vjp_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
+                       const float* out, const float* lse, const float* dout, float* D, float* dqk, float* dv, int B, int H, int F,
+                       int T, float scale, void* stream);
 
 
 /* ---- training: parameter gradients of the CQTDiff+ UNet (csrc/wgrad.hip), fp32 (the conv weight gradient also with bf16
