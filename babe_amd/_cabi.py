@@ -378,6 +378,10 @@ SIGS = {
     "babe_attn_qk_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
     "babe_attn_param_vjp_workspace": (_L, [_I, _I, _I, _I]),
     "babe_attn_param_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
+    "babe_attn_qk_wgrad_bf16_workspace": (_L, [_I, _I, _I]),
+    "babe_attn_qk_wgrad_bf16": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _F, _P]),
+    "babe_attn_param_vjp_bf16_workspace": (_L, [_I, _I, _I, _I]),
+    "babe_attn_param_vjp_bf16": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _P, _L, _I, _I, _I, _I, _F, _P]),
     "babe_gn_param_grad_nogelu": (_I, [_P, _P, _P, _P, _P, _L, _F, _P, _L, _P, _L, _I, _I, _I, _L, _P]),
     "babe_scale_channels": (_I, [_P, _P, _P, _I, _I, _L, _P]),
     "babe_model_load": (_P, [_S, _P]),

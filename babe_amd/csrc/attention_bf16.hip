@@ -1,4 +1,6 @@
-// Time attention of the CQTDiff+ ResnetBlock on the bf16 MFMA pipe: babe_attn_fwd_bf16 / babe_attn_vjp_bf16.  Layouts, mathematics
+// Time attention of the CQTDiff+ ResnetBlock on the bf16 MFMA pipe: babe_attn_fwd_bf16 / babe_attn_vjp_bf16, and for training on
+// this core babe_attn_param_vjp_bf16 (the relative-position table gradient as a fourth mode of the VJP kernel, so that it belongs
+// to exactly the P of the dQ pass; the qk bias gradient is the shared row sum of dqk).  Layouts, mathematics
 // and contract are those of attention.hip's header (Q and K rows straight from the qk Conv1d output, bias before scale,
 // lse [B][H][T], the VJP writes the gradients w.r.t. the qk rows and w.r.t. V; F a multiple of 64 up to 448, any T >= 1).
 //
@@ -125,6 +127,13 @@ __device__ __forceinline__ Head head_of(const float* qk, const float* qkb, const
     return p;
 }
 
+// table pass (MODE 3 of the VJP kernel): floats of a wave's parked dS tile, and of its array of diagonals.  A key tile at sb
+// (a multiple of 16 below T) touches the entries sb .. sb + 30
+constexpr int TILE_F = 16 * 17;
+__host__ __device__ constexpr int tbl_diag_len(int T) { return ((T + 31) & ~31) + 32; }
+inline long tbl_lds_bytes(int F, int T) { return 4L * TS * (F + 8) * 2 + 64 * 4 + 4L * TILE_F * 4 + 4L * tbl_diag_len(T) * 4; }
+constexpr int LDS_MAX = 160 * 1024;
+
 // LDS bytes: transposed images, natural images, the bias table, the forward's (max, sum) slots
 constexpr int lds_bytes(int F, int nt, int nn) { return nt * TS * (F + 8) * 2 + nn * F * NPAD * 2 + 64 * 4 + 4 * 16 * 2 * 4; }
 
@@ -223,7 +232,12 @@ __global__ __launch_bounds__(NTH) void attn_fwd_bf16_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- input-VJP.  grid (ceil(T/32), H, B), 256 threads
-// MODE 0: dQ (own = queries; streamed K, V);  1: dK (own = keys; streamed Q, dO);  2: dV (own = keys; streamed Q, dO).
+// MODE 0: dQ (own = queries; streamed K, V);  1: dK (own = keys; streamed Q, dO);  2: dV (own = keys; streamed Q, dO);
+// 3: the relative-position table gradient (babe_attn_param_vjp_bf16): the dQ pass up to its fp32 dS - the same images, the same
+// score_tile calls, the same exponential - without the second product and its sn image.  Every wave parks its 16 x 16 dS tile in
+// LDS, one lane per diagonal of the tile adds its sum (ascending query) into the wave's LDS array of diagonals, key chunks in
+// ascending order; at the end lane k of the st = 0 wave adds the diagonals of bucket k in ascending offset, each as (st = 0) +
+// (st = 1), and writes the 16-query tile's partial to tpart [B][H][ceil(T/16)][nbk]; demb_sum_kernel adds the query tiles in order.
 // own1/own2 and s1/s2 are the transposed images of the two score products (S: s1 x own1, dP: s2 x own2; dV has no dP), sn the
 // natural image of the last product's A operand: acc^T[f][own] += sum_streamed sn[f][streamed] * val[streamed][own], with
 // val = dS (dQ, dK) or P (dV).
@@ -232,10 +246,11 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
                                                             const float* __restrict__ a, const int* __restrict__ bucket,
                                                             const float* __restrict__ emb, int nbk, const float* __restrict__ dout,
                                                             const float* __restrict__ lse, const float* __restrict__ D,
-                                                            float* __restrict__ dqk, float* __restrict__ dv, int H, int T,
-                                                            float scale) {
+                                                            float* __restrict__ dqk, float* __restrict__ dv,
+                                                            float* __restrict__ tpart, int H, int T, float scale) {
     constexpr int F = FB * 64, NFT = F / 16, FP = F + 8;
     constexpr bool DP = MODE != 2;                                     // the pass needs dP = dO . V
+    constexpr bool TBL = MODE == 3, QOWN = MODE == 0 || MODE == 3;     // table gradient; the own side is the queries
     constexpr int IMG = TS * FP;
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned short* own1 = reinterpret_cast<unsigned short*>(smem);
@@ -243,16 +258,21 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
     unsigned short* s1 = own1 + (DP ? 2 : 1) * IMG;
     unsigned short* s2 = s1 + IMG;
     unsigned short* sn = s1 + (DP ? 2 : 1) * IMG;                      // [F][NPAD]
-    float* emb_lds = reinterpret_cast<float*>(sn + F * NPAD);          // [64]
+    float* emb_lds = reinterpret_cast<float*>(sn + (TBL ? 0 : F * NPAD));      // [64]  (the table pass has no sn)
     float* part = reinterpret_cast<float*>(s1);                        // after the loop: [2][F][PPAD]
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, lr = lane & 15, lg = lane >> 4, rt = w >> 1, st = w & 1;
+    const int DL = tbl_diag_len(T);
+    float* tile = emb_lds + 64 + w * TILE_F;                           // table pass: this wave's dS[m - sb][n - nb], [16][17]
+    float* diag = emb_lds + 64 + 4 * TILE_F + w * DL;                  // table pass: entry j = the diagonal m - n = j - 15 - nb
     const int o0 = blockIdx.x * TS, h = blockIdx.y;
     const Head p = head_of(qk, qkb, a, H, F, T);
     const float* dO = dout + p.hb * F * T;
     const float* lseh = lse + p.hb * T;
     const float* Dh = D + p.hb * T;
     if (bucket && tid < nbk) emb_lds[tid] = emb[tid * H + h];
-    if (MODE == 0) {
+    if (TBL)
+        for (int i = tid; i < 4 * DL; i += NTH) emb_lds[64 + 4 * TILE_F + i] = 0.f;
+    if (QOWN) {
         stage_t<F>(own1, p.Q, p.qb, T, o0);
         stage_t<F>(own2, dO, nullptr, T, o0);
     } else {
@@ -261,16 +281,16 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
     }
     const int oc = o0 + 16 * rt + lr;                                  // this lane's own column: a query (dQ) or a key
     const bool oact = o0 + 16 * rt < T, oin = oc < T;
-    const float Lq = (MODE == 0 && oin) ? lseh[oc] : 0.f, Dq = (MODE == 0 && oin) ? Dh[oc] : 0.f;
+    const float Lq = (QOWN && oin) ? lseh[oc] : 0.f, Dq = (QOWN && oin) ? Dh[oc] : 0.f;
     floatx4 acc[NFT];
 #pragma unroll
     for (int t = 0; t < NFT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < T; c0 += TS) {
         __syncthreads();
-        if (MODE == 0) {
+        if (QOWN) {
             stage_t<F>(s1, p.K, p.kb, T, c0);
             stage_t<F>(s2, p.V, nullptr, T, c0);
-            stage_n<F>(sn, p.K, p.kb, T, c0);
+            if (!TBL) stage_n<F>(sn, p.K, p.kb, T, c0);
         } else {
             stage_t<F>(s1, p.Q, p.qb, T, c0);
             if (DP) {
@@ -291,15 +311,29 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int sr = sb + 4 * lg + r;                            // streamed row: a key (dQ) or a query
-            const int m = MODE == 0 ? sr : oc, n = MODE == 0 ? oc : sr;
+            const int m = QOWN ? sr : oc, n = QOWN ? oc : sr;
             const bool ok = sr < T && oin;
             float pv = 0.f, Dn = Dq;
             if (ok) {
                 const float rb = bucket ? emb_lds[bucket[m - n + T - 1]] : 0.f;
-                pv = expf((s[r] + rb) * scale - (MODE == 0 ? Lq : lseh[n]));
+                pv = expf((s[r] + rb) * scale - (QOWN ? Lq : lseh[n]));
                 if (MODE == 1) Dn = Dh[n];
             }
             val[r] = DP ? pv * (dp[r] - Dn) : pv;
+        }
+        if (TBL) {                                        // the fp32 dS, before it would be rounded for the second product
+#pragma unroll
+            for (int r = 0; r < 4; ++r) tile[(4 * lg + r) * 17 + lr] = val[r];
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the tile is this wave's own: no workgroup barrier
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            if (lane < 31) {                              // diagonal (m - sb) - (n - nb) = lane - 15, queries ascending
+                const int lo = lane < 15 ? 15 - lane : 0, hi = lane > 15 ? 30 - lane : 15;
+                float sum = 0.f;
+                for (int q = lo; q <= hi; ++q) sum += tile[(q + lane - 15) * 17 + q];
+                diag[sb + lane] += sum;
+            }
+            continue;                                     // (the next chunk's barrier comes before the tile is written again)
         }
         const s16x4 vb = pack4(val);
         const unsigned short* na = sn + lr * NPAD + 16 * st + 4 * lg;
@@ -308,6 +342,19 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
     }
     // merge the two streamed halves of every own tile, st = 0 then st = 1
     __syncthreads();
+    if (TBL) {
+        const int nqt = (T + 15) >> 4, qt = 2 * blockIdx.x + rt, nb = o0 + 16 * rt;
+        if (st == 0 && lane < nbk && qt < nqt) {
+            const float* d1 = diag + DL;                  // the st = 1 wave of this query tile
+            float accb = 0.f;
+            for (int j = 0; j < DL; ++j) {
+                const int idx = j - 15 - nb + T - 1;
+                if (idx >= 0 && idx <= 2 * T - 2 && bucket[idx] == lane) accb += diag[j] + d1[j];
+            }
+            tpart[((long)p.hb * nqt + qt) * nbk + lane] = accb * scale;
+        }
+        return;
+    }
     float* pt = part + (long)rt * F * PPAD + lr;
     if (st == 1) {
 #pragma unroll
@@ -348,7 +395,19 @@ int launch_vjp(dim3 grid, hipStream_t s, const float* qk, const float* qkb, cons
     if (babe_lds_optin(done, {reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, MODE>)}, lds) != hipSuccess)
         return BABE_ERR_HIP;
     hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, MODE>), grid, dim3(NTH), lds, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk,
-                       dv, H, T, scale);
+                       dv, nullptr, H, T, scale);
+    return BABE_OK;
+}
+
+// the table pass: its LDS grows with T (tbl_lds_bytes, checked by the caller), so the opt-in is for the whole CU
+template <int FB>
+int launch_tbl(dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket, const float* emb,
+               int nbk, const float* dout, const float* lse, const float* D, float* tpart, int H, int T, float scale) {
+    static std::atomic<unsigned long long> done{0};
+    if (babe_lds_optin(done, {reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, 3>)}, LDS_MAX) != hipSuccess)
+        return BABE_ERR_HIP;
+    hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, 3>), grid, dim3(NTH), tbl_lds_bytes(FB * 64, T), s, qk, qkb, a, bucket, emb, nbk,
+                       dout, lse, D, nullptr, nullptr, tpart, H, T, scale);
     return BABE_OK;
 }
 
@@ -366,6 +425,7 @@ int launch_vjp(dim3 grid, hipStream_t s, const float* qk, const float* qkb, cons
 #define VJP_Q_FN(FB) launch_vjp<FB, 0>
 #define VJP_K_FN(FB) launch_vjp<FB, 1>
 #define VJP_V_FN(FB) launch_vjp<FB, 2>
+#define TBL_FN(FB) launch_tbl<FB>
 
 bool aligned4(std::initializer_list<const void*> ps) {
     for (const void* q : ps)
@@ -418,5 +478,48 @@ extern "C" int babe_attn_vjp_bf16(const float* qk, const float* qk_bias, const f
     ATTN_BF16_DISPATCH(F / 64, rc, VJP_V_FN, grid, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale);
     if (rc != BABE_OK) return optin_failed("attn_vjp_bf16");
     BABE_LAUNCH_CHECK();
+    return BABE_OK;
+}
+
+extern "C" long babe_attn_param_vjp_bf16_workspace(int B, int H, int T, int num_buckets) {
+    if (B <= 0 || H <= 0 || T <= 0 || num_buckets < 0 || num_buckets > 64) return -1;
+    return (long)B * H * T + (long)B * H * cdiv(T, 16) * num_buckets;
+}
+
+extern "C" int babe_attn_param_vjp_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
+                                        int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk,
+                                        float* ws, float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H,
+                                        int F, int T, float scale, void* stream) {
+    BABE_CHECK_ARG(!bucket == !emb && !bucket == !demb_rows,
+                   "attn_param_vjp_bf16: bucket table, embedding and demb_rows go together");
+    const int nbk = bucket ? num_buckets : 0;
+    if (int e = attn_check_shape("attn_param_vjp_bf16", B, H, F, T, nbk)) return e;
+    BABE_CHECK_ARG(demb_rows || dqkb_rows, "attn_param_vjp_bf16: nothing to compute");
+    BABE_CHECK_ARG(!dqkb_rows || (dqk && dqkb_bs >= 2L * H * F), "attn_param_vjp_bf16: dqkb_rows needs dqk and dqkb_bs >= 2HF");
+    BABE_CHECK_ARG(aligned4({qk, qk_bias, a, bucket, emb, out, lse, dout, dqk, ws, demb_rows, dqkb_rows}),
+                   "attn_param_vjp_bf16: a pointer is not 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (demb_rows) {
+        BABE_CHECK_ARG(qk && a && out && lse && dout && ws, "attn_param_vjp_bf16: null pointer");
+        BABE_CHECK_ARG(nbk > 0 && demb_bs >= (long)nbk * H, "attn_param_vjp_bf16: demb_bs %ld < num_buckets*H", demb_bs);
+        BABE_CHECK_ARG(tbl_lds_bytes(F, T) <= LDS_MAX, "attn_param_vjp_bf16: F=%d with T=%d needs %ld bytes of LDS (limit %d)", F, T,
+                       tbl_lds_bytes(F, T), LDS_MAX);
+        float* D = ws;                                    // the D of babe_attn_vjp_bf16: same kernel, same operands
+        float* tpart = ws + (long)B * H * T;
+        hipLaunchKernelGGL(attn_rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
+        BABE_LAUNCH_CHECK();
+        int rc;
+        ATTN_BF16_DISPATCH(F / 64, rc, TBL_FN, dim3(cdiv(T, TS), H, B), s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, tpart, H, T,
+                           scale);
+        if (rc != BABE_OK) return optin_failed("attn_param_vjp_bf16");
+        BABE_LAUNCH_CHECK();
+        hipLaunchKernelGGL(attn_demb_sum_kernel, dim3(B), dim3(256), 0, s, tpart, cdiv(T, 16), nbk, H, demb_rows, demb_bs);
+        BABE_LAUNCH_CHECK();
+    }
+    if (dqkb_rows) {
+        const int R = 2 * H * F;
+        hipLaunchKernelGGL(attn_rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
+        BABE_LAUNCH_CHECK();
+    }
     return BABE_OK;
 }

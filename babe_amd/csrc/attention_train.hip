@@ -12,6 +12,8 @@
 //    MFMAs.  Time steps are loaded one float at a time, so any T works (rows need no alignment); past T they are zero.
 //    The small levels (F = 64: 1024 x 512 = 32 tiles) split K into chunks of whole stages, each chunk's partial tile in the
 //    workspace and a second pass adding the chunks in order; the chunk count depends on (HF, T, B) only.
+//    babe_attn_qk_wgrad_bf16 is the same GEMM with both operands rounded once to bf16 on their way into LDS, on
+//    v_mfma_f32_32x32x16_bf16 (mixed-precision training on the bf16 attention core); plan, workspace and reduce pass are shared.
 //    Operand layout of v_mfma_f32_32x32x2_f32 (lane l): A[i][k] = A[l%32][l/32], B[k][j] = B[l/32][l%32],
 //    D[i][j]: lane l holds D[(r%4) + 8*(r/4) + 4*(l/32)][l%32], r = 0..15.
 //
@@ -24,7 +26,7 @@
 //
 // 3. norm2 / affine2: the plain per-channel scale pass that rebuilds proj_in's input (their parameter gradient,
 //    babe_gn_param_grad_nogelu, sits beside its GELU twin in wgrad.hip).
-#include "common.h"
+#include "attention_common.h"
 #include "../../include/babe_hip.h"
 #include <cmath>
 
@@ -148,6 +150,95 @@ __global__ __launch_bounds__(256) void qk_wgrad_reduce_kernel(const float* __res
     out[i] = beta == 0.f ? alpha * v : alpha * v + beta * out[i];
 }
 
+// ---- bf16 operands (babe_attn_qk_wgrad_bf16): the same GEMM, tile, stage, chunk plan (qk_plan), workspace layout and reduce pass
+// on v_mfma_f32_32x32x16_bf16.  dqk and a1 are read as fp32 (two adjacent time steps per load pair, any T, zero past T), rounded
+// once to bf16 (to nearest even) and kept in LDS as bf16 pairs, row stride QB = 40 elements (80 bytes: rows stay 16-byte aligned
+// and the 16 rows of a ds_read_b128 lane group start 20 banks apart, on 16 distinct 4-bank slots of the 64).  Positions are the
+// MFMA's k index: lane l's fragment is the 8 consecutive time steps 16 ks + 8 (l / 32) + j of row l % 32, one 16-byte LDS read,
+// two k steps per stage in ascending t.  Accumulators and output map are those of the fp32 kernel.
+typedef __bf16 qk_bf16x8 __attribute__((ext_vector_type(8)));
+constexpr int QB = QK + 8;
+
+__device__ __forceinline__ unsigned qk_pack(float lo, float hi) {      // two fp32 -> bf16 pair, round to nearest even
+    return (unsigned)__builtin_bit_cast(unsigned short, (__bf16)lo) | ((unsigned)__builtin_bit_cast(unsigned short, (__bf16)hi) << 16);
+}
+
+__global__ __launch_bounds__(256) void qk_wgrad_bf16_kernel(const float* __restrict__ dqk, const float* __restrict__ a1,
+                                                            float* __restrict__ out, int M, int N, int T, int B, int nst, int per,
+                                                            float alpha, float beta, int direct) {
+    __shared__ __align__(16) unsigned short Gs[QT * QB];
+    __shared__ __align__(16) unsigned short Xs[QT * QB];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, l31 = lane & 31, h = lane >> 5;
+    const int wm = wave & 1, wn = wave >> 1;
+    const int tiles_n = N / QT;
+    const int co0 = (blockIdx.x / tiles_n) * QT, ci0 = (blockIdx.x % tiles_n) * QT;
+    const long total = (long)B * nst;
+    const long s0 = (long)blockIdx.y * per;
+    const long s1 = s0 + per < total ? s0 + per : total;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    // loader: thread (lp, lr0) fetches the time steps 2 lp, 2 lp + 1 of the rows lr0 + 16 i of both operands
+    const int lp = tid & 15, lr0 = tid >> 4;
+    float gr[8][2], xr[8][2];
+    auto load = [&](long s) {
+        const int b = (int)(s / nst);
+        const int t = (int)(s % nst) * QK + 2 * lp;
+        const bool in0 = t < T, in1 = t + 1 < T;
+        const float* gp = dqk + ((long)b * M + co0 + lr0) * T + t;
+        const float* xp = a1 + ((long)b * N + ci0 + lr0) * T + t;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            gr[i][0] = in0 ? gp[(long)16 * i * T] : 0.f;
+            gr[i][1] = in1 ? gp[(long)16 * i * T + 1] : 0.f;
+            xr[i][0] = in0 ? xp[(long)16 * i * T] : 0.f;
+            xr[i][1] = in1 ? xp[(long)16 * i * T + 1] : 0.f;
+        }
+    };
+    if (s0 < s1) load(s0);
+    for (long s = s0; s < s1; ++s) {
+        __syncthreads();                   // the previous stage's reads are done
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            *reinterpret_cast<unsigned*>(Gs + (lr0 + 16 * i) * QB + 2 * lp) = qk_pack(gr[i][0], gr[i][1]);
+            *reinterpret_cast<unsigned*>(Xs + (lr0 + 16 * i) * QB + 2 * lp) = qk_pack(xr[i][0], xr[i][1]);
+        }
+        __syncthreads();
+        if (s + 1 < s1) load(s + 1);
+#pragma unroll
+        for (int ks = 0; ks < QK / 16; ++ks) {
+            const int k = 16 * ks + 8 * h;
+            const qk_bf16x8 a0 = *reinterpret_cast<const qk_bf16x8*>(Gs + (wm * 64 + l31) * QB + k);
+            const qk_bf16x8 a1v = *reinterpret_cast<const qk_bf16x8*>(Gs + (wm * 64 + 32 + l31) * QB + k);
+            const qk_bf16x8 b0 = *reinterpret_cast<const qk_bf16x8*>(Xs + (wn * 64 + l31) * QB + k);
+            const qk_bf16x8 b1 = *reinterpret_cast<const qk_bf16x8*>(Xs + (wn * 64 + 32 + l31) * QB + k);
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1v, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1v, b1, acc[1][1], 0, 0, 0);
+        }
+    }
+    float* dst = direct ? out : out + (long)blockIdx.y * M * N;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int co = co0 + wm * 64 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int ci = ci0 + wn * 64 + j * 32 + l31;
+                const long o = (long)co * N + ci;
+                const float v = acc[i][j][r];
+                if (direct)
+                    dst[o] = beta == 0.f ? alpha * v : alpha * v + beta * dst[o];
+                else
+                    dst[o] = v;
+            }
+}
+
 // ---------------------------------------------------------------- table / bias gradients
 constexpr int FMAX = 448;
 constexpr int LDS_LIMIT = 65536;
@@ -245,31 +336,6 @@ __global__ __launch_bounds__(64) void attn_demb_kernel(const float* __restrict__
     }
 }
 
-// demb_rows[b][k][h] = sum over query tiles, ascending; grid (B), 256 threads
-__global__ __launch_bounds__(256) void demb_sum_kernel(const float* __restrict__ part, int nqt, int nbk, int H,
-                                                       float* __restrict__ rows, long rows_bs) {
-    const int b = blockIdx.x;
-    for (int i = threadIdx.x; i < nbk * H; i += 256) {
-        const int k = i / H, h = i % H;
-        const float* p = part + ((long)b * H + h) * nqt * nbk + k;
-        float v = 0.f;
-        for (int q = 0; q < nqt; ++q) v += p[(long)q * nbk];
-        rows[(long)b * rows_bs + i] = v;
-    }
-}
-
-// rows[b][r] = sum_t x[b][r][t]; one wave per row; grid (ceil(R/4), B), 256 threads
-__global__ __launch_bounds__(256) void rowsum_t_kernel(const float* __restrict__ x, int R, int T, float* __restrict__ rows,
-                                                       long rows_bs) {
-    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63, b = blockIdx.y;
-    if (r >= R) return;
-    const float* p = x + ((long)b * R + r) * T;
-    double s = 0;
-    for (int t = lane; t < T; t += 64) s += (double)p[t];
-    s = wave_sum(s);
-    if (lane == 0) rows[(long)b * rows_bs + r] = (float)s;
-}
-
 #define DEMB_DISPATCH(FB, ...)                                                                           \
     switch (FB) {                                                                                        \
         case 1: hipLaunchKernelGGL(attn_demb_kernel<1>, __VA_ARGS__); break;                             \
@@ -331,6 +397,29 @@ extern "C" int babe_attn_qk_wgrad(const float* dqk, const float* a1, float* dW, 
     return BABE_OK;
 }
 
+extern "C" long babe_attn_qk_wgrad_bf16_workspace(int B, int HF, int T) { return babe_attn_qk_wgrad_workspace(B, HF, T); }
+
+extern "C" int babe_attn_qk_wgrad_bf16(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha,
+                                       float beta, void* stream) {
+    BABE_CHECK_ARG(dqk && a1 && dW, "attn_qk_wgrad_bf16: null pointer");
+    BABE_CHECK_ARG(qk_shape_ok(B, HF, T), "attn_qk_wgrad_bf16: unsupported shape B=%d HF=%d T=%d (HF a multiple of %d, at most %d)", B,
+                   HF, T, HF_STEP, HF_MAX);
+    const QkPlan p = qk_plan(B, HF, T);
+    BABE_CHECK_ARG(p.nsplit == 1 || ws, "attn_qk_wgrad_bf16: this shape needs a workspace (babe_attn_qk_wgrad_bf16_workspace)");
+    hipStream_t s = (hipStream_t)stream;
+    const int M = 2 * HF, N = HF;
+    const int direct = p.nsplit == 1;
+    hipLaunchKernelGGL(qk_wgrad_bf16_kernel, dim3(p.tiles, p.nsplit), dim3(256), 0, s, dqk, a1, direct ? dW : ws, M, N, T, B, p.nst,
+                       p.per, alpha, beta, direct);
+    BABE_LAUNCH_CHECK();
+    if (!direct) {
+        const long n = (long)M * N;
+        hipLaunchKernelGGL(qk_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, p.nsplit, n, dW, alpha, beta);
+        BABE_LAUNCH_CHECK();
+    }
+    return BABE_OK;
+}
+
 extern "C" long babe_attn_param_vjp_workspace(int B, int H, int T, int num_buckets) {
     if (B <= 0 || H <= 0 || T <= 0 || num_buckets < 0 || num_buckets > 64) return -1;
     return (long)B * H * T + (long)B * H * cdiv(T, 16) * num_buckets;
@@ -359,12 +448,12 @@ extern "C" int babe_attn_param_vjp(const float* qk, const float* qk_bias, const 
         DEMB_DISPATCH(F / 64, dim3(nqt, H, B), dim3(64), diag_len(T) * sizeof(float), s, qk, qk_bias, a, bucket, emb, nbk, dout,
                       lse, D, part, H, T, scale);
         BABE_LAUNCH_CHECK();
-        hipLaunchKernelGGL(demb_sum_kernel, dim3(B), dim3(256), 0, s, part, nqt, nbk, H, demb_rows, demb_bs);
+        hipLaunchKernelGGL(attn_demb_sum_kernel, dim3(B), dim3(256), 0, s, part, nqt, nbk, H, demb_rows, demb_bs);
         BABE_LAUNCH_CHECK();
     }
     if (dqkb_rows) {
         const int R = 2 * H * F;
-        hipLaunchKernelGGL(rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
+        hipLaunchKernelGGL(attn_rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
         BABE_LAUNCH_CHECK();
     }
     return BABE_OK;

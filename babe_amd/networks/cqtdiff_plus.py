@@ -11,8 +11,9 @@ There is no CPU path: device must be a GPU and libbabe_hip.so must be present.
 Time-attention layers (``attention_layers`` / ``attention_dict``, TimeAttentionBlock) run on the Python sequencer, in fp32
 (csrc/attention.hip) unless ``attention_precision`` opts in: 'f32' keeps the fp32 core inside a network of any precision, 'bf16'
 runs it on bf16 MFMA (csrc/attention_bf16.hip); without the option precision 'bf16' / 'bf16x3' refuse them.  Their parameter
-gradients (fp32 core only) are opt-in
-(``set_trainable(True, attention=True)``, csrc/attention_train.hip).
+gradients are opt-in: on the fp32 core ``set_trainable(True, attention=True)`` (csrc/attention_train.hip); a network on the bf16 core trains under the explicit
+``set_trainable(True, attention='bf16')``: table gradient from the bf16 core's own P (babe_attn_param_vjp_bf16), qk weight gradient
+on fp32 MFMA or, with ``wgrad='bf16'``, on bf16 MFMA (babe_attn_qk_wgrad_bf16), at bf16 bars instead of the reference's 2e-4.
 
 Frequency encodings (``use_fencoding``, AddFreqEncodingRFF) are never materialised as channels: the 64 encoding channels are
 constant over batch and time and feed only the init blocks' two (1,1) convs, so their share is folded into a bias table per conv
@@ -299,19 +300,31 @@ class Unet_CQT_oct_with_attention(nn.Module):
         grad.  The opt-in is about memory: a qk weight is a [16 F, 8 F] matrix per attention block (25.7 M floats at F = 448), and
         the attention_layers [0,0,0,0,1,1,1,1] layout carries about 141 M of them - weights, gradients and the two Adam moments
         come to about 2 GB on top of the attention-free network.  On a network without attention layers the flag does nothing.
-        A network whose attention core runs in bf16 (attention_precision='bf16') refuses the opt-in: training stays fp32-only.
+        A network whose attention core runs in bf16 (attention_precision='bf16') refuses attention=True, which promises gradients
+        that hold the reference's 2e-4 bar.  attention='bf16' is the opt-in for such a network (and raises on an fp32 core): the
+        forward and input-VJP of the training step are the sampler's, bit for bit; the relative-position table gradient comes
+        from the same bf16 P (babe_attn_param_vjp_bf16), the qk-bias gradient from the bf16 core's dqk, the qk weight gradient
+        from babe_attn_qk_wgrad, or from babe_attn_qk_wgrad_bf16 under wgrad='bf16'; norm2 / affine2 / gate2 and proj_in /
+        proj_out stay fp32.  The gradients then carry the bf16 bars (tests/attention_bf16_train_cases.py), not 2e-4.
         wgrad: arithmetic of the UNet body's conv weight gradients (H.*, res_conv, proj_in / proj_out, the pyramid convs): None,
         'f32' or 'bf16'.  'bf16' is mixed-precision training: both operands rounded once to bf16, fp32 accumulation, fp32 master
         weights and gradients (babe_conv_wgrad_bf16_rows).  The signal columns of a folded frequency-encoding conv, the
-        encoding columns, the attention branch and the GroupNorm / FiLM / Linear reductions stay in fp32.  None means 'f32' on a
+        encoding columns, the attention branch (but for the qk weight gradient of a bf16 core under attention='bf16') and the
+        GroupNorm / FiLM / Linear reductions stay in fp32.  None means 'f32' on a
         precision='f32' network (bit for bit what it always was); a precision='bf16' / 'bf16x3' network keeps refusing parameter
         gradients unless wgrad is given: then its forward and input-VJP run on its own conv kernels and the weight gradients
         on the kernel named here, from the fp32 activations the forward saved."""
         if wgrad not in (None, "f32", "bf16"):
             raise ValueError(f"set_trainable: wgrad must be None, 'f32' or 'bf16', got {wgrad!r}")
-        if flag and attention and self.bf16_attention:
+        if not isinstance(attention, bool) and not (isinstance(attention, str) and attention == "bf16"):
+            raise ValueError(f"set_trainable: attention must be False, True or 'bf16', got {attention!r}")
+        if flag and attention is True and self.bf16_attention:
             raise NotImplementedError("set_trainable(True, attention=True): the attention branch's parameter gradients need the "
-                                      "fp32 attention core; this network was built with attention_precision='bf16'")
+                                      "fp32 attention core; this network was built with attention_precision='bf16' "
+                                      "(opt in with attention='bf16')")
+        if flag and attention == "bf16" and self.has_attention and not self.bf16_attention:
+            raise NotImplementedError("set_trainable(True, attention='bf16') is for a network whose attention core runs in bf16 "
+                                      "(attention_precision='bf16'); on the fp32 core use attention=True")
         self._train_attention = bool(flag) and bool(attention)
         self._wgrad = wgrad if flag else None
         eng = getattr(self, "_engine", None)

@@ -436,7 +436,8 @@ class UnetEngine:
     def attn_vjp(self, blk, gz, c, pg=None):
         """gz <- gradient w.r.t. the attention branch's input z, given c*gz = gradient w.r.t. its output z' (in place).
         pg: ParamGrads of a training step: also the branch's parameter gradients (per row into pg.rows / pg.dfilm; the qk weight
-        gradient's operands into pg.qk, for param_grads)."""
+        gradient's operands into pg.qk, for param_grads).  On a bf16 core the table gradient comes from babe_attn_param_vjp_bf16
+        and the qk-bias gradient from the row sum of the bf16 core's dqk; everything else of the branch stays fp32."""
         at = blk.attn
         st = self._state
         z, stats, scale, gate, a1, qk, o, lse = st.attn[blk.idx]
@@ -458,7 +459,7 @@ class UnetEngine:
             if at.rel_pos or at.bias_qkv:
                 ops.attn_param_vjp(qk, a1, o, lse, do, dqk, at.scale, qk_bias=at.qk_bias, bucket=bucket, emb=at.emb,
                                    demb_rows=pg.row(p + "attn_block.rel_pos.relative_attention_bias.weight") if at.rel_pos else None,
-                                   dqkb_rows=pg.row(p + "attn_block.qk.bias") if at.bias_qkv else None)
+                                   dqkb_rows=pg.row(p + "attn_block.qk.bias") if at.bias_qkv else None, precision=self.attn_core)
         da1 = ops.conv2d(dqk, at.qk, self.buf(B, H * Fq, 1, T), transpose=True, res=dv.view(B, H * Fq, 1, T), rbeta=1.0)
         da0 = ops.conv2d(da1.view(B, H, Fq, T), at.proj_in, self.buf(B, N, Fq, T), transpose=True)
         if pg is not None:                                   # a0 = z * scale2 (no GELU), a1 = proj_in(a0); da0, da1 are unscaled
@@ -529,10 +530,13 @@ class UnetEngine:
             for v in shape:
                 n *= v
             grads[key] = flat[off:off + n].view(shape)
-        for blk, _ in self.attn_blocks:                  # the qk weight gradients: one launch per block over all batch rows
+        # the qk weight gradients: one launch per block over all batch rows.  Their GEMM follows the step's weight-gradient
+        # arithmetic on a bf16 attention core only; on the fp32 core it stays fp32 whatever pg.wgrad says
+        qk_prec = "bf16" if self.attn_core == "bf16" and pg.wgrad == "bf16" else "f32"
+        for blk, _ in self.attn_blocks:
             dqk, a1 = pg.qk[blk.p]
             HF = a1.shape[1]
-            grads[blk.p + "attn_block.qk.weight"] = ops.attn_qk_wgrad(dqk, a1, self.buf(2 * HF, HF, 1))
+            grads[blk.p + "attn_block.qk.weight"] = ops.attn_qk_wgrad(dqk, a1, self.buf(2 * HF, HF, 1), precision=qk_prec)
         h0, h1, h2, h3 = emb_keep
         B = h3.shape[0]
         fi = self.film_idx

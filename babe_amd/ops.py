@@ -598,27 +598,44 @@ def scale_channels(x, scale, out):
     return out
 
 
-def attn_qk_wgrad(dqk, a1, dW, alpha=1.0, beta=0.0, ws=None):
+def _attn_precision(who, precision):
+    if precision not in ("f32", "bf16"):
+        raise ValueError(f"{who}: precision must be 'f32' or 'bf16', got {precision!r}")
+    return "_bf16" if precision == "bf16" else ""
+
+
+def attn_qk_wgrad_workspace(B, HF, T, precision="f32"):
+    """Floats of workspace attn_qk_wgrad needs at this shape (0: none; > 0: K is split into chunks); -1: unsupported shape."""
+    return getattr(lib(), "babe_attn_qk_wgrad" + _attn_precision("attn_qk_wgrad_workspace", precision) + "_workspace")(B, HF, T)
+
+
+def attn_qk_wgrad(dqk, a1, dW, alpha=1.0, beta=0.0, ws=None, precision="f32"):
     """dW [2HF, HF] = alpha * sum_b dqk[b] a1[b]^T + beta * dW (babe_attn_qk_wgrad): the qk Conv1d weight gradient, summed over
-    the batch in a fixed order.  dqk [B,2HF,T], a1 [B,HF,T] dense."""
+    the batch in a fixed order.  dqk [B,2HF,T], a1 [B,HF,T] dense.  precision: 'f32' (exact fp32 MFMA) or 'bf16'
+    (babe_attn_qk_wgrad_bf16: both fp32 operands rounded once to bf16, fp32 accumulation)."""
+    name = "attn_qk_wgrad" + _attn_precision("attn_qk_wgrad", precision)
     B, M, T = dqk.shape
     HF = a1.shape[1]
     for t in (dqk, a1, dW):
         assert t.is_contiguous() and t.dtype == torch.float32
     assert a1.shape == (B, HF, T) and M == 2 * HF and dW.numel() == M * HF
-    n = lib().babe_attn_qk_wgrad_workspace(B, HF, T)
+    n = getattr(lib(), f"babe_{name}_workspace")(B, HF, T)
     if n < 0:
-        raise _lib.BabeHipError(f"attn_qk_wgrad: unsupported shape B={B} HF={HF} T={T} (HF a multiple of 512, at most 3584)")
+        raise _lib.BabeHipError(f"{name}: unsupported shape B={B} HF={HF} T={T} (HF a multiple of 512, at most 3584)")
     if n and ws is None:
         ws = torch.empty(n, device=dW.device, dtype=torch.float32)
     assert not n or (ws.numel() >= n and ws.is_contiguous())
-    check(lib().babe_attn_qk_wgrad(ptr(dqk), ptr(a1), ptr(dW), ptr(ws) if n else None, B, HF, T, alpha, beta, stream()), "attn_qk_wgrad")
+    check(getattr(lib(), "babe_" + name)(ptr(dqk), ptr(a1), ptr(dW), ptr(ws) if n else None, B, HF, T, alpha, beta, stream()), name)
     return dW
 
 
-def attn_param_vjp(qk, a, out, lse, dout, dqk, scale, qk_bias=None, bucket=None, emb=None, demb_rows=None, dqkb_rows=None):
+def attn_param_vjp(qk, a, out, lse, dout, dqk, scale, qk_bias=None, bucket=None, emb=None, demb_rows=None, dqkb_rows=None,
+                   precision="f32"):
     """Table and bias gradients of attn_fwd per batch row (babe_attn_param_vjp), from the operands of attn_vjp and its dqk:
-    demb_rows [B, nb*H] (with bucket / emb) and dqkb_rows [B, 2HF] (views with any row stride; None: not computed)."""
+    demb_rows [B, nb*H] (with bucket / emb) and dqkb_rows [B, 2HF] (views with any row stride; None: not computed).
+    precision: that of the attn_fwd / attn_vjp calls that wrote out, lse and dqk; 'bf16' is babe_attn_param_vjp_bf16, the table
+    gradient of exactly the P the bf16 core's dQ pass used."""
+    name = "attn_param_vjp" + _attn_precision("attn_param_vjp", precision)
     B, H, F, T = a.shape
     for t in (qk, a, out, lse, dout, dqk):
         assert t.is_contiguous() and t.dtype == torch.float32
@@ -632,11 +649,11 @@ def attn_param_vjp(qk, a, out, lse, dout, dqk, scale, qk_bias=None, bucket=None,
         assert demb_rows is None
     if dqkb_rows is not None:
         assert dqkb_rows.shape == (B, 2 * H * F) and dqkb_rows.stride(1) == 1
-    ws = torch.empty(max(1, lib().babe_attn_param_vjp_workspace(B, H, T, nb)), device=a.device, dtype=torch.float32)
-    check(lib().babe_attn_param_vjp(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(dqk),
+    ws = torch.empty(max(1, getattr(lib(), f"babe_{name}_workspace")(B, H, T, nb)), device=a.device, dtype=torch.float32)
+    check(getattr(lib(), "babe_" + name)(ptr(qk), ptr(qk_bias), ptr(a), ptr(bucket), ptr(emb), nb, ptr(out), ptr(lse), ptr(dout), ptr(dqk),
                                     ptr(ws), ptr(demb_rows), demb_rows.stride(0) if demb_rows is not None else 0, ptr(dqkb_rows),
                                     dqkb_rows.stride(0) if dqkb_rows is not None else 0, B, H, F, T, scale, stream()),
-          "attn_param_vjp")
+          name)
 
 
 def linear_bwd(dy, x, W, dW, db, dx=None, y=None, beta=0.0, ws=None):

@@ -101,7 +101,8 @@ def main(argv=None):
     dataset = build_dataset(args, seed)
     loader = torch.utils.data.DataLoader(dataset, batch_size=args.exp.batch, num_workers=args.exp.num_workers)
     net = Unet_CQT_oct_with_attention(args, device, precision=a.precision)
-    net.set_trainable(True, attention=net.has_attention, wgrad=a.wgrad)
+    # a bf16 attention core (network.attention_precision=bf16) trains under its own opt-in and bars
+    net.set_trainable(True, attention="bf16" if net.bf16_attention else net.has_attention, wgrad=a.wgrad)
     opt = args.exp.optimizer
     if opt.type != "adam":
         raise NotImplementedError(f"exp.optimizer.type={opt.type!r} (the reference implements 'adam' only)")

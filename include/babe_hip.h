@@ -961,6 +961,28 @@ int babe_attn_param_vjp(const float* qk, const float* qk_bias, const float* a, c
                         int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk, float* ws,
                         float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H, int F, int T, float scale,
                         void* stream);
+/* The two calls above for a network whose attention core is babe_attn_fwd_bf16 / babe_attn_vjp_bf16 (mixed-precision training;
+ * csrc/attention_bf16.hip, csrc/attention_train.hip).  Same arguments, layouts, fixed summation orders and refusals.
+ *
+ * babe_attn_param_vjp_bf16: out / lse / dout / dqk are those of the bf16 core.  The table gradient is a fourth mode of the
+ * babe_attn_vjp_bf16 kernel: the dQ pass up to its fp32 dS = P o (dP - D) (same bf16 images, same MFMA order, same exponential,
+ * D from the same row-dot pass), summed per diagonal before it would be rounded for the second product; the two waves of a
+ * 16-query tile merge st = 0 then st = 1, key chunks ascend, query tiles are added in order by a last pass.  dqkb_rows is the
+ * same row sum of dqk as above.  Four bf16 images of 32 time steps, four parked 16 x 16 tiles and four arrays of diagonals must
+ * fit the 160 KiB of LDS: 256 (F + 8) + 4608 + 16 (ceil32(T) + 32) bytes (F = 448: T <= 2624; F = 64: T <= 8700); anything
+ * larger is an argument error.
+ *
+ * babe_attn_qk_wgrad_bf16: dqk and a1 stay fp32 in memory and are rounded once, to nearest even, on their way into LDS; the
+ * product runs on v_mfma_f32_32x32x16_bf16 with fp32 accumulators in ascending (b, t).  Chunk plan and workspace size are those
+ * of babe_attn_qk_wgrad. */
+long babe_attn_qk_wgrad_bf16_workspace(int B, int HF, int T);
+int babe_attn_qk_wgrad_bf16(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha, float beta,
+                            void* stream);
+long babe_attn_param_vjp_bf16_workspace(int B, int H, int T, int num_buckets);
+int babe_attn_param_vjp_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
+                             int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk, float* ws,
+                             float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H, int F, int T,
+                             float scale, void* stream);
 /* babe_gn_param_grad for a = z * scale WITHOUT the GELU (norm2 / affine2 of the attention branch): dscale = cs * sum_i da*z. */
 int babe_gn_param_grad_nogelu(const float* z, const float* da, const float* stats, const float* gamma, const float* film_aff,
                               long film_bs, float cs, float* dgamma_rows, long dg_bs, float* dfilm, long dfilm_bs, int B, int C,

@@ -4,7 +4,7 @@ TFLOP/s measured fp32 MFMA peak for --wgrad f32, the 2.5 PFLOP/s dense bf16 SPEC
 document (profiles/train_bench.json, profiles/train_bench_wgrad_bf16.json).
 
     python tools/train_bench.py [--B 4] [--L 368368] [--reps 3] [--attention-layers 0,0,0,0,1,1,1,1]
-                                [--wgrad {f32,bf16}] [--precision {f32,bf16}]
+                                [--wgrad {f32,bf16}] [--precision {f32,bf16}] [--attention-precision {f32,bf16}]
 
 --wgrad: arithmetic of the conv weight gradients (set_trainable(True, wgrad=...)); --precision: the network's conv arithmetic
 (forward and input-VJP); --precision bf16 --wgrad bf16 is the full mixed-precision step.
@@ -12,6 +12,10 @@ document (profiles/train_bench.json, profiles/train_bench_wgrad_bf16.json).
 --attention-layers: train a network with time-attention layers (set_trainable(True, attention=True)); the report then also has the
 qk weight-gradient launches of one backward (babe_attn_qk_wgrad, one per attention block after the lane join): their summed time
 and share of the step.
+
+--attention-precision: arithmetic of the attention core (the network's attention_precision).  bf16 trains on the bf16 core
+(set_trainable(True, attention='bf16')); with --wgrad bf16 the qk weight gradients then run on babe_attn_qk_wgrad_bf16.  The
+report's attn_qk_wgrad_kernel names the entry point that ran.
 """
 import argparse
 import json
@@ -46,6 +50,8 @@ def main():
     ap.add_argument("--attention-layers", default=None, help="8 comma-separated flags, e.g. 0,0,0,0,1,1,1,1")
     ap.add_argument("--wgrad", choices=["f32", "bf16"], default="f32", help="conv weight-gradient arithmetic")
     ap.add_argument("--precision", choices=["f32", "bf16"], default="f32", help="the network's conv arithmetic")
+    ap.add_argument("--attention-precision", choices=["f32", "bf16"], default=None,
+                    help="arithmetic of the attention core (needed for attention layers in a --precision bf16 network)")
     a = ap.parse_args()
     att = [int(v) for v in a.attention_layers.split(",")] if a.attention_layers else None
     from babe_amd import ops
@@ -59,15 +65,15 @@ def main():
         adict = dict(num_heads=8, attn_dropout=0.0, bias_qkv=False, N=0, rel_pos_num_buckets=32, rel_pos_max_distance=64,
                      use_rel_pos=True, Nproj=8)
         args.network.attention_layers, args.network.attention_dict = att, adict
-    net = Unet_CQT_oct_with_attention(args, "cuda", precision=a.precision)
+    net = Unet_CQT_oct_with_attention(args, "cuda", precision=a.precision, attention_precision=a.attention_precision)
     net.load_state_dict(init_state_dict(FULL_NS, FULL_DILS, seed=0, attention_layers=att, attention_dict=adict))
-    net.set_trainable(True, attention=bool(att), wgrad=a.wgrad)
+    net.set_trainable(True, attention="bf16" if net.bf16_attention else bool(att), wgrad=a.wgrad)
     gen = torch.Generator().manual_seed(0)
     x = (0.1 * torch.randn(a.B, a.L, generator=gen)).cuda()
     cn = torch.linspace(-1, 0.5, a.B).reshape(a.B, 1).cuda()
     w = torch.randn(a.B, a.L, generator=gen).cuda()
     res = {"B": a.B, "L": a.L, "lanes": min(a.B, net.MAX_LANES) if net.concurrent_lanes_ok else 1, "attention_layers": att,
-           "precision": a.precision, "wgrad": a.wgrad}
+           "precision": a.precision, "wgrad": a.wgrad, "attention_precision": a.attention_precision}
 
     # input-VJP alone (the sampler's path) and the forward without training state
     def fwd_vjp():
@@ -90,7 +96,7 @@ def main():
         e.record()
         wg_ev.append((s, e))
     ue.UnetEngine._wg = wg
-    qk_ev = []
+    qk_ev, qk_kernels = [], set()
     orig_qk = ops.attn_qk_wgrad
 
     def qk_wgrad(*args, **kw):
@@ -99,6 +105,7 @@ def main():
         out = orig_qk(*args, **kw)
         e.record()
         qk_ev.append((s, e))
+        qk_kernels.add("babe_attn_qk_wgrad" + ("_bf16" if kw.get("precision", "f32") == "bf16" else ""))
         return out
     ops.attn_qk_wgrad = qk_wgrad
     eng = net.engine()
@@ -144,6 +151,7 @@ def main():
     step()
     res["step_ms"] = timed(step, a.reps)
     if att:                                            # the launches run back to back on one stream: their times add up
+        res["attn_qk_wgrad_kernel"] = "+".join(sorted(qk_kernels))
         res["attn_qk_wgrad_calls_per_backward"] = len(qk_ev) // a.reps
         res["attn_qk_wgrad_ms_sum"] = sum(s.elapsed_time(e) for s, e in qk_ev) / a.reps
         res["attn_qk_wgrad_share_of_step"] = round(res["attn_qk_wgrad_ms_sum"] / res["step_ms"], 4)
