@@ -50,12 +50,25 @@ class PackedConvLayout(C.Structure):
 IMAGE_SLOTS = ("fwd", "bwd", "fwd_wino", "bwd_wino", "fwd_wino4", "bwd_wino4", "fwd_wino45", "bwd_wino45", "fwd_wino85", "bwd_wino85")
 
 
+class CAttn(C.Structure):
+    """babe_unet_attn: the time-attention branch of a block (networks/unet_engine.py::_Attn)."""
+    _fields_ = [("H", C.c_int), ("F", C.c_int), ("scale", C.c_float),
+                ("proj_in", CPackedConv), ("qk", CPackedConv), ("proj_out", CPackedConv),
+                ("gamma", C.c_void_p), ("film_aff", C.c_int), ("film_gate", C.c_int),
+                ("qk_bias", C.c_void_p), ("emb", C.c_void_p), ("num_buckets", C.c_int), ("max_distance", C.c_int)]
+
+
+class AttnBucketThr(C.Structure):
+    """babe_attn_bucket_thr: the host data of the bucket-table kernel (babe_attn_bucket_thresholds)."""
+    _fields_ = [("half", C.c_int), ("max_distance", C.c_int), ("thr", C.c_int * 32)]
+
+
 class CBlock(C.Structure):
     """babe_unet_block"""
     _fields_ = [("N", C.c_int), ("nd", C.c_int), ("k53", C.c_int),
                 ("proj_in", CPackedConv), ("res_conv", CPackedConv), ("proj_out", CPackedConv), ("H", CPackedConv * 8),
                 ("gamma", C.c_void_p * 8), ("film_aff", C.c_int * 8), ("film_gate", C.c_int * 8),
-                ("fb_proj_in", C.c_void_p), ("fb_res_conv", C.c_void_p)]
+                ("fb_proj_in", C.c_void_p), ("fb_res_conv", C.c_void_p), ("attn", C.POINTER(CAttn))]
 
 
 class PwArgs(C.Structure):
@@ -73,7 +86,11 @@ class CPlanDesc(C.Structure):
     """babe_unet_plan_desc"""
     _fields_ = [("nocts", C.c_int), ("bpo", C.c_int), ("Ns", C.c_int * 8),
                 ("init_blk", CBlock * 8), ("main_blk", CBlock * 8), ("up_out", CBlock * 8), ("up_blk", CBlock * 8),
-                ("mid_blk", CBlock), ("mid_out", CBlock), ("pyr_conv", CPackedConv * 8)]
+                ("mid_blk", CBlock), ("mid_out", CBlock), ("pyr_conv", CPackedConv * 8), ("attn_core", C.c_int)]
+
+
+# babe_unet_plan_desc.attn_core / babe_model_options.attention, by the attention core's name (UnetEngine.attn_core)
+ATTN_CORES = {None: 0, "f32": 1, "bf16": 2}
 
 
 class CqtBands(C.Structure):
@@ -160,6 +177,11 @@ class ModelKV(C.Structure):
     _fields_ = [("key", C.c_char_p), ("str", C.c_char_p), ("num", C.c_double)]
 
 
+class ModelOptions(C.Structure):
+    """babe_model_options"""
+    _fields_ = [("precision", C.c_int), ("attention", C.c_int), ("reserved", C.c_int * 6)]
+
+
 class ModelSummary(C.Structure):
     """babe_model_summary"""
     _fields_ = [("L", C.c_int), ("fs", C.c_float), ("nocts", C.c_int), ("bpo", C.c_int), ("Ns", C.c_int * 8),
@@ -202,7 +224,8 @@ STRUCTS = {"babe_conv_args": ConvArgs, "babe_wgrad_args": WgradArgs, "babe_packe
            "babe_recording_desc": RecordingDesc,
            "babe_model_entry": ModelEntry, "babe_model_kv": ModelKV, "babe_model_summary": ModelSummary,
            "babe_denoiser_summary": DenoiserSummary, "babe_sinc_table": SincTable, "babe_file_desc": FileDesc,
-           "babe_opt_tensor": OptTensor, "babe_opt_chunk": OptChunk}
+           "babe_opt_tensor": OptTensor, "babe_opt_chunk": OptChunk,
+           "babe_unet_attn": CAttn, "babe_attn_bucket_thr": AttnBucketThr, "babe_model_options": ModelOptions}
 
 # C type -> ctypes: void* (and every data pointer; hipStream_t), long, int, float, double, const char*; None = void
 _P, _L, _I, _F, _D, _S = C.c_void_p, C.c_long, C.c_int, C.c_float, C.c_double, C.c_char_p
@@ -360,6 +383,8 @@ SIGS = {
     "babe_dn_stft": (_I, [_P, _L, _I, _P, _I, _I, _I, _I, _P, _P]),
     "babe_dn_istft": (_I, [_P, _P, _P, _L, _I, _I, _I, _I, _I, _P, _P]),
     "babe_attn_buckets": (_I, [_P, _I, _I, _I]),
+    "babe_attn_bucket_thresholds": (_I, [C.POINTER(AttnBucketThr), _I, _I]),
+    "babe_attn_bucket_table": (_I, [C.POINTER(AttnBucketThr), _I, _P, _P]),
     "babe_attn_fwd": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
     "babe_attn_vjp": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P]),
     "babe_attn_fwd_bf16": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _F, _P]),
@@ -388,7 +413,10 @@ SIGS = {
     "babe_model_create": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _P]),
     "babe_model_load_ex": (_P, [_S, _I, _P]),
     "babe_model_create_ex": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, _I, _P]),
+    "babe_model_load_opt": (_P, [_S, C.POINTER(ModelOptions), _P]),
+    "babe_model_create_opt": (_P, [C.POINTER(ModelEntry), _I, C.POINTER(ModelKV), _I, C.POINTER(ModelOptions), _P]),
     "babe_model_precision": (_I, [_P]),
+    "babe_model_attention": (_I, [_P]),
     "babe_model_destroy": (None, [_P]),
     "babe_model_info": (_I, [_P, C.POINTER(ModelSummary)]),
     "babe_model_setting": (_I, [_P, _S, C.POINTER(_D)]),

@@ -6,7 +6,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libbabe_hip.so")
-SOURCES = ["misc.hip", "conv.hip", "conv11p.hip", "pw_block.hip", "conv_fewco.hip", "conv_bf16.hip", "conv_bf16p.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4p.hip", "conv_wino45.hip", "conv_wino85.hip", "conv_auto.hip", "norm.hip", "resample.hip", "resample_sinc.hip", "degrade.hip", "edm_tasks.hip", "cqt.hip", "cqt_plan.hip", "fft_mixed.hip", "unet_engine.hip", "score_eval.hip", "sample.hip", "recording.hip", "model.hip", "randn.hip", "stft.hip", "sampler.hip", "denoiser.hip", "dn_engine.hip", "attention.hip", "attention_bf16.hip", "attention_train.hip", "wgrad.hip", "fenc.hip", "loss.hip", "metrics.hip", "optim.hip"]
+SOURCES = ["misc.hip", "conv.hip", "conv11p.hip", "pw_block.hip", "conv_fewco.hip", "conv_bf16.hip", "conv_bf16p.hip", "conv_wino.hip", "conv_wino4.hip", "conv_wino4p.hip", "conv_wino45.hip", "conv_wino85.hip", "conv_auto.hip", "norm.hip", "resample.hip", "resample_sinc.hip", "degrade.hip", "edm_tasks.hip", "cqt.hip", "cqt_plan.hip", "fft_mixed.hip", "unet_engine.hip", "score_eval.hip", "sample.hip", "recording.hip", "model.hip", "randn.hip", "stft.hip", "sampler.hip", "denoiser.hip", "dn_engine.hip", "attention.hip", "attention_bf16.hip", "attention_train.hip", "attn_buckets.hip", "wgrad.hip", "fenc.hip", "loss.hip", "metrics.hip", "optim.hip"]
 
 
 # Every source is built WITHOUT packed-fp32 instructions: no SLP vectoriser (-fno-slp-vectorize) and the target feature

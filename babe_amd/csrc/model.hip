@@ -8,6 +8,10 @@
 //   FiLM         _FilmIndex: blocks in CONSTRUCTION order (init i, main i per octave; mid_blk, mid_out; up_out i, up_blk i), per
 //                dilation layer the affine rows, then the gate rows
 //   encodings    the init blocks' 66 -> 2 column convs and their babe_fenc_bias tables
+//   attention    _Attn: per block with a time-attention layer the three (1,1) convs proj_in / proj_out / qk, packed under the same
+//                rule at the load precision, norm2's gamma, the qk bias and the relative-position table as uploaded, and affine2 /
+//                gate2 in the FiLM matrix after the block's dilation layers; only when the host chose an attention core
+//                (babe_model_options::attention), which becomes the plan's attn_core
 //   CQT          babe_cqt_plan_create_ex(fs, L, octaves, bins, beta, 8192)
 // The documented exception to "the library never allocates / never synchronises": create allocates ONE arena on the current
 // device (sized by a dry pass of the same layout function) plus the CQT plan's tables, and waits on `stream` once before it
@@ -29,7 +33,9 @@ using namespace babe_model;
 struct Model {
     NetCfg cfg;
     std::map<std::string, Setting> settings;
-    int device = -1, precision = 0;
+    int device = -1, precision = 0, attention = 0;
+    babe_unet_attn attn[17];         // the attention branches desc's blocks point to (the plan keeps copies of its own)
+    int nattn = 0;
     char* arena = nullptr;
     size_t arena_bytes = 0, upload_bytes = 0;
     long params = 0;
@@ -103,6 +109,20 @@ struct Builder {
                 }
                 J += b.N;
             }
+        if (b.attnF) {                                       // _Attn: affine2, then gate2, after all of the block's layers
+            babe_unet_attn& at = m.attn[m.nattn++];
+            memset(&at, 0, sizeof at);
+            blk.attn = &at;
+            for (int gate = 0; gate < 2; ++gate) {
+                const std::string k = b.p + (gate ? "gate2" : "affine2");
+                (gate ? at.film_gate : at.film_aff) = J;
+                if (!dry()) {
+                    memcpy(staged(W) + (size_t)J * E, T(k + ".weight").data, (size_t)b.N * E * sizeof(float));
+                    memcpy(staged(bias) + J, T(k + ".bias").data, (size_t)b.N * sizeof(float));
+                }
+                J += b.N;
+            }
+        }
     }
     float* fold(const std::string& name, int N) {          // w[:, :2] of a [N, 66, 1, 1] weight, contiguous
         float* d = c.take<float>((size_t)N * 2);
@@ -136,6 +156,18 @@ struct Builder {
             BABE_TRY(conv(blk.H[d], b.p + "H." + std::to_string(d) + ".weight"));
             blk.gamma[d] = dev[b.p + "norm." + std::to_string(d) + ".gamma"];
         }
+        if (b.attnF) {                                       // (film_rows made the branch and set its FiLM offsets)
+            const NetCfg& cfg = m.cfg;
+            babe_unet_attn& at = const_cast<babe_unet_attn&>(*blk.attn);
+            const std::string ab = b.p + "attn_block.";
+            at.H = cfg.heads, at.F = b.attnF, at.scale = (float)std::pow((double)b.attnF, -0.5);
+            BABE_TRY(conv(at.proj_in, ab + "proj_in.weight"));
+            BABE_TRY(conv(at.proj_out, ab + "proj_out.weight"));
+            BABE_TRY(conv(at.qk, dev[ab + "qk.weight"], 2 * cfg.heads * b.attnF, cfg.heads * b.attnF, 1, 1));      // Conv1d: [2HF, HF, 1]
+            at.gamma = dev[b.p + "norm2.gamma"];
+            if (cfg.bias_qkv) at.qk_bias = dev[ab + "qk.bias"];
+            if (cfg.rel_pos) at.emb = dev[ab + "rel_pos.relative_attention_bias.weight"], at.num_buckets = cfg.nbk, at.max_distance = cfg.maxd;
+        }
         return BABE_OK;
     }
 
@@ -145,7 +177,8 @@ struct Builder {
         const NetBlocks nb = net_blocks(cfg);
         babe_unet_plan_desc& D = m.desc;
         memset(&D, 0, sizeof D);
-        D.nocts = n, D.bpo = cfg.bpo;
+        m.nattn = 0;
+        D.nocts = n, D.bpo = cfg.bpo, D.attn_core = cfg.has_attention() ? m.attention : 0;
         for (int i = 0; i < n; ++i) D.Ns[i] = cfg.Ns[i];
         // ---- phase A: what is uploaded.  Every tensor of the file as it is ...
         for (const Tensor& t : f.tensors) dev[t.name] = upload(t.data, t.numel);
@@ -153,6 +186,8 @@ struct Builder {
         int J = 0;
         for (int i = 0; i < n; ++i) J += 2 * (nb.init[i].N * nb.init[i].nd + nb.main[i].N * nb.main[i].nd + nb.up_out[i].N * nb.up_out[i].nd + nb.up_blk[i].N * nb.up_blk[i].nd);
         J += 2 * (nb.mid_blk.N * nb.mid_blk.nd + nb.mid_out.N * nb.mid_out.nd);
+        for (int i = 0; i < n; ++i) J += 2 * ((nb.main[i].attnF ? nb.main[i].N : 0) + (nb.up_blk[i].attnF ? nb.up_blk[i].N : 0));
+        J += 2 * (nb.mid_blk.attnF ? nb.mid_blk.N : 0);
         float* W = c.take<float>((size_t)J * E);
         float* bias = c.take<float>((size_t)J);
         int at = 0;
@@ -210,13 +245,20 @@ void destroy(Model* m) {
 
 // f (validated here) -> a model on the current device, or nullptr with the message set.  t0: when the caller began (load: before
 // it read the file).
-void* create(File& f, int precision, void* stream, double t0) {
+void* create(File& f, int precision, int attention, void* stream, double t0) {
     std::unique_ptr<Model> guard(new Model);
     Model& m = *guard;
-    m.precision = precision;
+    m.precision = precision, m.attention = attention;
     std::string err;
-    if (!validate(f, m.cfg, err)) return babe_set_error("model: %s", err.c_str()), nullptr;
+    if (!validate(f, m.cfg, err, attention)) return babe_set_error("model: %s", err.c_str()), nullptr;
     const NetCfg& cfg = m.cfg;
+    if (cfg.has_attention() && cfg.rel_pos) {       // what babe_unet_plan_create would refuse of the bucket table, asked before any device call
+        babe_attn_bucket_thr thr;
+        if (babe_attn_bucket_thresholds(&thr, cfg.nbk, cfg.maxd) != BABE_OK) {
+            const std::string why = babe_last_error();
+            return babe_set_error("model: network.attention_dict: %s", why.c_str()), nullptr;
+        }
+    }
     // the CQT design is host-only: a length the plan does not cover is refused before any device call (its message is set)
     void* design = babe_cqt_design_create_ex(cfg.fs, cfg.L, cfg.nocts, cfg.bpo, cfg.beta, 8192);
     if (!design) {
@@ -288,9 +330,18 @@ static bool precision_ok(int precision, const char* who) {
     return false;
 }
 
-extern "C" void* babe_model_load_ex(const char* path, int precision, void* stream) {
+static bool attention_ok(int attention, const char* who) {
+    if (attention >= BABE_ATTENTION_REFUSE && attention <= BABE_ATTENTION_BF16) return true;
+    babe_set_error("%s: attention %d is none of BABE_ATTENTION_REFUSE (0), _F32 (1), _BF16 (2)", who, attention);
+    return false;
+}
+static bool options_ok(const babe_model_options* o, const char* who) {
+    if (!o) return babe_set_error("%s: null options", who), false;
+    return precision_ok(o->precision, who) && attention_ok(o->attention, who);
+}
+
+static void* model_load(const char* path, int precision, int attention, void* stream) {
     const double t0 = now_ms();
-    if (!precision_ok(precision, "model_load")) return nullptr;
     if (!path) return babe_set_error("model_load: null path"), nullptr;
     FILE* fh = fopen(path, "rb");
     if (!fh) return babe_set_error("model_load: cannot open %s: %s", path, strerror(errno)), nullptr;
@@ -308,14 +359,19 @@ extern "C" void* babe_model_load_ex(const char* path, int precision, void* strea
     File f;
     std::string err;
     if (!parse(buf.data(), buf.size(), f, err)) return babe_set_error("model_load: %s: %s", path, err.c_str()), nullptr;
-    return create(f, precision, stream, t0);
+    return create(f, precision, attention, stream, t0);
+}
+extern "C" void* babe_model_load_opt(const char* path, const babe_model_options* options, void* stream) {
+    return options_ok(options, "model_load") ? model_load(path, options->precision, options->attention, stream) : nullptr;
+}
+extern "C" void* babe_model_load_ex(const char* path, int precision, void* stream) {
+    return precision_ok(precision, "model_load") ? model_load(path, precision, BABE_ATTENTION_REFUSE, stream) : nullptr;
 }
 extern "C" void* babe_model_load(const char* path, void* stream) { return babe_model_load_ex(path, BABE_PRECISION_F32, stream); }
 
-extern "C" void* babe_model_create_ex(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision,
-                                      void* stream) {
+static void* model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision, int attention,
+                          void* stream) {
     const double t0 = now_ms();
-    if (!precision_ok(precision, "model_create")) return nullptr;
     if (!entries || !settings || n < 1 || nsettings < 1) return babe_set_error("model_create: null or empty tables"), nullptr;
     File f;
     std::string err;
@@ -331,7 +387,17 @@ extern "C" void* babe_model_create_ex(const babe_model_entry* entries, int n, co
         if (!add_tensor(f, entries[i].name, entries[i].ndim, entries[i].shape, entries[i].data, err))
             return babe_set_error("model_create: %s", err.c_str()), nullptr;
     }
-    return create(f, precision, stream, t0);
+    return create(f, precision, attention, stream, t0);
+}
+extern "C" void* babe_model_create_opt(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings,
+                                       const babe_model_options* options, void* stream) {
+    return options_ok(options, "model_create") ? model_create(entries, n, settings, nsettings, options->precision, options->attention, stream)
+                                               : nullptr;
+}
+extern "C" void* babe_model_create_ex(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision,
+                                      void* stream) {
+    return precision_ok(precision, "model_create") ? model_create(entries, n, settings, nsettings, precision, BABE_ATTENTION_REFUSE, stream)
+                                                   : nullptr;
 }
 extern "C" void* babe_model_create(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, void* stream) {
     return babe_model_create_ex(entries, n, settings, nsettings, BABE_PRECISION_F32, stream);
@@ -341,6 +407,12 @@ extern "C" int babe_model_precision(const void* model) {
     const Model* m = static_cast<const Model*>(model);
     if (!m) return babe_set_error("model_precision: null model"), -1;
     return m->precision;
+}
+
+extern "C" int babe_model_attention(const void* model) {
+    const Model* m = static_cast<const Model*>(model);
+    if (!m) return babe_set_error("model_attention: null model"), -1;
+    return m->attention;
 }
 
 extern "C" void babe_model_destroy(void* model) { destroy(static_cast<Model*>(model)); }

@@ -202,6 +202,10 @@ struct NetCfg {
     double fs = 0, beta = 0;
     int L = 0, nocts = 0, bpo = 0, emb_dim = 0, fenc = 0;
     int Ns[8] = {}, dils[8] = {};
+    // time attention (all zero without it): the core the host chose (1 fp32, 2 bf16), one flag per octave + the bottleneck, and
+    // attention_options' leaves of network.attention_dict
+    int attention = 0, att[8] = {}, heads = 0, bias_qkv = 0, rel_pos = 0, nbk = 0, maxd = 0;
+    bool has_attention() const { return std::any_of(att, att + 8, [](int v) { return v != 0; }); }
     // sampler defaults
     int T = 0, order = 0, hpf = 0, nfft = 0, K = 0, has_start_sigma = 0, weighting = 0;
     double xi = 0, start_sigma = 0;
@@ -227,14 +231,38 @@ inline bool integer(const File& f, const std::string& key, long lo, long hi, int
     return true;
 }
 
-// settings -> cfg; refuses what the library-side sequencers refuse (attention) and what the kernels do not cover
-inline bool net_config(const File& f, NetCfg& c, std::string& err) {
+// an optional integer leaf: absent (or, under network.attention_dict, the whole node "None") leaves v at its default
+inline bool integer_or(const File& f, const std::string& key, long lo, long hi, int& v, std::string& err) {
+    return f.settings.count(key) ? integer(f, key, lo, hi, v, err) : true;
+}
+
+// settings -> cfg; refuses what the kernels do not cover.  attention: the host's choice of the attention core (0: a file with
+// attention layers is refused, 1 fp32, 2 bf16 - babe_model_options::attention)
+inline bool net_config(const File& f, NetCfg& c, std::string& err, int attention = 0) {
     const std::string nw = "network.", cq = "network.cqt.", te = "tester.", ps = "tester.posterior_sampling.", dp = "tester.diff_params.",
                       bb = "tester.blind_bwe.", op = "tester.blind_bwe.optimization.", ic = "tester.blind_bwe.initial_conditions.";
+    if (attention < 0 || attention > 2) return err = fmt("attention = %d is none of 0 (refuse), 1 (fp32 core), 2 (bf16 core)", attention), false;
     for (int i = 0; i < 8; ++i) {                           // absent flags mean no attention
         auto it = f.settings.find(nw + "attention_layers." + std::to_string(i));
-        if (it != f.settings.end() && (it->second.is_string || it->second.num != 0))
+        if (it == f.settings.end()) continue;
+        if (!attention && (it->second.is_string || it->second.num != 0))
             return err = fmt("attention layers are not supported by the library-side sequencers (network.attention_layers.%d is set)", i), false;
+        if (!integer(f, it->first, 0, 1, c.att[i], err)) return false;
+    }
+    if (f.settings.count(nw + "attention_layers.8")) return err = "network.attention_layers has more entries than octaves plus the bottleneck", false;
+    if (c.has_attention()) {                                // cqtdiff_plus.attention_options: the reference's defaults where absent
+        const std::string ad = nw + "attention_dict.";
+        c.attention = attention, c.heads = 8, c.bias_qkv = 0, c.rel_pos = 1, c.nbk = 32, c.maxd = 64;
+        if (!integer_or(f, ad + "num_heads", 1, 64, c.heads, err) || !integer_or(f, ad + "bias_qkv", 0, 1, c.bias_qkv, err) ||
+            !integer_or(f, ad + "use_rel_pos", 0, 1, c.rel_pos, err))
+            return false;
+        if (c.rel_pos) {                                    // what babe_attn_bucket_thresholds and the kernels' 64-bucket tables take
+            if (!integer_or(f, ad + "rel_pos_num_buckets", 4, 64, c.nbk, err) || !integer_or(f, ad + "rel_pos_max_distance", 2, 65536, c.maxd, err))
+                return false;
+            if (c.nbk % 2) return err = fmt("%srel_pos_num_buckets = %d: an even count is expected", ad.c_str(), c.nbk), false;
+            if (c.maxd <= c.nbk / 4)
+                return err = fmt("%srel_pos_max_distance = %d: more than a quarter of the %d buckets is expected", ad.c_str(), c.maxd, c.nbk), false;
+        }
     }
     auto prec = f.settings.find(nw + "precision");
     if (prec != f.settings.end() && !(prec->second.is_string && prec->second.str == "f32"))
@@ -251,6 +279,8 @@ inline bool net_config(const File& f, NetCfg& c, std::string& err) {
     if (c.nocts != 7) return err = fmt("network.cqt.num_octs = %d: the network has 7 octaves", c.nocts), false;
     if (!integer(f, nw + "emb_dim", 1, 1 << 16, c.emb_dim, err) || !integer(f, nw + "use_fencoding", 0, 1, c.fenc, err)) return false;
     if (c.fenc && c.bpo != 64) return err = fmt("use_fencoding needs 64 bins per octave (got %d)", c.bpo), false;
+    // (the head dimension of level i is (i + 1) * bins_per_oct: a multiple of 64 up to 448 for the attention kernels)
+    if (c.has_attention() && c.bpo != 64) return err = fmt("attention layers need 64 bins per octave (got %d)", c.bpo), false;
     for (int i = 0; i < c.nocts; ++i) {
         if (!integer(f, nw + "Ns." + std::to_string(i), 8, 512, c.Ns[i], err) || !integer(f, nw + "num_dils." + std::to_string(i), 1, 8, c.dils[i], err))
             return false;
@@ -297,14 +327,15 @@ inline bool net_config(const File& f, NetCfg& c, std::string& err) {
     return true;
 }
 
-// One ResnetBlock as babe_amd/networks/cqtdiff_plus.py::param_specs lays it out (no attention).
+// One ResnetBlock as babe_amd/networks/cqtdiff_plus.py::param_specs lays it out.
 struct BlockSpec {
     std::string p;          // state_dict prefix, with the trailing dot
     int dim, dim_out, N, nd, KH, KW;
     bool proj_out, res_conv, proj_in;
+    int attnF = 0;          // the head dimension of the block's time-attention branch (its frequency rows); 0: none
 };
 inline BlockSpec block_spec(const std::string& p, int dim, int dim_out, int nd, int KH, int KW, bool after) {
-    BlockSpec b{p, dim, dim_out, after ? dim : dim_out, nd, KH, KW, false, false, false};
+    BlockSpec b{p, dim, dim_out, after ? dim : dim_out, nd, KH, KW, false, false, false, 0};
     b.proj_out = after && b.N != dim_out;
     b.res_conv = dim != dim_out;
     b.proj_in = dim != b.N;
@@ -321,14 +352,17 @@ inline NetBlocks net_blocks(const NetCfg& c) {
         const int din = i == 0 ? c.Ns[0] : c.Ns[i - 1], dout = c.Ns[i];
         nb.init[i] = block_spec("downs." + std::to_string(i) + ".0.", nin, din, 1, 1, 1, false);
         nb.main[i] = block_spec("downs." + std::to_string(i) + ".2.", din, dout, c.dils[i], 5, 3, false);
+        nb.main[i].attnF = c.att[i] ? (i + 1) * c.bpo : 0;
     }
     nb.mid_out = block_spec("middle.0.0.", c.Ns[n - 1], 2, 1, 1, 1, true);
     nb.mid_blk = block_spec("middle.0.1.", c.Ns[n - 1], c.Ns[n - 1], c.dils[n - 1], 5, 3, false);
+    nb.mid_blk.attnF = c.att[n] ? n * c.bpo : 0;           // (the flag after the octaves': the bottleneck)
     for (int ii = 0; ii < n; ++ii) {
         const int i = n - 1 - ii;
         const int din = 2 * c.Ns[i], dout = i == 0 ? c.Ns[0] : c.Ns[i - 1];
         nb.up_out[ii] = block_spec("ups." + std::to_string(ii) + ".0.", dout, 2, 1, 1, 1, true);
         nb.up_blk[ii] = block_spec("ups." + std::to_string(ii) + ".1.", din, dout, c.dils[i], 5, 3, false);
+        nb.up_blk[ii].attnF = c.att[i] ? (i + 1) * c.bpo : 0;
     }
     return nb;
 }
@@ -372,6 +406,19 @@ inline std::vector<Expected> expected_tensors(const NetCfg& c) {
             add(b.p + "gate." + k + ".bias", {b.N});
             add(b.p + "H." + k + ".weight", {b.N, b.N, b.KH, b.KW});
         }
+        if (b.attnF) {                                       // the time-attention branch (param_specs: after the block's other keys)
+            const long hF = (long)c.heads * b.attnF;
+            add(b.p + "norm2.gamma", {1, b.N, 1, 1});
+            for (const char* lin : {"affine2", "gate2"}) {
+                add(b.p + lin + ".weight", {b.N, c.emb_dim});
+                add(b.p + lin + ".bias", {b.N});
+            }
+            add(b.p + "attn_block.qk.weight", {2 * hF, hF, 1});
+            if (c.bias_qkv) add(b.p + "attn_block.qk.bias", {2 * hF});
+            add(b.p + "attn_block.proj_in.weight", {c.heads, b.N, 1, 1});
+            add(b.p + "attn_block.proj_out.weight", {b.N, c.heads, 1, 1});
+            if (c.rel_pos) add(b.p + "attn_block.rel_pos.relative_attention_bias.weight", {c.nbk, c.heads});
+        }
     };
     const NetBlocks nb = net_blocks(c);
     for (int i = 0; i < c.nocts; ++i) {
@@ -413,6 +460,8 @@ inline bool check_tensors(const File& f, const NetCfg& c, std::string& err) {
 }
 
 // Everything a loader checks before it touches a device.
-inline bool validate(const File& f, NetCfg& c, std::string& err) { return net_config(f, c, err) && check_tensors(f, c, err); }
+inline bool validate(const File& f, NetCfg& c, std::string& err, int attention = 0) {
+    return net_config(f, c, err, attention) && check_tensors(f, c, err);
+}
 
 }  // namespace babe_model

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <new>
 
 /* The two forms BOTH sequencers of the UNet layer path act on (this file's and babe_amd/networks/unet_engine.py's), one value
  * per process: the environment is read here, once, and nowhere else; babe_unet_form_set changes a form at run time and
@@ -44,6 +45,7 @@ extern "C" int babe_unet_form_set(int which, int on) {
 namespace {
 
 constexpr float RS2 = 0.70710678118654752440f;
+const double RS2D = 1.0 / std::sqrt(2.0);       // the Python sequencer's RS2, for scalars it multiplies before rounding
 constexpr int G_GROUPS = 8;
 constexpr float GN_EPS = 1e-7f;
 
@@ -57,6 +59,17 @@ View sub_f(const View& v, int f0, int nf) { View r = v; r.p = v.p + (long)f0 * v
 View sub_c(const View& v, int c0, int nc) { View r = v; r.p = v.p + (long)c0 * v.cs; r.C = nc; return r; }
 
 struct Saved { View z; float* stats; float* scale; float* gate; };
+// what an attention branch's forward leaves for its VJP (unet_engine.py: _State.attn); bucket: the table of this time length
+struct SavedAttn { View z; float* stats; float* scale; float* gate; float* a1; float* qk; float* o; float* lse; const int* bucket; };
+
+// The plan: the caller's descriptor, with every attention branch copied next to it (babe_unet_block::attn points into `at`) and
+// the host data of its bucket-table kernel.  A plan handle is read as its descriptor (the first member).
+struct AttnPlan { babe_unet_attn a; babe_attn_bucket_thr thr; };
+struct UnetPlan {
+    babe_unet_plan_desc d;
+    AttnPlan at[17];              // main_blk[8], mid_blk, up_blk[8]
+    int nat = 0;
+};
 
 }  // namespace
 
@@ -70,6 +83,9 @@ struct babe_unet_state_s {
     void* units = nullptr;         // the bf16 units of the layer being run (babe_scale_gelu_units), grown like scr_a
     size_t units_n = 0;            // in floats
     Saved saved[6][8][8];          // [kind][index][layer]: kinds 0 init, 1 main, 2 up_out, 3 up_blk, 4 mid_blk, 5 mid_out
+    SavedAttn attn[6 * 8];         // [kind * 8 + index]: the attention branch of that block
+    struct { int T; babe_attn_bucket_thr thr; int* tab; } buckets[17];      // the bucket tables this forward has built ...
+    int nbuckets = 0;              // ... one per distinct (time length, thresholds)
     View hs[8];
     const float* film = nullptr;
     long film_bs = 0;
@@ -190,6 +206,89 @@ struct Ctx {
     static int splits(long n) { return (int)babe_gn_splits(n); }      // split count of a GroupNorm group of n elements
     const float* film_at(int off) const { return S->film + off; }
 
+    // ---- the time-attention branch of a ResnetBlock (unet_engine.py attn_fwd / attn_vjp, launch for launch)
+    SavedAttn& attn_rec(const Saved* saved) const { return S->attn[(saved - &S->saved[0][0][0]) / 8]; }
+    static View view(float* p, int C, int F, int T) {
+        View v;
+        v.p = p; v.C = C; v.F = F; v.T = T; v.cs = (long)F * T; v.bs = (long)C * F * T;
+        return v;
+    }
+    // the [2T-1] relative-position bucket table of this time length, built in the workspace once per forward
+    const int* bucket_table(const babe_unet_attn& at, int T) {
+        const babe_attn_bucket_thr& thr = reinterpret_cast<const AttnPlan&>(at).thr;       // (the plan's copy: UnetPlan::at)
+        for (int i = 0; i < S->nbuckets; ++i)
+            if (S->buckets[i].T == T && !memcmp(&S->buckets[i].thr, &thr, sizeof thr)) return S->buckets[i].tab;
+        int* tab = reinterpret_cast<int*>(alloc((size_t)2 * T - 1));
+        if (!dry() && !err) ck(babe_attn_bucket_table(&thr, T, tab, st));
+        auto& e = S->buckets[S->nbuckets++];                 // (at most one per attention branch: 17)
+        e.T = T; e.thr = thr; e.tab = tab;
+        return tab;
+    }
+    // z' = (gate2 * proj_out(attention(...)) + z) / sqrt2; what attn_vjp needs stays in the workspace (rec)
+    View attn_fwd(const babe_unet_block& blk, SavedAttn& rec, const View& z) {
+        const babe_unet_attn& at = *blk.attn;
+        const int N = blk.N, H = at.H, Fq = z.F, T = z.T;
+        if (Fq != at.F && !err) {
+            babe_set_error("unet: an attention branch built for F=%d runs at F=%d", at.F, Fq);
+            err = BABE_ERR_ARG;
+        }
+        const long n = (long)(N / G_GROUPS) * Fq * T;
+        const int Sp = splits(n);
+        double* part = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * Sp * 2 * 2));
+        float* stats = alloc((size_t)B() * G_GROUPS * 3);
+        float* scale = alloc((size_t)B() * N);
+        View a1 = buf(H, Fq, T);
+        View qk = view(alloc((size_t)B() * 2 * H * Fq * T), 2 * H * Fq, 1, T);
+        View o = buf(H, Fq, T);
+        float* lse = alloc((size_t)B() * H * T);
+        const int* bucket = at.emb ? bucket_table(at, T) : nullptr;
+        float* gate;
+        if (B() == 1) gate = const_cast<float*>(film_at(at.film_gate));
+        else gate = alloc((size_t)B() * N);
+        View zn = buf(N, Fq, T);
+        rec = SavedAttn{z, stats, scale, gate, a1.p, qk.p, o.p, lse, bucket};
+        if (dry() || err) return zn;
+        ck(babe_gn_partial(z.p, part, B(), G_GROUPS, n, Sp, st));
+        ck(babe_gn_finalize(part, at.gamma, film_at(at.film_aff), S->film_bs, stats, scale, B(), N, G_GROUPS, n, Sp, GN_EPS, st));
+        conv(z, at.proj_in, a1, 1, false, nullptr, nullptr, scale, nullptr, 1.f, 0.f);
+        conv(view(a1.p, H * Fq, 1, T), at.qk, qk, 1, false, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f);
+        if (!err)
+            ck((P->attn_core == 2 ? babe_attn_fwd_bf16 : babe_attn_fwd)(qk.p, at.qk_bias, a1.p, bucket, at.emb, at.emb ? at.num_buckets : 0, o.p,
+                                                                        lse, B(), H, Fq, T, at.scale, st));
+        if (B() > 1 && !err) ck(babe_axpby4d(film_at(at.film_gate), S->film_bs, 0, gate, N, 0, B(), 1, 1, N, 1.f, 0.f, st));
+        conv(o, at.proj_out, zn, 1, false, nullptr, &z, nullptr, gate, RS2, RS2);
+        return zn;
+    }
+    // gz <- gradient w.r.t. the branch's input z, given cd * gz = gradient w.r.t. its output z' (in place).  The scalars are formed
+    // in double and rounded once, as the Python sequencer's RS2 * c is
+    void attn_vjp(const babe_unet_block& blk, const SavedAttn& rec, const View& gz, double cd) {
+        const babe_unet_attn& at = *blk.attn;
+        const View& z = rec.z;
+        const int N = blk.N, H = at.H, Fq = z.F, T = z.T;
+        const float rc = (float)(RS2D * cd);
+        const size_t m = mark();
+        View dout = buf(H, Fq, T);
+        View dqk = view(alloc((size_t)B() * 2 * H * Fq * T), 2 * H * Fq, 1, T);
+        View dv = buf(H, Fq, T);
+        float* D = alloc((size_t)B() * H * T);
+        View da1 = view(alloc((size_t)B() * H * Fq * T), H * Fq, 1, T);
+        View da0 = buf(N, Fq, T);
+        const int Sp = splits((long)(N / G_GROUPS) * Fq * T);
+        double* part = reinterpret_cast<double*>(alloc((size_t)B() * G_GROUPS * Sp * 2));
+        release(m);
+        if (dry() || err) return;
+        conv(gz, at.proj_out, dout, 1, true, nullptr, nullptr, rec.gate, nullptr, rc, 0.f);
+        if (!err)
+            ck((P->attn_core == 2 ? babe_attn_vjp_bf16 : babe_attn_vjp)(rec.qk, at.qk_bias, rec.a1, rec.bucket, at.emb, at.emb ? at.num_buckets : 0,
+                                                                        rec.o, rec.lse, dout.p, D, dqk.p, dv.p, B(), H, Fq, T, at.scale, st));
+        const View dvf = view(dv.p, H * Fq, 1, T);
+        conv(dqk, at.qk, da1, 1, true, nullptr, &dvf, nullptr, nullptr, 1.f, 1.f);
+        conv(view(da1.p, H, Fq, T), at.proj_in, da0, 1, true, nullptr, nullptr, nullptr, nullptr, 1.f, 0.f);
+        if (err) return;
+        ck(babe_gn_bwd_partial_nogelu(z.p, da0.p, rec.scale, part, B(), N, G_GROUPS, (long)Fq * T, Sp, st));
+        ck(babe_gn_bwd_apply_nogelu(z.p, da0.p, gz.p, rec.scale, rec.stats, part, gz.p, rc, B(), N, G_GROUPS, (long)Fq * T, Sp, GN_EPS, st));
+    }
+
     // ---- ResnetBlock (unet_engine.py block_fwd / block_vjp)
     // fold (an output head): the caller's next step is fold = RS2 * out + RS2 * fold; a block that runs as the fused pass
     // (babe_pw_block_supported) does that itself, writes fold instead of out and sets *folded
@@ -207,6 +306,7 @@ struct Ctx {
             z = buf(N, Fq, T);
             axpby(x, z);
         }
+        if (blk.attn) z = attn_fwd(blk, attn_rec(saved), z);
         // bf16 images: the GELU output goes to the wide (5,3) convs as bf16 units (half the bytes, both conv operands by LDS-DMA).
         // The buffer is carved wherever the static rule holds, whatever the per-layer verdict will be, so that
         // babe_unet_workspace_bytes does not depend on it; an fp32 plan never carves it.
@@ -245,7 +345,7 @@ struct Ctx {
             // carved as for the layer-by-layer form, so that babe_unet_workspace_bytes does not depend on the switch
             babe_pw_args pa;
             memset(&pa, 0, sizeof pa);
-            if (blk.nd == 1 && !blk.k53 && !dry() && !err) {
+            if (blk.nd == 1 && !blk.k53 && !blk.attn && !dry() && !err) {
                 pa.B = B(); pa.F = Fq; pa.T = T; pa.S = Sp;
                 pa.plan_splits = P->main_blk[0].H[0].splits;                     // the (5,3) layers carry the network's precision
                 pa.z = z.p; pa.z_bs = z.bs; pa.z_cs = z.cs;
@@ -332,7 +432,7 @@ struct Ctx {
         const int N = blk.N, Fq = g_out.F, T = g_out.T;
         const float beta = accumulate ? 1.f : 0.f;
         auto da_view = [&]() { View v; v.p = scratch_a((size_t)B() * N * Fq * T); v.C = N; v.F = Fq; v.T = T; v.cs = (long)Fq * T; v.bs = (long)N * Fq * T; return v; };
-        if (!blk.res_conv.Cout && !blk.proj_out.Cout && !blk.proj_in.Cout && !accumulate && blk.nd > 0 && g_out.dense()) {
+        if (!blk.res_conv.Cout && !blk.proj_out.Cout && !blk.proj_in.Cout && !accumulate && blk.nd > 0 && g_out.dense() && !blk.attn) {
             View gz;
             if (blk.nd > 1) gz = buf(N, Fq, T);
             View da = da_view();
@@ -371,6 +471,10 @@ struct Ctx {
             double* part;
             const int Sf = conv_vjp(gz, blk, d, da, saved[d], &part);
             gn_bwd(saved[d], da, gz, gz, RS2, nullptr, part, Sf);
+        }
+        if (blk.attn) {
+            attn_vjp(blk, attn_rec(saved), gz, c == 1.f ? 1.0 : RS2D);
+            c = 1.f;
         }
         if (blk.proj_in.Cout) conv(gz, blk.proj_in, g_in, 1, true, nullptr, &g_in, nullptr, nullptr, c, 1.f);
         else axpby(gz, g_in, c, 1.f);
@@ -554,6 +658,26 @@ bool desc_ok(const babe_unet_plan_desc* d) {
     }
     return block_ok(d->mid_blk, true) && block_ok(d->mid_out, true);
 }
+// One attention branch of block b, which runs at F frequency rows: what the sequencer dereferences, and the shapes the attention
+// kernels take (attn_check_shape, csrc/attention_common.h).  false: the message names the field.
+bool attn_ok(const babe_unet_attn& a, const babe_unet_block& b, int attn_core, int F) {
+    const char* bad = nullptr;
+    const auto conv11 = [](const babe_packed_conv& pc, int Cout, int Cin) {
+        return pc.Cout == Cout && pc.Cin == Cin && pc.KH == 1 && pc.KW == 1 && (pc.fwd || pc.w_raw) && (pc.bwd || pc.w_raw);
+    };
+    if (attn_core == 0) bad = "attn_core = 0 (choose the attention core: 1 fp32, 2 bf16) while a block has an attention branch";
+    else if (a.H < 1 || a.H > 64) bad = "babe_unet_attn.H (1..64 heads)";
+    else if (a.F != F || a.F % 64 || a.F < 64 || a.F > 448) bad = "babe_unet_attn.F (the block's frequency rows: a multiple of 64, at most 448)";
+    else if (!(a.scale > 0.f)) bad = "babe_unet_attn.scale";
+    else if (!a.gamma) bad = "babe_unet_attn.gamma";
+    else if (a.film_aff < 0 || a.film_gate < 0) bad = "babe_unet_attn.film_aff / film_gate";
+    else if (!conv11(a.proj_in, a.H, b.N)) bad = "babe_unet_attn.proj_in (a packed (1,1) conv N -> H)";
+    else if (!conv11(a.qk, 2 * a.H * a.F, a.H * a.F)) bad = "babe_unet_attn.qk (a packed (1,1) conv H*F -> 2*H*F)";
+    else if (!conv11(a.proj_out, b.N, a.H)) bad = "babe_unet_attn.proj_out (a packed (1,1) conv H -> N)";
+    else if (a.emb && (a.num_buckets < 4 || a.num_buckets > 64)) bad = "babe_unet_attn.num_buckets (4..64)";
+    if (bad) babe_set_error("unet_plan_create: bad attention descriptor: %s", bad);
+    return !bad;
+}
 
 }  // namespace
 
@@ -563,11 +687,36 @@ extern "C" void* babe_unet_plan_create(const babe_unet_plan_desc* desc) {
                        "multiple of 8, gamma / FiLM offsets / packed weights present)");
         return nullptr;
     }
-    auto* p = static_cast<babe_unet_plan_desc*>(malloc(sizeof(babe_unet_plan_desc)));
-    if (p) memcpy(p, desc, sizeof *p);
+    if (desc->attn_core < 0 || desc->attn_core > 2) {
+        babe_set_error("unet_plan_create: attn_core = %d is none of 0 (no attention), 1 (fp32 core), 2 (bf16 core)", desc->attn_core);
+        return nullptr;
+    }
+    for (int i = 0; i < 8; ++i)
+        if (desc->init_blk[i].attn || desc->up_out[i].attn || desc->mid_out.attn) {
+            babe_set_error("unet_plan_create: babe_unet_block.attn is set on an init block or an output head (main, middle and decoder "
+                           "blocks carry attention)");
+            return nullptr;
+        }
+    auto* p = new (std::nothrow) UnetPlan();
+    if (!p) return nullptr;
+    memcpy(&p->d, desc, sizeof p->d);
+    const int n = desc->nocts;
+    for (int k = 0; k < 2 * n + 1; ++k) {                // main_blk[0..n), mid_blk, up_blk[0..n)
+        babe_unet_block& b = k < n ? p->d.main_blk[k] : (k == n ? p->d.mid_blk : p->d.up_blk[k - n - 1]);
+        const int level = k < n ? k : (k == n ? n - 1 : n - 1 - (k - n - 1));
+        if (!b.attn) continue;
+        AttnPlan& ap = p->at[p->nat++];
+        ap.a = *b.attn;
+        b.attn = &ap.a;
+        if (!attn_ok(ap.a, b, desc->attn_core, desc->bpo * (level + 1)) ||
+            (ap.a.emb && babe_attn_bucket_thresholds(&ap.thr, ap.a.num_buckets, ap.a.max_distance) != BABE_OK)) {
+            delete p;                                    // (the message is attn_ok's or babe_attn_bucket_thresholds')
+            return nullptr;
+        }
+    }
     return p;
 }
-extern "C" void babe_unet_plan_destroy(void* plan) { free(plan); }
+extern "C" void babe_unet_plan_destroy(void* plan) { delete static_cast<UnetPlan*>(plan); }
 extern "C" void* babe_unet_state_create(void) { return new babe_unet_state_s(); }
 extern "C" void babe_unet_state_destroy(void* st) { delete static_cast<babe_unet_state_s*>(st); }
 
@@ -593,7 +742,9 @@ extern "C" long babe_unet_workspace_bytes(const void* plan, int B, const int* T_
     const float* cdummy[8] = {};
     c.forward(cdummy, dummy);
     c.vjp(cdummy, dummy);
-    return (long)S.high + 256;
+    // exactly what the two passes carve (a multiple of the 256-byte granule; every buffer carries its own skew of slack behind it):
+    // a workspace one granule smaller is refused by the evaluation ("workspace too small")
+    return (long)S.high;
 }
 
 /* outs[i] / C_in[j]: caller-owned [B][2][bpo][T] tensors (index 0 = lowest octave); film: [B][J] FiLM vector of every layer
@@ -607,7 +758,7 @@ extern "C" int babe_unet_fwd(const void* plan, void* state, const float* const* 
     auto* S = static_cast<babe_unet_state_s*>(state);
     if (int e = unet_set_shape(S, P, B, T_oct)) return e;
     S->ws = static_cast<float*>(workspace); S->cap = (size_t)workspace_bytes; S->off = 0; S->high = 0; S->dry = false;
-    S->scr_a = nullptr; S->scr_a_n = 0; S->units = nullptr; S->units_n = 0; S->film = film; S->film_bs = film_bs; S->have_fwd = false;
+    S->scr_a = nullptr; S->scr_a_n = 0; S->units = nullptr; S->units_n = 0; S->nbuckets = 0; S->film = film; S->film_bs = film_bs; S->have_fwd = false;
     Ctx c{P, S, (hipStream_t)stream};
     c.forward(C_in, const_cast<float**>(outs));
     if (c.err) return c.err;

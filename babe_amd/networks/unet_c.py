@@ -9,7 +9,7 @@ import ctypes as C
 
 import torch
 
-from .._cabi import CBlock, CPackedConv, CPlanDesc
+from .._cabi import ATTN_CORES, CAttn, CBlock, CPackedConv, CPlanDesc
 from .._lib import check, lib, ptr, stream, workspace
 
 
@@ -33,6 +33,21 @@ def fill_block(dst, b):
         dst.fb_proj_in, dst.fb_res_conv = ptr(b.fb_proj_in), ptr(b.fb_res_conv)
 
 
+def c_attn(at):
+    """_Attn -> babe_unet_attn: copies of its three convs' descriptors, pointers to its gamma, qk bias and table."""
+    dst = CAttn()
+    dst.H, dst.F, dst.scale = at.H, at.F, at.scale
+    _pc(dst.proj_in, at.proj_in)
+    _pc(dst.qk, at.qk)
+    _pc(dst.proj_out, at.proj_out)
+    dst.gamma = ptr(at.gamma)
+    dst.film_aff, dst.film_gate = at.film_off
+    dst.qk_bias, dst.emb = ptr(at.qk_bias), ptr(at.emb)
+    if at.emb is not None:
+        dst.num_buckets, dst.max_distance = at.nbk, at.maxd
+    return dst
+
+
 def c_block(b):
     """A _Block as a babe_unet_block of its own: what the fused (1,1) block passes take from the Python sequencer."""
     dst = CBlock()
@@ -42,17 +57,21 @@ def c_block(b):
 
 class CPlan:
     """The library's description of one engine's packed weights (babe_unet_plan): immutable, made on first use, shared by every
-    library-side state over that engine and destroyed with the last of them."""
+    library-side state over that engine and destroyed with the last of them.  An engine with time-attention layers gets one only
+    on request (get(eng, attention=True)): its blocks' _Attn objects as babe_unet_attn, eng.attn_core as the plan's attn_core."""
 
     handle = None
 
-    def get(self, eng):
+    def get(self, eng, attention=False):
         if self.handle is None:
-            if eng.has_attention:
+            if eng.has_attention and not attention:
                 raise NotImplementedError("the library-side UNet sequencer does not support time-attention layers "
                                           "(such networks run on the Python sequencer)")
             d = CPlanDesc()
             d.nocts, d.bpo = eng.nocts, eng.bpo
+            attns = []                                   # (the library copies them at plan creation)
+            if eng.has_attention:
+                d.attn_core = ATTN_CORES[eng.attn_core]
             for i, v in enumerate(eng.Ns):
                 d.Ns[i] = v
             for i in range(eng.nocts):
@@ -63,6 +82,11 @@ class CPlan:
                 _pc(d.pyr_conv[i], eng.pyr_conv[i])
             fill_block(d.mid_blk, eng.mid_blk)
             fill_block(d.mid_out, eng.mid_out)
+            for dst, blk in [(d.main_blk[i], eng.main_blk[i]) for i in range(eng.nocts)] + [(d.mid_blk, eng.mid_blk)] + \
+                    [(d.up_blk[i], eng.up_blk[i]) for i in range(eng.nocts)]:
+                if blk.attn is not None:
+                    attns.append(c_attn(blk.attn))
+                    dst.attn = C.pointer(attns[-1])
             self.handle = lib().babe_unet_plan_create(C.byref(d))
             if not self.handle:
                 raise RuntimeError("babe_unet_plan_create: " + lib().babe_last_error().decode())
@@ -81,8 +105,10 @@ class CUnet:
     """One library-side state and workspace over an engine's plan (UnetEngine.c_plan): one per engine state on the BABE_UNET_C
     path, one per lane for testing/eval_c.py.  Belongs to one stream at a time."""
 
-    def __init__(self, eng):
-        self.plan = eng.c_plan()
+    def __init__(self, eng, attention=False):
+        """attention=True: also for an engine with time-attention layers (UnetEngine.c_plan(attention=True)); without it such an
+        engine raises."""
+        self.plan = eng.c_plan(attention=True) if attention else eng.c_plan()
         self._owner = eng._plan                          # keeps the plan alive as long as this state
         self.n = eng.nocts
         self.state = lib().babe_unet_state_create()

@@ -634,10 +634,12 @@ class UnetEngine:
         return g_in
 
     # ------------------------------------------------------------------ forward
-    def c_plan(self):
+    def c_plan(self, attention=False):
         """The library-side plan over this engine's packed weights (networks/unet_c.py), made on first use.  Every handle and
-        every library-side state - the BABE_UNET_C path's and testing/eval_c.py's - shares this one."""
-        return self._plan.get(self)
+        every library-side state - the BABE_UNET_C path's and testing/eval_c.py's - shares this one.
+        attention=True: the opt-in for an engine with time-attention layers, whose plan carries its _Attn objects and attn_core;
+        without it such an engine raises (the Python routing, _c_engine, never asks for one)."""
+        return self._plan.get(self, attention=attention)
 
     def _c_engine(self):
         """The library-side sequencer of this handle's state (its own library-side state and workspace over c_plan()), or None:

@@ -11,14 +11,21 @@ from .._lib import BabeHipError, check, lib, stream
 
 class LibraryModel:
     """babe_model_load_ex(path, precision) on the current device and stream; `close()` (or garbage collection) destroys it.
-    precision: 'f32' | 'bf16' | 'bf16x3' (ops.PRECISIONS) - the host's choice, the file holds the fp32 masters.  Plans and
-    descriptors taken from it point into its arena: keep the object alive while they are in use."""
+    precision: 'f32' | 'bf16' | 'bf16x3' (ops.PRECISIONS) - the host's choice, the file holds the fp32 masters.
+    attention_precision: None - a file with time-attention layers is refused -, or the attention core such a file runs on, 'f32' |
+    'bf16' (babe_model_load_opt), as the Python network's option of that name.  Plans and descriptors taken from it point into
+    its arena: keep the object alive while they are in use."""
 
-    def __init__(self, path, precision="f32"):
+    def __init__(self, path, precision="f32", attention_precision=None):
+        from .._cabi import ATTN_CORES, ModelOptions
         from ..ops import PRECISIONS
-        self.handle = lib().babe_model_load_ex(str(path).encode(), PRECISIONS[precision], stream())
+        if attention_precision is None:
+            self.handle, who = lib().babe_model_load_ex(str(path).encode(), PRECISIONS[precision], stream()), "babe_model_load_ex"
+        else:
+            opt = ModelOptions(precision=PRECISIONS[precision], attention=ATTN_CORES[attention_precision])
+            self.handle, who = lib().babe_model_load_opt(str(path).encode(), C.byref(opt), stream()), "babe_model_load_opt"
         if not self.handle:
-            raise BabeHipError("babe_model_load_ex: " + lib().babe_last_error().decode())
+            raise BabeHipError(who + ": " + lib().babe_last_error().decode())
 
     def close(self):
         if getattr(self, "handle", None):
@@ -41,6 +48,11 @@ class LibraryModel:
     def precision(self):
         """babe_model_precision: 0 f32, 1 bf16, 2 bf16x3."""
         return lib().babe_model_precision(self.handle)
+
+    @property
+    def attention(self):
+        """babe_model_attention: 0 refused, 1 the fp32 core, 2 the bf16 core."""
+        return lib().babe_model_attention(self.handle)
 
     def setting(self, key):
         v = C.c_double()

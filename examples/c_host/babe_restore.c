@@ -1,14 +1,15 @@
 /* babe_restore: blind bandwidth extension of one clip batch from C - no Python, no torch in the process.
  *
  *     babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32] [--precision f32|bf16|bf16x3]
- *                  [--fir NUMTAPS FC WIDTH | --declip C]
+ *                  [--attention f32|bf16] [--fir NUMTAPS FC WIDTH | --declip C]
  *
  * model.babe: written by `python -m babe_amd.export`.  in.f32: B * L float32 samples at the model's rate (L and the rate are the
  * model's: babe_model_info), B clips one after the other.  out.f32: the B * L restored samples.  --params: the estimated filter
  * of each clip, B * 2 * K float32 (K cut-off frequencies in Hz, then K slopes in dB).  --T: sampling steps (default: the file's
  * tester.T); --seed: the noise is the library's counter-based generator under this seed (default 0), so the output is a function
  * of (model, input, seed, T, precision).  --precision: the conv arithmetic the loader packs the file's fp32 weights for (default
- * f32; bf16 is the fast one).  --fir: the input was degraded by a KNOWN low-pass FIR - scipy.signal.firwin(NUMTAPS, FC, width=WIDTH,
+ * f32; bf16 is the fast one).  --attention: the core a model with time-attention layers runs them on (without it such a file is
+ * refused).  --fir: the input was degraded by a KNOWN low-pass FIR - scipy.signal.firwin(NUMTAPS, FC, width=WIDTH,
  * window="kaiser", fs=the model's rate), designed here by babe_firwin_kaiser - and is restored against it, no filter is fitted;
  * --declip: the input was clipped at +-C and is restored against the clip.  With either, --params writes the initial filter back.
  * Links against libbabe_hip.so and the HIP runtime (babe_amd/build.py::build_example).
@@ -27,6 +28,8 @@
 static int precision_of(const char* s) {
     return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
 }
+
+static int attention_of(const char* s) { return !strcmp(s, "f32") ? BABE_ATTENTION_F32 : !strcmp(s, "bf16") ? BABE_ATTENTION_BF16 : -1; }
 
 static double setting(const void* model, const char* key, double fallback) {
     double v;
@@ -56,7 +59,7 @@ static int observe_fir(babe_eval_desc* e, int numtaps, double fc, double width, 
 }
 
 int main(int argc, char** argv) {
-    int status = 1, B = 1, T = 0, precision = BABE_PRECISION_F32, fir_n = 0;
+    int status = 1, B = 1, T = 0, precision = BABE_PRECISION_F32, attention = BABE_ATTENTION_REFUSE, fir_n = 0;
     double fir_fc = 0, fir_width = 0, declip = -1;
     long seed = 0;
     const char* params_path = NULL;
@@ -66,7 +69,7 @@ int main(int argc, char** argv) {
     FILE* fh = NULL;
     if (argc < 4) {
         fprintf(stderr, "usage: babe_restore model.babe in.f32 out.f32 [--seed N] [--T n] [--batch B] [--params out_params.f32] "
-                        "[--precision f32|bf16|bf16x3] [--fir NUMTAPS FC WIDTH | --declip C]\n");
+                        "[--precision f32|bf16|bf16x3] [--attention f32|bf16] [--fir NUMTAPS FC WIDTH | --declip C]\n");
         return 2;
     }
     for (int i = 4; i < argc; ++i) {
@@ -77,6 +80,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--params")) params_path = argv[++i];
         else if (!strcmp(argv[i], "--precision")) {
             if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
+        else if (!strcmp(argv[i], "--attention")) {
+            if ((attention = attention_of(argv[++i])) < 0) FAIL("--attention is one of f32, bf16");
         }
         else if (!strcmp(argv[i], "--fir")) {
             if (i + 3 >= argc) FAIL("--fir needs NUMTAPS FC WIDTH");
@@ -94,8 +100,9 @@ int main(int argc, char** argv) {
 
     /* [core] the listing of INTEGRATION.md section 2 */
     /* 1. the network: weights, packed images, CQT plan, STFT tables - one handle, one device arena */
-    model = babe_model_load_ex(argv[1], precision, NULL);
-    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
+    const babe_model_options options = {precision, attention, {0}};      /* attention: REFUSE unless --attention chose a core */
+    model = babe_model_load_opt(argv[1], &options, NULL);
+    if (!model) FAIL("babe_model_load_opt: %s", babe_last_error());
     babe_model_summary info;
     LIB(babe_model_info(model, &info), "babe_model_info");
     const long L = info.L;

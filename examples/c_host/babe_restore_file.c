@@ -3,6 +3,7 @@
  *
  *     babe_restore_file model.babe in.f32 RATE out.f32 [--denoiser denoiser.babe] [--seed N] [--T n] [--blind-segments N]
  *                       [--ix-start s] [--precision f32|bf16|bf16x3]
+ *                       [--attention f32|bf16]
  *
  * model.babe: written by `python -m babe_amd.export`; denoiser.babe: by `python -m babe_amd.export_denoiser`.  in.f32: the
  * recording, float32 samples of any length at RATE Hz.  out.f32: the restored recording at the MODEL's rate.  The file is
@@ -12,7 +13,8 @@
  * over the file), then the file is restored segment by segment, every segment out-painted from the end of the previous one.
  * The estimated filter is printed: K cut-off frequencies in Hz, then K slopes in dB.  --T: sampling steps (default: the file's
  * tester.T); --seed: the noise is the library's counter-based generator under this seed (default 0), so the output is a
- * function of (model, input, seed, T, blind segments).  Links against libbabe_hip.so and the HIP runtime
+ * function of (model, input, seed, T, blind segments).  --attention: the core a model with time-attention layers runs them
+ * on (without it such a file is refused).  Links against libbabe_hip.so and the HIP runtime
  * (babe_amd/build.py::build_example).  Exit status: 0, or 1 with the failing step and babe_last_error() on stderr. */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -33,13 +35,15 @@ static int precision_of(const char* s) {
     return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
 }
 
+static int attention_of(const char* s) { return !strcmp(s, "f32") ? BABE_ATTENTION_F32 : !strcmp(s, "bf16") ? BABE_ATTENTION_BF16 : -1; }
+
 static double setting(const void* model, const char* key, double fallback) {
     double v;
     return babe_model_setting(model, key, &v) == 0 ? v : fallback;
 }
 
 int main(int argc, char** argv) {
-    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32;
+    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32, attention = BABE_ATTENTION_REFUSE;
     long seed = 0, Lfile = 0, Lrec = 0, fs_file = 0;
     double ix_start = 0.0;
     const char* denoiser_path = NULL;
@@ -51,7 +55,7 @@ int main(int argc, char** argv) {
     FILE* fh = NULL;
     if (argc < 5) {
         fprintf(stderr, "usage: babe_restore_file model.babe in.f32 RATE out.f32 [--denoiser denoiser.babe] [--seed N] [--T n] "
-                        "[--blind-segments N] [--ix-start s] [--precision f32|bf16|bf16x3]\n");
+                        "[--blind-segments N] [--ix-start s] [--precision f32|bf16|bf16x3] [--attention f32|bf16]\n");
         return 2;
     }
     fs_file = atol(argv[3]);
@@ -65,6 +69,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ix-start")) ix_start = atof(argv[++i]);
         else if (!strcmp(argv[i], "--precision")) {
             if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
+        else if (!strcmp(argv[i], "--attention")) {
+            if ((attention = attention_of(argv[++i])) < 0) FAIL("--attention is one of f32, bf16");
         }
         else FAIL("unknown option %s", argv[i]);
     }
@@ -82,8 +89,9 @@ int main(int argc, char** argv) {
 
     /* [core] the listing of INTEGRATION.md, "A recording file at any rate, with the denoiser" */
     /* 1. the network, the denoiser and one evaluation's bookkeeping */
-    model = babe_model_load_ex(argv[1], precision, NULL);
-    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
+    const babe_model_options options = {precision, attention, {0}};      /* attention: REFUSE unless --attention chose a core */
+    model = babe_model_load_opt(argv[1], &options, NULL);
+    if (!model) FAIL("babe_model_load_opt: %s", babe_last_error());
     if (denoiser_path && !(denoiser = babe_denoiser_load(denoiser_path, NULL))) FAIL("babe_denoiser_load: %s", babe_last_error());
     state = babe_unet_state_create();
     if (!state) FAIL("babe_unet_state_create failed");

@@ -2,6 +2,7 @@
  *
  *     babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s]
  *                            [--precision f32|bf16|bf16x3]
+ *                            [--attention f32|bf16]
  *
  * model.babe: written by `python -m babe_amd.export`.  in.f32: the recording, float32 samples of any length at the model's rate.
  * out.f32: the restored recording, as many samples.  The low-pass filter of the recording is estimated blind on
@@ -9,7 +10,8 @@
  * over the file), then the file is restored segment by segment, every segment out-painted from the end of the previous one.
  * The estimated filter is printed: K cut-off frequencies in Hz, then K slopes in dB.  --T: sampling steps (default: the file's
  * tester.T); --seed: the noise is the library's counter-based generator under this seed (default 0), so the output is a
- * function of (model, input, seed, T, blind segments).  Links against libbabe_hip.so and the HIP runtime
+ * function of (model, input, seed, T, blind segments).  --attention: the core a model with time-attention layers runs them
+ * on (without it such a file is refused).  Links against libbabe_hip.so and the HIP runtime
  * (babe_amd/build.py::build_example).  Exit status: 0, or 1 with the failing step and babe_last_error() on stderr. */
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -30,13 +32,15 @@ static int precision_of(const char* s) {
     return !strcmp(s, "f32") ? BABE_PRECISION_F32 : !strcmp(s, "bf16") ? BABE_PRECISION_BF16 : !strcmp(s, "bf16x3") ? BABE_PRECISION_BF16X3 : -1;
 }
 
+static int attention_of(const char* s) { return !strcmp(s, "f32") ? BABE_ATTENTION_F32 : !strcmp(s, "bf16") ? BABE_ATTENTION_BF16 : -1; }
+
 static double setting(const void* model, const char* key, double fallback) {
     double v;
     return babe_model_setting(model, key, &v) == 0 ? v : fallback;
 }
 
 int main(int argc, char** argv) {
-    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32;
+    int status = 1, T = 0, n_blind = 1, precision = BABE_PRECISION_F32, attention = BABE_ATTENTION_REFUSE;
     long seed = 0, Lrec = 0;
     double ix_start = 0.0;
     void *model = NULL, *state = NULL, *ws = NULL;
@@ -45,7 +49,7 @@ int main(int argc, char** argv) {
     FILE* fh = NULL;
     if (argc < 4) {
         fprintf(stderr, "usage: babe_restore_recording model.babe in.f32 out.f32 [--seed N] [--T n] [--blind-segments N] [--ix-start s] "
-                        "[--precision f32|bf16|bf16x3]\n");
+                        "[--precision f32|bf16|bf16x3] [--attention f32|bf16]\n");
         return 2;
     }
     for (int i = 4; i < argc; ++i) {
@@ -56,6 +60,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--ix-start")) ix_start = atof(argv[++i]);
         else if (!strcmp(argv[i], "--precision")) {
             if ((precision = precision_of(argv[++i])) < 0) FAIL("--precision is one of f32, bf16, bf16x3");
+        }
+        else if (!strcmp(argv[i], "--attention")) {
+            if ((attention = attention_of(argv[++i])) < 0) FAIL("--attention is one of f32, bf16");
         }
         else FAIL("unknown option %s", argv[i]);
     }
@@ -73,8 +80,9 @@ int main(int argc, char** argv) {
 
     /* [core] the listing of INTEGRATION.md, "A whole recording from one call" */
     /* 1. the network and one evaluation's bookkeeping, as in babe_restore.c */
-    model = babe_model_load_ex(argv[1], precision, NULL);
-    if (!model) FAIL("babe_model_load_ex: %s", babe_last_error());
+    const babe_model_options options = {precision, attention, {0}};      /* attention: REFUSE unless --attention chose a core */
+    model = babe_model_load_opt(argv[1], &options, NULL);
+    if (!model) FAIL("babe_model_load_opt: %s", babe_last_error());
     state = babe_unet_state_create();
     if (!state) FAIL("babe_unet_state_create failed");
     babe_recording_desc d;

@@ -310,6 +310,22 @@ int babe_conv2d_bf16_units_shape(const babe_packed_conv* pc, int T);
 int babe_packed_conv_pack(const babe_packed_conv* pc, const float* w, void* stream);
 /* conv with the kernel chosen by the library; a->w_packed, Cin, Cout, KH, KW are filled in from pc / transpose */
 int babe_conv2d_auto(babe_conv_args* a, const babe_packed_conv* pc, int transpose, void* stream);
+/* The time-attention branch of a ResnetBlock (TimeAttentionBlock; babe_amd/networks/unet_engine.py::_Attn), between the block's
+ * proj_in and its dilation stack:
+ *   a1 = proj_in(z * scale2)   scale2 = gamma * (affine2(emb) + 1) / (std_g(z) + eps), no GELU
+ *   qk = qk(a1 as [B][H*F][1][T])      o = attention(qk, V = a1)      z' = (gate2(emb) * proj_out(o) + z) / sqrt2
+ * The attention core is the plan's (babe_unet_plan_desc::attn_core).  The relative-position bucket table of a time length is
+ * built in the workspace by babe_attn_bucket_table from thresholds computed once at plan creation. */
+typedef struct {
+    int H, F;                          /* heads; features per head = the block's frequency rows (a multiple of 64, at most 448) */
+    float scale;                       /* F^-1/2 */
+    babe_packed_conv proj_in, qk, proj_out;   /* N -> H (1,1); H*F -> 2*H*F (1,1) on the [B][H*F][1][T] view; H -> N (1,1) */
+    const float* gamma;                /* norm2's gamma [N] */
+    int film_aff, film_gate;           /* offsets of affine2 / gate2 in the FiLM row */
+    const float* qk_bias;              /* [2*H*F], or NULL */
+    const float* emb;                  /* relative-position table [num_buckets][H], or NULL: no relative bias */
+    int num_buckets, max_distance;     /* read with emb only */
+} babe_unet_attn;
 typedef struct {                       /* one ResnetBlock */
     int N, nd, k53;                    /* channels of the dilated stack, dilation layers (dilation 2^d when k53), (5,3) kernels? */
     babe_packed_conv proj_in, res_conv, proj_out, H[8];
@@ -317,14 +333,21 @@ typedef struct {                       /* one ResnetBlock */
     int film_aff[8], film_gate[8];     /* offsets of layer d's affine / gate vectors in the FiLM row */
     const float *fb_proj_in, *fb_res_conv;   /* babe_conv_args::fbias [N][bpo] of proj_in / res_conv: an init block with folded
                                               * frequency encodings (its packed convs hold the 2 signal columns); NULL: none */
+    const babe_unet_attn* attn;        /* the block's time-attention branch, NULL: none.  Main, middle and decoder blocks only;
+                                        * such a block never runs as the fused (1,1) pass */
 } babe_unet_block;
 typedef struct {
     int nocts, bpo;                    /* octaves (7), bins per octave (64) */
     int Ns[8];
     babe_unet_block init_blk[8], main_blk[8], up_out[8], up_blk[8], mid_blk, mid_out;
     babe_packed_conv pyr_conv[8];
+    int attn_core;                     /* what the attention branches launch: 0 none (a block with attn is refused), 1 babe_attn_fwd /
+                                        * _vjp (fp32), 2 babe_attn_fwd_bf16 / _vjp_bf16 */
 } babe_unet_plan_desc;
-void* babe_unet_plan_create(const babe_unet_plan_desc* desc);      /* copies the descriptor (pointers stay the caller's) */
+/* copies the descriptor and every babe_unet_attn it points to (the weights stay the caller's).  NULL with a message naming the
+ * field, before any launch: an attention branch with attn_core 0, a shape babe_attn_fwd refuses (F, num_buckets), a
+ * num_buckets / max_distance pair babe_attn_bucket_thresholds refuses, a missing image, gamma or FiLM offset */
+void* babe_unet_plan_create(const babe_unet_plan_desc* desc);
 void babe_unet_plan_destroy(void* plan);
 void* babe_unet_state_create(void);                                 /* one evaluation's bookkeeping; one per concurrent stream */
 void babe_unet_state_destroy(void* state);
@@ -857,6 +880,16 @@ int babe_dn_istft(const float* P, float* frames_ws, float* y, long y_bs, int Lou
  *   S[n][m] = (Q[:,n].K[:,m] + emb[bucket[m - n + T - 1]][h]) * scale;  out[:,n] = sum_m softmax_m(S[n]) V[:,m]
  * bucket [2T-1] (babe_attn_buckets) and emb [num_buckets][H] (at most 64 buckets): both NULL without the relative bias. */
 int babe_attn_buckets(int* out, int T, int num_buckets, int max_distance);   /* host function: T5 bidirectional buckets */
+/* The same table written on the device, for a sequencer that may neither allocate nor copy (csrc/unet_engine.hip).  The bucket of
+ * an offset d is non-decreasing in |d| and constant from max_distance on, so half - 1 thresholds describe it (half =
+ * num_buckets / 2): thr[k - 1] = the smallest |d| whose bucket within its half is >= k.  babe_attn_bucket_thresholds is a host
+ * function that derives them from babe_attn_buckets itself (no logarithm is evaluated anywhere else) and refuses what the table
+ * kernel cannot take: num_buckets odd or outside 4..64, max_distance outside num_buckets / 4 + 1 .. 65536, a table that is not
+ * monotone or does not reach its last bucket at max_distance.  babe_attn_bucket_table writes out[0 .. 2T-2] (device, int32) =
+ * babe_attn_buckets(T, num_buckets, max_distance) entry for entry; the thresholds travel by value as the kernel's argument. */
+typedef struct { int half, max_distance; int thr[32]; } babe_attn_bucket_thr;
+int babe_attn_bucket_thresholds(babe_attn_bucket_thr* out, int num_buckets, int max_distance);
+int babe_attn_bucket_table(const babe_attn_bucket_thr* thr, int T, int* out, void* stream);
 int babe_attn_fwd(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb, int num_buckets,
                   float* out, float* lse, int B, int H, int F, int T, float scale, void* stream);
 /* input-VJP of babe_attn_fwd for the gradient dout of out: dqk [B][2HF][T] (dQ and dK, the gradients w.r.t. the qk rows) and
@@ -1009,7 +1042,7 @@ int babe_scale_channels(const float* x, const float* scale, float* out, int B, i
  * and descriptor taken from it: destroy it last.
  * Refused with a message, before any device call, nothing allocated: a missing or empty file, a wrong magic, an unknown version, a
  * truncated file, tensor data that overlaps or leaves the file, a duplicate / missing / unexpected name, a shape that does not fit
- * the settings, attention flags, a file whose network.precision is not f32, a requested precision outside 0..2, use_fencoding with
+ * the settings, attention flags (unless babe_model_load_opt / _create_opt opt in), a file whose network.precision is not f32, a requested precision outside 0..2, use_fencoding with
  * bins per octave != 64, an audio length the mixed-radix FFT plan does not cover. */
 typedef struct { const char* name; int ndim; long shape[4]; const float* data; } babe_model_entry;   /* host fp32, state_dict name */
 typedef struct { const char* key; const char* str; double num; } babe_model_kv;                       /* str != NULL: a string setting */
@@ -1029,7 +1062,21 @@ void* babe_model_create(const babe_model_entry* entries, int n, const babe_model
 void* babe_model_load_ex(const char* path, int precision, void* stream);
 void* babe_model_create_ex(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings, int precision,
                            void* stream);
+/* the same with the attention core chosen as well.  attention = BABE_ATTENTION_REFUSE: a file with network.attention_layers set
+ * is refused, as by every form above (they are these with REFUSE); _F32 / _BF16: such a file loads and its attention branches run
+ * on babe_attn_fwd / _vjp or on the _bf16 pair, whatever `precision` is - the host's opt-in, as attention_precision is in Python.
+ * The loader reads network.attention_layers.* and the network.attention_dict.* leaves num_heads, bias_qkv, use_rel_pos,
+ * rel_pos_num_buckets, rel_pos_max_distance (defaults 8, 0, 1, 32, 64), expects the branch's tensors (norm2.gamma, affine2.*,
+ * gate2.*, attn_block.proj_in / proj_out / qk.weight, qk.bias with bias_qkv, rel_pos.relative_attention_bias.weight with
+ * use_rel_pos) and refuses what the kernels do not cover.  On a file without attention layers the choice does nothing.
+ * reserved: zero. */
+enum { BABE_ATTENTION_REFUSE = 0, BABE_ATTENTION_F32 = 1, BABE_ATTENTION_BF16 = 2 };
+typedef struct { int precision; int attention; int reserved[6]; } babe_model_options;
+void* babe_model_load_opt(const char* path, const babe_model_options* options, void* stream);
+void* babe_model_create_opt(const babe_model_entry* entries, int n, const babe_model_kv* settings, int nsettings,
+                            const babe_model_options* options, void* stream);
 int babe_model_precision(const void* model);                         /* what it was loaded with; -1: null model */
+int babe_model_attention(const void* model);                         /* the attention core it was loaded with (BABE_ATTENTION_*); -1: null model */
 void babe_model_destroy(void* model);
 int babe_model_info(const void* model, babe_model_summary* info);
 int babe_model_setting(const void* model, const char* key, double* value);   /* a numeric setting of the file; strings and unknown keys: error */
