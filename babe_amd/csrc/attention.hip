@@ -21,46 +21,11 @@
 // The scores are formed TRANSPOSED where the probabilities feed the next product as its B operand (forward, dQ: S^T, rows =
 // keys) and untransposed where they feed it as B over queries (dK/dV: S, rows = queries): the accumulator's four rows per lane
 // are then exactly the k-slots of four consecutive MFMA steps, so P never leaves its registers.
-#include "attention_common.h"
+#include "attention_f32.h"
 #include "../../include/babe_hip.h"
 #include <cmath>
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ float max16x4(float v) {           // max over the 4 lane groups that share l%16
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float sum16x4(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
-}
-
-struct AttnPtrs {
-    const float* q;       // batch-b, head-h base of Q rows (K rows follow at + F*T)
-    const float* qb;      // q-bias of the head (nullptr: none), K bias at + F
-    const float* v;       // a[b][h]
-    const int* bucket;    // [2T-1] or nullptr
-    const float* emb;     // [nb][H]
-};
-
-__device__ __forceinline__ float rel_bias(const AttnPtrs& p, const float* emb_lds, int m, int n, int T) {
-    return p.bucket ? emb_lds[p.bucket[m - n + T - 1]] : 0.f;
-}
-
-// 16 columns (time steps c0..c0+15) of a [F][T] operand into LDS [F][16], zero past T, plus an optional per-row bias
-__device__ __forceinline__ void stage16(float* dst, const float* src, const float* rb, int F, int T, int c0) {
-    for (int i = threadIdx.x; i < F * 16; i += 64) {
-        const int f = i >> 4, c = c0 + (i & 15);
-        dst[i] = c < T ? src[(long)f * T + c] + (rb ? rb[f] : 0.f) : 0.f;
-    }
-}
 
 // ---------------------------------------------------------------- forward (FB = F / 64)
 // grid (ceil(T/16), H, B), 64 threads
@@ -79,7 +44,6 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ 
     const float* qb = qkb ? qkb + h * 2 * F : nullptr;
     const float* kb = qkb ? qb + F : nullptr;
     const float* V = a + ((long)b * H + h) * F * T;
-    AttnPtrs p{Q, qb, V, bucket, emb};
     if (bucket && lane < nbk) emb_lds[lane] = emb[lane * H + h];
     stage16(Qs, Q, qb, F, T, n0);
     __syncthreads();
@@ -103,7 +67,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const float* __restrict__ 
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + 4 * lg + r;
-            x[r] = m < T ? (s[r] + rel_bias(p, emb_lds, m, n < T ? n : 0, T)) * scale : -INFINITY;
+            x[r] = m < T ? (s[r] + rel_bias(bucket, emb_lds, m, n < T ? n : 0, T)) * scale : -INFINITY;
             bm = fmaxf(bm, x[r]);
         }
         bm = max16x4(bm);                         // finite: key m0 < T is in every tile
@@ -156,7 +120,6 @@ __global__ __launch_bounds__(64) void attn_vjp_q_kernel(const float* __restrict_
     const float* kb = qkb ? qb + F : nullptr;
     const float* V = a + ((long)b * H + h) * F * T;
     const float* dO = dout + ((long)b * H + h) * F * T;
-    AttnPtrs p{Q, qb, V, bucket, emb};
     if (bucket && lane < nbk) emb_lds[lane] = emb[lane * H + h];
     stage16(Qs, Q, qb, F, T, n0);
     stage16(dOs, dO, nullptr, F, T, n0);
@@ -169,24 +132,8 @@ __global__ __launch_bounds__(64) void attn_vjp_q_kernel(const float* __restrict_
 #pragma unroll
     for (int t = 0; t < NFT; ++t) acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
     for (int m0 = 0; m0 < T; m0 += 16) {
-        floatx4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-        const int mk = m0 + lr;
-        const bool kin = mk < T;
-#pragma unroll 8
-        for (int f0 = 0; f0 < F; f0 += 4) {
-            const int f = f0 + lg;
-            const float kv = kin ? K[(long)f * T + mk] + (kb ? kb[f] : 0.f) : 0.f;
-            const float vv = kin ? V[(long)f * T + mk] : 0.f;
-            s = mfma(kv, Qs[f * 16 + lr], s);
-            dp = mfma(vv, dOs[f * 16 + lr], dp);
-        }
         float ds[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + 4 * lg + r;
-            const float pv = (m < T && nin) ? expf((s[r] + rel_bias(p, emb_lds, m, n, T)) * scale - L) : 0.f;
-            ds[r] = pv * (dp[r] - Dn);
-        }
+        ds_tile_q<F>(K, kb, V, Qs, dOs, bucket, emb_lds, m0, n, nin, L, Dn, T, scale, ds);
         // dQ^T[f][n] += sum_m K[f][m] dS^T[m][n]
 #pragma unroll
         for (int t = 0; t < NFT; ++t) {
@@ -228,7 +175,6 @@ __global__ __launch_bounds__(64) void attn_vjp_kv_kernel(const float* __restrict
     const float* dO = dout + ((long)b * H + h) * F * T;
     const float* lseh = lse + ((long)b * H + h) * T;
     const float* Dh = D + ((long)b * H + h) * T;
-    AttnPtrs p{Q, qb, V, bucket, emb};
     if (bucket && lane < nbk) emb_lds[lane] = emb[lane * H + h];
     stage16(Ks, K, kb, F, T, m0);
     stage16(Vs, V, nullptr, F, T, m0);
@@ -256,7 +202,7 @@ __global__ __launch_bounds__(64) void attn_vjp_kv_kernel(const float* __restrict
         for (int r = 0; r < 4; ++r) {
             const int n = n0 + 4 * lg + r;
             const bool ok = kin && n < T;
-            const float pv = ok ? expf((s[r] + rel_bias(p, emb_lds, m, n, T)) * scale - lseh[n]) : 0.f;
+            const float pv = ok ? expf((s[r] + rel_bias(bucket, emb_lds, m, n, T)) * scale - lseh[n]) : 0.f;
             pr[r] = pv;
             ds[r] = ok ? pv * (dp[r] - Dh[n]) : 0.f;
         }
@@ -289,70 +235,37 @@ __global__ __launch_bounds__(64) void attn_vjp_kv_kernel(const float* __restrict
     }
 }
 
-#define ATTN_DISPATCH(FB, KER, ...)                                                                       \
-    switch (FB) {                                                                                        \
-        case 1: hipLaunchKernelGGL(KER<1>, __VA_ARGS__); break;                                          \
-        case 2: hipLaunchKernelGGL(KER<2>, __VA_ARGS__); break;                                          \
-        case 3: hipLaunchKernelGGL(KER<3>, __VA_ARGS__); break;                                          \
-        case 4: hipLaunchKernelGGL(KER<4>, __VA_ARGS__); break;                                          \
-        case 5: hipLaunchKernelGGL(KER<5>, __VA_ARGS__); break;                                          \
-        case 6: hipLaunchKernelGGL(KER<6>, __VA_ARGS__); break;                                          \
-        default: hipLaunchKernelGGL(KER<7>, __VA_ARGS__); break;                                         \
+// the fp32 core behind attention_common.h's host bodies: one wave, 16 own rows per workgroup
+struct F32Core {
+    static constexpr int ROWS = 16;
+    template <int FB>
+    static int fwd(const char*, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, float* out, float* lse, int H, int T, float scale) {
+        hipLaunchKernelGGL(attn_fwd_kernel<FB>, grid, dim3(64), 0, s, qk, qkb, a, bucket, emb, nbk, out, lse, H, T, scale);
+        return BABE_OK;
     }
+    template <int FB>
+    static int vjp(const char*, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, const float* dout, const float* lse, const float* D, float* dqk, float* dv, int H,
+                   int T, float scale) {
+        hipLaunchKernelGGL(attn_vjp_q_kernel<FB>, grid, dim3(64), 0, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk, H, T, scale);
+        BABE_LAUNCH_CHECK();
+        hipLaunchKernelGGL(attn_vjp_kv_kernel<FB>, grid, dim3(64), 0, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T,
+                           scale);
+        return BABE_OK;
+    }
+};
 
 }  // namespace
 
-extern "C" int babe_attn_buckets(int* out, int T, int num_buckets, int max_distance) {
-    BABE_CHECK_ARG(out && T > 0 && num_buckets >= 4 && max_distance > num_buckets / 4, "attn_buckets: bad arguments");
-    // T5 bidirectional buckets exactly as the reference evaluates them in float32 (torch: n.float() / max_exact, log,
-    // division by the Python scalar log(max_distance / max_exact) as multiplication by its float reciprocal, then .long())
-    const int nb = num_buckets / 2, max_exact = nb / 2;
-    const float inv = 1.f / (float)std::log((double)max_distance / (double)max_exact);
-    for (int i = 0; i < 2 * T - 1; ++i) {
-        const int rel = i - (T - 1);          // key position - query position
-        const int n = rel < 0 ? -rel : rel;
-        int v;
-        if (n < max_exact) {
-            v = n;
-        } else {
-            const float lf = logf((float)n / (float)max_exact);
-            long large = max_exact + (long)(lf * inv * (float)(nb - max_exact));
-            if (large > nb - 1) large = nb - 1;
-            v = (int)large;
-        }
-        out[i] = (rel >= 0 ? nb : 0) + v;
-    }
-    return BABE_OK;
-}
-
 extern "C" int babe_attn_fwd(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
                              int num_buckets, float* out, float* lse, int B, int H, int F, int T, float scale, void* stream) {
-    BABE_CHECK_ARG(qk && a && out && lse, "attn_fwd: null pointer");
-    BABE_CHECK_ARG(!bucket == !emb, "attn_fwd: bucket table and embedding go together");
-    if (int e = attn_check_shape("attn_fwd", B, H, F, T, bucket ? num_buckets : 0)) return e;
-    const dim3 grid(cdiv(T, 16), H, B);
-    ATTN_DISPATCH(F / 64, attn_fwd_kernel, grid, dim3(64), 0, (hipStream_t)stream, qk, qk_bias, a, bucket, emb,
-                  bucket ? num_buckets : 0, out, lse, H, T, scale);
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return attn_fwd_host<F32Core>("attn_fwd", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, B, H, F, T, scale, stream);
 }
 
 extern "C" int babe_attn_vjp(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
                              int num_buckets, const float* out, const float* lse, const float* dout, float* D, float* dqk,
                              float* dv, int B, int H, int F, int T, float scale, void* stream) {
-    BABE_CHECK_ARG(qk && a && out && lse && dout && D && dqk && dv, "attn_vjp: null pointer");
-    BABE_CHECK_ARG(!bucket == !emb, "attn_vjp: bucket table and embedding go together");
-    if (int e = attn_check_shape("attn_vjp", B, H, F, T, bucket ? num_buckets : 0)) return e;
-    const int nbk = bucket ? num_buckets : 0;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn_rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
-    BABE_LAUNCH_CHECK();
-    const dim3 grid(cdiv(T, 16), H, B);
-    ATTN_DISPATCH(F / 64, attn_vjp_q_kernel, grid, dim3(64), 0, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, H, T,
-                  scale);
-    BABE_LAUNCH_CHECK();
-    ATTN_DISPATCH(F / 64, attn_vjp_kv_kernel, grid, dim3(64), 0, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, dv,
-                  H, T, scale);
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return attn_vjp_host<F32Core>("attn_vjp", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, dout, D, dqk, dv, B, H, F, T, scale,
+                                  stream);
 }

@@ -33,7 +33,6 @@
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -56,15 +55,6 @@ __device__ __forceinline__ floatx4 mfma16(const unsigned short* a, s16x4 b, floa
 __device__ __forceinline__ s16x4 pack4(const float* v) {
     const u32x2 w = {bf(v[0]) | (bf(v[1]) << 16), bf(v[2]) | (bf(v[3]) << 16)};
     return __builtin_bit_cast(s16x4, w);
-}
-
-__device__ __forceinline__ float max16x4(float v) {           // over the 4 lane groups that share l % 16
-    v = fmaxf(v, __shfl_xor(v, 16, 64));
-    return fmaxf(v, __shfl_xor(v, 32, 64));
-}
-__device__ __forceinline__ float sum16x4(float v) {
-    v += __shfl_xor(v, 16, 64);
-    return v + __shfl_xor(v, 32, 64);
 }
 
 // Time steps c0 .. c0 + 31 of a [F][T] operand (+ an optional per-row bias, added in fp32) as the transposed image dst[32][F + 8]:
@@ -111,28 +101,10 @@ __device__ __forceinline__ floatx4 score_tile(const unsigned short* a, const uns
     return s0 + s1;
 }
 
-struct Head {
-    const float *Q, *K, *qb, *kb, *V;
-    long hb;                    // (b * H + h): the head's index into [B][H][...] tensors
-};
-__device__ __forceinline__ Head head_of(const float* qk, const float* qkb, const float* a, int H, int F, int T) {
-    const int h = blockIdx.y, b = blockIdx.z;
-    Head p;
-    p.Q = qk + ((long)b * 2 * H * F + (long)h * 2 * F) * T;
-    p.K = p.Q + (long)F * T;
-    p.qb = qkb ? qkb + h * 2 * F : nullptr;
-    p.kb = qkb ? p.qb + F : nullptr;
-    p.hb = (long)b * H + h;
-    p.V = a + p.hb * F * T;
-    return p;
-}
-
 // table pass (MODE 3 of the VJP kernel): floats of a wave's parked dS tile, and of its array of diagonals.  A key tile at sb
 // (a multiple of 16 below T) touches the entries sb .. sb + 30
 constexpr int TILE_F = 16 * 17;
 __host__ __device__ constexpr int tbl_diag_len(int T) { return ((T + 31) & ~31) + 32; }
-inline long tbl_lds_bytes(int F, int T) { return 4L * TS * (F + 8) * 2 + 64 * 4 + 4L * TILE_F * 4 + 4L * tbl_diag_len(T) * 4; }
-constexpr int LDS_MAX = 160 * 1024;
 
 // LDS bytes: transposed images, natural images, the bias table, the forward's (max, sum) slots
 constexpr int lds_bytes(int F, int nt, int nn) { return nt * TS * (F + 8) * 2 + nn * F * NPAD * 2 + 64 * 4 + 4 * 16 * 2 * 4; }
@@ -327,12 +299,7 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");     // the tile is this wave's own: no workgroup barrier
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (lane < 31) {                              // diagonal (m - sb) - (n - nb) = lane - 15, queries ascending
-                const int lo = lane < 15 ? 15 - lane : 0, hi = lane > 15 ? 30 - lane : 15;
-                float sum = 0.f;
-                for (int q = lo; q <= hi; ++q) sum += tile[(q + lane - 15) * 17 + q];
-                diag[sb + lane] += sum;
-            }
+            attn_diag_add(tile, diag + sb, lane);
             continue;                                     // (the next chunk's barrier comes before the tile is written again)
         }
         const s16x4 vb = pack4(val);
@@ -347,10 +314,8 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
         if (st == 0 && lane < nbk && qt < nqt) {
             const float* d1 = diag + DL;                  // the st = 1 wave of this query tile
             float accb = 0.f;
-            for (int j = 0; j < DL; ++j) {
-                const int idx = j - 15 - nb + T - 1;
-                if (idx >= 0 && idx <= 2 * T - 2 && bucket[idx] == lane) accb += diag[j] + d1[j];
-            }
+            for (int j = 0; j < DL; ++j)
+                if (attn_diag_in_bucket(bucket, j, nb, T, lane)) accb += diag[j] + d1[j];
             tpart[((long)p.hb * nqt + qt) * nbk + lane] = accb * scale;
         }
         return;
@@ -376,56 +341,65 @@ __global__ __launch_bounds__(NTH) void attn_vjp_bf16_kernel(const float* __restr
     }
 }
 
-template <int FB>
-int launch_fwd(dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket, const float* emb,
-               int nbk, float* out, float* lse, int H, int T, float scale) {
-    constexpr int lds = lds_bytes(FB * 64, 2, 1);
-    static std::atomic<unsigned long long> done{0};
-    if (babe_lds_optin(done, {reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<FB>)}, lds) != hipSuccess) return BABE_ERR_HIP;
-    hipLaunchKernelGGL(attn_fwd_bf16_kernel<FB>, grid, dim3(NTH), lds, s, qk, qkb, a, bucket, emb, nbk, out, lse, H, T, scale);
-    return BABE_OK;
+// a kernel's opt-in for `bytes` of dynamic LDS (babe_lds_optin; `done` is the call site's), the failure under the caller's name
+int optin(const char* who, std::atomic<unsigned long long>& done, const void* kernel, int bytes) {
+    if (babe_lds_optin(done, {kernel}, bytes) == hipSuccess) return BABE_OK;
+    babe_set_error("%s: could not reserve the kernel's LDS: %s", who, hipGetErrorString(hipGetLastError()));
+    return BABE_ERR_HIP;
 }
 
-template <int FB, int MODE>
-int launch_vjp(dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket, const float* emb,
-               int nbk, const float* dout, const float* lse, const float* D, float* dqk, float* dv, int H, int T, float scale) {
-    constexpr int lds = MODE == 2 ? lds_bytes(FB * 64, 2, 1) : lds_bytes(FB * 64, 4, 1);
-    static_assert(lds <= 160 * 1024, "the images of one workgroup must fit the CU's LDS");
-    static std::atomic<unsigned long long> done{0};
-    if (babe_lds_optin(done, {reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, MODE>)}, lds) != hipSuccess)
-        return BABE_ERR_HIP;
-    hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, MODE>), grid, dim3(NTH), lds, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk,
-                       dv, nullptr, H, T, scale);
-    return BABE_OK;
-}
+// the bf16 core behind attention_common.h's host bodies: four waves, 32 own rows per workgroup
+struct Bf16Core {
+    static constexpr int ROWS = TS;
+    static constexpr int TBL_LDS_LIMIT = 160 * 1024;
+    // the table pass (MODE 3): two own and two streamed transposed images, the bias table, four parked tiles, four arrays of diagonals
+    static long tbl_lds_bytes(int F, int T) { return 4L * TS * (F + 8) * 2 + 64 * 4 + 4L * TILE_F * 4 + 4L * tbl_diag_len(T) * 4; }
 
-// the table pass: its LDS grows with T (tbl_lds_bytes, checked by the caller), so the opt-in is for the whole CU
-template <int FB>
-int launch_tbl(dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket, const float* emb,
-               int nbk, const float* dout, const float* lse, const float* D, float* tpart, int H, int T, float scale) {
-    static std::atomic<unsigned long long> done{0};
-    if (babe_lds_optin(done, {reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, 3>)}, LDS_MAX) != hipSuccess)
-        return BABE_ERR_HIP;
-    hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, 3>), grid, dim3(NTH), tbl_lds_bytes(FB * 64, T), s, qk, qkb, a, bucket, emb, nbk,
-                       dout, lse, D, nullptr, nullptr, tpart, H, T, scale);
-    return BABE_OK;
-}
-
-#define ATTN_BF16_DISPATCH(FB, rc, FN, ...)                       \
-    switch (FB) {                                                 \
-        case 1: rc = FN(1)(__VA_ARGS__); break;                   \
-        case 2: rc = FN(2)(__VA_ARGS__); break;                   \
-        case 3: rc = FN(3)(__VA_ARGS__); break;                   \
-        case 4: rc = FN(4)(__VA_ARGS__); break;                   \
-        case 5: rc = FN(5)(__VA_ARGS__); break;                   \
-        case 6: rc = FN(6)(__VA_ARGS__); break;                   \
-        default: rc = FN(7)(__VA_ARGS__); break;                  \
+    template <int FB>
+    static int fwd(const char* who, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, float* out, float* lse, int H, int T, float scale) {
+        constexpr int lds = lds_bytes(FB * 64, 2, 1);
+        static std::atomic<unsigned long long> done{0};
+        BABE_TRY(optin(who, done, reinterpret_cast<const void*>(&attn_fwd_bf16_kernel<FB>), lds));
+        hipLaunchKernelGGL(attn_fwd_bf16_kernel<FB>, grid, dim3(NTH), lds, s, qk, qkb, a, bucket, emb, nbk, out, lse, H, T, scale);
+        return BABE_OK;
     }
-#define FWD_FN(FB) launch_fwd<FB>
-#define VJP_Q_FN(FB) launch_vjp<FB, 0>
-#define VJP_K_FN(FB) launch_vjp<FB, 1>
-#define VJP_V_FN(FB) launch_vjp<FB, 2>
-#define TBL_FN(FB) launch_tbl<FB>
+
+    template <int FB, int MODE>
+    static int vjp_mode(const char* who, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a,
+                        const int* bucket, const float* emb, int nbk, const float* dout, const float* lse, const float* D, float* dqk,
+                        float* dv, int H, int T, float scale) {
+        constexpr int lds = MODE == 2 ? lds_bytes(FB * 64, 2, 1) : lds_bytes(FB * 64, 4, 1);
+        static_assert(lds <= 160 * 1024, "the images of one workgroup must fit the CU's LDS");
+        static std::atomic<unsigned long long> done{0};
+        BABE_TRY(optin(who, done, reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, MODE>), lds));
+        hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, MODE>), grid, dim3(NTH), lds, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk,
+                           dv, nullptr, H, T, scale);
+        return BABE_OK;
+    }
+    template <int FB>
+    static int vjp(const char* who, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, const float* dout, const float* lse, const float* D, float* dqk, float* dv, int H,
+                   int T, float scale) {
+        BABE_TRY((vjp_mode<FB, 0>(who, grid, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale)));
+        BABE_LAUNCH_CHECK();
+        BABE_TRY((vjp_mode<FB, 1>(who, grid, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale)));
+        BABE_LAUNCH_CHECK();
+        return vjp_mode<FB, 2>(who, grid, s, qk, qkb, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale);
+    }
+
+    // its LDS grows with T (tbl_lds_bytes, checked by the host body), so the opt-in is for the whole CU
+    template <int FB>
+    static int tbl(const char* who, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, const float* dout, const float* lse, const float* D, float* tpart, int H, int T,
+                   float scale) {
+        static std::atomic<unsigned long long> done{0};
+        BABE_TRY(optin(who, done, reinterpret_cast<const void*>(&attn_vjp_bf16_kernel<FB, 3>), TBL_LDS_LIMIT));
+        hipLaunchKernelGGL((attn_vjp_bf16_kernel<FB, 3>), grid, dim3(NTH), tbl_lds_bytes(FB * 64, T), s, qk, qkb, a, bucket, emb, nbk,
+                           dout, lse, D, nullptr, nullptr, tpart, H, T, scale);
+        return BABE_OK;
+    }
+};
 
 bool aligned4(std::initializer_list<const void*> ps) {
     for (const void* q : ps)
@@ -433,93 +407,33 @@ bool aligned4(std::initializer_list<const void*> ps) {
     return true;
 }
 
-int optin_failed(const char* who) {
-    babe_set_error("%s: could not reserve the kernel's LDS: %s", who, hipGetErrorString(hipGetLastError()));
-    return BABE_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" int babe_attn_fwd_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
                                   int num_buckets, float* out, float* lse, int B, int H, int F, int T, float scale, void* stream) {
-    BABE_CHECK_ARG(qk && a && out && lse, "attn_fwd_bf16: null pointer");
-    BABE_CHECK_ARG(!bucket == !emb, "attn_fwd_bf16: bucket table and embedding go together");
     BABE_CHECK_ARG(aligned4({qk, qk_bias, a, bucket, emb, out, lse}), "attn_fwd_bf16: a pointer is not 4-byte aligned");
-    if (int e = attn_check_shape("attn_fwd_bf16", B, H, F, T, bucket ? num_buckets : 0)) return e;
-    const dim3 grid(cdiv(T, TS), H, B);
-    int rc;
-    ATTN_BF16_DISPATCH(F / 64, rc, FWD_FN, grid, (hipStream_t)stream, qk, qk_bias, a, bucket, emb, bucket ? num_buckets : 0, out,
-                       lse, H, T, scale);
-    if (rc != BABE_OK) return optin_failed("attn_fwd_bf16");
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return attn_fwd_host<Bf16Core>("attn_fwd_bf16", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, B, H, F, T, scale, stream);
 }
 
 extern "C" int babe_attn_vjp_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
                                   int num_buckets, const float* out, const float* lse, const float* dout, float* D, float* dqk,
                                   float* dv, int B, int H, int F, int T, float scale, void* stream) {
-    BABE_CHECK_ARG(qk && a && out && lse && dout && D && dqk && dv, "attn_vjp_bf16: null pointer");
-    BABE_CHECK_ARG(!bucket == !emb, "attn_vjp_bf16: bucket table and embedding go together");
     BABE_CHECK_ARG(aligned4({qk, qk_bias, a, bucket, emb, out, lse, dout, D, dqk, dv}),
                    "attn_vjp_bf16: a pointer is not 4-byte aligned");
-    if (int e = attn_check_shape("attn_vjp_bf16", B, H, F, T, bucket ? num_buckets : 0)) return e;
-    const int nbk = bucket ? num_buckets : 0;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(attn_rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
-    BABE_LAUNCH_CHECK();
-    const dim3 grid(cdiv(T, TS), H, B);
-    int rc;
-    ATTN_BF16_DISPATCH(F / 64, rc, VJP_Q_FN, grid, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale);
-    if (rc != BABE_OK) return optin_failed("attn_vjp_bf16");
-    BABE_LAUNCH_CHECK();
-    ATTN_BF16_DISPATCH(F / 64, rc, VJP_K_FN, grid, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale);
-    if (rc != BABE_OK) return optin_failed("attn_vjp_bf16");
-    BABE_LAUNCH_CHECK();
-    ATTN_BF16_DISPATCH(F / 64, rc, VJP_V_FN, grid, s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, dqk, dv, H, T, scale);
-    if (rc != BABE_OK) return optin_failed("attn_vjp_bf16");
-    BABE_LAUNCH_CHECK();
-    return BABE_OK;
+    return attn_vjp_host<Bf16Core>("attn_vjp_bf16", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, dout, D, dqk, dv, B, H, F, T,
+                                   scale, stream);
 }
 
 extern "C" long babe_attn_param_vjp_bf16_workspace(int B, int H, int T, int num_buckets) {
-    if (B <= 0 || H <= 0 || T <= 0 || num_buckets < 0 || num_buckets > 64) return -1;
-    return (long)B * H * T + (long)B * H * cdiv(T, 16) * num_buckets;
+    return babe_attn_param_vjp_workspace(B, H, T, num_buckets);
 }
 
 extern "C" int babe_attn_param_vjp_bf16(const float* qk, const float* qk_bias, const float* a, const int* bucket, const float* emb,
                                         int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk,
                                         float* ws, float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H,
                                         int F, int T, float scale, void* stream) {
-    BABE_CHECK_ARG(!bucket == !emb && !bucket == !demb_rows,
-                   "attn_param_vjp_bf16: bucket table, embedding and demb_rows go together");
-    const int nbk = bucket ? num_buckets : 0;
-    if (int e = attn_check_shape("attn_param_vjp_bf16", B, H, F, T, nbk)) return e;
-    BABE_CHECK_ARG(demb_rows || dqkb_rows, "attn_param_vjp_bf16: nothing to compute");
-    BABE_CHECK_ARG(!dqkb_rows || (dqk && dqkb_bs >= 2L * H * F), "attn_param_vjp_bf16: dqkb_rows needs dqk and dqkb_bs >= 2HF");
     BABE_CHECK_ARG(aligned4({qk, qk_bias, a, bucket, emb, out, lse, dout, dqk, ws, demb_rows, dqkb_rows}),
                    "attn_param_vjp_bf16: a pointer is not 4-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    if (demb_rows) {
-        BABE_CHECK_ARG(qk && a && out && lse && dout && ws, "attn_param_vjp_bf16: null pointer");
-        BABE_CHECK_ARG(nbk > 0 && demb_bs >= (long)nbk * H, "attn_param_vjp_bf16: demb_bs %ld < num_buckets*H", demb_bs);
-        BABE_CHECK_ARG(tbl_lds_bytes(F, T) <= LDS_MAX, "attn_param_vjp_bf16: F=%d with T=%d needs %ld bytes of LDS (limit %d)", F, T,
-                       tbl_lds_bytes(F, T), LDS_MAX);
-        float* D = ws;                                    // the D of babe_attn_vjp_bf16: same kernel, same operands
-        float* tpart = ws + (long)B * H * T;
-        hipLaunchKernelGGL(attn_rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
-        BABE_LAUNCH_CHECK();
-        int rc;
-        ATTN_BF16_DISPATCH(F / 64, rc, TBL_FN, dim3(cdiv(T, TS), H, B), s, qk, qk_bias, a, bucket, emb, nbk, dout, lse, D, tpart, H, T,
-                           scale);
-        if (rc != BABE_OK) return optin_failed("attn_param_vjp_bf16");
-        BABE_LAUNCH_CHECK();
-        hipLaunchKernelGGL(attn_demb_sum_kernel, dim3(B), dim3(256), 0, s, tpart, cdiv(T, 16), nbk, H, demb_rows, demb_bs);
-        BABE_LAUNCH_CHECK();
-    }
-    if (dqkb_rows) {
-        const int R = 2 * H * F;
-        hipLaunchKernelGGL(attn_rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
-        BABE_LAUNCH_CHECK();
-    }
-    return BABE_OK;
+    return attn_param_vjp_host<Bf16Core>("attn_param_vjp_bf16", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, dout, dqk, ws,
+                                         demb_rows, demb_bs, dqkb_rows, dqkb_bs, B, H, F, T, scale, stream);
 }

@@ -18,21 +18,20 @@
 //    D[i][j]: lane l holds D[(r%4) + 8*(r/4) + 4*(l/32)][l%32], r = 0..15.
 //
 // 2. relative-position table gradient  demb[b][k][h] = sum_{n,m: bucket[m-n+T-1] = k} scale * dS[b,h,n,m], dS = P o (dP - D) as in
-//    attention.hip.  A kernel of its own that recomputes S and dP exactly as attn_vjp_q_kernel does (same operands, same MFMA
-//    order, so the same P): a wave owns 16 queries, parks each 16 x 16 dS tile in LDS, one lane per diagonal of the tile adds its
+//    attention.hip.  A kernel of its own whose dS tile is attn_vjp_q_kernel's (ds_tile_q, attention_f32.h: one function, so the
+//    same P): a wave owns 16 queries, parks each 16 x 16 dS tile in LDS, one lane per diagonal of the tile adds its
 //    sum (ascending query) into the wave's LDS array of diagonals, key tiles in ascending order; at the end lane k adds the
 //    diagonals of bucket k in ascending offset and writes the query tile's partial; a last pass adds the query tiles in order.
 //    The qk bias gradient is the row sum of dqk over t (double, fixed order).
 //
 // 3. norm2 / affine2: the plain per-channel scale pass that rebuilds proj_in's input (their parameter gradient,
 //    babe_gn_param_grad_nogelu, sits beside its GELU twin in wgrad.hip).
-#include "attention_common.h"
+#include "attention_f32.h"
 #include "../../include/babe_hip.h"
 #include <cmath>
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // ---------------------------------------------------------------- qk weight gradient
@@ -66,7 +65,9 @@ inline bool qk_shape_ok(int B, int HF, int T) {
     return B > 0 && T > 0 && HF >= HF_STEP && HF <= HF_MAX && HF % HF_STEP == 0;
 }
 
-// grid (tiles, nsplit), 256 threads.  direct: the only chunk, out = alpha * acc (+ beta * out); otherwise the raw partial tile
+// grid (tiles, nsplit), 256 threads.  direct: the only chunk, out = alpha * acc (+ beta * out); otherwise the raw partial tile.
+// Tile indices, chunk bounds, accumulator clear and the epilogue are written out in this kernel and in its bf16 twin below:
+// moved into shared device functions they compile to other index code ahead of the MFMA loop, which the F = 192 level's time follows.
 __global__ __launch_bounds__(256) void qk_wgrad_kernel(const float* __restrict__ dqk, const float* __restrict__ a1,
                                                        float* __restrict__ out, int M, int N, int T, int B, int nst, int per,
                                                        float alpha, float beta, int direct) {
@@ -240,31 +241,6 @@ __global__ __launch_bounds__(256) void qk_wgrad_bf16_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------- table / bias gradients
-constexpr int FMAX = 448;
-constexpr int LDS_LIMIT = 65536;
-
-__device__ __forceinline__ floatx4 mfma(float a, float b, floatx4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ void stage16(float* dst, const float* src, const float* rb, int F, int T, int c0) {
-    for (int i = threadIdx.x; i < F * 16; i += 64) {
-        const int f = i >> 4, c = c0 + (i & 15);
-        dst[i] = c < T ? src[(long)f * T + c] + (rb ? rb[f] : 0.f) : 0.f;
-    }
-}
-
-// D[b][h][n] = sum_f dO[f][n] O[f][n] (the sum attention.hip's VJP forms); grid (ceil(T/256), H, B), 256 threads
-__global__ __launch_bounds__(256) void rowdot_kernel(const float* __restrict__ dout, const float* __restrict__ out,
-                                                     float* __restrict__ D, int H, int F, int T) {
-    const int n = blockIdx.x * 256 + threadIdx.x;
-    if (n >= T) return;
-    const long base = ((long)blockIdx.z * H + blockIdx.y) * F * T + n;
-    float s = 0.f;
-    for (int f = 0; f < F; ++f) s += dout[base + (long)f * T] * out[base + (long)f * T];
-    D[((long)blockIdx.z * H + blockIdx.y) * T + n] = s;
-}
-
 inline int diag_len(int T) { return ((T + 15) & ~15) + 16; }
 
 // grid (ceil(T/16), H, B), 64 threads, dynamic LDS diag_len(T) floats.  part [B][H][gridDim.x][nbk]
@@ -281,78 +257,50 @@ __global__ __launch_bounds__(64) void attn_demb_kernel(const float* __restrict__
     __shared__ float tile[16 * 17];            // dS[m - m0][n - n0]
     extern __shared__ float diag[];            // entry j: the sum over the diagonal m - n = j - 15 - n0 of this wave's queries
     const int lane = threadIdx.x, lr = lane & 15, lg = lane >> 4;
-    const int n0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
-    const float* Q = qk + ((long)b * 2 * H * F + (long)h * 2 * F) * T;
-    const float* K = Q + (long)F * T;
-    const float* qb = qkb ? qkb + h * 2 * F : nullptr;
-    const float* kb = qkb ? qb + F : nullptr;
-    const float* V = a + ((long)b * H + h) * F * T;
-    const float* dO = dout + ((long)b * H + h) * F * T;
+    const int n0 = blockIdx.x * 16, h = blockIdx.y;
+    const Head p = head_of(qk, qkb, a, H, F, T);
     const int nd = ((T + 15) & ~15) + 16;
     if (lane < nbk) emb_lds[lane] = emb[lane * H + h];
     for (int i = lane; i < nd; i += 64) diag[i] = 0.f;
-    stage16(Qs, Q, qb, F, T, n0);
-    stage16(dOs, dO, nullptr, F, T, n0);
+    stage16(Qs, p.Q, p.qb, F, T, n0);
+    stage16(dOs, dout + p.hb * F * T, nullptr, F, T, n0);
     __syncthreads();
     const int n = n0 + lr;
     const bool nin = n < T;
-    const float L = nin ? lse[((long)b * H + h) * T + n] : 0.f;
-    const float Dn = nin ? D[((long)b * H + h) * T + n] : 0.f;
+    const float L = nin ? lse[p.hb * T + n] : 0.f;
+    const float Dn = nin ? D[p.hb * T + n] : 0.f;
     for (int m0 = 0; m0 < T; m0 += 16) {
-        floatx4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-        const int mk = m0 + lr;
-        const bool kin = mk < T;
-#pragma unroll 8
-        for (int f0 = 0; f0 < F; f0 += 4) {
-            const int f = f0 + lg;
-            const float kv = kin ? K[(long)f * T + mk] + (kb ? kb[f] : 0.f) : 0.f;
-            const float vv = kin ? V[(long)f * T + mk] : 0.f;
-            s = mfma(kv, Qs[f * 16 + lr], s);
-            dp = mfma(vv, dOs[f * 16 + lr], dp);
-        }
+        float ds[4];
+        ds_tile_q<F>(p.K, p.kb, p.V, Qs, dOs, bucket, emb_lds, m0, n, nin, L, Dn, T, scale, ds);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + 4 * lg + r;
-            float ds = 0.f;
-            if (m < T && nin) ds = expf((s[r] + emb_lds[bucket[m - n + T - 1]]) * scale - L) * (dp[r] - Dn);
-            tile[(4 * lg + r) * 17 + lr] = ds;
-        }
+        for (int r = 0; r < 4; ++r) tile[(4 * lg + r) * 17 + lr] = ds[r];
         __syncthreads();
-        if (lane < 31) {                       // diagonal (m - m0) - (n - n0) = lane - 15, queries ascending
-            const int lo = lane < 15 ? 15 - lane : 0, hi = lane > 15 ? 30 - lane : 15;
-            float sum = 0.f;
-            for (int q = lo; q <= hi; ++q) sum += tile[(q + lane - 15) * 17 + q];
-            diag[m0 + lane] += sum;
-        }
+        attn_diag_add(tile, diag + m0, lane);
         __syncthreads();
     }
-    if (lane < nbk) {                          // entry j holds the offset m - n = j - 15 - n0
+    if (lane < nbk) {
         float accb = 0.f;
-        for (int j = 0; j < nd; ++j) {
-            const int idx = j - 15 - n0 + T - 1;
-            if (idx >= 0 && idx <= 2 * T - 2 && bucket[idx] == lane) accb += diag[j];
-        }
-        part[(((long)b * H + h) * gridDim.x + blockIdx.x) * nbk + lane] = accb * scale;
+        for (int j = 0; j < nd; ++j)
+            if (attn_diag_in_bucket(bucket, j, n0, T, lane)) accb += diag[j];
+        part[((long)p.hb * gridDim.x + blockIdx.x) * nbk + lane] = accb * scale;
     }
 }
 
-#define DEMB_DISPATCH(FB, ...)                                                                           \
-    switch (FB) {                                                                                        \
-        case 1: hipLaunchKernelGGL(attn_demb_kernel<1>, __VA_ARGS__); break;                             \
-        case 2: hipLaunchKernelGGL(attn_demb_kernel<2>, __VA_ARGS__); break;                             \
-        case 3: hipLaunchKernelGGL(attn_demb_kernel<3>, __VA_ARGS__); break;                             \
-        case 4: hipLaunchKernelGGL(attn_demb_kernel<4>, __VA_ARGS__); break;                             \
-        case 5: hipLaunchKernelGGL(attn_demb_kernel<5>, __VA_ARGS__); break;                             \
-        case 6: hipLaunchKernelGGL(attn_demb_kernel<6>, __VA_ARGS__); break;                             \
-        default: hipLaunchKernelGGL(attn_demb_kernel<7>, __VA_ARGS__); break;                            \
+// the table half of the fp32 core (the other half is attention.hip's F32Core), behind attention_common.h's attn_param_vjp_host
+struct F32Table {
+    static constexpr int ROWS = 16;
+    static constexpr int TBL_LDS_LIMIT = 65536;        // static + dynamic: no opt-in
+    // static LDS of attn_demb_kernel<F/64> + its diagonals
+    static long tbl_lds_bytes(int F, int T) { return 4L * (2L * F * 16 + 64 + 16 * 17 + diag_len(T)); }
+    template <int FB>
+    static int tbl(const char*, dim3 grid, hipStream_t s, const float* qk, const float* qkb, const float* a, const int* bucket,
+                   const float* emb, int nbk, const float* dout, const float* lse, const float* D, float* part, int H, int T,
+                   float scale) {
+        hipLaunchKernelGGL(attn_demb_kernel<FB>, grid, dim3(64), diag_len(T) * sizeof(float), s, qk, qkb, a, bucket, emb, nbk, dout,
+                           lse, D, part, H, T, scale);
+        return BABE_OK;
     }
-
-inline bool pv_shape_ok(int B, int H, int F, int T, int nbk) {
-    return B > 0 && H > 0 && T > 0 && F % 64 == 0 && F >= 64 && F <= FMAX && nbk >= 0 && nbk <= 64;
-}
-
-// static LDS of attn_demb_kernel<F/64> + its diagonals
-inline long demb_lds_bytes(int F, int T) { return 4L * (2L * F * 16 + 64 + 16 * 17 + diag_len(T)); }
+};
 
 // ---------------------------------------------------------------- scale pass
 // grid (ceil(hw/1024), C, B), 256 threads
@@ -368,6 +316,29 @@ __global__ __launch_bounds__(256) void scale_channels_kernel(const float* __rest
     }
 }
 
+// babe_attn_qk_wgrad (`who` = "attn_qk_wgrad") and babe_attn_qk_wgrad_bf16: the same plan, workspace and reduce pass around `kernel`
+template <class Kernel>
+int qk_wgrad_host(const char* who, Kernel kernel, const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T,
+                  float alpha, float beta, void* stream) {
+    BABE_CHECK_ARG(dqk && a1 && dW, "%s: null pointer", who);
+    BABE_CHECK_ARG(qk_shape_ok(B, HF, T), "%s: unsupported shape B=%d HF=%d T=%d (HF a multiple of %d, at most %d)", who, B, HF, T,
+                   HF_STEP, HF_MAX);
+    const QkPlan p = qk_plan(B, HF, T);
+    BABE_CHECK_ARG(p.nsplit == 1 || ws, "%s: this shape needs a workspace (babe_%s_workspace)", who, who);
+    hipStream_t s = (hipStream_t)stream;
+    const int M = 2 * HF, N = HF;
+    const int direct = p.nsplit == 1;
+    hipLaunchKernelGGL(kernel, dim3(p.tiles, p.nsplit), dim3(256), 0, s, dqk, a1, direct ? dW : ws, M, N, T, B, p.nst, p.per, alpha,
+                       beta, direct);
+    BABE_LAUNCH_CHECK();
+    if (!direct) {
+        const long n = (long)M * N;
+        hipLaunchKernelGGL(qk_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, p.nsplit, n, dW, alpha, beta);
+        BABE_LAUNCH_CHECK();
+    }
+    return BABE_OK;
+}
+
 }  // namespace
 
 extern "C" long babe_attn_qk_wgrad_workspace(int B, int HF, int T) {
@@ -378,46 +349,14 @@ extern "C" long babe_attn_qk_wgrad_workspace(int B, int HF, int T) {
 
 extern "C" int babe_attn_qk_wgrad(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha,
                                   float beta, void* stream) {
-    BABE_CHECK_ARG(dqk && a1 && dW, "attn_qk_wgrad: null pointer");
-    BABE_CHECK_ARG(qk_shape_ok(B, HF, T), "attn_qk_wgrad: unsupported shape B=%d HF=%d T=%d (HF a multiple of %d, at most %d)", B, HF,
-                   T, HF_STEP, HF_MAX);
-    const QkPlan p = qk_plan(B, HF, T);
-    BABE_CHECK_ARG(p.nsplit == 1 || ws, "attn_qk_wgrad: this shape needs a workspace (babe_attn_qk_wgrad_workspace)");
-    hipStream_t s = (hipStream_t)stream;
-    const int M = 2 * HF, N = HF;
-    const int direct = p.nsplit == 1;
-    hipLaunchKernelGGL(qk_wgrad_kernel, dim3(p.tiles, p.nsplit), dim3(256), 0, s, dqk, a1, direct ? dW : ws, M, N, T, B, p.nst, p.per,
-                       alpha, beta, direct);
-    BABE_LAUNCH_CHECK();
-    if (!direct) {
-        const long n = (long)M * N;
-        hipLaunchKernelGGL(qk_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, p.nsplit, n, dW, alpha, beta);
-        BABE_LAUNCH_CHECK();
-    }
-    return BABE_OK;
+    return qk_wgrad_host("attn_qk_wgrad", qk_wgrad_kernel, dqk, a1, dW, ws, B, HF, T, alpha, beta, stream);
 }
 
 extern "C" long babe_attn_qk_wgrad_bf16_workspace(int B, int HF, int T) { return babe_attn_qk_wgrad_workspace(B, HF, T); }
 
 extern "C" int babe_attn_qk_wgrad_bf16(const float* dqk, const float* a1, float* dW, float* ws, int B, int HF, int T, float alpha,
                                        float beta, void* stream) {
-    BABE_CHECK_ARG(dqk && a1 && dW, "attn_qk_wgrad_bf16: null pointer");
-    BABE_CHECK_ARG(qk_shape_ok(B, HF, T), "attn_qk_wgrad_bf16: unsupported shape B=%d HF=%d T=%d (HF a multiple of %d, at most %d)", B,
-                   HF, T, HF_STEP, HF_MAX);
-    const QkPlan p = qk_plan(B, HF, T);
-    BABE_CHECK_ARG(p.nsplit == 1 || ws, "attn_qk_wgrad_bf16: this shape needs a workspace (babe_attn_qk_wgrad_bf16_workspace)");
-    hipStream_t s = (hipStream_t)stream;
-    const int M = 2 * HF, N = HF;
-    const int direct = p.nsplit == 1;
-    hipLaunchKernelGGL(qk_wgrad_bf16_kernel, dim3(p.tiles, p.nsplit), dim3(256), 0, s, dqk, a1, direct ? dW : ws, M, N, T, B, p.nst,
-                       p.per, alpha, beta, direct);
-    BABE_LAUNCH_CHECK();
-    if (!direct) {
-        const long n = (long)M * N;
-        hipLaunchKernelGGL(qk_wgrad_reduce_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ws, p.nsplit, n, dW, alpha, beta);
-        BABE_LAUNCH_CHECK();
-    }
-    return BABE_OK;
+    return qk_wgrad_host("attn_qk_wgrad_bf16", qk_wgrad_bf16_kernel, dqk, a1, dW, ws, B, HF, T, alpha, beta, stream);
 }
 
 extern "C" long babe_attn_param_vjp_workspace(int B, int H, int T, int num_buckets) {
@@ -429,34 +368,8 @@ extern "C" int babe_attn_param_vjp(const float* qk, const float* qk_bias, const 
                                    int num_buckets, const float* out, const float* lse, const float* dout, const float* dqk,
                                    float* ws, float* demb_rows, long demb_bs, float* dqkb_rows, long dqkb_bs, int B, int H, int F,
                                    int T, float scale, void* stream) {
-    BABE_CHECK_ARG(!bucket == !emb && !bucket == !demb_rows, "attn_param_vjp: bucket table, embedding and demb_rows go together");
-    const int nbk = bucket ? num_buckets : 0;
-    BABE_CHECK_ARG(pv_shape_ok(B, H, F, T, nbk), "attn_param_vjp: unsupported shape B=%d H=%d F=%d T=%d buckets=%d", B, H, F, T, nbk);
-    BABE_CHECK_ARG(demb_rows || dqkb_rows, "attn_param_vjp: nothing to compute");
-    BABE_CHECK_ARG(!dqkb_rows || (dqk && dqkb_bs >= 2L * H * F), "attn_param_vjp: dqkb_rows needs dqk and dqkb_bs >= 2HF");
-    hipStream_t s = (hipStream_t)stream;
-    if (demb_rows) {
-        BABE_CHECK_ARG(qk && a && out && lse && dout && ws, "attn_param_vjp: null pointer");
-        BABE_CHECK_ARG(nbk > 0 && demb_bs >= (long)nbk * H, "attn_param_vjp: demb_bs %ld < num_buckets*H", demb_bs);
-        BABE_CHECK_ARG(demb_lds_bytes(F, T) <= LDS_LIMIT, "attn_param_vjp: F=%d with T=%d needs %ld bytes of LDS (limit %d)", F, T,
-                       demb_lds_bytes(F, T), LDS_LIMIT);
-        float* D = ws;
-        float* part = ws + (long)B * H * T;
-        const int nqt = cdiv(T, 16);
-        hipLaunchKernelGGL(rowdot_kernel, dim3(cdiv(T, 256), H, B), dim3(256), 0, s, dout, out, D, H, F, T);
-        BABE_LAUNCH_CHECK();
-        DEMB_DISPATCH(F / 64, dim3(nqt, H, B), dim3(64), diag_len(T) * sizeof(float), s, qk, qk_bias, a, bucket, emb, nbk, dout,
-                      lse, D, part, H, T, scale);
-        BABE_LAUNCH_CHECK();
-        hipLaunchKernelGGL(attn_demb_sum_kernel, dim3(B), dim3(256), 0, s, part, nqt, nbk, H, demb_rows, demb_bs);
-        BABE_LAUNCH_CHECK();
-    }
-    if (dqkb_rows) {
-        const int R = 2 * H * F;
-        hipLaunchKernelGGL(attn_rowsum_t_kernel, dim3(cdiv(R, 4), B), dim3(256), 0, s, dqk, R, T, dqkb_rows, dqkb_bs);
-        BABE_LAUNCH_CHECK();
-    }
-    return BABE_OK;
+    return attn_param_vjp_host<F32Table>("attn_param_vjp", qk, qk_bias, a, bucket, emb, num_buckets, out, lse, dout, dqk, ws, demb_rows,
+                                         demb_bs, dqkb_rows, dqkb_bs, B, H, F, T, scale, stream);
 }
 
 extern "C" int babe_scale_channels(const float* x, const float* scale, float* out, int B, int C, long hw, void* stream) {

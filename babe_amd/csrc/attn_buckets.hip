@@ -1,4 +1,4 @@
-// The relative-position bucket table of the time attention (babe_attn_buckets, csrc/attention.hip) written ON THE DEVICE, for the
+// The relative-position bucket table of the time attention: on the host (babe_attn_buckets), and written ON THE DEVICE, for the
 // library-side UNet sequencer (csrc/unet_engine.hip): the table's length 2T-1 is known at call time only, and that sequencer
 // allocates nothing, copies nothing from the host and never synchronises.  The bucket of a key-minus-query offset d is
 // non-decreasing in |d| and constant from max_distance on, so `half - 1` thresholds (half = num_buckets / 2) and the sign
@@ -6,6 +6,7 @@
 // by value.  No logarithm is evaluated on the device.
 #include "common.h"
 #include "../../include/babe_hip.h"
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -22,6 +23,29 @@ __global__ __launch_bounds__(256) void attn_bucket_table_kernel(babe_attn_bucket
 }
 
 }  // namespace
+
+extern "C" int babe_attn_buckets(int* out, int T, int num_buckets, int max_distance) {
+    BABE_CHECK_ARG(out && T > 0 && num_buckets >= 4 && max_distance > num_buckets / 4, "attn_buckets: bad arguments");
+    // T5 bidirectional buckets exactly as the reference evaluates them in float32 (torch: n.float() / max_exact, log,
+    // division by the Python scalar log(max_distance / max_exact) as multiplication by its float reciprocal, then .long())
+    const int nb = num_buckets / 2, max_exact = nb / 2;
+    const float inv = 1.f / (float)std::log((double)max_distance / (double)max_exact);
+    for (int i = 0; i < 2 * T - 1; ++i) {
+        const int rel = i - (T - 1);          // key position - query position
+        const int n = rel < 0 ? -rel : rel;
+        int v;
+        if (n < max_exact) {
+            v = n;
+        } else {
+            const float lf = logf((float)n / (float)max_exact);
+            long large = max_exact + (long)(lf * inv * (float)(nb - max_exact));
+            if (large > nb - 1) large = nb - 1;
+            v = (int)large;
+        }
+        out[i] = (rel >= 0 ? nb : 0) + v;
+    }
+    return BABE_OK;
+}
 
 extern "C" int babe_attn_bucket_thresholds(babe_attn_bucket_thr* out, int num_buckets, int max_distance) {
     BABE_CHECK_ARG(out, "attn_bucket_thresholds: null output");

@@ -54,6 +54,32 @@ def test_attn_param_vjp_vs_float64(F, T, B, bias):
     assert (demb.view(B, 32, H)[:, ~reached] == 0.0).all()
 
 
+@pytest.mark.parametrize("F,T", [(64, 33), (448, 64)])
+def test_attn_param_vjp_is_deterministic_and_row_independent(F, T):
+    """Two runs bit for bit, and row 1 of a B = 2 call equals the B = 1 call on that row: the kernels' header promises fixed
+    summation orders and per-row outputs that do not depend on which other rows share the call (a training step may split its
+    batch rows between calls).  T = 33 has three key tiles with a ragged last one, F = 448 is the widest head."""
+    from babe_amd import ops
+
+    def grads(qk, a, dout):
+        out, lse, dqk, _ = run(qk, a, qb, bucket, emb, scale, dout)
+        demb = torch.full((qk.shape[0], 32 * H), float("nan"), device="cuda")
+        dqkb = torch.full((qk.shape[0], 2 * H * F), float("nan"), device="cuda")
+        ops.attn_param_vjp(qk, a, out, lse, dout, dqk, scale, qk_bias=qb, bucket=bucket, emb=emb, demb_rows=demb, dqkb_rows=dqkb)
+        torch.cuda.synchronize()
+        return demb, dqkb
+
+    qk, a, qb, bucket, emb = make(2, F, T, True, bias=True)
+    scale = F ** -0.5
+    dout = torch.randn(a.shape, generator=torch.Generator().manual_seed(11)).cuda()
+    demb, dqkb = grads(qk, a, dout)
+    demb2, dqkb2 = grads(qk, a, dout)
+    assert torch.isfinite(demb).all() and torch.isfinite(dqkb).all()
+    assert torch.equal(demb, demb2) and torch.equal(dqkb, dqkb2)
+    demb1, dqkb1 = grads(qk[1:].contiguous(), a[1:].contiguous(), dout[1:].contiguous())
+    assert torch.equal(demb[1:], demb1) and torch.equal(dqkb[1:], dqkb1)
+
+
 @pytest.mark.parametrize("F,T,B", [(64, 1, 1), (64, 8, 3), (64, 37, 2), (64, 1024, 3), (448, 64, 2), (320, 100, 1)])
 def test_attn_qk_wgrad_vs_float64(F, T, B):
     """T = 1, T not a multiple of 4 (rows not 16-byte aligned), the K-split levels (F = 64) and the single-chunk ones, beta = 0
