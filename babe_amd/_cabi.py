@@ -251,6 +251,8 @@ SIGS = {
     "babe_conv_packed_size_wino4": (_L, [_I, _I, _I, _I]),
     "babe_conv2d_wino45": (_I, [C.POINTER(ConvArgs), _P, _P]),
     "babe_conv2d_wino45_supported": (_I, [C.POINTER(ConvArgs)]),
+    "babe_conv2d_wino45_preferred": (_I, [C.POINTER(ConvArgs)]),
+    "babe_conv2d_fewco_supported": (_I, [C.POINTER(ConvArgs)]),
     "babe_conv_pack_weights_wino45": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "babe_conv_packed_size_wino45": (_L, [_I, _I, _I]),
     "babe_prof_nslots": (_I, []),
